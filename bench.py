@@ -3,8 +3,14 @@
 (forward + PDE partials + d loss/d theta + Adam) on BASELINE.json configs[1]:
 3 -> 8x64 tanh -> 4, Navier_Stokes residual, 2^20 synthetic (t,x,y) points per GPU, fp32.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the JSON line (metric, value, unit, ms_per_step = wall
+milliseconds of one timed step, ...).  --full adds what the headline does not need: HIP events around the kernel chain
+of every timed step and the "roofline" object built on them, and the CPU baseline ("cpu_baseline", ~15 s; skipped
+with --no-cpu-baseline).  --dump-outputs DIR writes what the last timed step left to its caller (parameters, gradient,
+term sums, Adam moments) as DIR/<name>.npy in float32; inputs are seeded, so the same arguments give the same inputs.
 
 Both forms run N ranks, one process per GPU.  Under torch.distributed.run the ranks already exist
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment); started plainly with --gpus N > 1 this
@@ -164,6 +170,22 @@ def run_lbfgs_stage(args):
                    "points_per_gpu": N, "lbfgs_iterations": iters, "drivers": out}}), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor as out_dir/<name>.npy in float32 (the arrays a caller of the timed step receives)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: t.detach().float().cpu().numpy() for k, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a.astype(np.float32, copy=False))
+    log(f"dumped {', '.join(f'{k}{list(a.shape)}' for k, a in host.items())} ({total} bytes) to {out_dir}")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -171,14 +193,21 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--points", type=int, default=PTS_PER_GPU, help="points per GPU")
     ap.add_argument("--engine", type=int, default=0, help="0 auto, 1 generic, 2 fused, 3 wide, 4/5 fused tile/coop")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: per-step kernel events + roofline, and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--bf16", action="store_true", help="bf16 MFMA operands (wide engine only; extra evidence)")
     ap.add_argument("--workload", default="ns8x64", choices=sorted(WORKLOADS) + ["lbfgs8x64"],
                     help="default = the headline BASELINE configs[1]; others are extra evidence, not the contract line")
     ap.add_argument("--test-evaluator", default=os.environ.get("PINN_BENCH_TEST_EVALUATOR"),
                     help="module:factory of a CPU evaluator (tests only: rehearses the N-rank launcher and the "
                          "all-reduce path with gloo on a machine without GPUs; the line it prints is marked invalid)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---- launcher: `python bench.py --gpus N` with no torch.distributed.run around it ------------------------------
@@ -261,6 +290,9 @@ def main(argv=None):
         if args.gpus != 1:
             print("bench.py: --workload lbfgs8x64 is a one-GPU measurement", file=sys.stderr, flush=True)
             sys.exit(2)
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs covers the Adam-step workloads, not lbfgs8x64", file=sys.stderr, flush=True)
+            sys.exit(2)
         return run_lbfgs_stage(args)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args, argv))
@@ -324,16 +356,17 @@ def main(argv=None):
 
     def mk_events():
         return None if cpu_test else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    ev = [mk_events() for _ in range(args.steps)]         # around the loss+gradient kernel chain
+    kern_ev = args.full and not cpu_test                 # --full: kernel-chain time per step for the roofline object
+    ev = [mk_events() for _ in range(args.steps)] if kern_ev else None   # around the loss+gradient kernel chain
     ev_ar = [mk_events() for _ in range(args.steps)]      # around the all-reduce
     host_ar = [0.0]
 
     def step(i, timed_idx=None):
         grad.zero_()
         timed = timed_idx is not None and not cpu_test
-        if timed: ev[timed_idx][0].record()
+        if timed and kern_ev: ev[timed_idx][0].record()
         eng.residual_loss_grad(spec, scale, params, X, grad, sums=sums)
-        if timed: ev[timed_idx][1].record()
+        if timed and kern_ev: ev[timed_idx][1].record()
         if dist is not None:
             if timed: ev_ar[timed_idx][0].record()
             t_ar = time.perf_counter()
@@ -366,24 +399,14 @@ def main(argv=None):
     loss = float((sums * scale).sum())
     log(f"{args.steps} steps in {dt:.3f} s; loss {loss:.5e}")
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"params": params, "grad": grad, "term_sums": sums, "adam_m": m, "adam_v": v})
+
     if rank == 0:
         if cpu_test:
-            kern_ms = None
             ar_ms = host_ar[0] / args.steps * 1e3 if dist is not None else 0.0
         else:
-            kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
             ar_ms = sum(a.elapsed_time(b) for a, b in ev_ar) / args.steps if dist is not None else 0.0
-        traffic, traffic_src = None, None   # HBM bytes per launch from the committed PMC passes of this same command
-        src = PMC_SUMMARIES.get((args.workload, bool(args.bf16)))
-        if src is not None and not cpu_test and args.engine in (0, 2, 3):
-            try:
-                pm = json.load(open(os.path.join(ROOT, src[0])))
-                traffic = pm[src[1]] * N
-                traffic_src = f"rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE, {src[0]}"
-            except Exception:
-                pass
-        achieved = N * flop_pt / (kern_ms * 1e-3) / 1e12 if kern_ms else None
-        peak = PEAK_BF16_MFMA_TFLOPS if args.bf16 else PEAK_F32_MFMA_TFLOPS
         ms_step = dt / args.steps * 1e3
         out = {
             "metric": "collocation-point residuals/sec (fwd+PDE-grad+Adam)",
@@ -399,14 +422,27 @@ def main(argv=None):
                        "parallelism": f"dp{world}", "engine": args.engine, "final_loss": loss,
                        "allreduce_bytes": (P + nt) * 4 if dist is not None else 0,
                        "allreduce_ms": ar_ms, "allreduce_frac_of_step": ar_ms / ms_step if ms_step > 0 else 0.0},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak,
-                         "unit": "TFLOP/s", "frac": achieved / peak if achieved else None, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "kernel": "pinn_residual_loss_grad (fwd jet + residual + reverse sweep)",
-                         "kernel_ms": kern_ms, "flop_per_point": flop_pt},
         }
-        if world == 1 and not args.no_cpu_baseline and args.workload == "ns8x64" and not cpu_test:
-            out["cpu_baseline"] = cpu_baseline(usable_cpus())
+        if args.full:
+            kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps if kern_ev else None
+            traffic, traffic_src = None, None   # HBM bytes per launch from the committed PMC passes of this same command
+            src = PMC_SUMMARIES.get((args.workload, bool(args.bf16)))
+            if src is not None and not cpu_test and args.engine in (0, 2, 3):
+                try:
+                    pm = json.load(open(os.path.join(ROOT, src[0])))
+                    traffic = pm[src[1]] * N
+                    traffic_src = f"rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE, {src[0]}"
+                except Exception:
+                    pass
+            achieved = N * flop_pt / (kern_ms * 1e-3) / 1e12 if kern_ms else None
+            peak = PEAK_BF16_MFMA_TFLOPS if args.bf16 else PEAK_F32_MFMA_TFLOPS
+            out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": peak,
+                               "unit": "TFLOP/s", "frac": achieved / peak if achieved else None, "traffic": traffic,
+                               "traffic_source": traffic_src,
+                               "kernel": "pinn_residual_loss_grad (fwd jet + residual + reverse sweep)",
+                               "kernel_ms": kern_ms, "flop_per_point": flop_pt}
+            if world == 1 and not args.no_cpu_baseline and args.workload == "ns8x64" and not cpu_test:
+                out["cpu_baseline"] = cpu_baseline(usable_cpus())
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -2,12 +2,14 @@
 rehearsed on CPU: gloo, two ranks, the oracle standing in for the HIP engine (tests/cpu_evaluator.py).
 What is checked is the plumbing a GPU node will run — N real processes, rank-sharded points, ONE
 all-reduce of [grad | sums] per step, max-over-ranks timing, one JSON line from rank 0 with n_gpus = N —
-and that a 2-rank run computes the same loss as one process over both shards."""
+and that a 2-rank run computes the same loss as one process over both shards.  Also the options around the
+line: --dump-outputs (seeded inputs, same outputs run to run), --full (the extras), --steps."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,3 +62,33 @@ def test_launcher_refuses_more_gpus_than_visible():
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 2 and "refusing" in out.stderr
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+DUMPED = ("params", "grad", "term_sums", "adam_m", "adam_v")
+
+
+def test_plain_line_and_dumped_outputs_are_reproducible(tmp_path):
+    dumps = []
+    for k in range(2):
+        out = run_bench(["--gpus", "1", "--dump-outputs", str(tmp_path / f"run{k}")])
+        assert out.returncode == 0, out.stderr[-3000:]
+        r = json_line(out)
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0
+        assert "roofline" not in r and "cpu_baseline" not in r                 # extras belong to --full
+        dumps.append({n: np.load(tmp_path / f"run{k}" / f"{n}.npy") for n in DUMPED})
+    for n in DUMPED:
+        a = dumps[0][n]
+        assert a.dtype == np.float32 and a.shape == ((3,) if n == "term_sums" else (29636,)) and np.isfinite(a).all(), n
+        assert np.array_equal(a, dumps[1][n]), n                                # same arguments, same inputs
+    assert np.any(dumps[0]["grad"] != 0) and np.any(dumps[0]["adam_v"] > 0)
+    assert abs(float(dumps[0]["term_sums"].sum()) / 48 - r["config"]["final_loss"]) <= 1e-5 * r["config"]["final_loss"]
+
+
+def test_steps_set_the_timed_steps_and_full_adds_the_extras():
+    out = run_bench(["--gpus", "1", "--steps", "3", "--full"])
+    assert out.returncode == 0, out.stderr[-3000:]
+    r = json_line(out)
+    assert r["steps"] == 3 and "3 steps in" in out.stderr
+    assert r["roofline"]["flop_per_point"] == 695_424 and r["roofline"]["kernel"].startswith("pinn_residual_loss_grad")
+    out = run_bench(["--gpus", "1", "--steps", "0"])
+    assert out.returncode == 2 and "--steps must be >= 1" in out.stderr

@@ -7,7 +7,7 @@ TAG=$1; shift
 OUT=$R/gpurun_out/evidence_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py "$@" > $OUT/bench.json 2> $OUT/bench.log || { echo bench failed; tail -5 $OUT/bench.log; exit 1; }
+python3 $R/bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.log || { echo bench failed; tail -5 $OUT/bench.log; exit 1; }
 cat $OUT/bench.json
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 12 --warmup 8 --no-cpu-baseline "$@" > $OUT/stats.log 2>&1 || echo FAIL stats
 i=0
