@@ -1,7 +1,7 @@
 /*
  * pinn_hip.h — C-ABI of libpinn_hip.so, the MI355X (gfx950) engine for the
- * PINN depth-inversion hot path: tanh-MLP forward + first-order input-Jacobian
- * ("jet") + PDE residual loss + parameter gradient.
+ * PINN depth-inversion hot path: tanh-MLP forward + first- and second-order input
+ * derivatives ("jets") + PDE residual loss + parameter gradient.
  *
  * The reference (rezasalatin/PINN_depthEstimation) has no FFI; its boundary is
  * the Python call surface.  Every entry point below names the reference code it
@@ -12,6 +12,9 @@
  *                           compute_gradient(out_c, in_j) column in one pass
  *   pinn_jet_backward       the double-backward torch runs under loss.backward()
  *                           (train.py:191) for a generic consumer of the jet
+ *   pinn_forward_jet2       physics.py:6-15 applied twice: every second derivative
+ *                           compute_gradient(compute_gradient(out_c, in_i), in_j)
+ *   pinn_jet2_backward      loss.backward() (train.py:191) through those second derivatives
  *   pinn_residual_loss[_grad] physics.py:18-33,37-47,50-88,91-120 (continuity_only,
  *                           continuity_ftemp, Navier_Stokes, physics_equation)
  *                           fused with loss.backward() (train.py:154,191)
@@ -47,7 +50,7 @@
 extern "C" {
 #endif
 
-#define PINN_ABI_VERSION 3
+#define PINN_ABI_VERSION 4
 
 #define PINN_MAX_DIRS 3   /* tangent directions (inputs with requires_grad) */
 #define PINN_MAX_ROLES 8
@@ -154,6 +157,28 @@ int32_t pinn_forward_jet(const pinn_desc* desc, const float* params, const float
 int32_t pinn_jet_backward(const pinn_desc* desc, const float* params, const float* X, int64_t N,
                           const float* gY, const float* gdY, float* grad_flat,
                           void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- second-order jets --------------------------------------------------------------------------------------------
+ * k = desc->k differentiated inputs (1..3) give P = k (k + 1) / 2 unordered pairs (i, j), i <= j, stored upper triangle
+ * row-major: (0,0), (0,1), .., (0,k-1), (1,1), ..  d2Y: (P, N, d_out), d2Y[p] = d^2 Y / d X[:, dir_col[i]] d X[:, dir_col[j]].
+ * Engines: GENERIC runs the VALU layer kernels (any shape, tanh or LeakyReLU, dropout: the mask multiplies all three
+ * orders).  FUSED (and its sub-values) runs the MFMA layer kernels (v_mfma_f32_16x16x4_f32): fp32, every layer at most
+ * 64 wide, no dropout; other requests are refused with PINN_ERR_UNSUPPORTED (dropout named in its own message).  AUTO
+ * takes the MFMA kernels where they apply, else the VALU ones.  WIDE and PINN_PREC_BF16 are refused; k = 0 is
+ * PINN_ERR_INVALID.  The workspace of these calls is
+ * their own (pinn_query_jet2_workspace); large point sets run in chunks, so it stops growing past about 1 GiB. */
+int32_t pinn_query_jet2_workspace(const pinn_desc* desc, int64_t N, int64_t* bytes);
+
+/* physics.py:6-15 applied twice (train.py:191 differentiates the result once more, pinn_jet2_backward).
+ * Y (N, d_out) and dY (k, N, d_out) as pinn_forward_jet, either may be NULL; d2Y (P, N, d_out) is required. */
+int32_t pinn_forward_jet2(const pinn_desc* desc, const float* params, const float* X, int64_t N,
+                          float* Y, float* dY, float* d2Y, void* ws, int64_t ws_bytes, void* stream);
+
+/* train.py:191 through second derivatives: grad_flat (P,) += d/dtheta [ sum(gY*Y) + sum(gdY*dY) + sum(gd2Y*d2Y) ];
+ * any of gY, gdY, gd2Y may be NULL (treated as 0). */
+int32_t pinn_jet2_backward(const pinn_desc* desc, const float* params, const float* X, int64_t N,
+                           const float* gY, const float* gdY, const float* gd2Y, float* grad_flat,
+                           void* ws, int64_t ws_bytes, void* stream);
 
 /* term_sums[t] = sum over points of (residual field t)^2  (device, n_terms floats, overwritten) */
 int32_t pinn_residual_loss(const pinn_desc* desc, const pinn_residual_spec* spec,

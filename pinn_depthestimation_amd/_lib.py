@@ -16,7 +16,7 @@ PINN_MAX_ROLES = 8
 ACT_TANH, ACT_LEAKY_RELU = 0, 1
 ENGINE_AUTO, ENGINE_GENERIC, ENGINE_FUSED, ENGINE_WIDE = 0, 1, 2, 3
 ENGINE_FUSED_TILE, ENGINE_FUSED_COOP, ENGINE_FUSED_BATCH = 4, 5, 6     # sub-values of ENGINE_FUSED: force one of its kernels (pinn_hip.h)
-ABI_VERSION = 3
+ABI_VERSION = 4
 PREC_F32, PREC_BF16 = 0, 1
 
 RES_NAVIER_STOKES, RES_PHYSICS_EQUATION, RES_CONTINUITY_FTEMP, RES_CONTINUITY_ONLY = 1, 2, 3, 4
@@ -64,6 +64,9 @@ _SIGNATURES = {
     "pinn_forward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "pinn_forward_jet": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "pinn_jet_backward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
+    "pinn_query_jet2_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.c_int64, C.POINTER(C.c_int64)]),
+    "pinn_forward_jet2": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
+    "pinn_jet2_backward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "pinn_residual_loss": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int64, _P,
                                        _P, C.c_int64, _P]),
     "pinn_residual_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P,

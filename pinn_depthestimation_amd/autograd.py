@@ -17,6 +17,21 @@ fused pinn_residual_loss_grad); torch only threads the pieces together:
 so `compute_gradient(pred, var)` keeps its signature and any user expression
 (h*U, (h+z)*u ...) goes through ordinary autograd, while physics.<residual> can
 recognise outputs of DNN.forward (JetTensor) and call the fused kernel instead.
+
+Second derivatives (compute_gradient of a compute_gradient, e.g. u_xx, u_xy):
+  first compute_gradient, under create_graph=True (grad mode on in the backward)
+                        -> _AttachTangentInputs  identity on dY whose backward hands
+                                              d(.)/dX_i = sum_j sum_c gdY[j,:,c]*d2Y[pair(i,j),:,c]
+                                              to the input columns
+  second compute_gradient-> _Jet2Tangents     d2Y (P, N, d_out), pair rows (i, j), i <= j
+                                              (pinn_forward_jet2), created lazily, graph-connected
+                                              to the params: its backward is pinn_jet2_backward
+                           _AttachJet2Inputs  marks d2Y as input-dependent so that a THIRD
+                                              derivative raises PinnError instead of a silent zero
+A plain loss.backward() (grad mode off in the backward) takes neither input branch: x.grad
+gets the first-order path through Y only, exactly as for first-order losses, and no jet2
+kernel runs for it.  Networks whose losses never ask for a second derivative make the same
+kernel calls as before (the tangents' attach node is an identity in their backward).
 """
 from __future__ import annotations
 
@@ -103,13 +118,45 @@ class JetHandle:
         self.grad_cols: Tuple[int, ...] = tuple(grad_cols)
         self.sources = sources            # per grad col: ("leaf", tensor) | ("node", grad_fn) | None
         self._dY: Optional[torch.Tensor] = None
+        self._dY_att: Optional[torch.Tensor] = None     # dY behind _AttachTangentInputs (second-order graphs)
+        self._d2Y: Optional[torch.Tensor] = None
+        self._d2Y_att: Optional[torch.Tensor] = None
+        self._X_node: Optional[torch.Tensor] = None
+
+    def _x_node(self) -> torch.Tensor:
+        """X_graph as a non-leaf (a view of a leaf input): _engine_reaches() can ask about a non-leaf's node in
+        every kind of backward pass, a leaf's only under .backward()."""
+        if self._X_node is None:
+            self._X_node = self.X_graph if self.X_graph.grad_fn is not None else self.X_graph.view_as(self.X_graph)
+        return self._X_node
+
+    def _stale(self, t: Optional[torch.Tensor]) -> bool:
+        return t is not None and torch.is_grad_enabled() and not t.requires_grad and \
+            any(p.requires_grad for p in self.model._ordered_params())
 
     def tangents(self) -> torch.Tensor:
-        stale = self._dY is not None and torch.is_grad_enabled() and not self._dY.requires_grad and \
-            any(p.requires_grad for p in self.model._ordered_params())
-        if self._dY is None or stale:   # never reuse tangents that were built outside the graph
+        if self._dY is None or self._stale(self._dY):   # never reuse tangents that were built outside the graph
             self._dY = _JetTangents.apply(self.model, self.X, self.grad_cols, self.drop, *self.model._ordered_params())
+            self._dY_att = None
         return self._dY
+
+    def tangents_attached(self) -> torch.Tensor:
+        """dY, also graph-connected to the input X_graph (one attach node per handle, so that every first
+        derivative of this forward pass feeds the same node and dY's own backward sees what it saw before)."""
+        dY = self.tangents()
+        if self._dY_att is None:
+            self._dY_att = _AttachTangentInputs.apply(dY, self._x_node(), self)
+        return self._dY_att
+
+    def second_tangents(self) -> torch.Tensor:
+        """d2Y (P, N, d_out) from pinn_forward_jet2, graph-connected to the params and (for the third-order
+        check) to X_graph; cached like tangents()."""
+        if self._d2Y is None or self._stale(self._d2Y):
+            self._d2Y = _Jet2Tangents.apply(self.model, self.X, self.grad_cols, self.drop, *self.model._ordered_params())
+            self._d2Y_att = None
+        if self._d2Y_att is None:
+            self._d2Y_att = _AttachJet2Inputs.apply(self._d2Y, self._x_node(), self)
+        return self._d2Y_att
 
     def direction_of(self, var: torch.Tensor) -> Optional[int]:
         """Index j such that `var` is the input tensor behind X[:, grad_cols[j]], else None."""
@@ -137,11 +184,93 @@ class _AttachInputs(torch.autograd.Function):
         h = ctx.handle
         gX = None
         if ctx.needs_input_grad[1]:
-            dY = h.tangents()                                  # (k, N, d_out), carries the param graph
+            # (k, N, d_out), carries the param graph; under create_graph also the input graph (second order)
+            dY = h.tangents_attached() if torch.is_grad_enabled() and h.X_graph.requires_grad else h.tangents()
             cols = (gY.unsqueeze(0) * dY).sum(-1)              # (k, N)
             gX = torch.zeros(h.X.shape, dtype=gY.dtype, device=gY.device)
             gX = gX.index_copy(1, torch.tensor(h.grad_cols, device=gY.device), cols.t())
         return gY, gX, None
+
+
+def _pair_table(k: int) -> List[List[int]]:
+    """pair[i][j] = row of d2Y holding d^2 / dx_i dx_j: pairs (i, j), i <= j, upper triangle row-major."""
+    idx, p = [[0] * k for _ in range(k)], 0
+    for i in range(k):
+        for j in range(i, k):
+            idx[i][j] = idx[j][i] = p
+            p += 1
+    return idx
+
+
+def _engine_reaches(t: torch.Tensor) -> bool:
+    """Will the running backward pass deliver a gradient through non-leaf t (toward autograd.grad's inputs, or
+    toward every leaf under .backward())?  Asked of t's node.  torch._C._will_engine_execute_node is private API
+    (checked against torch 2.10; tests/test_jet2_cpu.py fails if it goes away or changes meaning)."""
+    return bool(torch._C._will_engine_execute_node(t.grad_fn))
+
+
+class _AttachTangentInputs(torch.autograd.Function):
+    """Identity on dY that routes input-gradients of first derivatives through the second-order jet:
+    d(.)/dX[:, grad_cols[i]] = sum_j sum_c gdY[j,:,c] * d2Y[pair(i,j),:,c].  Only takes that branch in a
+    backward that builds a graph (create_graph=True, as compute_gradient does) and reaches X."""
+
+    @staticmethod
+    def forward(ctx, dY, X_graph, handle):
+        ctx.handle = handle
+        return dY.view_as(dY)
+
+    @staticmethod
+    def backward(ctx, gdY):
+        h = ctx.handle
+        gX = None
+        if ctx.needs_input_grad[1] and torch.is_grad_enabled() and _engine_reaches(h._x_node()):
+            d2Y = h.second_tangents()                          # (P, N, d_out)
+            k = len(h.grad_cols)
+            pidx = torch.tensor(_pair_table(k), device=gdY.device)
+            cols = (gdY.unsqueeze(0) * d2Y[pidx]).sum(1).sum(-1)   # (k, N): sum over j, then over output columns
+            gX = torch.zeros(h.X.shape, dtype=gdY.dtype, device=gdY.device)
+            gX = gX.index_copy(1, torch.tensor(h.grad_cols, device=gdY.device), cols.t())
+        return gdY, gX, None
+
+
+class _Jet2Tangents(torch.autograd.Function):
+    """d2Y[p] = d^2 net(X) / dX_i dX_j for pair p = (i, j)  (P, N, d_out), one second-order forward-mode pass."""
+
+    @staticmethod
+    def forward(ctx, model, X, grad_cols, drop, *params):
+        eng = engine_for(model, grad_cols, X.device, drop)
+        ctx.model, ctx.drop, ctx.grad_cols = model, drop, tuple(grad_cols)
+        ctx.save_for_backward(X)
+        _, _, d2Y = eng.forward_jet2(model.flat_params(), X)
+        return d2Y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gd2Y):
+        (X,) = ctx.saved_tensors
+        model = ctx.model
+        grad = torch.zeros_like(model.flat_params())
+        engine_for(model, ctx.grad_cols, X.device, ctx.drop).jet2_backward(model.flat_params(), X, None, None,
+                                                                           gd2Y.contiguous(), grad)
+        return (None, None, None, None, *_split_flat(model, grad))
+
+
+class _AttachJet2Inputs(torch.autograd.Function):
+    """Identity on d2Y that refuses to differentiate it by the inputs: the engine carries jets up to second
+    order, so a third derivative is an error rather than a silent zero.  A backward without create_graph
+    passes (no input contribution, as for the lower orders)."""
+
+    @staticmethod
+    def forward(ctx, d2Y, X_graph, handle):
+        ctx.handle = handle
+        return d2Y.view_as(d2Y)
+
+    @staticmethod
+    def backward(ctx, gd2Y):
+        if ctx.needs_input_grad[1] and torch.is_grad_enabled() and _engine_reaches(ctx.handle._x_node()):
+            raise PinnError("third-order input derivatives are not supported: the HIP engine carries input "
+                            "derivatives up to second order (compute_gradient of a second derivative)")
+        return gd2Y, None, None
 
 
 class JetTensor(torch.Tensor):

@@ -89,6 +89,15 @@ int generic_jet_backward(const Net& n, const float* params, const float* X, int6
 int generic_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N,
                  void* ws, int64_t ws_bytes, hipStream_t s);
 
+// second-order jets (pinn_jet2.hip): generic VALU layer kernels, or MFMA layer kernels (mfma = true) where
+// jet2_mfma_supports(); one workspace layout serves both
+int64_t jet2_workspace_bytes(const Net& n, int64_t N);
+bool jet2_mfma_supports(const Net& n);
+int jet2_forward(const Net& n, bool mfma, const float* params, const float* X, int64_t N, float* Y, float* dY,
+                 float* d2Y, void* ws, int64_t ws_bytes, hipStream_t s);
+int jet2_backward(const Net& n, bool mfma, const float* params, const float* X, int64_t N, const float* gY,
+                  const float* gdY, const float* gd2Y, float* grad, void* ws, int64_t ws_bytes, hipStream_t s);
+
 // fused MFMA engine (pinn_fused.hip)
 bool fused_supports(const Net& n, bool want_grad);
 bool fused_supports_adam(const Net& n, const LossReq& rq, int64_t N);   // one-pass requests only

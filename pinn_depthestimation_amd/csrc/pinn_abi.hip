@@ -455,4 +455,54 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, co
   return PINN_OK;
 }
 
+// ---- second-order jets (physics.py:6-15 applied twice; their parameter gradient, train.py:191) ----------------------
+// Validation shared by the three jet2 entries; *mfma = which layer kernels run.  GENERIC: the VALU kernels, any shape.
+// FUSED (and its sub-values): the MFMA kernels, fp32 networks at most 64 wide without dropout, refused otherwise.
+// AUTO: MFMA where it applies, else the generic kernels (dropout, wider networks).
+static int jet2_net(const pinn_desc* desc, Net* n, bool* mfma) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  if (n->k < 1) { set_error("jet2 needs k >= 1 differentiated inputs (k = %d)", n->k); return PINN_ERR_INVALID; }
+  if (n->prec != PINN_PREC_F32) { set_error("jet2 is implemented in fp32 only (precision bf16 refused)"); return PINN_ERR_UNSUPPORTED; }
+  const int asked = (desc->engine == PINN_ENGINE_FUSED_TILE || desc->engine == PINN_ENGINE_FUSED_COOP ||
+                     desc->engine == PINN_ENGINE_FUSED_BATCH) ? PINN_ENGINE_FUSED : desc->engine;
+  if (asked == PINN_ENGINE_WIDE) { set_error("jet2 does not run on the wide engine: use engine AUTO, FUSED or GENERIC"); return PINN_ERR_UNSUPPORTED; }
+  const bool ok = jet2_mfma_supports(*n);
+  if (asked == PINN_ENGINE_FUSED && !ok) {
+    if (n->drop_p > 0.f)
+      set_error("jet2 with dropout_p > 0 is not served by the MFMA (fused) path: use engine AUTO or GENERIC");
+    else
+      set_error("the MFMA (fused) jet2 path serves layers at most 64 wide (d_in %d, width %d, d_out %d): use engine AUTO or GENERIC",
+                n->d_in, n->W, n->d_out);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  *mfma = ok && asked != PINN_ENGINE_GENERIC;
+  return PINN_OK;
+}
+
+int32_t pinn_query_jet2_workspace(const pinn_desc* desc, int64_t N, int64_t* bytes) {
+  Net n; bool mfma; int rc = jet2_net(desc, &n, &mfma); if (rc) return rc;
+  if (!bytes || N < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
+  const int64_t b = jet2_workspace_bytes(n, N);
+  if (b < 0) { set_error("too many layers for the jet2 kernels"); return PINN_ERR_UNSUPPORTED; }
+  *bytes = b;
+  return PINN_OK;
+}
+
+int32_t pinn_forward_jet2(const pinn_desc* desc, const float* params, const float* X, int64_t N, float* Y, float* dY,
+                          float* d2Y, void* ws, int64_t ws_bytes, void* stream) {
+  Net n; bool mfma; int rc = jet2_net(desc, &n, &mfma); if (rc) return rc;
+  if (!params || (!X && N > 0) || N < 0 || (!d2Y && N > 0)) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
+  if (N == 0) return PINN_OK;
+  return jet2_forward(n, mfma, params, X, N, Y, dY, d2Y, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int32_t pinn_jet2_backward(const pinn_desc* desc, const float* params, const float* X, int64_t N, const float* gY,
+                           const float* gdY, const float* gd2Y, float* grad_flat, void* ws, int64_t ws_bytes,
+                           void* stream) {
+  Net n; bool mfma; int rc = jet2_net(desc, &n, &mfma); if (rc) return rc;
+  if (!params || (!X && N > 0) || N < 0 || !grad_flat) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
+  if (N == 0 || (!gY && !gdY && !gd2Y)) return PINN_OK;   // nothing to add
+  return jet2_backward(n, mfma, params, X, N, gY, gdY, gd2Y, grad_flat, ws, ws_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -157,8 +157,8 @@ class Engine:
         self.desc = desc
         self.device = torch.device(device)
         self._cdesc: Dict[Tuple[int, int], PinnDesc] = {}
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._ws_need: Dict[Tuple[int, int], int] = {}
+        self._ws: Dict[object, torch.Tensor] = {}
+        self._ws_need: Dict[tuple, int] = {}
         self._packed_tok = None      # (workspace, params storage, params version, caller's token) after loss_grad_adam_step
         self.dropout_seed = 0        # training-mode dropout: the caller sets a fresh seed per forward pass; the
                                      # reverse sweep of that pass must run under the same one (include/pinn_hip.h)
@@ -216,6 +216,20 @@ class Engine:
             self._ws[e] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         return ws
 
+    def jet2_workspace(self, N: int, engine: Optional[int] = None) -> torch.Tensor:
+        """Workspace of the second-order calls (pinn_query_jet2_workspace), cached apart from workspace()'s."""
+        e = self.desc.engine if engine is None else engine
+        key = ("jet2", e, N)
+        need = self._ws_need.get(key)
+        if need is None:
+            c_need = C.c_int64()
+            check(self.lib.pinn_query_jet2_workspace(C.byref(self._d(e)), N, C.byref(c_need)), "pinn_query_jet2_workspace")
+            need = self._ws_need[key] = c_need.value
+        ws = self._ws.get(("jet2", e))
+        if ws is None or ws.numel() < need:
+            self._ws[("jet2", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return ws
+
     # ---- calls ------------------------------------------------------------------------
     def forward(self, params: torch.Tensor, X: torch.Tensor, engine=None) -> torch.Tensor:
         N = X.shape[0]
@@ -246,6 +260,38 @@ class Engine:
         ws = self.workspace(N, ENGINE_GENERIC)
         self._run("pinn_jet_backward", self.lib.pinn_jet_backward, C.byref(self._d(ENGINE_GENERIC)), _ptr(params), _ptr(X), N, _ptr(gY),
                                          _ptr(gdY), _ptr(grad), _ptr(ws), ws.numel())
+        return grad
+
+    @property
+    def n_pairs(self) -> int:
+        """Second-order pairs (i, j), i <= j, of the differentiated inputs: the rows of d2Y."""
+        return self.desc.k * (self.desc.k + 1) // 2
+
+    def forward_jet2(self, params: torch.Tensor, X: torch.Tensor, engine=None):
+        """(Y, dY, d2Y): Y (N, d_out), dY (k, N, d_out), d2Y (P, N, d_out) with row p = pair (i, j) of the
+        differentiated columns, upper triangle row-major (pinn_forward_jet2)."""
+        N = X.shape[0]
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        Y = torch.empty(N, self.desc.d_out, dtype=torch.float32, device=X.device)
+        dY = torch.empty(self.desc.k, N, self.desc.d_out, dtype=torch.float32, device=X.device)
+        d2Y = torch.empty(self.n_pairs, N, self.desc.d_out, dtype=torch.float32, device=X.device)
+        ws = self.jet2_workspace(N, engine)
+        self._run("pinn_forward_jet2", self.lib.pinn_forward_jet2, C.byref(self._d(engine)), _ptr(params), _ptr(X), N,
+                  _ptr(Y), _ptr(dY), _ptr(d2Y), _ptr(ws), ws.numel())
+        return Y, dY, d2Y
+
+    def jet2_backward(self, params, X, gY: Optional[torch.Tensor], gdY: Optional[torch.Tensor],
+                      gd2Y: Optional[torch.Tensor], grad: torch.Tensor, engine=None) -> torch.Tensor:
+        """grad += d/d params [sum(gY*Y) + sum(gdY*dY) + sum(gd2Y*d2Y)] (pinn_jet2_backward); any adjoint may be None."""
+        N = X.shape[0]
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        self._chk(grad, "grad", (self.n_params,))
+        if gY is not None: self._chk(gY, "gY", (N, self.desc.d_out))
+        if gdY is not None: self._chk(gdY, "gdY", (self.desc.k, N, self.desc.d_out))
+        if gd2Y is not None: self._chk(gd2Y, "gd2Y", (self.n_pairs, N, self.desc.d_out))
+        ws = self.jet2_workspace(N, engine)
+        self._run("pinn_jet2_backward", self.lib.pinn_jet2_backward, C.byref(self._d(engine)), _ptr(params), _ptr(X), N,
+                  _ptr(gY), _ptr(gdY), _ptr(gd2Y), _ptr(grad), _ptr(ws), ws.numel())
         return grad
 
     def residual_loss(self, spec: ResidualSpec, params, X, engine=None) -> torch.Tensor:

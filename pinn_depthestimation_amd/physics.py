@@ -6,6 +6,8 @@ output columns of one DNN.forward call (what train.py:144-154 / train_newmethod.
 pass), the whole loss and d loss / d theta come from one pinn_residual_loss_grad kernel.
 Otherwise it evaluates the same formulas through compute_gradient, whose derivatives come
 from the forward-mode jet (autograd.py) — still the HIP engine, never a CPU path.
+compute_gradient nests once: compute_gradient(compute_gradient(u, x), y) comes from the
+second-order jet (pinn_forward_jet2); a third derivative raises PinnError.
 """
 from __future__ import annotations
 
@@ -16,7 +18,8 @@ from .autograd import fused_residual
 
 def compute_gradient(pred, var):
     """d pred / d var per collocation point, differentiable w.r.t. the network parameters
-    (reference physics.py:6-15)."""
+    (reference physics.py:6-15).  Applied to its own result it gives second derivatives (u_xx, u_xy),
+    still differentiable w.r.t. the parameters; applied a third time it raises PinnError."""
     (grad,) = torch.autograd.grad(pred, var, grad_outputs=torch.ones_like(pred),
                                   retain_graph=True, create_graph=True)
     return grad
