@@ -47,10 +47,7 @@ typedef short sh4 __attribute__((ext_vector_type(4)));
 constexpr int CHAIN_WAVES = 4;
 constexpr int CHAIN_THREADS = CHAIN_WAVES * 64;
 constexpr int CHAIN_RING = 6;              // weight slabs in the LDS ring of the reverse chain (next to its prefetch areas)
-#ifndef PINN_CHAIN_RING_FWD
-#define PINN_CHAIN_RING_FWD 6
-#endif
-constexpr int CHAIN_RING_FWD = PINN_CHAIN_RING_FWD;   // ... of the forward chain
+constexpr int CHAIN_RING_FWD = 6;          // ... of the forward chain
 // dynamic LDS of k_chain_fwd8 at padded width 16*ntw: ring + one spare slot (the ring's dummy copies) + every layer's
 // bias + (folded first layer) 16 B of W_0 per unit.  ONE formula for the launcher and for wide_supports(): the depth
 // limit of bf16 mode is whatever still fits the CU's 160 KB (L <= 43 at width 256, far more at width 128).
@@ -59,22 +56,13 @@ __host__ __device__ constexpr size_t chain_fwd8_lds_bytes(int ntw, int L, bool f
   return (size_t)CHAIN_RING_FWD * (ntw / 2) * 2 * 1024 + (size_t)ntw * 1024 + (size_t)(L + 1) * 16 * ntw * 4 +
          (fold_first ? (size_t)16 * ntw * 16 : 0);
 }
-#ifndef PINN_BWD_PREFETCH
-#define PINN_BWD_PREFETCH 8
-#endif
-constexpr int BWD_PREFETCH = PINN_BWD_PREFETCH;       // k_chain_bwd: the same, inside a layer
-#ifndef PINN_FWD8_PREFETCH
-#define PINN_FWD8_PREFETCH 4
-#endif
-constexpr int FWD8_PREFETCH = PINN_FWD8_PREFETCH;     // k-steps of the next slab read before the barrier (0: off)
+constexpr int BWD_PREFETCH = 8;            // k_chain_bwd: the same, inside a layer
+constexpr int FWD8_PREFETCH = 4;           // k-steps of the next slab read before the barrier (0: off)
 // Weight precision of the REVERSE chain.  Measured on the reference's 12 x 256 golden (G10): rounding the weights to
 // bf16 in the FORWARD pass moves the gradient by 1.2e-1 (the loss is evaluated at a shifted point of a stiff
 // surface) — the forward chain always multiplies by hi + lo.  Rounding them in the reverse pass alone is a random,
-// averaging error: gradient 5.2e-3 instead of 3.3e-3 for 7 % of the step (2^20 points: 40.0 vs 42.9 ms).  Default 1
-// (hi + lo in both directions): the stated bf16 tolerance of this engine is 5e-3.
-#ifndef PINN_CHAIN_BWD_LO
-#define PINN_CHAIN_BWD_LO 1
-#endif
+// averaging error: gradient 5.2e-3 instead of 3.3e-3 for 7 % of the step (2^20 points: 40.0 vs 42.9 ms).  Hence
+// hi + lo in both directions: the stated bf16 tolerance of this engine is 5e-3.
 constexpr int WG_UNITS = 4;                // LDS ring slots of the weight-gradient kernel (half tiles)
 
 struct ChainParams {
@@ -124,11 +112,7 @@ struct ChainParams {
 #define CHAIN_DIAG_END(P) do { } while (0)
 #endif
 
-#ifdef PINN_CHAIN_EXP_NOMFMA   // timing experiment only (results are garbage): how fast do the weight copies run alone?
-__device__ __forceinline__ f4 mfma32(bf8 a, bf8 b, f4 c) { asm volatile("" ::"v"(a), "v"(b)); return c; }
-#else
 __device__ __forceinline__ f4 mfma32(bf8 a, bf8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-#endif
 
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -156,17 +140,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t jet_rsrc(const void* tile_base
 // between: with default-policy jet traffic the weight copies ran at the beyond-L2 LDS-DMA rate (~25 GB/s per CU,
 // = the 16 KB of every GEMM step: the steps were bound by them, not by their 64 MFMAs).  Jets are written once
 // and read once much later: stores go out write-through / no L2 allocation (sc1), loads are non-temporal (nt).
-#ifndef PINN_CHAIN_JET_ST_AUX
-#define PINN_CHAIN_JET_ST_AUX 18   // sc1 | nt (measured: reverse chain 15.05 -> 14.8 ms against sc1 alone; default policy: forward +0.35 ms)
-#endif
-#ifndef PINN_CHAIN_JET_LD_AUX
-#define PINN_CHAIN_JET_LD_AUX 2    // nt
-#endif
+constexpr int CHAIN_JET_ST_AUX = 18;   // sc1 | nt (measured: reverse chain 15.05 -> 14.8 ms against sc1 alone; default policy: forward +0.35 ms)
+constexpr int CHAIN_JET_LD_AUX = 2;    // nt
 __device__ __forceinline__ bf8 ld_blk(__amdgpu_buffer_rsrc_t r, unsigned lane_off, int blk_off) {
-  return __builtin_bit_cast(bf8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, blk_off, PINN_CHAIN_JET_LD_AUX));
+  return __builtin_bit_cast(bf8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, blk_off, CHAIN_JET_LD_AUX));
 }
 __device__ __forceinline__ void st_blk(__amdgpu_buffer_rsrc_t r, unsigned lane_off, int blk_off, bf8 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), r, (int)lane_off, blk_off, PINN_CHAIN_JET_ST_AUX);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), r, (int)lane_off, blk_off, CHAIN_JET_ST_AUX);
 }
 
 // a wave-uniform 64-bit value the compiler cannot prove uniform (derived from threadIdx): moved to SGPRs so
@@ -596,8 +576,7 @@ template <int NTW, int K1>
 __global__ __launch_bounds__(CHAIN_THREADS, 1) void k_chain_bwd(const ChainParams P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NS = NTW / 2;
-  constexpr bool LO = PINN_CHAIN_BWD_LO != 0;
-  constexpr int SLAB = NS * (LO ? 2 : 1) * 1024;     // the hi pieces are the first NS planes of a packed slab
+  constexpr int SLAB = NS * 2 * 1024;     // the hi pieces are the first NS planes of a packed slab, the lo pieces the next NS
   constexpr int QD = SLAB / 4 / 1024;
   constexpr int R = CHAIN_RING;
   // fragment prefetch across the barrier (see k_chain_fwd8): inside a layer the barrier of a step certifies the NEXT
@@ -741,7 +720,7 @@ __global__ __launch_bounds__(CHAIN_THREADS, 1) void k_chain_bwd(const ChainParam
           if (pf_cur) {                            // copy i = block (piece i / K1, quantity i % K1): piece-major
 #pragma unroll
             for (int i = 2 * MT; i < 2 * MT + chain_pf_at<NPF>(MT); ++i)
-              dma_1k<PINN_CHAIN_JET_LD_AUX>(pf_src + ((i % K1) * NS + i / K1) * 1024, pf + i * 1024, lane);
+              dma_1k<CHAIN_JET_LD_AUX>(pf_src + ((i % K1) * NS + i / K1) * 1024, pf + i * 1024, lane);
           }
         }
         if (live) {
@@ -758,11 +737,9 @@ __global__ __launch_bounds__(CHAIN_THREADS, 1) void k_chain_bwd(const ChainParam
           const bf8 ahi = (havepf && s < PFB) ? pfh[s < PFB ? s : 0] : *reinterpret_cast<const bf8*>(sl + s * 1024);
 #pragma unroll
           for (int c = 0; c < K1; ++c) acc[c][MT] = mfma32(ahi, zj[c][s], acc[c][MT]);
-          if constexpr (LO) {
-            const bf8 alo = (havepf && s < PFB) ? pfl[s < PFB ? s : 0] : *reinterpret_cast<const bf8*>(sl + (NS + s) * 1024);
+          const bf8 alo = (havepf && s < PFB) ? pfl[s < PFB ? s : 0] : *reinterpret_cast<const bf8*>(sl + (NS + s) * 1024);
 #pragma unroll
-            for (int c = 0; c < K1; ++c) acc[c][MT] = mfma32(alo, zj[c][s], acc[c][MT]);
-          }
+          for (int c = 0; c < K1; ++c) acc[c][MT] = mfma32(alo, zj[c][s], acc[c][MT]);
         }
         ring.consumed();
         if constexpr (PFB > 0 && MT + 1 < NTW) {
@@ -770,7 +747,7 @@ __global__ __launch_bounds__(CHAIN_THREADS, 1) void k_chain_bwd(const ChainParam
 #pragma unroll
           for (int s = 0; s < PFB; ++s) {
             pfh[s] = *reinterpret_cast<const bf8*>(sn + s * 1024);
-            if constexpr (LO) pfl[s] = *reinterpret_cast<const bf8*>(sn + (NS + s) * 1024);
+            pfl[s] = *reinterpret_cast<const bf8*>(sn + (NS + s) * 1024);
           }
         }
         ++g;
@@ -852,7 +829,7 @@ __global__ __launch_bounds__(P8_THREADS, 2) void k_chain_wgrad8(const ChainParam
       int c = 2 * ku + cq;
       if (c >= K1) c = K1 - 1;                     // odd K1: the missing quantity is masked at the MFMA operand
       const unsigned short* src = (op ? Al : Zl) + ((t * K1 + c) * NS + s) * 512;
-      dma_1k<PINN_CHAIN_JET_LD_AUX>(src, dst + jj * 1024, lane);
+      dma_1k<CHAIN_JET_LD_AUX>(src, dst + jj * 1024, lane);
     }
   };
   f4 dw[MTB][NCB];

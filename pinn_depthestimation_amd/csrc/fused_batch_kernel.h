@@ -42,31 +42,16 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-#ifndef PINN_BATCH_T
-#define PINN_BATCH_T 0     // 0: batch_tiles(); > 0 forces a value (experiments)
-#endif
-#ifndef PINN_BATCH_OCC
-#define PINN_BATCH_OCC 0     // 0: batch_occ(); > 0 forces a value (experiments)
-#endif
-#ifndef PINN_BATCH_OCC16
-#define PINN_BATCH_OCC16 2   // width <= 16: two waves per SIMD (256 registers each) with half the tiles per batch
-#endif
-#ifndef PINN_BATCH_PF
-#define PINN_BATCH_PF 4       // tiles of spilled activations in flight ahead of the reverse sweep
-#endif
-constexpr int BATCH_PF = PINN_BATCH_PF;
-#ifndef PINN_BATCH_SKIP
-#define PINN_BATCH_SKIP 0     // diagnostic builds only (wrong results): 1 no spill stores, 2 no spill loads, 4 no LDS transposes,
-#endif                        // 8 no weight-gradient MFMAs, 16 no tanh, 32 no gradient flush
+constexpr int BATCH_OCC16 = 2;   // width <= 16: two waves per SIMD (256 registers each) with half the tiles per batch
+constexpr int BATCH_PF = 4;       // tiles of spilled activations in flight ahead of the reverse sweep
 // Tiles per wave and batch: as many as the 512-register file takes WITHOUT a spill (a scratch reload shares the
 // vector-memory counter with the activation prefetch and drains it: bwg_* comment).  hipcc's resource report per
 // instance: width <= 16: 8 tiles at K1 = 3, 4 at K1 = 4; width <= 32: 4 at K1 = 3, 2 at K1 = 4.
 __host__ __device__ constexpr int batch_occ(int WP, int K1) {     // waves per SIMD (= workgroups per CU)
-  return PINN_BATCH_OCC > 0 ? PINN_BATCH_OCC : (WP == 16 ? PINN_BATCH_OCC16 : 1);
+  return WP == 16 ? BATCH_OCC16 : 1;
 }
 __host__ __device__ constexpr int batch_tiles(int WP, int K1) {
-  return PINN_BATCH_T > 0 ? PINN_BATCH_T
-       : WP == 16 ? (batch_occ(WP, K1) == 2 ? (K1 <= 3 ? 4 : 2) : (K1 <= 3 ? 8 : 4)) : (K1 <= 3 ? 4 : 2);
+  return WP == 16 ? (batch_occ(WP, K1) == 2 ? (K1 <= 3 ? 4 : 2) : (K1 <= 3 ? 8 : 4)) : (K1 <= 3 ? 4 : 2);
 }
 constexpr int BATCH_WAVES = 4;
 constexpr int BATCH_THREADS = BATCH_WAVES * 64;
@@ -98,7 +83,7 @@ __device__ __forceinline__ void bactivate(const f4 (&acc)[K1][NTH], const f4 (&b
   for (int s = 0; s < KS; ++s) {
     const float z = acc[0][s >> 2][s & 3] + bias[s >> 2][s & 3];
     float av, sd;
-    if constexpr (ACT == PINN_ACT_TANH) { av = (PINN_BATCH_SKIP & 16) ? z : tanh_f32(z); sd = fmaf(-av, av, 1.f); }
+    if constexpr (ACT == PINN_ACT_TANH) { av = tanh_f32(z); sd = fmaf(-av, av, 1.f); }
     else { av = z > 0.f ? z : 0.01f * z; sd = z > 0.f ? 1.f : 0.01f; }
     a[0][s] = av;
 #pragma unroll
@@ -180,9 +165,9 @@ __device__ __forceinline__ void bunspill(const float* __restrict__ slot, float (
 //                        read by the caller before its VALU work.  dw[MT][NT] += sum_c sum_points Z (x) A;
 //                        bs[MT] += this lane's share of sum_points Z[0][MT] (lane groups combined at flush time).
 // Pads of quantity c: tb + c*(MT_N+NT_N) KB, Z tiles first.  One wave's LDS operations execute in order: no barrier.
-// pad layout of the weight-gradient operands: fused_kernel.h's second one (feature-major rows, PINN_FUSED_TR2) or the first
+// pad layout of the weight-gradient operands: fused_kernel.h's second one (feature-major rows) or the first
 #ifndef PINN_BATCH_TR2
-#define PINN_BATCH_TR2 PINN_FUSED_TR2
+#define PINN_BATCH_TR2 1
 #endif
 __device__ __forceinline__ void btr_write(float* __restrict__ tb, f4 v, int p, int q) {
 #if PINN_BATCH_TR2
@@ -481,7 +466,6 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
       f4 acc[2][K1][NTH];
       auto gemm = [&](auto tc) {
         constexpr int t = decltype(tc)::value;
-        if constexpr (!(PINN_BATCH_SKIP & 1))
         bspill<KS, K1>(scr + t * tstride + (int64_t)(l - 1) * SLOTF, a[t], lane);    // a_l, re-read by the reverse sweep
         zero_tiles<NTH, K1>(acc[t & 1]);
         bgemm<KS, NTH, NTH, K1>(w, a[t], acc[t & 1]);
@@ -592,27 +576,12 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
         badjoint<ACT, KS, NTH, K1>(g2, ai, a[t]);      // (VALU: covers the transposed reads)
         __builtin_amdgcn_sched_barrier(0);
         // ai is dead: its registers take tile t + PF of this layer, or tile t + PF - T of the next one down
-        if constexpr (!(PINN_BATCH_SKIP & 2)) {
-          if constexpr (t + PF < T) bunspill<KS, K1>(scr + (t + PF) * tstride + (int64_t)(l - 1) * SLOTF, pf[t % PF], lane);
-          else bunspill<KS, K1>(scr + (t + PF - T) * tstride + (int64_t)(ln - 1) * SLOTF, pf[t % PF], lane);
-        }
+        if constexpr (t + PF < T) bunspill<KS, K1>(scr + (t + PF) * tstride + (int64_t)(l - 1) * SLOTF, pf[t % PF], lane);
+        else bunspill<KS, K1>(scr + (t + PF - T) * tstride + (int64_t)(ln - 1) * SLOTF, pf[t % PF], lane);
         bwg_tail<NTH, NTH, K1, NACC>(dw, bs, ztr, atr, tb, p, q);
       });
-      if constexpr (!(PINN_BATCH_SKIP & 32))
-      {
       if constexpr (WGFLUSH) bwgrad_flush_wg<NTH, NTH, NACC, KS, KS>(gacc, w_off_p<WP>(l), P.PW + b_off_p<WP>(l), dw, bs, comb + (flushes++ & 1) * (batch_comb_floats(WP) / 2), wave, lane);
       else bwgrad_flush<NTH, NTH, NACC, SINK, KS, KS>(gacc, w_off_p<WP>(l), P.PW + b_off_p<WP>(l), dw, bs, lane);
-      }
-      else {   // diagnostic: no flush, but every accumulator stays live
-        float acc_ = bs[0];
-#pragma unroll
-        for (int a_ = 0; a_ < NACC; ++a_)
-#pragma unroll
-          for (int MT = 0; MT < NTH; ++MT)
-#pragma unroll
-            for (int NT = 0; NT < NTH; ++NT) acc_ += (dw[a_][MT][NT][0] + dw[a_][MT][NT][1]) + (dw[a_][MT][NT][2] + dw[a_][MT][NT][3]);
-        sums[MAX_SUMS - 1] += acc_;
-      }
 #pragma unroll
       for (int MT = 0; MT < NTH; ++MT)
 #pragma unroll

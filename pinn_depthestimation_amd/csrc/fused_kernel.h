@@ -32,28 +32,9 @@ namespace pinn {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-#ifndef PINN_FUSED_WAVES
-#define PINN_FUSED_WAVES 4
-#endif
-#ifndef PINN_FUSED_BATCH_FLUSH
-#define PINN_FUSED_BATCH_FLUSH 4   // row blocks of the LDS gradient flush read per round trip (0 = one block at a time)
-#endif
-#ifndef PINN_FUSED_ADJ_IN_FLUSH
-#define PINN_FUSED_ADJ_IN_FLUSH 0   // 1: run the activation adjoint between the LDS flush's reads and its adds
-#endif
-#ifndef PINN_FUSED_MID_IO
-#define PINN_FUSED_MID_IO 1   // spill stores / activation reloads issued from inside the GEMMs (see gemm_stream)
-#endif
-#ifndef PINN_FUSED_W16_WAVES
-#define PINN_FUSED_W16_WAVES 3   // waves per SIMD the width-16 kernels are compiled for (workgroups per CU follow in pinn_fused.hip)
-#endif
-#ifndef PINN_FUSED_EARLY_LOCK
-#define PINN_FUSED_EARLY_LOCK 1   // global gradient copy: lock + request the current values before the dW MFMAs
-#endif
-#ifndef PINN_FUSED_XPREF
-#define PINN_FUSED_XPREF 1   // 1: request the next tile's input coordinates one tile ahead
-#endif
-constexpr int FUSED_WAVES = PINN_FUSED_WAVES;
+constexpr int FUSED_WAVES = 4;
+constexpr int FUSED_W16_WAVES = 3;   // waves per SIMD the width-16 kernels are compiled for (workgroups per CU follow in pinn_fused.hip)
+constexpr int FUSED_FLUSH_ROWS = 4;  // row blocks of the gradient flush read per round trip
 constexpr int FUSED_THREADS = FUSED_WAVES * 64;
 constexpr int TB_FLOATS = 256;                // one 16x16 fp32 block, XOR-swizzled (see transpose_write)
 constexpr int TB_PER_WAVE = 8;                // 4 pads for the Zbar tiles + 4 for the A tiles of one quantity
@@ -177,13 +158,6 @@ __device__ __forceinline__ void zero_tiles(f4 (&v)[K1][NT]) {
   for (int c = 0; c < K1; ++c)
 #pragma unroll
     for (int MT = 0; MT < NT; ++MT) v[c][MT] = f4{0.f, 0.f, 0.f, 0.f};
-}
-template <int NT, int K1>
-__device__ __forceinline__ void copy_tiles(f4 (&d)[K1][NT], const f4 (&srcv)[K1][NT]) {
-#pragma unroll
-  for (int c = 0; c < K1; ++c)
-#pragma unroll
-    for (int MT = 0; MT < NT; ++MT) d[c][MT] = srcv[c][MT];
 }
 
 template <int NT, int K1>
@@ -351,15 +325,12 @@ __device__ __forceinline__ f4 transpose_read(const float* __restrict__ tb, int p
   return o;
 }
 
-// Second pad layout (PINN_FUSED_TR2, weight_grad of the tile kernel only): row = FEATURE (16 points = 64 B), the row's four
+// Second pad layout (weight_grad of the tile kernel only): row = FEATURE (16 points = 64 B), the row's four
 // 16-byte chunks rotated by 2 * (feature >> 2).  The write side does the transposition — lane (point p, q) scatters its
 // features 4q + r as dwords (two ds_write2_b32, 2-way on the 32 write banks: free) — and the read side takes element s
 // <-> point 4 kq + s (the contraction order over points is free as long as both operands use the same one): ONE
 // conflict-free ds_read_b128 per block instead of two ds_read2st64_b32 behind a 2-way-conflicted ds_write_b128.
 // Measured A/B (round 3, same box): 8x64 6.295 -> 6.258 ms, 10x10 on the tile kernel 0.774 -> 0.764, 100x20 24.19 -> 24.02.
-#ifndef PINN_FUSED_TR2
-#define PINN_FUSED_TR2 1
-#endif
 __device__ __forceinline__ void transpose_write2(float* __restrict__ tb, f4 v, int p, int q) {
   float* d = tb + (4 * q) * 16 + 4 * (((p >> 2) + 2 * q) & 3) + (p & 3);
 #pragma unroll
@@ -406,23 +377,14 @@ struct GradSink {
     if (lane == 0) __hip_atomic_store(locks + l, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   __device__ __forceinline__ void add1(int idx, float v) const { acc[idx] += v; }
-  __device__ __forceinline__ void add4(int idx, f4 v) const {   // idx: float index, multiple of 4
-    f4* ptr = reinterpret_cast<f4*>(acc + idx);
-    *ptr = *ptr + v;
-  }
 };
 
 // dW[16MT + 4q + r][16NT + n] += sum_c sum_points Z[c][MT](feature, point) * A[c][NT](feature, point)
 // db[16MT + m]                += sum_points Z[0][MT](feature m, point)
 // A: the layer-input jet in acc layout (registers).
-struct NoHook { __device__ __forceinline__ void operator()() const {} };
-
-// `between` (optional) runs after the flush's LDS reads have been issued and before their adds: vector
-// work that does not depend on the flush (the activation adjoint) then covers the LDS round trip.
-template <int MT_N, int NT_N, int K1, class Sink, class Hook = NoHook>
+template <int MT_N, int NT_N, int K1, class Sink>
 __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int woff, int boff, const f4 (&Z)[K1][MT_N],
-                                            const f4 (&A)[K1][NT_N], float* __restrict__ tb, int lane,
-                                            const Hook& between = Hook()) {
+                                            const f4 (&A)[K1][NT_N], float* __restrict__ tb, int lane) {
   const int p = lane & 15, q = lane >> 4;
   f4 dw[MT_N][NT_N];
   float bs[MT_N];
@@ -434,7 +396,7 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
   // that the global round trip hides behind the transposes and MFMAs below instead of sitting in the
   // flush (waves of a workgroup are on different layers almost always: holding the lock longer is free).
   f4 early[Sink::LDS ? 1 : MT_N][Sink::LDS ? 1 : NT_N];
-  if constexpr (!Sink::LDS && PINN_FUSED_EARLY_LOCK) {
+  if constexpr (!Sink::LDS) {
     sink.lock(layer, lane);
 #pragma unroll
     for (int MT = 0; MT < MT_N; ++MT)
@@ -447,7 +409,6 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
   // MT_N*NT_N*4 MFMAs of quantity c.
   f4 zt[2][MT_N], at[2][NT_N];
   auto stage = [&](int c, f4 (&z)[MT_N], f4 (&a)[NT_N]) {
-#if PINN_FUSED_TR2
 #pragma unroll
     for (int MT = 0; MT < MT_N; ++MT) transpose_write2(tb + MT * TB_FLOATS, Z[c][MT], p, q);
 #pragma unroll
@@ -456,16 +417,6 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
     for (int MT = 0; MT < MT_N; ++MT) z[MT] = transpose_read2(tb + MT * TB_FLOATS, p, q);
 #pragma unroll
     for (int NT = 0; NT < NT_N; ++NT) a[NT] = transpose_read2(tb + (4 + NT) * TB_FLOATS, p, q);
-#else
-#pragma unroll
-    for (int MT = 0; MT < MT_N; ++MT) transpose_write(tb + MT * TB_FLOATS, Z[c][MT], p, q);
-#pragma unroll
-    for (int NT = 0; NT < NT_N; ++NT) transpose_write(tb + (4 + NT) * TB_FLOATS, A[c][NT], p, q);
-#pragma unroll
-    for (int MT = 0; MT < MT_N; ++MT) z[MT] = transpose_read(tb + MT * TB_FLOATS, p, q);
-#pragma unroll
-    for (int NT = 0; NT < NT_N; ++NT) a[NT] = transpose_read(tb + (4 + NT) * TB_FLOATS, p, q);
-#endif
   };
   stage(0, zt[0], at[0]);
 #pragma unroll
@@ -493,18 +444,17 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
     t += __shfl_xor(t, 32, 64);
     bs[MT] = t;
   }
-  if constexpr (!Sink::LDS && PINN_FUSED_EARLY_LOCK) {
+  if constexpr (!Sink::LDS) {
 #pragma unroll
     for (int MT = 0; MT < MT_N; ++MT)
 #pragma unroll
       for (int NT = 0; NT < NT_N; ++NT)
         *reinterpret_cast<f4*>(sink.acc + woff + ((MT * NT_N + NT) * 64 + lane) * 4) = early[MT][NT] + dw[MT][NT];
   } else {
-  sink.lock(layer, lane);
-  if constexpr (PINN_FUSED_BATCH_FLUSH != 0) {   // (LDS copy or global copy alike)
-    // one LDS round trip per FLUSH_ROWS row blocks (all reads issued, then adds + writes) instead of
+    sink.lock(layer, lane);
+    // one LDS round trip per FUSED_FLUSH_ROWS row blocks (all reads issued, then adds + writes) instead of
     // one per 16x16 block: with a single wave per SIMD the serialized read-add-write chain is exposed
-    constexpr int FR = PINN_FUSED_BATCH_FLUSH < MT_N ? PINN_FUSED_BATCH_FLUSH : MT_N;
+    constexpr int FR = FUSED_FLUSH_ROWS < MT_N ? FUSED_FLUSH_ROWS : MT_N;
 #pragma unroll
     for (int M0 = 0; M0 < MT_N; M0 += FR) {
       f4 cur[FR][NT_N];
@@ -513,8 +463,7 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
 #pragma unroll
         for (int NT = 0; NT < NT_N; ++NT)
           cur[MT - M0][NT] = *reinterpret_cast<const f4*>(sink.acc + woff + ((MT * NT_N + NT) * 64 + lane) * 4);
-      __builtin_amdgcn_sched_barrier(0);
-      if (M0 == 0) between();
+      __builtin_amdgcn_sched_barrier(0);   // (a pair: with one, the width-32 kernels' register allocation changes)
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int MT = M0; MT < M0 + FR && MT < MT_N; ++MT)
@@ -522,13 +471,6 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
         for (int NT = 0; NT < NT_N; ++NT)
           *reinterpret_cast<f4*>(sink.acc + woff + ((MT * NT_N + NT) * 64 + lane) * 4) = cur[MT - M0][NT] + dw[MT][NT];
     }
-  } else {
-    between();
-#pragma unroll
-    for (int MT = 0; MT < MT_N; ++MT)
-#pragma unroll
-      for (int NT = 0; NT < NT_N; ++NT) sink.add4(woff + ((MT * NT_N + NT) * 64 + lane) * 4, dw[MT][NT]);
-  }
   }
   if (q == 0) {
 #pragma unroll
@@ -756,7 +698,7 @@ __device__ __forceinline__ void loss_epilogue(const FusedParams& P, const f4 (&o
 // kernels place the weights accordingly (pinn_fused.hip, PACK_IN / PACK_OUT) and the host hands the epilogue PADDED row
 // indices in out_col / dir_col, so the epilogue code is the same.
 template <int WP, int K1, bool GRAD, bool LDSACC, int ACT, int EPI = EPI_GENERIC, int KRO = 0, bool DROP = false>
-__global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FUSED_WAVES / 4) void k_fused(const FusedParams P) {
+__global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_WAVES / 4) void k_fused(const FusedParams P) {
   static_assert(!DROP || (ACT == PINN_ACT_TANH && KRO == 0), "dropout instances: tanh, natural unit order");
   constexpr bool IO1 = KRO > 0;
   constexpr int KRI = IO1 ? 1 : 4;          // k-steps of the first layer's contraction (d_in <= 4 when IO1)
@@ -799,7 +741,6 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FU
 #ifdef PINN_DIAG
   unsigned long long diag[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
 #endif
-#if PINN_FUSED_XPREF
   auto load_x = [&](int64_t t, f4& x) {
     int64_t pc = t * 16 + p;
     pc = pc < P.N ? pc : P.N - 1;
@@ -811,7 +752,6 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FU
   };
   f4 xnext;
   load_x(gw < P.n_tiles ? gw : 0, xnext);
-#endif
   for (int64_t tile = gw; tile < P.n_tiles; tile += nw) {
     PINN_STAMP(11);
     const int64_t pt = tile * 16 + p;
@@ -819,21 +759,14 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FU
     const int64_t ptc = valid ? pt : P.N - 1;
     DropLane dl;
     if constexpr (DROP) dl.init(P.drop_seed, P.drop_thresh, P.drop_scale, P.drop_keep, pt);
-#if PINN_FUSED_XPREF
     const f4 xcur = xnext;
     load_x(tile + nw < P.n_tiles ? tile + nw : tile, xnext);
-#endif
     // ---- layer-0 input jet: features 4q + r of (x, unit tangents) --------------------------
     auto input_jet = [&](f4 (&b)[K1][1]) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int f = 4 * q + r;                 // PADDED input index (dir_col holds padded indices when IO1)
-#if PINN_FUSED_XPREF
         b[0][0][r] = xcur[r];
-#else
-        const int fr = IO1 ? (r == 0 ? q : 16) : f;
-        b[0][0][r] = (fr < P.d_in) ? P.X[ptc * P.d_in + fr] : 0.f;
-#endif
 #pragma unroll
         for (int c = 1; c < K1; ++c) b[c][0][r] = (f == P.dir_col[c - 1]) ? 1.f : 0.f;
       }
@@ -856,27 +789,17 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FU
       PINN_STAMP(0);
       activate_to<ACT, NTH, K1, DROP>(acc0, bias, a, &dl, 0, q);
     }
-#if !PINN_FUSED_MID_IO
-    if (GRAD && L > 1) spill<NTH, K1>(scr, a, lane);      // a_L itself stays in registers for the reverse sweep
-#endif
     PINN_STAMP(1);
     for (int l = 1; l < L; ++l) {
       f4 bias[NTH];
       load_bias<NTH>(Bp_ + b_off_p<WP>(l), bias, q);
       f4 nx[K1][NTH];
       zero_tiles<NTH, K1>(nx);
-#if PINN_FUSED_MID_IO
       // a_l (this GEMM's B operand) is spilled from INSIDE the GEMM (see gemm_stream); a_L is never spilled
       auto sp = [&]() { if (GRAD) spill<NTH, K1>(scr + (l - 1) * SLOT, a, lane); };
       gemm_stream<NTH, NTH, K1>(Wp_ + w_off_p<WP>(l), Wp_ + w_off_p<WP>(l + 1), ws, a, nx, p, q, sp);
       PINN_STAMP(0);
       activate_to<ACT, NTH, K1, DROP>(nx, bias, a, &dl, l, q);
-#else
-      gemm_stream<NTH, NTH, K1>(Wp_ + w_off_p<WP>(l), Wp_ + w_off_p<WP>(l + 1), ws, a, nx, p, q);
-      PINN_STAMP(0);
-      activate_to<ACT, NTH, K1, DROP>(nx, bias, a, &dl, l, q);
-      if (GRAD && l < L - 1) spill<NTH, K1>(scr + l * SLOT, a, lane);   // (the last hidden jet is never re-read)
-#endif
       PINN_STAMP(1);
     }
     f4 out[K1][1];
@@ -891,12 +814,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FU
     // reverse-sweep operands whose latency the residual evaluation below hides
     f4 wtl[NTH][1];
     f4 ai[K1][NTH];
-    if constexpr (GRAD) {
-      load_w<1, NTH>(WTp_ + w_off_p<WP>(L), wtl, p, q);
-#if !PINN_FUSED_MID_IO
-      unspill<NTH, K1>(scr + (L > 1 ? L - 2 : 0) * SLOT, ai, lane);            // a_{L-1}
-#endif
-    }
+    if constexpr (GRAD) load_w<1, NTH>(WTp_ + w_off_p<WP>(L), wtl, p, q);
 
     // ---- outputs / loss -----------------------------------------------------------------------
     f4 G[K1][1];
@@ -922,30 +840,13 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FU
         PINN_STAMP(3);
         f4 g2[K1][NTH];
         zero_tiles<NTH, K1>(g2);
-#if PINN_FUSED_MID_IO
         // a_l is requested from inside the GEMM (see gemm_stream) and used by the weight gradient after it
         auto ld = [&]() { unspill<NTH, K1>(scr + (l - 1) * SLOT, ai, lane); };
         gemm_stream<NTH, NTH, K1>(WTp_ + w_off_p<WP>(l), WTp_ + w_off_p<WP>(l >= 2 ? l - 1 : 1), ws, z, g2, p, q, ld);
-#else
-        gemm_stream<NTH, NTH, K1>(WTp_ + w_off_p<WP>(l), WTp_ + w_off_p<WP>(l >= 2 ? l - 1 : 1), ws, z, g2, p, q);
-#endif
         PINN_STAMP(6);
-#if PINN_FUSED_ADJ_IN_FLUSH
-        f4 zn[K1][NTH];
-        auto adj = [&]() { activate_adjoint_to<ACT, NTH, K1, DROP>(g2, ai, zn, &dl, l - 1, q); };
-        weight_grad<NTH, NTH, K1>(sink, l, w_off_p<WP>(l), P.PW + b_off_p<WP>(l), z, ai, tb, lane, adj);
-        copy_tiles<NTH, K1>(z, zn);
-#if !PINN_FUSED_MID_IO
-        if (l >= 2) unspill<NTH, K1>(scr + (l - 2) * SLOT, ai, lane);            // a_{l-1}
-#endif
-#else
         weight_grad<NTH, NTH, K1>(sink, l, w_off_p<WP>(l), P.PW + b_off_p<WP>(l), z, ai, tb, lane);
         PINN_STAMP(5);
         activate_adjoint_to<ACT, NTH, K1, DROP>(g2, ai, z, &dl, l - 1, q);
-#if !PINN_FUSED_MID_IO
-        if (l >= 2) unspill<NTH, K1>(scr + (l - 2) * SLOT, ai, lane);            // a_{l-1}
-#endif
-#endif
         PINN_STAMP(4);
       }
       {  // layer 0: z = zbar_0, input = (x, unit tangents)
@@ -986,7 +887,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? PINN_FUSED_W16_WAVES : FU
   }
 }
 
-// launcher implemented once per WP in pinn_fused_wXX.hip
+// launcher: pinn_fused_launch.inc, one translation unit per WP (pinn_fused_wXX.hip)
 template <int WP>
 int launch_fused(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 

@@ -91,10 +91,16 @@ int make_net(const pinn_desc* d, Net* n) {
   return PINN_OK;
 }
 
+// the engine desc asks for, with the fused engine's kernel choices (FUSED_TILE / _COOP / _BATCH) folded into FUSED
+static int asked_engine(const pinn_desc* d) {
+  return (d->engine == PINN_ENGINE_FUSED_TILE || d->engine == PINN_ENGINE_FUSED_COOP || d->engine == PINN_ENGINE_FUSED_BATCH)
+             ? PINN_ENGINE_FUSED : d->engine;
+}
+
 // 1 = generic, 2 = fused, 3 = wide
 static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc) {
   *rc = PINN_OK;
-  const int asked = (d->engine == PINN_ENGINE_FUSED_TILE || d->engine == PINN_ENGINE_FUSED_COOP || d->engine == PINN_ENGINE_FUSED_BATCH) ? PINN_ENGINE_FUSED : d->engine;
+  const int asked = asked_engine(d);
   if (n.drop_p > 0.f) {     // training-mode dropout: the fused tile kernel for gradient passes at padded width 64
                             // (pinn_fused_w64_drop.hip), the generic engine's kernels for everything else
     if (n.prec != PINN_PREC_F32) { set_error("dropout_p > 0 is implemented in fp32 only"); *rc = PINN_ERR_UNSUPPORTED; return PINN_ENGINE_GENERIC; }
@@ -129,6 +135,25 @@ static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc
   if (fused_supports(n, want_grad)) return PINN_ENGINE_FUSED;
   if (wide_supports(n)) return PINN_ENGINE_WIDE;
   return PINN_ENGINE_GENERIC;
+}
+
+// runs rq on the engine pick_engine() chooses for it
+static int run_loss(const pinn_desc* desc, const Net& n, bool want_grad, const LossReq& rq, const float* params,
+                    const float* X, int64_t N, void* ws, int64_t ws_bytes, void* stream) {
+  int rc; const int e = pick_engine(desc, n, want_grad, &rc); if (rc) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  return e == PINN_ENGINE_FUSED ? fused_loss(n, rq, params, X, N, ws, ws_bytes, s)
+       : e == PINN_ENGINE_WIDE ? wide_loss(n, rq, params, X, N, ws, ws_bytes, s)
+                               : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
+}
+
+// the fidelity columns: each must name an output of the network; copied into rq->out_col
+static int set_out_cols(const Net& n, int n_cols, const int32_t* out_col, LossReq* rq) {
+  for (int j = 0; j < n_cols; ++j) {
+    if (out_col[j] < 0 || out_col[j] >= n.d_out) { set_error("out_col[%d]=%d out of range", j, out_col[j]); return PINN_ERR_INVALID; }
+    rq->out_col[j] = out_col[j];
+  }
+  return PINN_OK;
 }
 
 static int residual_terms(int id) {
@@ -289,10 +314,7 @@ static int32_t residual_impl(const pinn_desc* desc, const pinn_residual_spec* sp
   rq.kind = 0; rq.n_split = -1; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums;
   rq.grad = want_grad ? grad_flat : nullptr; rq.n_terms = residual_terms(spec->residual_id);
   if (N == 0) { (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), (hipStream_t)stream); return PINN_OK; }
-  const int e = pick_engine(desc, n, want_grad, &rc); if (rc) return rc;
-  return e == PINN_ENGINE_FUSED ? fused_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream)
-       : e == PINN_ENGINE_WIDE ? wide_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream)
-                               : generic_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
+  return run_loss(desc, n, want_grad, rq, params, X, N, ws, ws_bytes, stream);
 }
 
 int32_t pinn_residual_loss(const pinn_desc* desc, const pinn_residual_spec* spec, const float* params,
@@ -316,16 +338,10 @@ int32_t pinn_mse_loss_grad(const pinn_desc* desc, const float* params, const flo
   if (n_cols < 1 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 1..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
   LossReq rq; memset(&rq, 0, sizeof(rq));
   rq.kind = 1; rq.n_split = -1; rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
-  for (int j = 0; j < n_cols; ++j) {
-    if (out_col[j] < 0 || out_col[j] >= n.d_out) { set_error("out_col[%d]=%d out of range", j, out_col[j]); return PINN_ERR_INVALID; }
-    rq.out_col[j] = out_col[j];
-  }
+  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
   if (N == 0) { (void)hipMemsetAsync(col_sums, 0, n_cols * sizeof(float), (hipStream_t)stream); return PINN_OK; }
   n.k = 0; n.K1 = 1;  // the fidelity term needs no input derivatives
-  const int e = pick_engine(desc, n, grad_flat != nullptr, &rc); if (rc) return rc;
-  return e == PINN_ENGINE_FUSED ? fused_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream)
-       : e == PINN_ENGINE_WIDE ? wide_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream)
-                               : generic_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
+  return run_loss(desc, n, grad_flat != nullptr, rq, params, X, N, ws, ws_bytes, stream);
 }
 
 static int32_t residual_mse_impl(int64_t n_split, const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
@@ -343,10 +359,7 @@ static int32_t residual_mse_impl(int64_t n_split, const pinn_desc* desc, const p
   LossReq rq; memset(&rq, 0, sizeof(rq));
   rq.kind = 2; rq.n_split = n_split; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums; rq.n_terms = residual_terms(spec->residual_id);
   rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
-  for (int j = 0; j < n_cols; ++j) {
-    if (out_col[j] < 0 || out_col[j] >= n.d_out) { set_error("out_col[%d]=%d out of range", j, out_col[j]); return PINN_ERR_INVALID; }
-    rq.out_col[j] = out_col[j];
-  }
+  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
   if (N == 0) {
     (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), (hipStream_t)stream);
     (void)hipMemsetAsync(col_sums, 0, n_cols * sizeof(float), (hipStream_t)stream);
@@ -356,10 +369,7 @@ static int32_t residual_mse_impl(int64_t n_split, const pinn_desc* desc, const p
     rq.kind = 0; rq.n_split = -1;
     (void)hipMemsetAsync(col_sums, 0, n_cols * sizeof(float), (hipStream_t)stream);
   }
-  const int e = pick_engine(desc, n, true, &rc); if (rc) return rc;
-  return e == PINN_ENGINE_FUSED ? fused_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream)
-       : e == PINN_ENGINE_WIDE ? wide_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream)
-                               : generic_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
+  return run_loss(desc, n, true, rq, params, X, N, ws, ws_bytes, stream);
 }
 
 int32_t pinn_residual_mse_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
@@ -410,10 +420,7 @@ int32_t pinn_loss_grad_adam_step(const pinn_desc* desc, const pinn_residual_spec
   LossReq rq; memset(&rq, 0, sizeof(rq));
   rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums; rq.n_terms = residual_terms(spec->residual_id);
   rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
-  for (int j = 0; j < n_cols; ++j) {
-    if (out_col[j] < 0 || out_col[j] >= n.d_out) { set_error("out_col[%d]=%d out of range", j, out_col[j]); return PINN_ERR_INVALID; }
-    rq.out_col[j] = out_col[j];
-  }
+  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
   if (n_res == N) { rq.kind = 0; rq.n_split = -1; }      // residual term only
   else { rq.kind = 2; rq.n_split = n_res < 0 ? -1 : n_res; }
   const int e = pick_engine(desc, n, true, &rc); if (rc) return rc;
@@ -463,8 +470,7 @@ static int jet2_net(const pinn_desc* desc, Net* n, bool* mfma) {
   int rc = make_net(desc, n); if (rc) return rc;
   if (n->k < 1) { set_error("jet2 needs k >= 1 differentiated inputs (k = %d)", n->k); return PINN_ERR_INVALID; }
   if (n->prec != PINN_PREC_F32) { set_error("jet2 is implemented in fp32 only (precision bf16 refused)"); return PINN_ERR_UNSUPPORTED; }
-  const int asked = (desc->engine == PINN_ENGINE_FUSED_TILE || desc->engine == PINN_ENGINE_FUSED_COOP ||
-                     desc->engine == PINN_ENGINE_FUSED_BATCH) ? PINN_ENGINE_FUSED : desc->engine;
+  const int asked = asked_engine(desc);
   if (asked == PINN_ENGINE_WIDE) { set_error("jet2 does not run on the wide engine: use engine AUTO, FUSED or GENERIC"); return PINN_ERR_UNSUPPORTED; }
   const bool ok = jet2_mfma_supports(*n);
   if (asked == PINN_ENGINE_FUSED && !ok) {

@@ -5,7 +5,7 @@
 namespace pinn {
 
 constexpr int CNTW_ = CHAIN_NTW;
-constexpr size_t CHAIN_RING_LDS = (size_t)CHAIN_RING * (CNTW_ / 2) * (PINN_CHAIN_BWD_LO ? 2 : 1) * 1024;
+constexpr size_t CHAIN_RING_LDS = (size_t)CHAIN_RING * (CNTW_ / 2) * 2 * 1024;
 constexpr size_t CHAIN_WG_LDS = (size_t)WG_UNITS * 4 * (CNTW_ / 2) * 1024;
 
 template <class K>

@@ -1,41 +1,3 @@
-// pinn_fused_w16.hip — instantiations of the fused MFMA chain kernel for padded hidden width 16
-#include <type_traits>
-#include "fused_kernel.h"
-
-namespace pinn {
-
-template <int K1, bool GRAD, bool LDSACC, int ACT>
-static int launch_one_act(const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  auto kern = k_fused<16, K1, GRAD, LDSACC, ACT>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(FUSED_THREADS), lds, s, P);
-  return check_launch("fused kernel (WP=16)");
-}
-
-template <int K1, bool GRAD, bool LDSACC>
-static int launch_one(const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  return P.act == PINN_ACT_TANH ? launch_one_act<K1, GRAD, LDSACC, PINN_ACT_TANH>(P, grid, lds, s)
-                                : launch_one_act<K1, GRAD, LDSACC, PINN_ACT_LEAKY_RELU>(P, grid, lds, s);
-}
-
-template <>
-int launch_fused<16>(int K1, bool grad, const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  if (!grad) {
-    switch (K1) {
-      case 1: return launch_one<1, false, false>(P, grid, lds, s);
-      case 2: return launch_one<2, false, false>(P, grid, lds, s);
-      case 3: return launch_one<3, false, false>(P, grid, lds, s);
-      case 4: return launch_one<4, false, false>(P, grid, lds, s);
-    }
-  } else {
-    switch (K1) {
-      case 1: return P.acc_lds ? launch_one<1, true, true>(P, grid, lds, s) : launch_one<1, true, false>(P, grid, lds, s);
-      case 3: return P.acc_lds ? launch_one<3, true, true>(P, grid, lds, s) : launch_one<3, true, false>(P, grid, lds, s);
-      case 4: return P.acc_lds ? launch_one<4, true, true>(P, grid, lds, s) : launch_one<4, true, false>(P, grid, lds, s);
-    }
-  }
-  set_error("fused engine: no kernel for K1=%d grad=%d", K1, (int)grad);
-  return PINN_ERR_UNSUPPORTED;
-}
-
-}  // namespace pinn
+// pinn_fused_w16.hip — fused tile kernel instances, padded hidden width 16 (see pinn_fused_launch.inc)
+#define FUSED_WP 16
+#include "pinn_fused_launch.inc"

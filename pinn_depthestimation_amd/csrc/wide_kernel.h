@@ -21,18 +21,15 @@
 namespace pinn {
 
 // weight-gradient operand pads: fp32 mode uses fused_kernel.h's feature-major layout (one conflict-free ds_read_b128 per
-// block, PINN_FUSED_TR2); bf16 mode keeps the first layout (its operands are packed pairwise from consecutive points)
-#ifndef PINN_WIDE_TR2
-#define PINN_WIDE_TR2 PINN_FUSED_TR2
-#endif
+// block); bf16 mode keeps the first layout (its operands are packed pairwise from consecutive points)
 template <bool BF16>
 __device__ __forceinline__ void wtr_write(float* __restrict__ tb, f4 v, int p, int q) {
-  if constexpr (!BF16 && PINN_WIDE_TR2) transpose_write2(tb, v, p, q);
+  if constexpr (!BF16) transpose_write2(tb, v, p, q);
   else transpose_write(tb, v, p, q);
 }
 template <bool BF16>
 __device__ __forceinline__ f4 wtr_read(const float* __restrict__ tb, int p, int q) {
-  if constexpr (!BF16 && PINN_WIDE_TR2) return transpose_read2(tb, p, q);
+  if constexpr (!BF16) return transpose_read2(tb, p, q);
   else return transpose_read<BF16>(tb, p, q);
 }
 
@@ -40,9 +37,6 @@ __device__ __forceinline__ f4 wtr_read(const float* __restrict__ tb, int p, int 
 constexpr int WIDE_WAVES = 4;
 constexpr int WIDE_THREADS = WIDE_WAVES * 64;
 constexpr int WIDE_MAX_PADS = 20;   // 4 zbar tiles + 16 input tiles of one quantity
-#ifndef PINN_WIDE_SHARE_A
-#define PINN_WIDE_SHARE_A 1
-#endif
 
 struct WideLayer {
   const float* W;        // this layer's padded weights, row-major [16*NTO][16*NTI] (fwd) or W^T (bwd)
@@ -356,7 +350,6 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) void k_wide_wgrad(const FusedParam
     for (int NT = 0; NT < NTN; ++NT) dw[MT][NT] = f4{0.f, 0.f, 0.f, 0.f};
   }
   const int gw = blockIdx.x * GPW + wave / RB, nw = gridDim.x * GPW;
-#if PINN_WIDE_SHARE_A
   // W = 256 hidden layers (four row blocks = the four waves, all on the same tile): the 16 input tiles
   // every wave needs are loaded and transposed ONCE per workgroup — each wave handles four of them
   // into a shared, double-buffered set of pads, one barrier per (tile, quantity) — instead of once
@@ -422,9 +415,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) void k_wide_wgrad(const FusedParam
         buf ^= 1;
       }
     }
-  } else
-#endif
-  {
+  } else {
   // raw (acc-layout) tiles of ONE quantity, fetched one step ahead of their use: with a single wave
   // per SIMD the HBM/L2 latency of these loads is otherwise fully exposed before every transpose.
   f4 rz[MTB], ra[NTN];
