@@ -142,9 +142,8 @@ const char* pinn_last_error(void);
 /* P = sum_l (in_l*out_l + out_l), layers = [d_in] + [width]*n_hidden + [d_out] (train.py:56) */
 int32_t pinn_param_count(const pinn_desc* desc, int64_t* count);
 
-/* bytes of workspace a call on N points needs with the engine desc->engine selects.
- * pinn_jet_backward always runs on the generic engine: query with
- * engine = PINN_ENGINE_GENERIC for it. */
+/* bytes of workspace a call on N points needs with the engine desc->engine selects: enough for every call on
+ * that descriptor, pinn_jet_backward included (which picks its engine by the rules stated at its declaration). */
 int32_t pinn_query_workspace(const pinn_desc* desc, int64_t N, int64_t* bytes);
 
 int32_t pinn_forward(const pinn_desc* desc, const float* params, const float* X, int64_t N,
@@ -153,7 +152,16 @@ int32_t pinn_forward(const pinn_desc* desc, const float* params, const float* X,
 int32_t pinn_forward_jet(const pinn_desc* desc, const float* params, const float* X, int64_t N,
                          float* Y, float* dY, void* ws, int64_t ws_bytes, void* stream);
 
-/* grad_flat (P,) += d/dtheta [ sum(gY*Y) + sum(gdY*dY) ];  gdY may be NULL (treated as 0) */
+/* grad_flat (P,) += d/dtheta [ sum(gY*Y) + sum(gdY*dY) ];  gY or gdY may be NULL (treated as 0).  gdY is (k, N, d_out)
+ * in the order of desc->dir_col, as pinn_forward_jet writes dY.
+ * Engines.  GENERIC: the layer-wise kernels, any shape.  FUSED (every sub-value: this call has one MFMA kernel, the tile
+ * kernel with the caller's adjoints in place of a residual): fp32, width <= 64, d_in and d_out <= 16, tanh or LeakyReLU,
+ * k in {0, 2, 3} or gdY == NULL, dropout_p == 0; anything else is refused with PINN_ERR_UNSUPPORTED and the reason in
+ * pinn_last_error().  WIDE: refused.  AUTO: the MFMA path where FUSED would be served, otherwise GENERIC.
+ * Reproducibility.  GENERIC is bit-reproducible from run to run.  The MFMA path launches one workgroup per 16-point
+ * tile, up to W workgroups (W = 1 to 3 per compute unit, by shape); while N <= 16 * W every gradient copy is
+ * added to by a single wave in program order and the copies are summed in a fixed order: bit-reproducible.  Above that
+ * size several waves share a copy and two runs differ in the last bits, as for every other fused gradient call. */
 int32_t pinn_jet_backward(const pinn_desc* desc, const float* params, const float* X, int64_t N,
                           const float* gY, const float* gdY, float* grad_flat,
                           void* ws, int64_t ws_bytes, void* stream);

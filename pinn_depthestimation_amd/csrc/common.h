@@ -106,6 +106,10 @@ int fused_forward(const Net& n, const float* params, const float* X, int64_t N, 
                   void* ws, int64_t ws_bytes, hipStream_t s);
 int fused_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N,
                void* ws, int64_t ws_bytes, hipStream_t s);
+// pinn_jet_backward on the tile kernel (fused_kernel.h, EPI_ADJ): grad += d/dtheta [sum(gY * Y) + sum(gdY * dY)]
+bool fused_jet_backward_supports(const Net& n);
+int fused_jet_backward(const Net& n, const float* params, const float* X, int64_t N, const float* gY,
+                       const float* gdY, float* grad, void* ws, int64_t ws_bytes, hipStream_t s);
 
 // wide MFMA engine, 64 < W <= 256 (pinn_wide.hip)
 bool wide_supports(const Net& n);

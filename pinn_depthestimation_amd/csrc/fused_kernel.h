@@ -72,6 +72,8 @@ struct FusedParams {
   int io1;                   // k_fused<..., IO1 = true>: inputs / outputs in k-step-major order (see k_fused)
   uint32_t drop_seed, drop_thresh;   // k_fused<..., DROP = true>: nn.Dropout in training mode (common.h: dropout_bits)
   float drop_scale, drop_keep;       // 1 / (1 - p), 1 - p
+  const float* gY;                   // k_fused<..., EPI_ADJ>: the caller's output adjoints, gY (N, d_out) and gdY (K1 - 1, N, d_out)
+  const float* gdY;                  // in the engine's direction order (row c - 1 belongs to dir_col[c - 1]); either may be null
 };
 
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
@@ -581,13 +583,31 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 
 // Everything that happens on the output tile of one 16-point tile: optional Y/dY stores, PDE
 // residual and/or fidelity MSE (train.py:131-157), loss partial sums, output adjoint G.
-constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3;
+// EPI_ADJ ("external adjoint", pinn_jet_backward): no residual, no MSE, no stores, no loss sums — the output adjoint
+// comes from the caller (load_adjoint below) and loss_epilogue is not called at all.
+constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4;
+
+// The mirror of the generic epilogue's Y / dY store: lane (p, q), register r of G[c][0] is output o = 4q + r of point pt;
+// G[0] <- gY, G[c] <- gdY row c - 1.  Zero for o >= d_out, for the invalid points of the last tile and for a null array.
+template <int K1>
+__device__ __forceinline__ void load_adjoint(const FusedParams& P, f4 (&G)[K1][1], int64_t pt, bool valid, int q) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int o = 4 * q + r;
+    const bool ok = valid && o < P.d_out;
+    G[0][0][r] = (ok && P.gY != nullptr) ? P.gY[pt * P.d_out + o] : 0.f;
+#pragma unroll
+    for (int c = 1; c < K1; ++c)
+      G[c][0][r] = (ok && P.gdY != nullptr) ? P.gdY[((int64_t)(c - 1) * P.N + pt) * P.d_out + o] : 0.f;
+  }
+}
 
 template <int K1, bool GRAD, bool SPLIT, int EPI = EPI_GENERIC>
 __device__ __forceinline__ void loss_epilogue_impl(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
                                               float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
                                               const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
                                               int64_t ptc, bool valid, int p, int q, bool primary = true) {
+  static_assert(EPI != EPI_ADJ, "EPI_ADJ has no epilogue: k_fused calls load_adjoint instead");
   // EPI != 0: an epilogue specialised to ONE residual family, residual loss only, no output stores.
   // The generic epilogue keeps every family, the fidelity columns and the Y/dY stores behind runtime
   // switches; at width 64 that costs 146 spilled SGPRs (372 v_readlane per tile) against 4 with the
@@ -700,6 +720,7 @@ __device__ __forceinline__ void loss_epilogue(const FusedParams& P, const f4 (&o
 template <int WP, int K1, bool GRAD, bool LDSACC, int ACT, int EPI = EPI_GENERIC, int KRO = 0, bool DROP = false>
 __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_WAVES / 4) void k_fused(const FusedParams P) {
   static_assert(!DROP || (ACT == PINN_ACT_TANH && KRO == 0), "dropout instances: tanh, natural unit order");
+  static_assert(EPI != EPI_ADJ || (GRAD && KRO == 0 && !DROP), "external-adjoint instances: gradient pass, natural unit order, no dropout");
   constexpr bool IO1 = KRO > 0;
   constexpr int KRI = IO1 ? 1 : 4;          // k-steps of the first layer's contraction (d_in <= 4 when IO1)
   constexpr int KRL = IO1 ? KRO : 4;        // k-steps of the output layer's reverse contraction
@@ -728,7 +749,12 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
 
   ScatterMap<K1> sm, sm_mse;
   build_scatter_maps<K1>(P, q, sm, sm_mse);
-  const int gw = blockIdx.x * FUSED_WAVES + wave, nw = gridDim.x * FUSED_WAVES;
+  // EPI_ADJ numbers the waves WORKGROUP-MAJOR: launched with one workgroup per tile (pinn_fused.hip), only wave 0 of a
+  // workgroup has work while n_tiles <= gridDim.x, its adds into the workgroup's gradient copy happen in program order
+  // and the result is bit-reproducible from run to run (include/pinn_hip.h, pinn_jet_backward).  Either numbering is a
+  // bijection onto [0, nw): the spill slots stay private.
+  const int nw = gridDim.x * FUSED_WAVES;
+  const int gw = EPI == EPI_ADJ ? wave * (int)gridDim.x + (int)blockIdx.x : (int)blockIdx.x * FUSED_WAVES + wave;
   // restrict-qualified views: weights / biases / inputs are read-only for the whole launch and the
   // spill slot is private to this wave, so loads may be scheduled across the spill stores
   float* __restrict__ scr = P.scratch + (int64_t)gw * P.scratch_per_wave;
@@ -802,8 +828,15 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
       activate_to<ACT, NTH, K1, DROP>(nx, bias, a, &dl, l, q);
       PINN_STAMP(1);
     }
+    f4 G[K1][1];
     f4 out[K1][1];
-    {
+    if constexpr (EPI == EPI_ADJ) {
+      // the output adjoint does not depend on the outputs: no output GEMM; the caller's adjoints are requested here,
+      // behind the forward chain (held across it they would spill at width 64) and in front of the two weight loads
+      // below, and first used by the output layer's weight gradient
+      load_adjoint<K1>(P, G, pt, valid, q);
+      load_wblk<NTH>(WTp_ + w_off_p<WP>(L > 1 ? L - 1 : 0), 0, ws, p, q);
+    } else {
       f4 bias_o[1];
       load_bias<1>(Bp_ + b_off_p<WP>(L), bias_o, q);
       zero_tiles<1, K1>(out);
@@ -817,8 +850,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
     if constexpr (GRAD) load_w<1, NTH>(WTp_ + w_off_p<WP>(L), wtl, p, q);
 
     // ---- outputs / loss -----------------------------------------------------------------------
-    f4 G[K1][1];
-    loss_epilogue<K1, GRAD, (WP < 64), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+    if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
 
     PINN_STAMP(2);
     // ---- reverse sweep ------------------------------------------------------------------------
@@ -890,5 +922,8 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
 // launcher: pinn_fused_launch.inc, one translation unit per WP (pinn_fused_wXX.hip)
 template <int WP>
 int launch_fused(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+// external-adjoint instances: pinn_fused_adj.inc, one translation unit per WP (pinn_fused_adj_wXX.hip)
+template <int WP>
+int launch_fused_adj(int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 
 }  // namespace pinn

@@ -137,6 +137,32 @@ static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc
   return PINN_ENGINE_GENERIC;
 }
 
+// pinn_jet_backward: GENERIC or FUSED (the tile kernel's external-adjoint instances, whatever fused kernel desc.engine
+// names).  AUTO takes the MFMA path where it exists and the generic engine for everything else (k = 1 with gdY, dropout,
+// width > 64, d_in / d_out > 16, bf16); an explicit FUSED request the path does not serve is refused, WIDE always.
+static int pick_jet_backward_engine(const pinn_desc* d, const Net& n, int* rc) {
+  *rc = PINN_OK;
+  const int asked = asked_engine(d);
+  if (asked == PINN_ENGINE_GENERIC) return PINN_ENGINE_GENERIC;
+  if (asked == PINN_ENGINE_WIDE) {
+    set_error("pinn_jet_backward is not implemented on the wide engine: use engine AUTO, GENERIC or FUSED");
+    *rc = PINN_ERR_UNSUPPORTED;
+    return PINN_ENGINE_GENERIC;
+  }
+  const bool ok = fused_jet_backward_supports(n);
+  if (asked == PINN_ENGINE_FUSED && !ok) {
+    const char* why = n.drop_p > 0.f ? "dropout_p > 0 has no external-adjoint kernel"
+                    : n.prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only"
+                    : n.K1 == 2 ? "k = 1 (one differentiated input) with gdY has no gradient kernel"
+                    : n.W > 64 ? "hidden width above 64"
+                    : (n.d_in > 16 || n.d_out > 16) ? "d_in or d_out above 16" : "network too deep for the per-layer locks";
+    set_error("pinn_jet_backward on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, hidden layers %d); "
+              "engine AUTO or GENERIC runs this request on the generic engine", why, n.W, n.d_in, n.d_out, n.k, n.L);
+    *rc = PINN_ERR_UNSUPPORTED;
+  }
+  return ok ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
+}
+
 // runs rq on the engine pick_engine() chooses for it
 static int run_loss(const pinn_desc* desc, const Net& n, bool want_grad, const LossReq& rq, const float* params,
                     const float* X, int64_t N, void* ws, int64_t ws_bytes, void* stream) {
@@ -254,6 +280,15 @@ int32_t pinn_query_workspace(const pinn_desc* desc, int64_t N, int64_t* bytes) {
     if (rc1 && rc2) { *err = rc1; return -1; }      // neither kind of call is served on the engine asked for
     int64_t b = rc1 ? -1 : ws_of(e);
     if (rc2 == PINN_OK && (rc1 || eg != e)) { const int64_t bg = ws_of(eg); if (bg > b) b = bg; }
+    if (b >= 0) {   // pinn_jet_backward picks its engine by its own rule (a request refused there fails by itself)
+      int rcj = PINN_OK;
+      const int ej = pick_jet_backward_engine(desc, nn, &rcj);
+      if (rcj == PINN_OK) {
+        Net t = nn; t.fused_kernel = FUSED_KERNEL_TILE;
+        const int64_t bj = ej == PINN_ENGINE_FUSED ? fused_workspace_bytes(t, N) : generic_workspace_bytes(nn, N);
+        if (bj > b) b = bj;
+      }
+    }
     return b;
   };
   int64_t b = need(n, &rc);
@@ -298,8 +333,9 @@ int32_t pinn_jet_backward(const pinn_desc* desc, const float* params, const floa
   if (!params || (!X && N > 0) || N < 0 || !grad_flat || (!gY && !gdY && N > 0)) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
   if (N == 0) return PINN_OK;
   if (!gdY) { n.k = 0; n.K1 = 1; }
-  // generic consumer of the jet: the layer-wise engine handles every shape
-  return generic_jet_backward(n, params, X, N, gY, gdY, grad_flat, ws, ws_bytes, (hipStream_t)stream);
+  const int e = pick_jet_backward_engine(desc, n, &rc); if (rc) return rc;
+  return e == PINN_ENGINE_FUSED ? fused_jet_backward(n, params, X, N, gY, gdY, grad_flat, ws, ws_bytes, (hipStream_t)stream)
+                                : generic_jet_backward(n, params, X, N, gY, gdY, grad_flat, ws, ws_bytes, (hipStream_t)stream);
 }
 
 static int32_t residual_impl(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,

@@ -85,6 +85,14 @@ int grid_for(int64_t n_tiles, bool one_per_cu, int per_cu = 2) {
   if (want < 1) want = 1;
   return (int)(want < cap ? want : cap);
 }
+// External-adjoint pass (pinn_jet_backward): one workgroup per TILE up to the same cap.  With the kernel's workgroup-major
+// wave numbering (fused_kernel.h, EPI_ADJ) a single wave per workgroup has work while n_tiles <= grid, so every gradient
+// copy is added to in program order and the call is bit-reproducible for N <= 16 x grid.
+int adj_grid_for(int64_t n_tiles, bool one_per_cu, int per_cu = 2) {
+  const int64_t cap = (int64_t)cu_count() * (one_per_cu ? 1 : per_cu);
+  const int64_t want = n_tiles < 1 ? 1 : n_tiles;
+  return (int)(want < cap ? want : cap);
+}
 
 struct WsLayout {
   int64_t wp, wtp, bp, scratch, wg_sums, wg_grads, total;
@@ -100,6 +108,10 @@ WsLayout ws_layout(const Net& n, const Geo& g, int64_t N) {
     const int64_t cap = 2 * (int64_t)cu_count();
     const int64_t coop_grid = n_tiles < cap ? n_tiles : cap;
     if (coop_grid > w.max_grid) w.max_grid = (int)coop_grid;
+  }
+  {   // ... and so does the external-adjoint pass, up to the tile kernel's own cap
+    const int adj_grid = adj_grid_for(n_tiles, false, g.WP == 16 ? FUSED_W16_WAVES : 2);
+    if (adj_grid > w.max_grid) w.max_grid = adj_grid;
   }
   int64_t off = 0;
   w.wp = off; off += al((int64_t)g.PW * 4);
@@ -320,8 +332,14 @@ __global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int c
   }
 }
 
+// what pinn_jet_backward hands the tile kernel instead of a loss: the caller's output adjoints, and where the gradient goes
+struct AdjReq {
+  const float* gY; const float* gdY;   // either may be null
+  float* grad;                         // device flat grad (+=)
+};
+
 int run(const Net& n, bool grad, const LossReq* rq, const float* params, const float* X, int64_t N, float* Y,
-        float* dY, void* ws, int64_t ws_bytes, hipStream_t s) {
+        float* dY, void* ws, int64_t ws_bytes, hipStream_t s, const AdjReq* adj = nullptr) {
   const Geo g = geo_of(n);
   const WsLayout w = ws_layout(n, g, N);
   if (!ws || ws_bytes < w.total) {
@@ -362,8 +380,10 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
       for (int j = 0; j < PINN_MAX_ROLES; ++j) P.mse_col[j] = j < rq->n_cols ? rq->out_col[j] : -1;
     }
   }
-  const bool batch = use_batch(n, g, grad, N);
-  const bool coop = !batch && use_coop(n, g, grad, N);
+  if (adj) { P.gY = adj->gY; P.gdY = adj->gdY; }
+  // (the external-adjoint epilogue exists in the tile kernel only: every kernel choice of desc.engine lands there)
+  const bool batch = !adj && use_batch(n, g, grad, N);
+  const bool coop = !adj && !batch && use_coop(n, g, grad, N);
   if (coop) {
     P.acc_lds = grad ? 1 : 0;
     P.lds_acc_floats = grad ? g.PP : 0;
@@ -380,6 +400,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   // networks' kernels fit 2 waves per SIMD, which hides their per-layer latencies
   const bool one_per_cu = grad && P.acc_lds && !(g.WP <= 32 && 2 * (int64_t)lds <= LDS_LIMIT);
   int grid = grid_for(P.n_tiles, one_per_cu, g.WP == 16 && FUSED_W16_WAVES * (int64_t)lds <= LDS_LIMIT ? FUSED_W16_WAVES : 2);
+  if (adj) grid = adj_grid_for(P.n_tiles, one_per_cu, g.WP == 16 && FUSED_W16_WAVES * (int64_t)lds <= LDS_LIMIT ? FUSED_W16_WAVES : 2);
   if (coop) {   // one workgroup per tile, at most one per CU (gradient kernels fill the LDS)
     const int64_t cap = (int64_t)cu_count() * (grad ? 1 : 2);
     grid = (int)(P.n_tiles < cap ? (P.n_tiles < 1 ? 1 : P.n_tiles) : cap);
@@ -419,6 +440,19 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     }
   }
   int rc;
+  if (adj) {
+    if (n.drop_p > 0.f) { set_error("fused engine: no dropout instance of the external-adjoint kernel"); return PINN_ERR_UNSUPPORTED; }
+    switch (g.WP) {
+      case 16: rc = launch_fused_adj<16>(n.K1, P, grid, lds, s); break;
+      case 32: rc = launch_fused_adj<32>(n.K1, P, grid, lds, s); break;
+      default: rc = launch_fused_adj<64>(n.K1, P, grid, lds, s); break;
+    }
+    if (rc) return rc;
+    const int64_t np = n.n_params();
+    hipLaunchKernelGGL(k_reduce_grads, dim3((unsigned)((np + 63) / 64)), dim3(256), 0, s, n, g.WP,
+                       (const float*)P.wg_grads, n_copies, g.PP, g.PW, adj->grad, 0);
+    return check_launch("fused reductions");
+  }
   if (n.drop_p > 0.f) {     // training-mode dropout: its own instances of the tile kernel (pinn_fused_w64_drop.hip)
     P.drop_seed = n.drop_seed; P.drop_thresh = n.drop_thresh; P.drop_scale = 1.f / (1.f - n.drop_p); P.drop_keep = 1.f - n.drop_p;
     if (!(grad && g.WP == 64 && P.acc_lds && n.act == PINN_ACT_TANH)) { set_error("fused engine: no dropout kernel for this request"); return PINN_ERR_UNSUPPORTED; }
@@ -493,6 +527,13 @@ bool fused_supports(const Net& n, bool want_grad) {
   return n.W <= 64 && n.d_in <= 16 && n.d_out <= 16 && n.L >= 1 && n.K1 >= 1 && n.K1 <= 4;
 }
 
+// pinn_jet_backward on the tile kernel's external-adjoint instances (pinn_fused_adj_wXX.hip): every gradient shape of
+// the tile kernel without dropout.  desc.engine's kernel choice does not matter here (run() always takes the tile kernel).
+bool fused_jet_backward_supports(const Net& n) {
+  Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
+  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && fused_supports(t, true);
+}
+
 // The folded update needs the whole request in ONE pass (the split request on the width-64 tile kernel runs as two).
 bool fused_supports_adam(const Net& n, const LossReq& rq, int64_t N) {
   if (!rq.grad || !fused_supports(n, true)) return false;
@@ -511,6 +552,13 @@ int64_t fused_workspace_bytes(const Net& n, int64_t N) {
 int fused_forward(const Net& n, const float* params, const float* X, int64_t N, float* Y, float* dY, void* ws,
                   int64_t ws_bytes, hipStream_t s) {
   return run(n, false, nullptr, params, X, N, Y, dY, ws, ws_bytes, s);
+}
+
+int fused_jet_backward(const Net& n, const float* params, const float* X, int64_t N, const float* gY, const float* gdY,
+                       float* grad, void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (!fused_jet_backward_supports(n)) { set_error("fused engine: no external-adjoint kernel for this request (k = %d)", n.k); return PINN_ERR_UNSUPPORTED; }
+  const AdjReq adj{gY, gdY, grad};
+  return run(n, true, nullptr, params, X, N, nullptr, nullptr, ws, ws_bytes, s, &adj);
 }
 
 int fused_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,

@@ -251,14 +251,17 @@ class Engine:
         return Y, dY
 
     def jet_backward(self, params, X, gY: Optional[torch.Tensor], gdY: Optional[torch.Tensor],
-                     grad: torch.Tensor) -> torch.Tensor:
+                     grad: torch.Tensor, engine=None) -> torch.Tensor:
+        """grad += d/d params [sum(gY*Y) + sum(gdY*dY)] (pinn_jet_backward); either adjoint may be None.  engine=None
+        is the descriptor's engine: AUTO runs the MFMA tile kernel where it serves the request (width <= 64, no dropout,
+        k != 1 when gdY is given) and the generic engine otherwise; FUSED is refused where AUTO would fall back."""
         N = X.shape[0]
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
         self._chk(grad, "grad", (self.n_params,))
         if gY is not None: self._chk(gY, "gY", (N, self.desc.d_out))
         if gdY is not None: self._chk(gdY, "gdY", (self.desc.k, N, self.desc.d_out))
-        ws = self.workspace(N, ENGINE_GENERIC)
-        self._run("pinn_jet_backward", self.lib.pinn_jet_backward, C.byref(self._d(ENGINE_GENERIC)), _ptr(params), _ptr(X), N, _ptr(gY),
+        ws = self.workspace(N, engine)
+        self._run("pinn_jet_backward", self.lib.pinn_jet_backward, C.byref(self._d(engine)), _ptr(params), _ptr(X), N, _ptr(gY),
                                          _ptr(gdY), _ptr(grad), _ptr(ws), ws.numel())
         return grad
 

@@ -78,7 +78,8 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False):
 
     corrected=True (an extension, not reference behaviour) evaluates what the line evidently
     meant, E = 1/8 * rho * g * Hrms**2, with Sxx = E (2kh/sinh(2kh) + 1/2), Syy = E kh/sinh(2kh)
-    (physics.py:107-109); it runs on the generic compute_gradient path (HIP jet + autograd)."""
+    (physics.py:107-109); it is written with compute_gradient like any user residual: the forward jet and the
+    parameter gradient (pinn_jet_backward) both run on the MFMA tile kernel, torch autograd evaluates the formula between."""
     if not corrected:
         fused = fused_residual("physics_equation", (x, y), (h, U, V, eta_mean, Hrms, k))
         if fused is not None:
