@@ -292,7 +292,17 @@ int32_t pinn_adam_step(float* params, const float* grad, float* m, float* v, int
  * physical row indices); logical pair i (0 = oldest) is physical row (head + i) % m; k pairs in use.
  * pinn_lbfgs_push stores (s, y) in row `slot` and refreshes row and column `slot` of M.
  * pinn_lbfgs_direction writes d = -H_k g (H the initial scaling ys/yy); tmp: 4m doubles, coef: 2m
- * floats, q: P floats of scratch.  Unused rows of S, Y must be zero.  m <= 256. */
+ * floats, q: P floats of scratch.  m <= 256.
+ * What the caller must initialise:
+ *  - S and Y must be zeroed once, before the first push.  Both calls read ALL m rows of S and Y, also the
+ *    rows no pair has been stored in yet, and push writes row `slot` only.  Zero is the contract: finite
+ *    rows would give the same direction today (an unused row's coefficient is exactly 0), but nothing
+ *    tests or promises that.
+ *  - tmp, coef and q may hold anything on entry: each is written before it is read.
+ *  - Of M, pinn_lbfgs_direction reads only the rows and columns of the k pairs in use, and a push has
+ *    written each of them.  (Push also writes the entries of row and column `slot` that belong to unused
+ *    rows: they are s . 0 = 0.)
+ * tests/test_lbfgs_gpu.py fills the scratch and the unused part of M with 1e30 and gets the same bits. */
 int32_t pinn_lbfgs_push(float* S, float* Y, double* M, int32_t m, int64_t P, int32_t slot,
                         const float* s, const float* y, void* stream);
 int32_t pinn_lbfgs_direction(const float* S, const float* Y, const double* M, int32_t m, int64_t P,

@@ -286,6 +286,26 @@ def lbfgs_trajectory(params, loss_fn, max_iter: int, lr=1.0, max_eval=None, hist
     return losses, [p.detach() for p in params]
 
 
+def lbfgs_two_loop(S, Y, g, H):
+    """The textbook L-BFGS two-loop recursion (Nocedal & Wright, Algorithm 7.4; the loops of
+    torch.optim.LBFGS.step) in float64.  S, Y: (k, P) steps and gradient differences, oldest pair first;
+    g: (P,) gradient; H: the initial scaling y.s / y.y.  Returns d = -(inverse-Hessian approximation) g."""
+    S = torch.as_tensor(S).detach().to(torch.float64)
+    Y = torch.as_tensor(Y).detach().to(torch.float64)
+    k = S.shape[0]
+    q = torch.as_tensor(g).detach().to(torch.float64).neg()
+    ro = [1.0 / torch.dot(Y[i], S[i]) for i in range(k)]
+    al = [None] * k
+    for i in range(k - 1, -1, -1):
+        al[i] = ro[i] * torch.dot(S[i], q)
+        q = q - al[i] * Y[i]
+    r = q * float(H)
+    for i in range(k):
+        be = ro[i] * torch.dot(Y[i], r)
+        r = r + (al[i] - be) * S[i]
+    return r
+
+
 def scipy_lbfgsb_trajectory(params, loss_fn, options):
     """The stale l_bfgs_b_optimizer wrapper's contract (bytecode only, never executed):
     scipy.optimize.minimize(fun, x0, jac=True, method='L-BFGS-B', options=...) over the flattened weights,

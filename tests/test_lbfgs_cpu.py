@@ -2,7 +2,9 @@
 import pytest
 import torch
 
-from pinn_depthestimation_amd.lbfgs import FlatLBFGS
+from oracle import pinn_oracle as O
+from pinn_depthestimation_amd.lbfgs import FlatLBFGS, _History
+from tests.lbfgs_util import REPLAY_MIN_PAIRS, REPLAY_P, rel_l2, torch_lbfgs_replay
 
 
 def problem(dtype, seed=0, n=64, d=6, h=8):
@@ -99,3 +101,36 @@ def test_line_search_budget_is_torchs(max_iter, max_eval):
     assert len(a[1]) == len(b[1])
     assert torch.allclose(torch.tensor(a[1]), torch.tensor(b[1]), rtol=1e-9, atol=1e-14)
     assert (a[0] - b[0]).abs().max() < 1e-9
+
+
+def test_two_loop_oracle_is_torchs_direction_and_history_matches_past_the_roll():
+    """oracle.lbfgs_two_loop (textbook recursion, fp64) on torch.optim.LBFGS's own stored pairs gives torch's own
+    direction, iteration by iteration, through the filling of the 100-pair history and 69 roll-outs after it; and
+    lbfgs._History (the triangular reformulation, float64) fed the same pairs gives the same direction."""
+    hist = _History(100, torch.zeros(REPLAY_P, dtype=torch.float64))
+    worst_oracle = worst_hist = 0.0
+    checked = rolled = 0
+    for r in torch_lbfgs_replay():
+        if r["new"] is not None:
+            hist.push(*r["new"])
+        if not r["S"]:
+            continue
+        rolled += r["stored"] > 100
+        d = O.lbfgs_two_loop(torch.stack(r["S"]), torch.stack(r["Y"]), r["g"], r["H"])
+        e_oracle, e_hist = rel_l2(d, r["d"]), rel_l2(hist.direction(r["g"], r["H"]), r["d"])
+        worst_oracle, worst_hist = max(worst_oracle, e_oracle), max(worst_hist, e_hist)
+        checked += 1
+        assert e_oracle < 1e-12, (r["it"], e_oracle)
+        assert e_hist < 1e-10, (r["it"], e_hist)
+    print(f"replay: {r['stored']} pairs stored, {checked} directions checked, {rolled} after the roll; "
+          f"two-loop vs torch {worst_oracle:.2e}, _History fp64 vs torch {worst_hist:.2e}")
+    assert r["stored"] >= REPLAY_MIN_PAIRS and len(r["S"]) == 100 and rolled >= 30, (r["stored"], len(r["S"]), rolled)
+
+
+def test_two_loop_oracle_on_a_hand_worked_case():
+    """One pair, P = 2, worked by hand: s = (1, 0), y = (2, 1), g = (1, 1), H = 0.4.
+    ro = 1/2; q = -g; al = ro s.q = -1/2; q = -g + y/2 = (0, -1/2); r = H q = (0, -0.2);
+    be = ro y.r = -0.1; d = r + (al - be) s = (-0.4, -0.2)."""
+    d = O.lbfgs_two_loop(torch.tensor([[1.0, 0.0]]), torch.tensor([[2.0, 1.0]]), torch.tensor([1.0, 1.0]), 0.4)
+    assert d.dtype == torch.float64
+    assert torch.allclose(d, torch.tensor([-0.4, -0.2], dtype=torch.float64), rtol=0, atol=1e-15)
