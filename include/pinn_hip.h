@@ -18,6 +18,8 @@
  *   pinn_residual_loss[_grad] physics.py:18-33,37-47,50-88,91-120 (continuity_only,
  *                           continuity_ftemp, Navier_Stokes, physics_equation)
  *                           fused with loss.backward() (train.py:154,191)
+ *   pinn_residual_fields    the same four residuals' signed per-point fields (physics.py:81-83, 113-115, 20-23, 27-28),
+ *                           before they are squared and averaged: residual maps, adaptive resampling
  *   pinn_mse_loss_grad      train.py:131-141 (weighted fidelity MSE) + backward
  *   pinn_residual_mse_loss_grad  train_newmethod.py:122-159 (both on one forward) + backward
  *   pinn_residual_mse_split_loss_grad  train.py:131-157 (fidelity set + collocation set, one launch)
@@ -50,6 +52,9 @@
 extern "C" {
 #endif
 
+/* Version 4 covers pinn_query_fields_workspace / pinn_residual_fields as well: they were ADDED to it (no existing entry,
+ * struct or constant changed), so a caller built against the earlier version-4 header runs unchanged and the number
+ * stays.  A caller that needs the two entries looks the symbols up. */
 #define PINN_ABI_VERSION 4
 
 #define PINN_MAX_DIRS 3   /* tangent directions (inputs with requires_grad) */
@@ -192,6 +197,29 @@ int32_t pinn_jet2_backward(const pinn_desc* desc, const float* params, const flo
 int32_t pinn_residual_loss(const pinn_desc* desc, const pinn_residual_spec* spec,
                            const float* params, const float* X, int64_t N,
                            float* term_sums, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- per-point residual fields -----------------------------------------------------------------------------------
+ * The residual's signed field values at every point, before squaring: Navier_Stokes (fc, fm_x, fm_y), physics_equation
+ * (fc, fx, fy), continuity_ftemp / continuity_only (fc, da) with da = h - anchor on the points with x < threshold of
+ * continuity_only and 0 everywhere else (always 0 for continuity_ftemp).  desc->k must equal the residual's number of
+ * directions (3 for Navier_Stokes, 2 for the others): PINN_ERR_UNSUPPORTED otherwise.  N >= 1.
+ * Engines.  FUSED (every sub-value: one MFMA kernel, the tile kernel run forward-only with a field-storing epilogue):
+ * fp32, width <= 64, d_in and d_out <= 16, tanh or LeakyReLU, dropout_p == 0; anything else is refused with
+ * PINN_ERR_UNSUPPORTED and the reason in pinn_last_error().  GENERIC, WIDE: the engine's pinn_forward_jet into a staging
+ * area in the workspace, 65536 points at a time, then one point-wise fp32 kernel per chunk (the precision mode belongs to
+ * the jet).  AUTO: the MFMA path where FUSED would be served, else the staged one on the engine AUTO picks for
+ * pinn_forward_jet.  With dropout_p > 0 (staged path only) the mask's point index restarts at every chunk.
+ * The call has a workspace of its own (pinn_query_workspace answers what it always did). */
+#define PINN_NS_FIELDS 3
+#define PINN_PE_FIELDS 3
+#define PINN_CF_FIELDS 2
+#define PINN_CO_FIELDS 2
+int32_t pinn_query_fields_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes);
+/* fields (n_fields, N) row-major, overwritten: fields[f][n] = residual field f at X[n]
+ * (physics.py:81-83, 113-115, 20-23, 27-28); sum_n fields[t][n]^2 == pinn_residual_loss's term_sums[t] */
+int32_t pinn_residual_fields(const pinn_desc* desc, const pinn_residual_spec* spec, const float* params,
+                             const float* X, int64_t N, float* fields,
+                             void* ws, int64_t ws_bytes, void* stream);
 
 /* as above, and grad_flat (P,) += sum_t term_scale[t] * d term_sums[t] / d theta.
  * term_scale is a DEVICE array (n_terms floats) so that a data-dependent

@@ -21,6 +21,7 @@ PREC_F32, PREC_BF16 = 0, 1
 
 RES_NAVIER_STOKES, RES_PHYSICS_EQUATION, RES_CONTINUITY_FTEMP, RES_CONTINUITY_ONLY = 1, 2, 3, 4
 RES_TERMS = {RES_NAVIER_STOKES: 3, RES_PHYSICS_EQUATION: 3, RES_CONTINUITY_FTEMP: 1, RES_CONTINUITY_ONLY: 3}
+RES_FIELDS = {RES_NAVIER_STOKES: 3, RES_PHYSICS_EQUATION: 3, RES_CONTINUITY_FTEMP: 2, RES_CONTINUITY_ONLY: 2}   # pinn_residual_fields' rows
 
 
 class PinnDesc(C.Structure):
@@ -47,7 +48,7 @@ class PinnAdamState(C.Structure):
     ]
 
 
-ERR_UNSUPPORTED = -2
+ERR_INVALID, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -2, -3
 
 
 class PinnError(RuntimeError):
@@ -69,6 +70,9 @@ _SIGNATURES = {
     "pinn_jet2_backward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "pinn_residual_loss": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int64, _P,
                                        _P, C.c_int64, _P]),
+    "pinn_query_fields_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.POINTER(C.c_int64)]),
+    "pinn_residual_fields": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int64, _P,
+                                         _P, C.c_int64, _P]),
     "pinn_residual_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P,
                                             C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "pinn_mse_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, _P, C.c_int64, C.c_int32,

@@ -111,6 +111,15 @@ bool fused_jet_backward_supports(const Net& n);
 int fused_jet_backward(const Net& n, const float* params, const float* X, int64_t N, const float* gY,
                        const float* gdY, float* grad, void* ws, int64_t ws_bytes, hipStream_t s);
 
+// pinn_residual_fields on the tile kernel (fused_kernel.h, EPI_FIELD): fields (NF, N) of the residual in `spec`
+bool fused_fields_supports(const Net& n);
+int64_t fused_fields_workspace_bytes(const Net& n);
+int fused_residual_fields(const Net& n, const pinn_residual_spec& spec, const float* params, const float* X, int64_t N,
+                          float* fields, void* ws, int64_t ws_bytes, hipStream_t s);
+// ... and from a staged jet (pinn_fields.hip): Y (n, d_out), dY (k, n, d_out) of points [n0, n0 + n) -> fields[f * N + n0 + i]
+int fields_from_jet(const Net& net, const pinn_residual_spec& spec, const float* X, const float* Y, const float* dY,
+                    int64_t n, int64_t n0, int64_t N, float* fields, hipStream_t s);
+
 // wide MFMA engine, 64 < W <= 256 (pinn_wide.hip)
 bool wide_supports(const Net& n);
 int64_t wide_workspace_bytes(const Net& n, int64_t N);

@@ -51,7 +51,10 @@ struct FusedParams {
   const float* Bp;    // padded biases
   float* scratch;     // activation spill, scratch_per_wave floats per wave
   int64_t scratch_per_wave;
-  float* Y; float* dY;  // forward outputs (may be null)
+  float* Y; float* dY;  // forward outputs (may be null).  k_fused<..., EPI_FIELD> stores no outputs: there Y is the residual
+                        // fields' array, field-major (NF, N), and dY is null — a member of its own would change the kernel
+                        // argument block of EVERY k_fused instance, and with it the register allocation of the
+                        // register-starved width-64 forward kernels (measured: AGPRs 8 -> 4, spilled SGPRs 36 -> 39)
   int loss_kind;        // bit 0: PDE residual, bit 1: fidelity MSE (both: one pass, train_newmethod.py:122-159)
   int residual_id;
   int out_col[PINN_MAX_ROLES];   // residual: output column of each role
@@ -585,7 +588,9 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 // residual and/or fidelity MSE (train.py:131-157), loss partial sums, output adjoint G.
 // EPI_ADJ ("external adjoint", pinn_jet_backward): no residual, no MSE, no stores, no loss sums — the output adjoint
 // comes from the caller (load_adjoint below) and loss_epilogue is not called at all.
-constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4;
+// EPI_FIELD (pinn_residual_fields): forward only — the residual's signed field values of every point are stored
+// (field_epilogue below) and nothing else happens: no sums, no Y / dY stores, no adjoint, no reverse sweep.
+constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5;
 
 // The mirror of the generic epilogue's Y / dY store: lane (p, q), register r of G[c][0] is output o = 4q + r of point pt;
 // G[0] <- gY, G[c] <- gdY row c - 1.  Zero for o >= d_out, for the invalid points of the last tile and for a null array.
@@ -602,12 +607,50 @@ __device__ __forceinline__ void load_adjoint(const FusedParams& P, f4 (&G)[K1][1
   }
 }
 
+// EPI_FIELD: gather the roles' jets as residual_tile does, evaluate RES::fields and store field f of point pt at
+// fields[f * N + pt] (fields = P.Y, see FusedParams) — field-major, as dY: each field is a contiguous map and a tile's store of one field is 64
+// contiguous bytes (lane group q == 0, one float per valid point).
+template <class RES, int K1>
+__device__ __forceinline__ void field_tile(const FusedParams& P, const f4 (&out)[K1][1], int64_t pt, bool valid,
+                                           bool masked, int p, int q) {
+  constexpr int NR = RES::NR, ND = RES::ND, NF = RES::NF;
+  float v[1 + ND][NR], f[NF];
+#pragma unroll
+  for (int c = 0; c <= ND; ++c) {
+    const f4 tile = (c == 0) ? out[0][0] : pick_q<K1>(out, P.q_of[c - 1]);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) v[c][r] = gather_out(tile, P.out_col[r], p);
+  }
+  if constexpr (std::is_same<RES, ResContinuity>::value)
+    RES::fields(v, f, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
+  else
+    RES::fields(v, f);
+  if (valid && q == 0) {
+#pragma unroll
+    for (int t = 0; t < NF; ++t) P.Y[(int64_t)t * P.N + pt] = f[t];
+  }
+}
+// K1 decides the family (the host refuses any other pairing): 4 = Navier-Stokes; 3 = physics_equation or continuity, told
+// apart by one wave-uniform branch on residual_id.
+template <int K1>
+__device__ __forceinline__ void field_epilogue(const FusedParams& P, const f4 (&out)[K1][1], int64_t pt, int64_t ptc,
+                                               bool valid, int p, int q) {
+  static_assert(K1 == 3 || K1 == 4, "EPI_FIELD: K1 = 1 + the residual's directions");
+  if constexpr (K1 == 4) field_tile<ResNavierStokes, K1>(P, out, pt, valid, false, p, q);
+  else if (P.residual_id == PINN_RES_PHYSICS_EQUATION) field_tile<ResPhysicsEquation, K1>(P, out, pt, valid, false, p, q);
+  else {
+    const bool masked = P.residual_id == PINN_RES_CONTINUITY_ONLY && P.X[ptc * P.d_in + P.xcol] < P.thr;
+    field_tile<ResContinuity, K1>(P, out, pt, valid, masked, p, q);
+  }
+}
+
 template <int K1, bool GRAD, bool SPLIT, int EPI = EPI_GENERIC>
 __device__ __forceinline__ void loss_epilogue_impl(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
                                               float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
                                               const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
                                               int64_t ptc, bool valid, int p, int q, bool primary = true) {
   static_assert(EPI != EPI_ADJ, "EPI_ADJ has no epilogue: k_fused calls load_adjoint instead");
+  static_assert(EPI != EPI_FIELD, "EPI_FIELD has its own epilogue: k_fused calls field_epilogue instead");
   // EPI != 0: an epilogue specialised to ONE residual family, residual loss only, no output stores.
   // The generic epilogue keeps every family, the fidelity columns and the Y/dY stores behind runtime
   // switches; at width 64 that costs 146 spilled SGPRs (372 v_readlane per tile) against 4 with the
@@ -721,6 +764,7 @@ template <int WP, int K1, bool GRAD, bool LDSACC, int ACT, int EPI = EPI_GENERIC
 __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_WAVES / 4) void k_fused(const FusedParams P) {
   static_assert(!DROP || (ACT == PINN_ACT_TANH && KRO == 0), "dropout instances: tanh, natural unit order");
   static_assert(EPI != EPI_ADJ || (GRAD && KRO == 0 && !DROP), "external-adjoint instances: gradient pass, natural unit order, no dropout");
+  static_assert(EPI != EPI_FIELD || (!GRAD && !LDSACC && KRO == 0 && !DROP), "field instances: forward only, natural unit order, no dropout");
   constexpr bool IO1 = KRO > 0;
   constexpr int KRI = IO1 ? 1 : 4;          // k-steps of the first layer's contraction (d_in <= 4 when IO1)
   constexpr int KRL = IO1 ? KRO : 4;        // k-steps of the output layer's reverse contraction
@@ -850,7 +894,8 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
     if constexpr (GRAD) load_w<1, NTH>(WTp_ + w_off_p<WP>(L), wtl, p, q);
 
     // ---- outputs / loss -----------------------------------------------------------------------
-    if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+    if constexpr (EPI == EPI_FIELD) field_epilogue<K1>(P, out, pt, ptc, valid, p, q);
+    else if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
 
     PINN_STAMP(2);
     // ---- reverse sweep ------------------------------------------------------------------------
@@ -898,6 +943,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
   }
 #endif
 
+  if constexpr (EPI == EPI_FIELD) return;   // nothing to reduce: the fields are already where they belong
   // ---- per-workgroup reductions ------------------------------------------------------------------
 #pragma unroll
   for (int j = 0; j < MAX_SUMS; ++j) {
@@ -925,5 +971,8 @@ int launch_fused(int K1, bool grad, const FusedParams& P, int grid, size_t lds_b
 // external-adjoint instances: pinn_fused_adj.inc, one translation unit per WP (pinn_fused_adj_wXX.hip)
 template <int WP>
 int launch_fused_adj(int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+// field instances: pinn_fused_field.inc, one translation unit per WP (pinn_fused_field_wXX.hip)
+template <int WP>
+int launch_fused_field(int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 
 }  // namespace pinn

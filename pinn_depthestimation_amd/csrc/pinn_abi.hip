@@ -498,6 +498,103 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, co
   return PINN_OK;
 }
 
+// ---- per-point residual fields -------------------------------------------------------------------------------------
+// Two paths.  The fused tile kernel's field instances (one launch, nothing staged) where fused_fields_supports(); for
+// every other request the descriptor's own pinn_forward_jet into a staging area, FIELDS_CHUNK points at a time (fixed:
+// the staging stays bounded however large the pool), followed by the point-wise kernel of pinn_fields.hip.
+// AUTO: the first where it applies, else the second.  FUSED (and sub-values): the first or refused, as pinn_jet_backward.
+// GENERIC / WIDE: the second, on that engine.
+static constexpr int64_t FIELDS_CHUNK = 1 << 16;
+static int64_t al256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+static int residual_dirs(int id) { return id == PINN_RES_NAVIER_STOKES ? 3 : 2; }
+static int residual_n_fields(int id) {
+  switch (id) {
+    case PINN_RES_NAVIER_STOKES: return PINN_NS_FIELDS;
+    case PINN_RES_PHYSICS_EQUATION: return PINN_PE_FIELDS;
+    case PINN_RES_CONTINUITY_FTEMP: return PINN_CF_FIELDS;
+    case PINN_RES_CONTINUITY_ONLY: return PINN_CO_FIELDS;
+  }
+  return -1;
+}
+
+struct FieldsPlan {
+  bool fused;                            // the tile kernel's field instances
+  int64_t chunk, y_off, dy_off, in_off, inner_bytes, total;   // staged path: layout of the workspace
+};
+
+// validation shared by the query and the call (no HIP call before it has passed)
+static int fields_plan(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, Net* n, pinn_residual_spec* nspec,
+                       FieldsPlan* pl) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  rc = check_spec(*n, spec, nspec); if (rc) return rc;
+  if (n->k != residual_dirs(nspec->residual_id)) {
+    set_error("pinn_residual_fields: the network carries k = %d tangent directions, residual %d has %d (k must equal the "
+              "residual's number of directions)", n->k, nspec->residual_id, residual_dirs(nspec->residual_id));
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (N < 1) { set_error("pinn_residual_fields: N = %lld, need at least one point", (long long)N); return PINN_ERR_INVALID; }
+  const int asked = asked_engine(desc);
+  const bool fused_ok = fused_fields_supports(*n);
+  if (asked == PINN_ENGINE_FUSED && !fused_ok) {
+    const char* why = n->drop_p > 0.f ? "dropout_p > 0 has no field kernel"
+                    : n->prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only"
+                    : n->W > 64 ? "hidden width above 64"
+                    : (n->d_in > 16 || n->d_out > 16) ? "d_in or d_out above 16" : "network too deep for the tile kernel";
+    set_error("pinn_residual_fields on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, hidden layers %d); "
+              "engine AUTO runs this request through the forward jet", why, n->W, n->d_in, n->d_out, n->k, n->L);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  pl->fused = fused_ok && (asked == PINN_ENGINE_AUTO || asked == PINN_ENGINE_FUSED);
+  if (pl->fused) {
+    pl->chunk = N; pl->y_off = pl->dy_off = pl->in_off = 0; pl->inner_bytes = 0;
+    pl->total = fused_fields_workspace_bytes(*n);
+    return PINN_OK;
+  }
+  const int e = pick_engine(desc, *n, false, &rc); if (rc) return rc;   // the engine pinn_forward_jet will run on
+  pl->chunk = N < FIELDS_CHUNK ? N : FIELDS_CHUNK;
+  pl->inner_bytes = e == PINN_ENGINE_FUSED ? fused_workspace_bytes(*n, pl->chunk)
+                  : e == PINN_ENGINE_WIDE ? wide_workspace_bytes(*n, pl->chunk) : generic_workspace_bytes(*n, pl->chunk);
+  if (pl->inner_bytes < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
+  int64_t off = 0;
+  pl->y_off = off; off += al256(pl->chunk * n->d_out * 4);
+  pl->dy_off = off; off += al256((int64_t)n->k * pl->chunk * n->d_out * 4);
+  pl->in_off = off; off += al256(pl->inner_bytes);
+  pl->total = off;
+  return PINN_OK;
+}
+
+int32_t pinn_query_fields_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
+  Net n; pinn_residual_spec nspec; FieldsPlan pl;
+  int rc = fields_plan(desc, spec, N, &n, &nspec, &pl); if (rc) return rc;
+  if (!bytes) { set_error("bytes is NULL"); return PINN_ERR_INVALID; }
+  *bytes = pl.total;
+  return PINN_OK;
+}
+
+int32_t pinn_residual_fields(const pinn_desc* desc, const pinn_residual_spec* spec, const float* params, const float* X,
+                             int64_t N, float* fields, void* ws, int64_t ws_bytes, void* stream) {
+  Net n; pinn_residual_spec nspec; FieldsPlan pl;
+  int rc = fields_plan(desc, spec, N, &n, &nspec, &pl); if (rc) return rc;
+  if (!params || !X || !fields) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
+  if (!ws || ws_bytes < pl.total) {
+    set_error("workspace too small: need %lld bytes, got %lld", (long long)pl.total, (long long)ws_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  if (pl.fused) return fused_residual_fields(n, nspec, params, X, N, fields, ws, ws_bytes, s);
+  char* base = (char*)ws;
+  float* Y = (float*)(base + pl.y_off);
+  float* dY = (float*)(base + pl.dy_off);
+  for (int64_t n0 = 0; n0 < N; n0 += pl.chunk) {
+    const int64_t nc = N - n0 < pl.chunk ? N - n0 : pl.chunk;
+    const float* Xc = X + n0 * n.d_in;
+    rc = forward_impl(desc, params, Xc, nc, Y, dY, base + pl.in_off, pl.inner_bytes, stream, true); if (rc) return rc;
+    rc = fields_from_jet(n, nspec, Xc, Y, dY, nc, n0, N, fields, s); if (rc) return rc;
+  }
+  return PINN_OK;
+}
+
 // ---- second-order jets (physics.py:6-15 applied twice; their parameter gradient, train.py:191) ----------------------
 // Validation shared by the three jet2 entries; *mfma = which layer kernels run.  GENERIC: the VALU kernels, any shape.
 // FUSED (and its sub-values): the MFMA kernels, fp32 networks at most 64 wide without dropout, refused otherwise.

@@ -100,7 +100,9 @@ struct WsLayout {
 };
 int64_t al(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
-WsLayout ws_layout(const Net& n, const Geo& g, int64_t N) {
+// lean (pinn_residual_fields: a forward-only pass that spills nothing, sums nothing and has no gradient copies): the
+// packed weights only — the answer no longer depends on N.
+WsLayout ws_layout(const Net& n, const Geo& g, int64_t N, bool lean = false) {
   WsLayout w;
   const int64_t n_tiles = (N + 15) / 16;
   w.max_grid = grid_for(n_tiles, false, g.WP == 16 ? FUSED_W16_WAVES : 2);
@@ -127,9 +129,10 @@ WsLayout ws_layout(const Net& n, const Geo& g, int64_t N) {
     }
     if (b > scratch_bytes) scratch_bytes = b;
   }
+  if (lean) scratch_bytes = 0;
   w.scratch = off; off += al(scratch_bytes);
-  w.wg_sums = off; off += al((int64_t)w.max_grid * MAX_SUMS * 4);
-  const int64_t copies = w.max_grid;   // one (padded) gradient copy per workgroup, in LDS or — too large for it — here
+  w.wg_sums = off; off += al(lean ? 0 : (int64_t)w.max_grid * MAX_SUMS * 4);
+  const int64_t copies = lean ? 0 : w.max_grid;   // one (padded) gradient copy per workgroup, in LDS or — too large for it — here
   w.wg_grads = off; off += al(copies * g.PP * 4);
   w.total = off;
   return w;
@@ -338,10 +341,16 @@ struct AdjReq {
   float* grad;                         // device flat grad (+=)
 };
 
+// what pinn_residual_fields hands the tile kernel instead of a loss: the residual and where its fields go, (NF, N)
+struct FieldReq {
+  pinn_residual_spec spec;   // normalised (pinn_abi.hip, check_spec)
+  float* fields;
+};
+
 int run(const Net& n, bool grad, const LossReq* rq, const float* params, const float* X, int64_t N, float* Y,
-        float* dY, void* ws, int64_t ws_bytes, hipStream_t s, const AdjReq* adj = nullptr) {
+        float* dY, void* ws, int64_t ws_bytes, hipStream_t s, const AdjReq* adj = nullptr, const FieldReq* fld = nullptr) {
   const Geo g = geo_of(n);
-  const WsLayout w = ws_layout(n, g, N);
+  const WsLayout w = ws_layout(n, g, N, fld != nullptr);
   if (!ws || ws_bytes < w.total) {
     set_error("workspace too small: need %lld bytes, got %lld", (long long)w.total, (long long)ws_bytes);
     return PINN_ERR_WORKSPACE;
@@ -381,9 +390,17 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     }
   }
   if (adj) { P.gY = adj->gY; P.gdY = adj->gdY; }
-  // (the external-adjoint epilogue exists in the tile kernel only: every kernel choice of desc.engine lands there)
-  const bool batch = !adj && use_batch(n, g, grad, N);
-  const bool coop = !adj && !batch && use_coop(n, g, grad, N);
+  if (fld) {   // the residual's roles as a residual loss sets them; nothing else of a loss request
+    P.Y = fld->fields; P.dY = nullptr;   // (fused_kernel.h, FusedParams: the field instances' output array)
+    P.residual_id = fld->spec.residual_id;
+    for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = fld->spec.out_col[j];
+    for (int d = 0; d < PINN_MAX_DIRS; ++d) P.q_of[d] = 1 + fld->spec.dir_of[d];
+    P.thr = fld->spec.param[0]; P.anchor = fld->spec.param[1];
+    P.xcol = n.dir_col[fld->spec.dir_of[0]];
+  }
+  // (the external-adjoint and the field epilogues exist in the tile kernel only: every kernel choice of desc.engine lands there)
+  const bool batch = !adj && !fld && use_batch(n, g, grad, N);
+  const bool coop = !adj && !fld && !batch && use_coop(n, g, grad, N);
   if (coop) {
     P.acc_lds = grad ? 1 : 0;
     P.lds_acc_floats = grad ? g.PP : 0;
@@ -440,6 +457,15 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     }
   }
   int rc;
+  if (fld) {   // forward-only grid (grid_for above, grad == false), natural unit order (perm == 0), no reductions;
+               // no dynamic LDS: these instances touch neither the pads nor the gradient copy
+    switch (g.WP) {
+      case 16: rc = launch_fused_field<16>(n.K1, P, grid, 0, s); break;
+      case 32: rc = launch_fused_field<32>(n.K1, P, grid, 0, s); break;
+      default: rc = launch_fused_field<64>(n.K1, P, grid, 0, s); break;
+    }
+    return rc;
+  }
   if (adj) {
     if (n.drop_p > 0.f) { set_error("fused engine: no dropout instance of the external-adjoint kernel"); return PINN_ERR_UNSUPPORTED; }
     switch (g.WP) {
@@ -532,6 +558,26 @@ bool fused_supports(const Net& n, bool want_grad) {
 bool fused_jet_backward_supports(const Net& n) {
   Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
   return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && fused_supports(t, true);
+}
+
+// pinn_residual_fields on the tile kernel's field instances (pinn_fused_field_wXX.hip): every forward shape of the tile
+// kernel in fp32 without dropout whose k is the residual's number of directions (K1 = 3 or 4).  desc.engine's kernel choice
+// does not matter here (run() always takes the tile kernel).
+bool fused_fields_supports(const Net& n) {
+  Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
+  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && (n.K1 == 3 || n.K1 == 4) && fused_supports(t, false);
+}
+
+int64_t fused_fields_workspace_bytes(const Net& n) {
+  if (!fused_fields_supports(n)) return -1;
+  return ws_layout(n, geo_of(n), 1, true).total;
+}
+
+int fused_residual_fields(const Net& n, const pinn_residual_spec& spec, const float* params, const float* X, int64_t N,
+                          float* fields, void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (!fused_fields_supports(n)) { set_error("fused engine: no field kernel for this request (k = %d)", n.k); return PINN_ERR_UNSUPPORTED; }
+  const FieldReq fld{spec, fields};
+  return run(n, false, nullptr, params, X, N, nullptr, nullptr, ws, ws_bytes, s, nullptr, &fld);
 }
 
 // The folded update needs the whole request in ONE pass (the split request on the width-64 tile kernel runs as two).

@@ -51,6 +51,24 @@ struct ResNavierStokes {
       g[3][2] = rx * w; g[3][3] = rc * H + ry * w;
     }
   }
+  // the signed fields themselves (pinn_residual_fields): f = (fc, fm_x, fm_y), eval's expressions term for term
+  static constexpr int NF = 3;
+  __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
+    const float z_t = v[1][1], u_t = v[1][2], w_t = v[1][3];
+    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
+    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
+    const float G = 9.81f;
+    const float CB = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78));
+    const float H = h + z;
+    const float Hx = h_x + z_x, Hy = h_y + z_y;
+    const float hu_x = Hx * u + H * u_x;
+    const float hv_y = Hy * w + H * w_y;
+    const float Fbr_x = CB * Hx * H, Fbr_y = CB * Hy * H;
+    f[0] = z_t + hu_x + hv_y;                                // physics.py:81
+    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;        // physics.py:82
+    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;        // physics.py:83
+  }
 };
 
 // physics.py:91-120  physics_equation(x, y, h, U, V, eta_mean, Hrms, k)
@@ -94,6 +112,21 @@ struct ResPhysicsEquation {
       g[2][3] = ry * G;        // d/deta_y
     }
   }
+  // f = (fc, fx, fy), eval's expressions term for term
+  static constexpr int NF = 3;
+  __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
+    const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
+    const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
+    const float G = 9.81f, RHO = 1025.f;
+    const float RC = (float)(1025 * 0.002);
+    const float tbx = (RC * U) * fabsf(U);
+    const float tby = (RC * V) * fabsf(V);
+    const float D = 1.0f / (RHO * (eta + h));
+    f[0] = U_x + V_y;                                        // physics.py:113
+    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;            // physics.py:114
+    f[2] = U * V_x + V * V_y + G * e_y + D * tby;            // physics.py:115
+  }
 };
 
 // physics.py:37-47 continuity_ftemp(x, y, h, U, V); physics.py:18-33 continuity_only
@@ -126,6 +159,16 @@ struct ResContinuity {
       g[1][0] = rc * U; g[1][1] = rc * h;
       g[2][0] = rc * V; g[2][2] = rc * h;
     }
+  }
+  // f = (fc, da): da = h - anchor on the masked points of continuity_only, 0 elsewhere and for continuity_ftemp
+  static constexpr int NF = 2;
+  __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF],
+                                       bool anchor_on, bool masked, float anchor) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2];
+    const float h_x = v[1][0], U_x = v[1][1];
+    const float h_y = v[2][0], V_y = v[2][2];
+    f[0] = h_x * U + h * U_x + h_y * V + h * V_y;            // physics.py:20-23,39-42
+    f[1] = (anchor_on && masked) ? (h - anchor) : 0.f;       // physics.py:27-28
   }
 };
 

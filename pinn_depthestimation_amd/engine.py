@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import (ACT_LEAKY_RELU, ACT_TANH, ENGINE_AUTO, ENGINE_FUSED, ENGINE_FUSED_BATCH, ENGINE_FUSED_COOP, ENGINE_FUSED_TILE, ENGINE_GENERIC,
                    ENGINE_WIDE, RES_CONTINUITY_FTEMP,
-                   RES_CONTINUITY_ONLY, RES_NAVIER_STOKES, RES_PHYSICS_EQUATION, RES_TERMS, PinnDesc, PinnError,
+                   RES_CONTINUITY_ONLY, RES_FIELDS, RES_NAVIER_STOKES, RES_PHYSICS_EQUATION, RES_TERMS, PinnDesc, PinnError,
                    PinnResidualSpec, check)
 
 ACTIVATION_OF_INIT = {"xavier": ACT_TANH, "kaiming": ACT_LEAKY_RELU}  # dnn.py:18-21
@@ -99,6 +99,11 @@ class ResidualSpec:
     @property
     def n_terms(self) -> int:
         return RES_TERMS[self.residual_id]
+
+    @property
+    def n_fields(self) -> int:
+        """Rows of Engine.residual_fields: (fc, fm_x, fm_y) / (fc, fx, fy) / (fc, da)."""
+        return RES_FIELDS[self.residual_id]
 
     def c_struct(self) -> PinnResidualSpec:
         s = PinnResidualSpec()
@@ -305,6 +310,35 @@ class Engine:
         self._run("pinn_residual_loss", self.lib.pinn_residual_loss, C.byref(self._d(engine)), C.byref(spec.c_struct()), _ptr(params),
                                           _ptr(X), N, _ptr(sums), _ptr(ws), ws.numel())
         return sums
+
+    def fields_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
+        """Workspace of residual_fields (pinn_query_fields_workspace), cached apart from workspace()'s."""
+        e = self.desc.engine if engine is None else engine
+        key = ("fields", e, spec.residual_id, N)
+        need = self._ws_need.get(key)
+        if need is None:
+            c_need = C.c_int64()
+            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
+                check(self.lib.pinn_query_fields_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
+                      "pinn_query_fields_workspace")
+            need = self._ws_need[key] = c_need.value
+        ws = self._ws.get(("fields", e))
+        if ws is None or ws.numel() < need:
+            self._ws[("fields", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def residual_fields(self, spec: ResidualSpec, params, X, engine=None) -> torch.Tensor:
+        """The residual's signed per-point fields, (n_fields, N): row f is field f at every row of X
+        (pinn_residual_fields); sum over points of row t squared is residual_loss's term_sums[t].  engine=None is the
+        descriptor's engine: AUTO runs the MFMA tile kernel's field instances where they exist (width <= 64, fp32, no
+        dropout) and the forward jet plus a point-wise kernel otherwise; FUSED is refused where AUTO would fall back."""
+        N = X.shape[0]
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        out = torch.empty(spec.n_fields, N, dtype=torch.float32, device=X.device)
+        ws = self.fields_workspace(spec, N, engine)
+        self._run("pinn_residual_fields", self.lib.pinn_residual_fields, C.byref(self._d(engine)), C.byref(spec.c_struct()),
+                  _ptr(params), _ptr(X), N, _ptr(out), _ptr(ws), ws.numel())
+        return out
 
     def residual_loss_grad(self, spec: ResidualSpec, term_scale: torch.Tensor, params, X, grad: torch.Tensor,
                            engine=None, sums: Optional[torch.Tensor] = None) -> torch.Tensor:

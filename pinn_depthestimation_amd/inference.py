@@ -21,7 +21,11 @@ from . import operations as op
 from . import physics
 from .config import PinnConfig, load_config
 from .dnn import DNN
-from .engine import RESIDUAL_ROLES
+from .engine import ACTIVATION_OF_INIT, RESIDUAL_ROLES, Engine, NetDesc, ResidualSpec
+
+
+FIELD_NAMES = {"Navier_Stokes": ("fc", "fm_x", "fm_y"), "physics_equation": ("fc", "fx", "fy"),
+               "continuity_ftemp": ("fc", "da"), "continuity_only": ("fc", "da")}
 
 
 class Tester:
@@ -100,6 +104,33 @@ class Tester:
                 pred = self.model(torch.cat(cols, dim=-1))
             self._publish(pred)
         return pred.detach().cpu().numpy()
+
+    def residual_fields(self, test_input_data, input_min_max: Optional[dict] = None):
+        """Residual maps beside test(): the residual's signed per-point fields on the test grid, one array per field
+        (Navier_Stokes: fc, fm_x, fm_y; physics_equation: fc, fx, fy; continuity: fc, da), computed by the engine in
+        eval mode (Engine.residual_fields).  Returns (n_fields, N); when the grid is ny x nx each field is also
+        published as `plot_res_<name>` (ny, nx), and the inputs as `plot_input_<key>` exactly as test() does."""
+        cfg = self.config
+        data = torch.as_tensor(np.asarray(test_input_data)).float().to(self.device).contiguous()
+        names = list(self.test_input_vars)
+        grad_cols = tuple(i for i, k in enumerate(names) if "true" in self.test_input_vars[k].get("requires_grad", []))
+        spec = ResidualSpec.from_names(self.residual, names, grad_cols, self.test_output_vars)
+        key = (tuple(self.model.layer_sizes), grad_cols)
+        if getattr(self, "_fields_engine_key", None) != key:
+            self._fields_engine = Engine(NetDesc.from_layers(self.model.layer_sizes, grad_cols,
+                                                             ACTIVATION_OF_INIT[self.model.init_type]), self.device)
+            self._fields_engine_key = key
+        F = self._fields_engine.residual_fields(spec, self.model.flat_params(), data)
+        out = F.cpu().numpy()
+        if self.nx and self.ny and data.shape[0] == self.nx * self.ny:
+            for i, k in enumerate(names):
+                grid = data[:, i].cpu().numpy().reshape(self.ny, self.nx)
+                if input_min_max is not None and k in input_min_max:
+                    grid = op.denormalize(grid, input_min_max[k][0], input_min_max[k][1])
+                setattr(self, f"plot_input_{k}", grid)
+            for name, row in zip(FIELD_NAMES[self.residual], out):
+                setattr(self, f"plot_res_{name}", row.reshape(self.ny, self.nx))
+        return out
 
     def _publish(self, pred):
         for i, key in enumerate(self.test_output_vars):

@@ -28,6 +28,31 @@ from .lbfgs import FlatLBFGS
 from .parallel import Reducer
 
 
+def rad_cdf(score: torch.Tensor) -> torch.Tensor:
+    """Running sum of the scores in float64 (a float32 sum over a large pool stalls once it outgrows its addends)."""
+    return torch.cumsum(score.to(torch.float64), 0)
+
+
+def rad_indices(score: torch.Tensor, u: torch.Tensor, cdf: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Draw indices with probability proportional to `score` (N non-negative values) from uniforms `u` in [0, 1):
+    inverse-CDF sampling, idx = searchsorted(cdf, u * cdf[-1]) with the CDF accumulated in float64, clamped to N - 1
+    (u -> 1 may land on the last edge).  side='right': a zero-score point owns an empty interval and is never drawn.
+    `cdf`: rad_cdf(score) kept from an earlier call (the trainer forms it once per re-scoring, not once per closure)."""
+    if cdf is None:
+        cdf = rad_cdf(score)
+    idx = torch.searchsorted(cdf, u.to(torch.float64) * cdf[-1], right=True)
+    return idx.clamp_(max=score.numel() - 1)
+
+
+def rad_score(fields: torch.Tensor, k: float, c: float) -> torch.Tensor:
+    """RAD's sampling density (Wu et al. 2023, eq. 2) up to normalisation: eps^k / mean(eps^k) + c with
+    eps_n = sqrt(sum_f fields[f][n]^2), in float64.  An all-zero residual leaves the constant (uniform)."""
+    eps = fields.to(torch.float64).square().sum(0).sqrt()
+    ek = eps.pow(k)
+    m = ek.mean()
+    return torch.where(m > 0, ek / m, torch.zeros_like(ek)) + c
+
+
 def _as_f32(a, device) -> Optional[torch.Tensor]:
     if a is None:
         return None
@@ -140,6 +165,10 @@ class HipEvaluator:
     def predict(self, theta, X):
         return self.eng.forward(theta, X)
 
+    def residual_fields(self, theta, X):
+        """(n_fields, N) signed residual fields at the rows of X, in eval mode: the engine without dropout, as predict."""
+        return self.eng.residual_fields(self.spec, theta, X)
+
 
 class PINN:
     """The physics-guided network harness (reference `class pinn`, train.py:46)."""
@@ -149,7 +178,8 @@ class PINN:
                  reducer: Optional[Reducer] = None, evaluator: Optional[Callable] = None,
                  dnn: Optional[DNN] = None, engine: int = 0, mat_dump_iter: Optional[int] = None,
                  mat_dump_path: str = "data_at50k.mat", residual_batch: Optional[int] = None, seed: int = 1234,
-                 log_flush_every: int = 100, lbfgs_impl: str = "flat", precision: int = 0, fold_adam: bool = True):
+                 log_flush_every: int = 100, lbfgs_impl: str = "flat", precision: int = 0, fold_adam: bool = True,
+                 resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0):
         cfg = config if isinstance(config, PinnConfig) else load_config(config)
         self.config, self.device = cfg, torch.device(device)
         self.reducer = reducer or Reducer()
@@ -211,6 +241,21 @@ class PINN:
             self._gen = torch.Generator(device=dev).manual_seed(seed + self.reducer.rank)
             self._res_unit = torch.full((nt,), 1.0 / (residual_batch * self.reducer.world), dtype=torch.float32, device=dev)
             self._res_scale = (self.weight_residual * self._res_unit).contiguous()
+        # resample = "rad": residual-based adaptive distribution (Wu et al. 2023) — the mini-batch is drawn with
+        # probability proportional to eps^k / mean(eps^k) + c over this rank's pool, eps the per-point residual
+        # magnitude (Engine.residual_fields), re-scored every rad_every iterations.  A biased sampler by design: no
+        # importance re-weighting, _res_unit as for the uniform mini-batch; each rank scores and samples its own shard.
+        if resample not in ("uniform", "rad"):
+            raise PinnError(f"resample={resample!r}: use 'uniform' or 'rad'")
+        if resample == "rad":
+            if residual == "continuity_only":
+                raise PinnError("resample='rad' is not supported with continuity_only's data-dependent mean")
+            if residual_batch is None:
+                raise PinnError("resample='rad' draws a mini-batch of the collocation pool: it needs residual_batch")
+            if int(rad_every) < 1 or rad_k < 0 or rad_c < 0:
+                raise PinnError(f"rad_every={rad_every} must be >= 1, rad_k={rad_k} and rad_c={rad_c} must be >= 0")
+        self.resample, self.rad_every, self.rad_k, self.rad_c = resample, int(rad_every), float(rad_k), float(rad_c)
+        self._rad_score, self._rad_cdf, self._rad_at = None, None, None
         self.mat_dump_iter, self.mat_dump_path = mat_dump_iter, mat_dump_path
         self.lbfgs_impl = lbfgs_impl     # "flat": lbfgs.FlatLBFGS (batched recursion); "torch": torch.optim.LBFGS
         self.iter = 0                                                      # train.py:73
@@ -254,7 +299,15 @@ class PINN:
             self.evaluator.training = self.dnn.training          # dropout follows the module's mode (train.py:186)
         Xr = self.Xr
         if self.residual_batch is not None:
-            idx = torch.randint(0, self.Xr.shape[0], (self.residual_batch,), device=self.device, generator=self._gen)
+            if self.resample == "rad":
+                if self._rad_score is None or self.iter - self._rad_at >= self.rad_every:
+                    self._rad_score = rad_score(self.evaluator.residual_fields(self.theta, self.Xr), self.rad_k, self.rad_c)
+                    self._rad_cdf = rad_cdf(self._rad_score)
+                    self._rad_at = self.iter
+                u = torch.rand(self.residual_batch, device=self.device, generator=self._gen, dtype=torch.float64)
+                idx = rad_indices(self._rad_score, u, self._rad_cdf)
+            else:
+                idx = torch.randint(0, self.Xr.shape[0], (self.residual_batch,), device=self.device, generator=self._gen)
             Xr = self.Xr.index_select(0, idx)
         self._ensure_loss_mat()
         nxt = self.iter + 1
@@ -471,6 +524,12 @@ class PINN:
         if self.config.lbfgs["max_it"] > 0:
             self.optimizer_LBFGS.step(self.closure)                                # ONE step, train.py:200
         self.flush_log()
+
+    def residual_fields(self, X=None) -> torch.Tensor:
+        """The residual's signed per-point fields (n_fields, N) at X (default: this rank's collocation shard), in
+        eval mode: Navier_Stokes (fc, fm_x, fm_y), physics_equation (fc, fx, fy), continuity (fc, da)."""
+        X = self.Xr if X is None else _as_f32(X, self.device)
+        return self.evaluator.residual_fields(self.dnn.flat_params(), X)
 
     def predict(self, inputs) -> torch.Tensor:
         """Forward on a grid (test.py:76): (N, d_in) -> (N, d_out)."""
