@@ -42,6 +42,27 @@
  *   - stream: a hipStream_t passed as void* (torch's current stream).  Calls only
  *     enqueue work; they never synchronise the device or the stream.
  *   - workspace: query with pinn_query_workspace, allocate once, pass to calls.
+ *
+ * Buffer contract (pinned by tests/test_abi_contract_gpu.py: guard bands around every buffer, workspaces full of 1e30)
+ *   - The workspace may hold ANYTHING on entry: every call writes what it reads (packed weights with their padding,
+ *     spill slots, partial sums, gradient copies) and reads no integer, offset or pointer from it.  The one exception
+ *     is the caller's own promise adam->packed_valid (pinn_loss_grad_adam_step).
+ *   - One workspace may be reused across calls of any kind, descriptor, engine, precision and N, in any order, as long
+ *     as it is at least as large as the query for the call at hand; no call writes past the size queried for it.
+ *     Results do not depend on the calls that came before.
+ *   - Outputs are written at exactly their stated extents, ragged last tiles and padded columns included: Y (N, d_out),
+ *     dY (k, N, d_out), d2Y (P, N, d_out), fields (n_fields, N), term_sums (n_terms), col_sums (n_cols), grad_flat /
+ *     m / v / params (P), losses (n_loss_rows, or n_iters x n_loss_rows), out2 (2), n_rows_out (1), d (P), tmp (4m),
+ *     coef (2m), q (P); X_out up to its capacity of ceil(ny/ix) * ceil(nx/iy) rows (rows past n_rows_out: unspecified).
+ *   - Read-only, never written: params (except by the two Adam entries and pinn_adam_step), X, T, gY, gdY, gd2Y,
+ *     term_scale, col_scale, loss_rows, grad of pinn_adam_step, data / grids / minmax, g, s, y; S, Y, M in
+ *     pinn_lbfgs_direction; rows of S, Y other than `slot` and entries of M outside row and column `slot` in
+ *     pinn_lbfgs_push.
+ *   - grad_flat is += in pinn_jet_backward, pinn_jet2_backward, pinn_residual_loss_grad, pinn_mse_loss_grad,
+ *     pinn_residual_mse_loss_grad and pinn_residual_mse_split_loss_grad (the caller zeroes it, or accumulates several
+ *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step and pinn_adam_loop.  Y, dY, d2Y, fields,
+ *     term_sums, col_sums, losses, X_out, n_rows_out, out2 and d are overwritten, whatever they held.
+ *   - N = 0 where it is accepted: the sums are zeroed, grad_flat and the workspace are not touched.
  */
 #ifndef PINN_HIP_H
 #define PINN_HIP_H
@@ -109,7 +130,10 @@ typedef struct pinn_desc {
    * draws a new seed per forward pass.  Kept units are scaled by 1 / (1 - p), tangents included.
    * Gradient passes of tanh networks of hidden width 33..64 run on the fused tile kernel's dropout instances (the mask
    * re-derived in registers); every other call with dropout_p > 0 runs on the generic engine.  AUTO picks accordingly;
-   * FUSED is refused for requests it does not serve, WIDE always. */
+   * FUSED is refused for requests it does not serve, WIDE always.
+   * pinn_residual_mse_split_loss_grad on those dropout instances runs as two passes (collocation points, then fidelity
+   * points): the mask's point index restarts at 0 at the first fidelity point, as it does at every chunk of
+   * pinn_residual_fields' staged path.  On the generic engine the index runs through all N points. */
   float dropout_p;
   uint32_t dropout_seed;
 } pinn_desc;
