@@ -248,6 +248,25 @@ __device__ __forceinline__ void load_bias(const float* __restrict__ b, f4 (&bias
 template <int ACT, int NT, int K1, bool DROP = false>
 __device__ __forceinline__ void activate_to(const f4 (&acc)[K1][NT], const f4 (&bias)[NT], f4 (&a)[K1][NT],
                                             const DropLane* dl = nullptr, int layer = 0, int q = 0) {
+  if constexpr (ACT == PINN_ACT_TANH && !DROP) {
+    // explicit packed fp32 on the register pairs (0, 1) and (2, 3) of every f4: bias add, tanh (tanh_f32x2), s = 1 - a^2 and
+    // the tangent products — per element the operations of the scalar form below in the same order (bitwise the same result)
+#pragma unroll
+    for (int MT = 0; MT < NT; ++MT)
+#pragma unroll
+      for (int h = 0; h < 4; h += 2) {
+        const f2 z = f2{acc[0][MT][h], acc[0][MT][h + 1]} + f2{bias[MT][h], bias[MT][h + 1]};
+        const f2 av = tanh_f32x2(z);
+        const f2 s = __builtin_elementwise_fma(-av, av, f2{1.f, 1.f});
+        a[0][MT][h] = av[0]; a[0][MT][h + 1] = av[1];
+#pragma unroll
+        for (int c = 1; c < K1; ++c) {
+          const f2 t = f2{acc[c][MT][h], acc[c][MT][h + 1]} * s;
+          a[c][MT][h] = t[0]; a[c][MT][h + 1] = t[1];
+        }
+      }
+    return;
+  }
 #pragma unroll
   for (int MT = 0; MT < NT; ++MT)
 #pragma unroll
@@ -345,6 +364,19 @@ __device__ __forceinline__ f4 transpose_read2(const float* __restrict__ tb, int 
   return *reinterpret_cast<const f4*>(tb + p * 16 + 4 * ((q + 2 * (p >> 2)) & 3));
 }
 
+// t + (t of lane ^ 16) and t + (t of lane ^ 32) for the bias row sums: v_permlane16_swap / v_permlane32_swap (gfx950) exchange
+// whole 16- / 32-lane rows between two registers inside the vector ALU.  Swapping t with a copy of itself leaves
+// {r0, r0, r2, r2} and {r1, r1, r3, r3} (rows r0..r3 of t), resp. {lo, lo} and {hi, hi}; their sum is the __shfl_xor form's
+// (the operands of an fp32 add commute: bitwise the same) without its ds_bpermute, its address and its LDS round trip.
+__device__ __forceinline__ float add_xor16(float t) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(t), __float_as_uint(t), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float add_xor32(float t) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(t), __float_as_uint(t), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
 constexpr int MAX_LOCKS = 128;
 
 // Where dW/db contributions go.
@@ -387,12 +419,18 @@ struct GradSink {
 // dW[16MT + 4q + r][16NT + n] += sum_c sum_points Z[c][MT](feature, point) * A[c][NT](feature, point)
 // db[16MT + m]                += sum_points Z[0][MT](feature m, point)
 // A: the layer-input jet in acc layout (registers).
-template <int MT_N, int NT_N, int K1, class Sink>
+// UNIT_A (layer 0): A[0] is the coordinate block and A[c >= 1] the constant unit tangent delta(feature, dir_col[c - 1]), the same
+// for every point.  In operand layout (lane = feature p, element s = a point) that is a lane predicate, so those operands are
+// built in registers and only A[0] goes through the pad: per tile 6 LDS writes, 3 LDS reads and the tangent part of the input jet
+// less, the same products into the same accumulators in the same k-order.
+template <int MT_N, int NT_N, int K1, bool UNIT_A = false, class Sink>
 __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int woff, int boff, const f4 (&Z)[K1][MT_N],
-                                            const f4 (&A)[K1][NT_N], float* __restrict__ tb, int lane) {
+                                            const f4 (&A)[K1][NT_N], float* __restrict__ tb, int lane,
+                                            const int* __restrict__ dir_col = nullptr) {
+  static_assert(!UNIT_A || NT_N == 1, "unit tangents: the layer-0 input block");
   const int p = lane & 15, q = lane >> 4;
   f4 dw[MT_N][NT_N];
-  float bs[MT_N];
+  float bs[MT_N], bcur[MT_N];
 #pragma unroll
   for (int MT = 0; MT < MT_N; ++MT)
 #pragma unroll
@@ -416,12 +454,20 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
   auto stage = [&](int c, f4 (&z)[MT_N], f4 (&a)[NT_N]) {
 #pragma unroll
     for (int MT = 0; MT < MT_N; ++MT) transpose_write2(tb + MT * TB_FLOATS, Z[c][MT], p, q);
+    const bool unit = UNIT_A && c > 0;
+    if (!unit) {
 #pragma unroll
-    for (int NT = 0; NT < NT_N; ++NT) transpose_write2(tb + (4 + NT) * TB_FLOATS, A[c][NT], p, q);
+      for (int NT = 0; NT < NT_N; ++NT) transpose_write2(tb + (4 + NT) * TB_FLOATS, A[c][NT], p, q);
+    }
 #pragma unroll
     for (int MT = 0; MT < MT_N; ++MT) z[MT] = transpose_read2(tb + MT * TB_FLOATS, p, q);
+    if (!unit) {
 #pragma unroll
-    for (int NT = 0; NT < NT_N; ++NT) a[NT] = transpose_read2(tb + (4 + NT) * TB_FLOATS, p, q);
+      for (int NT = 0; NT < NT_N; ++NT) a[NT] = transpose_read2(tb + (4 + NT) * TB_FLOATS, p, q);
+    } else {
+      const float e = (p == dir_col[c - 1]) ? 1.f : 0.f;
+      a[0] = f4{e, e, e, e};
+    }
   };
   stage(0, zt[0], at[0]);
 #pragma unroll
@@ -440,14 +486,10 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
 #pragma unroll
         for (int NT = 0; NT < NT_N; ++NT) dw[MT][NT] = mfma4(zt[c & 1][MT][s], at[c & 1][NT][s], dw[MT][NT]);
   }
-  // ... and the 4 lane groups here, after the last MFMA block: lgkmcnt retires in order, so a ds_bpermute
-  // issued right behind the next quantity's transposes would have made quantity 0's MFMAs wait for them
+  // ... and the 4 lane groups here, after the last MFMA block (row swaps in the vector ALU: add_xor16 / add_xor32)
 #pragma unroll
   for (int MT = 0; MT < MT_N; ++MT) {
-    float t = bs[MT];
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    bs[MT] = t;
+    bs[MT] = add_xor32(add_xor16(bs[MT]));
   }
   if constexpr (!Sink::LDS) {
 #pragma unroll
@@ -468,6 +510,10 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
 #pragma unroll
         for (int NT = 0; NT < NT_N; ++NT)
           cur[MT - M0][NT] = *reinterpret_cast<const f4*>(sink.acc + woff + ((MT * NT_N + NT) * 64 + lane) * 4);
+      if (M0 == 0) {   // the bias sums' current values ride the first batch of reads (every lane group reads, group 0 writes below)
+#pragma unroll
+        for (int MT = 0; MT < MT_N; ++MT) bcur[MT] = sink.acc[boff + 16 * MT + p];
+      }
       __builtin_amdgcn_sched_barrier(0);   // (a pair: with one, the width-32 kernels' register allocation changes)
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -479,7 +525,10 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
   }
   if (q == 0) {
 #pragma unroll
-    for (int MT = 0; MT < MT_N; ++MT) sink.add1(boff + 16 * MT + p, bs[MT]);
+    for (int MT = 0; MT < MT_N; ++MT) {
+      if constexpr (Sink::LDS) sink.acc[boff + 16 * MT + p] = bcur[MT] + bs[MT];
+      else sink.add1(boff + 16 * MT + p, bs[MT]);
+    }
   }
   sink.unlock(layer, lane);
 }
@@ -491,11 +540,16 @@ __device__ __forceinline__ float pick4(f4 v, int i) {
 __device__ __forceinline__ float gather_out(f4 tile, int o, int p) {
   return __shfl(pick4(tile, o & 3), p + 16 * (o >> 2), 64);
 }
+// (the operands are passed BY VALUE: written as `(qi == c) ? out[c][0] : v` the conditional load became a select of
+// ADDRESSES and one load — a dynamically indexed stack array.  The output tiles then lived in scratch memory, 64-80 bytes
+// per lane in every residual instance, and each of the epilogue's reloads waited with vmcnt(0), i.e. for the reverse
+// sweep's prefetched weight blocks as well)
+__device__ __forceinline__ f4 select4(bool take, f4 a, f4 b) { return take ? a : b; }
 template <int K1>
 __device__ __forceinline__ f4 pick_q(const f4 (&out)[K1][1], int qi) {
   f4 v = out[0][0];
 #pragma unroll
-  for (int c = 1; c < K1; ++c) v = (qi == c) ? out[c][0] : v;
+  for (int c = 1; c < K1; ++c) v = select4(qi == c, out[c][0], v);
   return v;
 }
 
@@ -928,8 +982,10 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
       }
       {  // layer 0: z = zbar_0, input = (x, unit tangents)
         f4 b1[K1][1];
-        input_jet(b1);   // recomputed rather than kept live across the whole tile
-        weight_grad<NTH, 1, K1>(sink, 0, 0, P.PW + b_off_p<WP>(0), z, b1, tb, lane);
+        input_jet(b1);   // recomputed rather than kept live across the whole tile; with UNIT_A weight_grad reads the coordinates only
+        // (UNIT_A for the LDS-copy instances only: with it, clang 22 crashes in its 'Rewrite AGPR-Copy-MFMA' pass on the
+        // width-64 LeakyReLU instance that keeps its gradient copy in global memory)
+        weight_grad<NTH, 1, K1, LDSACC>(sink, 0, 0, P.PW + b_off_p<WP>(0), z, b1, tb, lane, P.dir_col);
       }
     }
     PINN_STAMP(7);

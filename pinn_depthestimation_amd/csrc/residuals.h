@@ -190,4 +190,27 @@ __device__ inline float tanh_f32(float x) {
   return ax < 0.625f ? small : big;
 }
 
+// Two tanh_f32 evaluations on one register pair, every fp32 operation written on the pair (v_pk_mul_f32 / v_pk_fma_f32 /
+// v_pk_add_f32): per element the same operations in the same order as tanh_f32, so each half is bitwise tanh_f32 of its
+// input.  The one liberty: |x| is taken BEHIND the doubling and the multiply by log2(e) instead of in front of them — both
+// are sign-symmetric, the magnitudes are the same bits — so that these two run packed (packed fp32 has no |.| modifier;
+// v_exp_f32 has).  __expf(y) is v_exp_f32(y * log2(e)) with exactly this constant (0x3fb8aa3b).
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ inline f2 tanh_f32x2(f2 x) {
+  const f2 x2 = x * x;
+  f2 p = f2{-5.70498872745e-3f, -5.70498872745e-3f};
+  p = __builtin_elementwise_fma(p, x2, f2{2.06390887954e-2f, 2.06390887954e-2f});
+  p = __builtin_elementwise_fma(p, x2, f2{-5.37397155531e-2f, -5.37397155531e-2f});
+  p = __builtin_elementwise_fma(p, x2, f2{1.33314422036e-1f, 1.33314422036e-1f});
+  p = __builtin_elementwise_fma(p, x2, f2{-3.33332819422e-1f, -3.33332819422e-1f});
+  const f2 small = __builtin_elementwise_fma(p * x2, x, x);
+  const f2 t = (x + x) * f2{0x1.715476p+0f, 0x1.715476p+0f};                    // +-(2|x|) log2(e)
+  const f2 e = f2{__builtin_amdgcn_exp2f(fabsf(t[0])), __builtin_amdgcn_exp2f(fabsf(t[1]))};
+  const f2 d = e + f2{1.f, 1.f};
+  const f2 r = f2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+  const f2 big = __builtin_elementwise_fma(f2{-2.f, -2.f}, r, f2{1.f, 1.f});
+  return f2{fabsf(x[0]) < 0.625f ? small[0] : copysignf(big[0], x[0]),
+            fabsf(x[1]) < 0.625f ? small[1] : copysignf(big[1], x[1])};
+}
+
 }  // namespace pinn

@@ -13,7 +13,7 @@ KEYS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "SGPRs Spill
 def parse(path):
     out, cur = collections.OrderedDict(), None
     for line in open(path, errors="replace"):
-        m = re.search(r"remark:\s+(.*?)\s*\[-Rpass", line)
+        m = re.search(r"remark:\s+(?:\S+:\d+:\d+:\s+)?(.*?)\s*\[-Rpass", line)   # (newer clang puts file:line:col in front)
         if not m:
             continue
         body = m.group(1)
