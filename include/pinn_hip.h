@@ -97,7 +97,8 @@ extern "C" {
 #define PINN_ENGINE_FUSED_TILE 4  /* one wave per 16-point tile (the large-N kernel) */
 #define PINN_ENGINE_FUSED_COOP 5  /* four waves per tile (small point sets; padded hidden width 64 only) */
 #define PINN_ENGINE_FUSED_BATCH 6 /* layer-major batches of tiles per wave (narrow nets: hidden width <= 32, tanh, gradient
-                                   * passes; AUTO picks it from 4096 points; other requests fall back to _TILE) */
+                                   * passes and pinn_jet_backward; AUTO picks it from 4096 points; other requests fall back
+                                   * to _TILE) */
 
 /* GEMM operand precision.  Everything outside the MFMAs (tanh, residual, adjoints, gradient
  * accumulation, Adam) is fp32 in both modes. */
@@ -183,17 +184,35 @@ int32_t pinn_forward_jet(const pinn_desc* desc, const float* params, const float
 
 /* grad_flat (P,) += d/dtheta [ sum(gY*Y) + sum(gdY*dY) ];  gY or gdY may be NULL (treated as 0).  gdY is (k, N, d_out)
  * in the order of desc->dir_col, as pinn_forward_jet writes dY.
- * Engines.  GENERIC: the layer-wise kernels, any shape.  FUSED (every sub-value: this call has one MFMA kernel, the tile
- * kernel with the caller's adjoints in place of a residual): fp32, width <= 64, d_in and d_out <= 16, tanh or LeakyReLU,
+ * Engines.  GENERIC: the layer-wise kernels, any shape.  FUSED: fp32, width <= 64, d_in and d_out <= 16, tanh or LeakyReLU,
  * k in {0, 2, 3} or gdY == NULL, dropout_p == 0; anything else is refused with PINN_ERR_UNSUPPORTED and the reason in
  * pinn_last_error().  WIDE: refused.  AUTO: the MFMA path where FUSED would be served, otherwise GENERIC.
- * Reproducibility.  GENERIC is bit-reproducible from run to run.  The MFMA path launches one workgroup per 16-point
+ * FUSED has two kernels for this call, both with the caller's adjoints in place of a residual.  The batch kernel serves
+ * what it serves for a gradient request: tanh, width <= 32, d_in <= 8, k in {2, 3} with gdY.  FUSED_BATCH forces it at any
+ * N; FUSED and AUTO take it from PINN_JET_BACKWARD_BATCH_MIN_TILES 16-point tiles on and the tile kernel below; FUSED_TILE
+ * and FUSED_COOP keep the tile kernel.  Every other served request (LeakyReLU, k = 0 or gdY == NULL, d_in > 8, width
+ * 33..64) runs on the tile kernel under every FUSED value, FUSED_BATCH included.  pinn_jet_backward_kernel below tells
+ * which kernel a call would run.
+ * Reproducibility.  GENERIC is bit-reproducible from run to run.  The tile kernel launches one workgroup per 16-point
  * tile, up to W workgroups (W = 1 to 3 per compute unit, by shape); while N <= 16 * W every gradient copy is
  * added to by a single wave in program order and the copies are summed in a fixed order: bit-reproducible.  Above that
- * size several waves share a copy and two runs differ in the last bits, as for every other fused gradient call. */
+ * size several waves share a copy and two runs differ in the last bits, as for every other fused gradient call.
+ * The batch kernel, where four gradient copies fit in LDS (e.g. 10 x 10): a copy per wave, no lock and no atomic, each
+ * wave adds in program order, the four copies and then the workgroups are summed in a fixed order: bit-reproducible at
+ * every N on a given device.  Where the gradient is too large for that (e.g. 40 x 20, 100 x 20) the batch kernel adds
+ * into shared copies with atomics and two runs differ in the last bits at every N. */
 int32_t pinn_jet_backward(const pinn_desc* desc, const float* params, const float* X, int64_t N,
                           const float* gY, const float* gdY, float* grad_flat,
                           void* ws, int64_t ws_bytes, void* stream);
+
+/* AUTO / FUSED run pinn_jet_backward on the batch kernel from this many 16-point tiles on (4096 points; measured on
+ * MI355X at 10 x 10, 20 x 20 and 100 x 20: DESIGN.md 2.4b) */
+#define PINN_JET_BACKWARD_BATCH_MIN_TILES 256
+
+/* *kernel = the kernel a pinn_jet_backward call with this descriptor, N and gdY (with_gdY != 0) or without would run:
+ * PINN_ENGINE_GENERIC, PINN_ENGINE_FUSED_TILE or PINN_ENGINE_FUSED_BATCH.  A request the call refuses is refused here
+ * with the same code and message.  Host logic only: no device is needed or touched. */
+int32_t pinn_jet_backward_kernel(const pinn_desc* desc, int64_t N, int32_t with_gdY, int32_t* kernel);
 
 /* ---- second-order jets --------------------------------------------------------------------------------------------
  * k = desc->k differentiated inputs (1..3) give P = k (k + 1) / 2 unordered pairs (i, j), i <= j, stored upper triangle

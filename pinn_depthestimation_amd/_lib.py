@@ -65,6 +65,7 @@ _SIGNATURES = {
     "pinn_forward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "pinn_forward_jet": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "pinn_jet_backward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
+    "pinn_jet_backward_kernel": (C.c_int32, [C.POINTER(PinnDesc), C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
     "pinn_query_jet2_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_forward_jet2": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
     "pinn_jet2_backward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P]),

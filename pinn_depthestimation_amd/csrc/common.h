@@ -108,6 +108,9 @@ int fused_loss(const Net& n, const LossReq& rq, const float* params, const float
                void* ws, int64_t ws_bytes, hipStream_t s);
 // pinn_jet_backward on the tile kernel (fused_kernel.h, EPI_ADJ): grad += d/dtheta [sum(gY * Y) + sum(gdY * dY)]
 bool fused_jet_backward_supports(const Net& n);
+// which fused kernel a served pinn_jet_backward request runs: PINN_ENGINE_FUSED_TILE or PINN_ENGINE_FUSED_BATCH (pure host
+// logic: the decision run() itself takes)
+int fused_jet_backward_kernel(const Net& n, int64_t N);
 int fused_jet_backward(const Net& n, const float* params, const float* X, int64_t N, const float* gY,
                        const float* gdY, float* grad, void* ws, int64_t ws_bytes, hipStream_t s);
 

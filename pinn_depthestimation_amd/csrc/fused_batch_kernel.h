@@ -362,8 +362,39 @@ __device__ __forceinline__ void bwgrad_flush_wg(float* __restrict__ acc, int wof
 }
 __host__ __device__ constexpr int batch_comb_floats(int WP) { return 2 * BATCH_WAVES * ((WP / 16) * (WP / 16) * 256 + 64); }   // two buffers
 
+// load_adjoint of fused_kernel.h (same lanes, same zeros: o >= d_out, the invalid points of a ragged tile or batch, a null
+// array) with every load UNCONDITIONAL: a refused element reads an in-range element (point 0 / output 0; a null array:
+// the other array, pinn_jet_backward refuses two nulls) and is zeroed by a select.  load_adjoint's own ternaries come out
+// of the compiler as an exec-masked region per register with a scalar branch per array inside (80 branches per
+// four-tile batch), and a load behind a runtime branch is what collapses the vmcnt bookkeeping in this kernel (reverse
+// sweep below).  One per-lane row offset; the planes of gdY are uniform offsets.
+template <int K1>
+__device__ __forceinline__ void bload_adjoint(const FusedParams& P, f4 (&G)[K1][1], int64_t pt, bool valid, int q) {
+  const bool hy = P.gY != nullptr, hd = P.gdY != nullptr;
+  const float* __restrict__ gy = hy ? P.gY : P.gdY;
+  const float* __restrict__ gd = hd ? P.gdY : P.gY;
+  const int64_t plane = hd ? P.N * P.d_out : 0;
+  const int64_t row = (valid ? pt : 0) * P.d_out;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int o = 4 * q + r;
+    const bool ok = valid && o < P.d_out;
+    const int64_t e = row + (o < P.d_out ? o : 0);
+    const float vy = gy[e];
+    G[0][0][r] = ok && hy ? vy : 0.f;
+#pragma unroll
+    for (int c = 1; c < K1; ++c) {
+      const float vd = gd[(c - 1) * plane + e];
+      G[c][0][r] = ok && hd ? vd : 0.f;
+    }
+  }
+}
+
 // WP: padded hidden width (16 / 32); KS = ceil(W / 4): k-steps of a hidden contraction; KS0 = ceil(d_in / 4);
 // T: tiles per wave and batch.  Gradient passes only (the forward-only calls stay on k_fused).
+// EPI: EPI_GENERIC (the loss epilogue of fused_kernel.h) or EPI_ADJ (pinn_jet_backward: the caller's output adjoints
+// instead of a loss; instances in pinn_fused_batch_adj_w*_k*.hip).  Everything from the output layer's pad writes on —
+// abar_L, dW_L, the reverse sweep, layer 0, both gradient sinks — is the same code for both.
 template <int WP, int KS, int KS0, int K1, int T, int SINK, int ACT, int EPI = EPI_GENERIC>
 __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batch(const FusedParams P) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -394,7 +425,7 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
 #pragma unroll
   for (int j = 0; j < MAX_SUMS; ++j) sums[j] = 0.f;
   ScatterMap<K1> sm, sm_mse;
-  build_scatter_maps<K1>(P, q, sm, sm_mse);
+  if constexpr (EPI != EPI_ADJ) build_scatter_maps<K1>(P, q, sm, sm_mse);
 
   const int gw = blockIdx.x * BATCH_WAVES + wave;
   constexpr int SLOTF = K1 * KS * 64;                       // floats of one (tile, layer) spill slot
@@ -420,6 +451,12 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
 #pragma unroll
       for (int s = 0; s < KS0; ++s) xin[t][s] = (4 * s + q < P.d_in) ? P.X[pc * P.d_in + 4 * s + q] : 0.f;
     });
+    // EPI_ADJ: the caller's output adjoints of tile t sit in gadj[t & 1] (two register sets: tile t + 1 is requested
+    // while tile t is worked on, output-layer step below).  The one-tile instances have nothing to overlap there, so
+    // they request their tile here, in front of the forward chain (4 K1 registers, in kernels far from the file's edge);
+    // the full-batch instances request tile 0 behind the chain — 4 K1 T registers held across it would not fit.
+    f4 gadj[2][K1][1];
+    if constexpr (EPI == EPI_ADJ && T == 1) bload_adjoint<K1>(P, gadj[0], tile0 * 16 + p, tile0 * 16 + p < P.N, q);
     float tang[K1][KS0];         // unit tangents (the same for every tile)
 #pragma unroll
     for (int c = 1; c < K1; ++c)
@@ -486,11 +523,15 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
     }
     // ---- output layer + loss + its adjoint, tile by tile: a[t] <- zbar_L(t) --------------------------------------
     {
+      // EPI_ADJ (pinn_jet_backward): the output adjoint does not depend on the outputs — no W_L / b_L loads, no output
+      // GEMM, no epilogue; G is the caller's (bload_adjoint: zeros for the invalid points of a ragged tile or batch, for
+      // o >= d_out and for a null array, so a tile past the end contributes exact zeros to every sink below)
       f4 wo[1][NTH], wtl[NTH][1];
-      bload_w<NTH, 1>(Wp_ + w_off_p<WP>(L), WP, wo, p, q);
+      if constexpr (EPI != EPI_ADJ) bload_w<NTH, 1>(Wp_ + w_off_p<WP>(L), WP, wo, p, q);
       bload_w<1, NTH>(WTp_ + w_off_p<WP>(L), 16, wtl, p, q);
       f4 bias_o[1];
-      load_bias<1>(Bp_ + b_off_p<WP>(L), bias_o, q);
+      if constexpr (EPI != EPI_ADJ) load_bias<1>(Bp_ + b_off_p<WP>(L), bias_o, q);
+      if constexpr (EPI == EPI_ADJ && T > 1) bload_adjoint<K1>(P, gadj[0], tile0 * 16 + p, tile0 * 16 + p < P.N, q);
       f4 dwl[NACC][1][NTH];
       float bsl[1];
       bwg_zero<1, NTH, NACC>(dwl, bsl);
@@ -500,18 +541,25 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
         const int64_t pt = (tile0 + t) * 16 + p;
         const bool valid = pt < P.N;
         const int64_t ptc = valid ? pt : P.N - 1;
-        f4 out[K1][1];
-        zero_tiles<1, K1>(out);
-        bgemm<KS, NTH, 1, K1>(wo, a[t], out);
-        out[0][0] += bias_o[0];
         f4 G[K1][1];
-        loss_epilogue<K1, true, true, EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+        if constexpr (EPI == EPI_ADJ) {
+#pragma unroll
+          for (int c = 0; c < K1; ++c) G[c][0] = gadj[t & 1][c][0];
+        } else {
+          f4 out[K1][1];
+          zero_tiles<1, K1>(out);
+          bgemm<KS, NTH, 1, K1>(wo, a[t], out);
+          out[0][0] += bias_o[0];
+          loss_epilogue<K1, true, true, EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+        }
 #pragma unroll
         for (int c = 0; c < K1; ++c) {
           btr_write(tb + c * (1 + NTH) * TB_FLOATS, G[c][0], p, q);
           bwg_write_ks<NTH, KS>(tb + (c * (1 + NTH) + 1) * TB_FLOATS, a[t][c], p, q);
         }
         __builtin_amdgcn_sched_barrier(0);
+        // tile t + 1's adjoints (64 K1 bytes per point, read once) fly under this tile's abar_L GEMM and weight gradient
+        if constexpr (EPI == EPI_ADJ && t + 1 < T) bload_adjoint<K1>(P, gadj[(t + 1) & 1], pt + 16, pt + 16 < P.N, q);
         f4 g[K1][NTH];
         zero_tiles<NTH, K1>(g);
         {   // abar_L = W_L^T G: contraction over the (naturally ordered) outputs, all four k-steps
@@ -614,19 +662,24 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
   }
 
   // ---- per-workgroup reductions (as k_fused) --------------------------------------------------------------------
+  // (EPI_ADJ has no loss: wg_sums is neither written here nor read by the host after such a pass)
+  if constexpr (EPI != EPI_ADJ) {
 #pragma unroll
-  for (int j = 0; j < MAX_SUMS; ++j) {
-    float v = sums[j];
+    for (int j = 0; j < MAX_SUMS; ++j) {
+      float v = sums[j];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) lsum[wave * MAX_SUMS + j] = v;
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+      if (lane == 0) lsum[wave * MAX_SUMS + j] = v;
+    }
   }
   __syncthreads();
-  if (threadIdx.x < MAX_SUMS) {
-    float v = 0.f;
+  if constexpr (EPI != EPI_ADJ) {
+    if (threadIdx.x < MAX_SUMS) {
+      float v = 0.f;
 #pragma unroll
-    for (int w2 = 0; w2 < BATCH_WAVES; ++w2) v += lsum[w2 * MAX_SUMS + threadIdx.x];
-    P.wg_sums[(int64_t)blockIdx.x * MAX_SUMS + threadIdx.x] = v;
+      for (int w2 = 0; w2 < BATCH_WAVES; ++w2) v += lsum[w2 * MAX_SUMS + threadIdx.x];
+      P.wg_sums[(int64_t)blockIdx.x * MAX_SUMS + threadIdx.x] = v;
+    }
   }
   if (SINK == BSINK_LDS_WAVE) {   // (the __syncthreads above covers the waves' last flushes)
     float* dst = P.wg_grads + (int64_t)blockIdx.x * PP;
@@ -638,6 +691,8 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
 // launchers: one translation unit per padded width (pinn_fused_batch_w16.hip / _w32.hip)
 template <int WP>
 int launch_fused_batch(int W, int d_in, int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+template <int WP>      // the EPI_ADJ instances (pinn_fused_batch_adj_w{16,32}_k{3,4}.hip)
+int launch_fused_batch_adj(int W, int d_in, int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 bool fused_batch_has_kernel(int WP, int W, int d_in, int K1, int act);
 
 }  // namespace pinn

@@ -137,8 +137,8 @@ static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc
   return PINN_ENGINE_GENERIC;
 }
 
-// pinn_jet_backward: GENERIC or FUSED (the tile kernel's external-adjoint instances, whatever fused kernel desc.engine
-// names).  AUTO takes the MFMA path where it exists and the generic engine for everything else (k = 1 with gdY, dropout,
+// pinn_jet_backward: GENERIC or FUSED (the external-adjoint instances of the tile or the batch kernel: which of the two,
+// fused_jet_backward_kernel says; whether the call is served does not depend on the fused kernel desc.engine names).  AUTO takes the MFMA path where it exists and the generic engine for everything else (k = 1 with gdY, dropout,
 // width > 64, d_in / d_out > 16, bf16); an explicit FUSED request the path does not serve is refused, WIDE always.
 static int pick_jet_backward_engine(const pinn_desc* d, const Net& n, int* rc) {
   *rc = PINN_OK;
@@ -336,6 +336,15 @@ int32_t pinn_jet_backward(const pinn_desc* desc, const float* params, const floa
   const int e = pick_jet_backward_engine(desc, n, &rc); if (rc) return rc;
   return e == PINN_ENGINE_FUSED ? fused_jet_backward(n, params, X, N, gY, gdY, grad_flat, ws, ws_bytes, (hipStream_t)stream)
                                 : generic_jet_backward(n, params, X, N, gY, gdY, grad_flat, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int32_t pinn_jet_backward_kernel(const pinn_desc* desc, int64_t N, int32_t with_gdY, int32_t* kernel) {
+  Net n; int rc = make_net(desc, &n); if (rc) return rc;
+  if (!kernel || N < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
+  if (!with_gdY) { n.k = 0; n.K1 = 1; }      // as pinn_jet_backward with gdY == NULL: the plain network
+  const int e = pick_jet_backward_engine(desc, n, &rc); if (rc) return rc;
+  *kernel = e == PINN_ENGINE_FUSED ? fused_jet_backward_kernel(n, N) : PINN_ENGINE_GENERIC;
+  return PINN_OK;
 }
 
 static int32_t residual_impl(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,

@@ -57,12 +57,19 @@ bool batch_supported(const Net& n, const Geo& g) {
   return n.drop_p == 0.f && g.WP <= 32 && n.L >= 1 && n.L + 1 <= MAX_LOCKS && fused_batch_has_kernel(g.WP, n.W, n.d_in, n.K1, n.act);
 }
 constexpr int64_t BATCH_MIN_TILES = 256;   // AUTO: below this many tiles (4096 points) the tile kernel keeps the request
-bool use_batch(const Net& n, const Geo& g, bool grad, int64_t N) {
+// pinn_jet_backward switches at a tile count of its own (pinn_hip.h; measured: DESIGN.md 2.4b)
+constexpr int64_t ADJ_BATCH_MIN_TILES = PINN_JET_BACKWARD_BATCH_MIN_TILES;
+// (min_points: the loss calls count a ragged last tile, (N + 15) / 16 >= BATCH_MIN_TILES)
+bool use_batch(const Net& n, const Geo& g, bool grad, int64_t N, int64_t min_points = 16 * BATCH_MIN_TILES - 15) {
   if (!grad || !batch_supported(n, g)) return false;
   if (n.fused_kernel == FUSED_KERNEL_BATCH) return true;
   if (n.fused_kernel != FUSED_KERNEL_AUTO) return false;
-  return (N + 15) / 16 >= BATCH_MIN_TILES;
+  return N >= min_points;
 }
+// ... for an external-adjoint pass: the same rule as a gradient request (the batch kernel's EPI_ADJ instances cover the
+// loss instances' grid), so LeakyReLU, k = 0, d_in > 8 and width 33..64 stay on the tile kernel under every engine value
+// (full tiles: N >= 16 x PINN_JET_BACKWARD_BATCH_MIN_TILES)
+bool use_batch_adj(const Net& n, const Geo& g, int64_t N) { return use_batch(n, g, true, N, 16 * ADJ_BATCH_MIN_TILES); }
 // tiles per wave and batch: the full batch once every wave of the chip gets one, else ONE tile per wave (the latency of
 // a layer step scales with the batch, and a small point set wants its tiles spread over as many waves as there are)
 int batch_T_for(const Geo& g, int K1, int64_t n_tiles) {
@@ -398,8 +405,9 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     P.thr = fld->spec.param[0]; P.anchor = fld->spec.param[1];
     P.xcol = n.dir_col[fld->spec.dir_of[0]];
   }
-  // (the external-adjoint and the field epilogues exist in the tile kernel only: every kernel choice of desc.engine lands there)
-  const bool batch = !adj && !fld && use_batch(n, g, grad, N);
+  // (the field epilogue exists in the tile kernel only: every kernel choice of desc.engine lands there; the external-adjoint
+  // one in the tile and in the batch kernel)
+  const bool batch = !fld && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
   const bool coop = !adj && !fld && !batch && use_coop(n, g, grad, N);
   if (coop) {
     P.acc_lds = grad ? 1 : 0;
@@ -417,7 +425,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   // networks' kernels fit 2 waves per SIMD, which hides their per-layer latencies
   const bool one_per_cu = grad && P.acc_lds && !(g.WP <= 32 && 2 * (int64_t)lds <= LDS_LIMIT);
   int grid = grid_for(P.n_tiles, one_per_cu, g.WP == 16 && FUSED_W16_WAVES * (int64_t)lds <= LDS_LIMIT ? FUSED_W16_WAVES : 2);
-  if (adj) grid = adj_grid_for(P.n_tiles, one_per_cu, g.WP == 16 && FUSED_W16_WAVES * (int64_t)lds <= LDS_LIMIT ? FUSED_W16_WAVES : 2);
+  if (adj && !batch) grid = adj_grid_for(P.n_tiles, one_per_cu, g.WP == 16 && FUSED_W16_WAVES * (int64_t)lds <= LDS_LIMIT ? FUSED_W16_WAVES : 2);
   if (coop) {   // one workgroup per tile, at most one per CU (gradient kernels fill the LDS)
     const int64_t cap = (int64_t)cu_count() * (grad ? 1 : 2);
     grid = (int)(P.n_tiles < cap ? (P.n_tiles < 1 ? 1 : P.n_tiles) : cap);
@@ -468,15 +476,18 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   }
   if (adj) {
     if (n.drop_p > 0.f) { set_error("fused engine: no dropout instance of the external-adjoint kernel"); return PINN_ERR_UNSUPPORTED; }
-    switch (g.WP) {
+    if (batch) rc = g.WP == 16 ? launch_fused_batch_adj<16>(n.W, n.d_in, n.K1, P, grid, lds, s)
+                               : launch_fused_batch_adj<32>(n.W, n.d_in, n.K1, P, grid, lds, s);
+    else switch (g.WP) {
       case 16: rc = launch_fused_adj<16>(n.K1, P, grid, lds, s); break;
       case 32: rc = launch_fused_adj<32>(n.K1, P, grid, lds, s); break;
       default: rc = launch_fused_adj<64>(n.K1, P, grid, lds, s); break;
     }
     if (rc) return rc;
+    // (no loss sums after an adjoint pass: wg_sums is not read)
     const int64_t np = n.n_params();
     hipLaunchKernelGGL(k_reduce_grads, dim3((unsigned)((np + 63) / 64)), dim3(256), 0, s, n, g.WP,
-                       (const float*)P.wg_grads, n_copies, g.PP, g.PW, adj->grad, 0);
+                       (const float*)P.wg_grads, n_copies, g.PP, g.PW, adj->grad, perm | (rmajor ? PACK_RMAJOR : 0));
     return check_launch("fused reductions");
   }
   if (n.drop_p > 0.f) {     // training-mode dropout: its own instances of the tile kernel (pinn_fused_w64_drop.hip)
@@ -537,6 +548,15 @@ int launch_fused_batch(int W, int d_in, int K1, const FusedParams& P, int grid, 
 }
 template int launch_fused_batch<16>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
 template int launch_fused_batch<32>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
+// ... and their external-adjoint siblings: pinn_fused_batch_adj_w{16,32}_k{3,4}.hip
+template <int WP, int K1>
+int launch_fused_batch_adj_k(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s);
+template <int WP>
+int launch_fused_batch_adj(int W, int d_in, int K1, const FusedParams& P, int grid, size_t lds, hipStream_t s) {
+  return K1 == 3 ? launch_fused_batch_adj_k<WP, 3>(W, d_in, P, grid, lds, s) : launch_fused_batch_adj_k<WP, 4>(W, d_in, P, grid, lds, s);
+}
+template int launch_fused_batch_adj<16>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
+template int launch_fused_batch_adj<32>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
 bool fused_batch_has_kernel(int WP, int W, int d_in, int K1, int act) {
   return (WP == 16 || WP == 32) && W >= 1 && d_in <= 8 && (K1 == 3 || K1 == 4) && act == PINN_ACT_TANH;
 }
@@ -553,11 +573,15 @@ bool fused_supports(const Net& n, bool want_grad) {
   return n.W <= 64 && n.d_in <= 16 && n.d_out <= 16 && n.L >= 1 && n.K1 >= 1 && n.K1 <= 4;
 }
 
-// pinn_jet_backward on the tile kernel's external-adjoint instances (pinn_fused_adj_wXX.hip): every gradient shape of
-// the tile kernel without dropout.  desc.engine's kernel choice does not matter here (run() always takes the tile kernel).
+// pinn_jet_backward on the external-adjoint instances of the tile kernel (pinn_fused_adj_wXX.hip): every gradient shape of
+// the tile kernel without dropout.  desc.engine's kernel choice does not matter for WHETHER the call is served (a request
+// the batch kernel has no instance for runs on the tile kernel), only for which of the two kernels serves it:
 bool fused_jet_backward_supports(const Net& n) {
   Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
   return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && fused_supports(t, true);
+}
+int fused_jet_backward_kernel(const Net& n, int64_t N) {
+  return use_batch_adj(n, geo_of(n), N) ? PINN_ENGINE_FUSED_BATCH : PINN_ENGINE_FUSED_TILE;
 }
 
 // pinn_residual_fields on the tile kernel's field instances (pinn_fused_field_wXX.hip): every forward shape of the tile

@@ -1,0 +1,6 @@
+// pinn_fused_batch_adj_w32_k3.hip — batch kernel instances with the external-adjoint epilogue (pinn_jet_backward), padded
+// hidden width 32, K1 = 3 (see pinn_fused_batch.inc)
+#define BATCH_WP 32
+#define BATCH_K1 3
+#define BATCH_EPI EPI_ADJ
+#include "pinn_fused_batch.inc"

@@ -258,8 +258,9 @@ class Engine:
     def jet_backward(self, params, X, gY: Optional[torch.Tensor], gdY: Optional[torch.Tensor],
                      grad: torch.Tensor, engine=None) -> torch.Tensor:
         """grad += d/d params [sum(gY*Y) + sum(gdY*dY)] (pinn_jet_backward); either adjoint may be None.  engine=None
-        is the descriptor's engine: AUTO runs the MFMA tile kernel where it serves the request (width <= 64, no dropout,
-        k != 1 when gdY is given) and the generic engine otherwise; FUSED is refused where AUTO would fall back."""
+        is the descriptor's engine: AUTO runs an MFMA kernel where one serves the request (width <= 64, no dropout,
+        k != 1 when gdY is given; the batch kernel for narrow tanh networks from 4096 points on, else the tile kernel)
+        and the generic engine otherwise; FUSED is refused where AUTO would fall back.  jet_backward_kernel() tells which."""
         N = X.shape[0]
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
         self._chk(grad, "grad", (self.n_params,))
@@ -269,6 +270,15 @@ class Engine:
         self._run("pinn_jet_backward", self.lib.pinn_jet_backward, C.byref(self._d(engine)), _ptr(params), _ptr(X), N, _ptr(gY),
                                          _ptr(gdY), _ptr(grad), _ptr(ws), ws.numel())
         return grad
+
+    def jet_backward_kernel(self, N: int, with_gdY: bool = True, engine: Optional[int] = None) -> int:
+        """The kernel a jet_backward call on N points would run (pinn_jet_backward_kernel): ENGINE_GENERIC,
+        ENGINE_FUSED_TILE or ENGINE_FUSED_BATCH.  Raises PinnError where the call itself would be refused.  Host logic
+        only: no device is touched."""
+        kern = C.c_int32()
+        check(self.lib.pinn_jet_backward_kernel(C.byref(self._d(engine)), int(N), 1 if with_gdY else 0, C.byref(kern)),
+              "pinn_jet_backward_kernel")
+        return kern.value
 
     @property
     def n_pairs(self) -> int:
