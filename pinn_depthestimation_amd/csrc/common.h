@@ -10,6 +10,8 @@ namespace pinn {
 
 void set_error(const char* fmt, ...);
 
+inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }   // workspace regions start on 256-byte boundaries
+
 // layer geometry helpers: layers = [d_in] + [width]*n_hidden + [d_out] (train.py:56)
 constexpr int FUSED_KERNEL_AUTO = 0, FUSED_KERNEL_TILE = 1, FUSED_KERNEL_COOP = 2, FUSED_KERNEL_BATCH = 3;
 struct Net {
@@ -55,12 +57,15 @@ __host__ __device__ inline uint32_t dropout_threshold(float p) {
   return t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
 }
 
+// torch.optim.Adam's scalars, formed in double as Python forms them and cast to fp32 once (adam_scalars, reduce_adam.h)
+struct AdamScalars { float w1, b2, w2, eps, step_size, bc2_sqrt; };   // 1 - b1, b2, 1 - b2, eps, lr / bc1, sqrt(bc2)
+
 // what a loss call asks the engines for
 // torch.optim.Adam's update folded into the kernel that finishes a loss + gradient pass (pinn_loss_grad_adam_step)
 struct AdamReq {
   float* params;        // updated in place (the pass itself read the PACKED copy of them in the workspace)
   float* m; float* v;
-  float w1, b2, w2, eps, step_size, bc2_sqrt;   // as pinn_adam_step forms them
+  AdamScalars c;        // the scalars pinn_adam_step hands k_adam
   bool packed_valid;    // the workspace's packed weights already equal params (left there by the previous call)
   int n_loss_rows; const float* loss_rows; float* losses;   // optional weighted loss values (see pinn_adam_state)
 };

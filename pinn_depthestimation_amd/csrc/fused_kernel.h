@@ -79,6 +79,26 @@ struct FusedParams {
   const float* gdY;                  // in the engine's direction order (row c - 1 belongs to dir_col[c - 1]); either may be null
 };
 
+// host: the residual's roles (spec: normalised by check_spec, pinn_abi.hip) -> P
+inline void set_residual_roles(FusedParams& P, const Net& n, const pinn_residual_spec& spec) {
+  P.residual_id = spec.residual_id;
+  for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = spec.out_col[j];
+  for (int d = 0; d < PINN_MAX_DIRS; ++d) P.q_of[d] = 1 + spec.dir_of[d];
+  P.thr = spec.param[0]; P.anchor = spec.param[1];
+  P.xcol = n.dir_col[spec.dir_of[0]];
+}
+// host: the loss part of P (memset to 0 before) for a loss request of the fused or the wide engine
+inline void set_loss(FusedParams& P, const Net& n, const LossReq& rq) {
+  P.n_split = rq.n_split;
+  P.loss_kind = rq.kind == 0 ? 1 : (rq.kind == 1 ? 2 : 3);
+  if (P.loss_kind & 1) { P.scale = rq.scale; set_residual_roles(P, n, rq.spec); }
+  else for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = -1;
+  if (P.loss_kind & 2) {
+    P.n_cols = rq.n_cols; P.T = rq.T; P.mse_scale = rq.mse_scale;
+    for (int j = 0; j < PINN_MAX_ROLES; ++j) P.mse_col[j] = j < rq.n_cols ? rq.out_col[j] : -1;
+  }
+}
+
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }

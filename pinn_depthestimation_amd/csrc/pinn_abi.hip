@@ -5,6 +5,7 @@
 #include <utility>
 #include <vector>
 #include "common.h"
+#include "reduce_adam.h"
 
 namespace pinn {
 
@@ -163,6 +164,11 @@ static int pick_jet_backward_engine(const pinn_desc* d, const Net& n, int* rc) {
   return ok ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
 }
 
+static int64_t engine_workspace_bytes(int engine, const Net& n, int64_t N) {
+  return engine == PINN_ENGINE_FUSED ? fused_workspace_bytes(n, N)
+       : engine == PINN_ENGINE_WIDE ? wide_workspace_bytes(n, N) : generic_workspace_bytes(n, N);
+}
+
 // runs rq on the engine pick_engine() chooses for it
 static int run_loss(const pinn_desc* desc, const Net& n, bool want_grad, const LossReq& rq, const float* params,
                     const float* X, int64_t N, void* ws, int64_t ws_bytes, void* stream) {
@@ -182,15 +188,22 @@ static int set_out_cols(const Net& n, int n_cols, const int32_t* out_col, LossRe
   return PINN_OK;
 }
 
-static int residual_terms(int id) {
-  switch (id) {
-    case PINN_RES_NAVIER_STOKES: return PINN_NS_TERMS;
-    case PINN_RES_PHYSICS_EQUATION: return PINN_PE_TERMS;
-    case PINN_RES_CONTINUITY_FTEMP: return PINN_CF_TERMS;
-    case PINN_RES_CONTINUITY_ONLY: return PINN_CO_TERMS;
-  }
-  return -1;
+// What each residual uses: its first `roles` output roles and `dirs` direction roles; how many loss terms and per-point
+// fields it has (pinn_hip.h's numbers: ResContinuity::NT is the kernels' 3 for both continuity residuals).  Null for an
+// id that names no residual.
+struct ResidualInfo { int id, roles, dirs, terms, fields; };
+static const ResidualInfo* residual_info(int id) {
+  static const ResidualInfo table[] = {{PINN_RES_NAVIER_STOKES, 4, 3, PINN_NS_TERMS, PINN_NS_FIELDS},
+                                       {PINN_RES_PHYSICS_EQUATION, 6, 2, PINN_PE_TERMS, PINN_PE_FIELDS},
+                                       {PINN_RES_CONTINUITY_FTEMP, 3, 2, PINN_CF_TERMS, PINN_CF_FIELDS},
+                                       {PINN_RES_CONTINUITY_ONLY, 3, 2, PINN_CO_TERMS, PINN_CO_FIELDS}};
+  for (const ResidualInfo& r : table) if (r.id == id) return &r;
+  return nullptr;
 }
+// (-1 for an id that names no residual)
+static int residual_terms(int id) { const ResidualInfo* r = residual_info(id); return r ? r->terms : -1; }
+static int residual_dirs(int id) { const ResidualInfo* r = residual_info(id); return r ? r->dirs : -1; }
+static int residual_n_fields(int id) { const ResidualInfo* r = residual_info(id); return r ? r->fields : -1; }
 
 // Checks the roles the residual USES (its first nr output roles, nd direction roles) and returns in *norm a copy whose
 // unused entries are inert: out_col = -1 (matches no output column), dir_of = -1 (quantity 0 is never a direction).
@@ -199,14 +212,9 @@ static int residual_terms(int id) {
 // real role sat there, and the output adjoint of that column was read from beyond the roles' rows.
 static int check_spec(const Net& n, const pinn_residual_spec* sp, pinn_residual_spec* norm) {
   if (!sp) { set_error("spec is NULL"); return PINN_ERR_INVALID; }
-  int nr = 0, nd = 0;
-  switch (sp->residual_id) {
-    case PINN_RES_NAVIER_STOKES: nr = 4; nd = 3; break;
-    case PINN_RES_PHYSICS_EQUATION: nr = 6; nd = 2; break;
-    case PINN_RES_CONTINUITY_FTEMP:
-    case PINN_RES_CONTINUITY_ONLY: nr = 3; nd = 2; break;
-    default: set_error("unknown residual_id %d", sp->residual_id); return PINN_ERR_INVALID;
-  }
+  const ResidualInfo* ri = residual_info(sp->residual_id);
+  if (!ri) { set_error("unknown residual_id %d", sp->residual_id); return PINN_ERR_INVALID; }
+  const int nr = ri->roles, nd = ri->dirs;
   for (int r = 0; r < nr; ++r)
     if (sp->out_col[r] < 0 || sp->out_col[r] >= n.d_out) {
       set_error("out_col[%d]=%d outside the %d output columns", r, sp->out_col[r], n.d_out);
@@ -223,24 +231,19 @@ static int check_spec(const Net& n, const pinn_residual_spec* sp, pinn_residual_
   return PINN_OK;
 }
 
+// The one column-sum kernel of the library: the fused, wide and generic hosts launch it through reduce_sums (reduce_adam.h).
+__global__ void k_reduce_sums(const float* __restrict__ rows, int64_t n_rows, int stride, int col0, float* __restrict__ out) {
+  const double v = column_sum(rows, n_rows, stride, col0 + blockIdx.x);
+  if (threadIdx.x == 0) out[blockIdx.x] = (float)v;
+}
+void reduce_sums(const float* rows, int64_t n_rows, int stride, int col0, int n, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_reduce_sums, dim3(n), dim3(256), 0, s, rows, n_rows, stride, col0, out);
+}
+
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                       float* __restrict__ v, int64_t P, float w1, float b2, float w2, float eps, float step_size,
-                       float bc2_sqrt) {
-  // torch.optim.Adam, _single_tensor_adam (the path train.py:192 takes on CPU):
-  //   exp_avg.lerp_(grad, 1-b1); exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1-b2)
-  //   denom = (exp_avg_sq.sqrt() / sqrt(bc2)).add_(eps); param.addcdiv_(exp_avg, denom, value=-lr/bc1)
-  // Scalars are formed in double on the host exactly as Python does, then cast to
-  // fp32 once; contraction is off so every op rounds where torch's rounds.
-#pragma clang fp contract(off)
+                       float* __restrict__ v, int64_t P, AdamScalars c) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  const float gi = g[i];
-  const float mi = m[i] + w1 * (gi - m[i]);
-  float vi = v[i] * b2;
-  vi = vi + (w2 * gi) * gi;
-  m[i] = mi; v[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] - step_size * (mi / denom);
+  if (i < P) p[i] = adam_update(p[i], g[i], m[i], v[i], c);
 }
 
 }  // namespace pinn
@@ -270,10 +273,7 @@ int32_t pinn_query_workspace(const pinn_desc* desc, int64_t N, int64_t* bytes) {
   // (pinn_forward, pinn_mse_loss_grad, pinn_jet_backward without gdY: k = 0), which may land on yet another engine
   // (k = 1 at width 65..256: jets on the generic kernels, plain forwards on the wide engine)
   auto need = [&](const Net& nn, int* err) -> int64_t {
-    auto ws_of = [&](int e) {
-      return e == PINN_ENGINE_FUSED ? fused_workspace_bytes(nn, N)
-           : e == PINN_ENGINE_WIDE ? wide_workspace_bytes(nn, N) : generic_workspace_bytes(nn, N);
-    };
+    auto ws_of = [&](int e) { return engine_workspace_bytes(e, nn, N); };
     int rc1 = PINN_OK, rc2 = PINN_OK;
     const int e = pick_engine(desc, nn, false, &rc1);
     const int eg = pick_engine(desc, nn, true, &rc2);
@@ -439,11 +439,8 @@ int32_t pinn_adam_step(float* params, const float* grad, float* m, float* v, int
                        double beta1, double beta2, double eps, void* stream) {
   if (!params || !grad || !m || !v || P < 0 || step < 1) { set_error("bad arguments"); return PINN_ERR_INVALID; }
   if (P == 0) return PINN_OK;
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
   hipLaunchKernelGGL(k_adam, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grad, m,
-                     v, P, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                     (float)(lr / bc1), (float)sqrt(bc2));
+                     v, P, adam_scalars(lr, beta1, beta2, eps, step));
   return check_launch("adam");
 }
 
@@ -474,11 +471,8 @@ int32_t pinn_loss_grad_adam_step(const pinn_desc* desc, const pinn_residual_spec
     return PINN_ERR_UNSUPPORTED;
   }
   AdamReq a;
-  const double bc1 = 1.0 - pow(adam->beta1, (double)adam->step);
-  const double bc2 = 1.0 - pow(adam->beta2, (double)adam->step);
   a.params = params; a.m = adam->m; a.v = adam->v;
-  a.w1 = (float)(1.0 - adam->beta1); a.b2 = (float)adam->beta2; a.w2 = (float)(1.0 - adam->beta2); a.eps = (float)adam->eps;
-  a.step_size = (float)(adam->lr / bc1); a.bc2_sqrt = (float)sqrt(bc2);
+  a.c = adam_scalars(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step);
   a.packed_valid = adam->packed_valid != 0;
   if (adam->n_loss_rows < 0 || adam->n_loss_rows > 8 || (adam->n_loss_rows > 0 && (!adam->loss_rows || !adam->losses))) {
     set_error("bad loss_rows arguments"); return PINN_ERR_INVALID;
@@ -514,18 +508,6 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, co
 // AUTO: the first where it applies, else the second.  FUSED (and sub-values): the first or refused, as pinn_jet_backward.
 // GENERIC / WIDE: the second, on that engine.
 static constexpr int64_t FIELDS_CHUNK = 1 << 16;
-static int64_t al256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-static int residual_dirs(int id) { return id == PINN_RES_NAVIER_STOKES ? 3 : 2; }
-static int residual_n_fields(int id) {
-  switch (id) {
-    case PINN_RES_NAVIER_STOKES: return PINN_NS_FIELDS;
-    case PINN_RES_PHYSICS_EQUATION: return PINN_PE_FIELDS;
-    case PINN_RES_CONTINUITY_FTEMP: return PINN_CF_FIELDS;
-    case PINN_RES_CONTINUITY_ONLY: return PINN_CO_FIELDS;
-  }
-  return -1;
-}
 
 struct FieldsPlan {
   bool fused;                            // the tile kernel's field instances
@@ -562,13 +544,12 @@ static int fields_plan(const pinn_desc* desc, const pinn_residual_spec* spec, in
   }
   const int e = pick_engine(desc, *n, false, &rc); if (rc) return rc;   // the engine pinn_forward_jet will run on
   pl->chunk = N < FIELDS_CHUNK ? N : FIELDS_CHUNK;
-  pl->inner_bytes = e == PINN_ENGINE_FUSED ? fused_workspace_bytes(*n, pl->chunk)
-                  : e == PINN_ENGINE_WIDE ? wide_workspace_bytes(*n, pl->chunk) : generic_workspace_bytes(*n, pl->chunk);
+  pl->inner_bytes = engine_workspace_bytes(e, *n, pl->chunk);
   if (pl->inner_bytes < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
   int64_t off = 0;
-  pl->y_off = off; off += al256(pl->chunk * n->d_out * 4);
-  pl->dy_off = off; off += al256((int64_t)n->k * pl->chunk * n->d_out * 4);
-  pl->in_off = off; off += al256(pl->inner_bytes);
+  pl->y_off = off; off += align256(pl->chunk * n->d_out * 4);
+  pl->dy_off = off; off += align256((int64_t)n->k * pl->chunk * n->d_out * 4);
+  pl->in_off = off; off += align256(pl->inner_bytes);
   pl->total = off;
   return PINN_OK;
 }

@@ -1,8 +1,10 @@
 // pinn_fused.hip — host side of the fused MFMA engine: weight packing, workspace carve,
 // launch geometry, cross-workgroup reductions.  Kernel: fused_kernel.h.
+#include <algorithm>
 #include <type_traits>
 #include "fused_coop_kernel.h"
 #include "fused_batch_kernel.h"
+#include "reduce_adam.h"
 
 namespace pinn {
 
@@ -29,6 +31,13 @@ Geo geo_of(const Net& n) {
 }
 
 int cu_count() { return device_cu_count(); }   // of the CURRENT device (common.h: cached per device)
+// every launch grid of this file: `want` workgroups, at least one, at most per_cu on each compute unit
+int capped_grid(int64_t want, int per_cu) {
+  const int64_t cap = (int64_t)cu_count() * per_cu;
+  return (int)(want < 1 ? 1 : (want < cap ? want : cap));
+}
+// workgroups per CU of the tile kernel where LDS allows: the width-16 instances are compiled for FUSED_W16_WAVES waves per SIMD
+int tile_wgs_per_cu(int WP) { return WP == 16 ? FUSED_W16_WAVES : 2; }
 
 constexpr int64_t LDS_LIMIT = 160 * 1024;
 
@@ -81,51 +90,37 @@ int64_t batch_lds_comb_bytes(int WP) { return (int64_t)batch_comb_floats(WP) * 4
 int batch_ks(const Net& n) { return n.W <= 12 ? 3 : (n.W <= 16 ? 4 : (n.W <= 20 ? 5 : 8)); }   // k-steps of the kernel instance
 int batch_grid(int64_t n_tiles, int T, int occ) {
   const int64_t nb = (n_tiles + T - 1) / T;
-  const int64_t want = (nb + BATCH_WAVES - 1) / BATCH_WAVES;
-  const int64_t cap = (int64_t)cu_count() * occ;
-  return (int)(want < 1 ? 1 : (want < cap ? want : cap));
+  return capped_grid((nb + BATCH_WAVES - 1) / BATCH_WAVES, occ);
 }
 
 int grid_for(int64_t n_tiles, bool one_per_cu, int per_cu = 2) {
-  int64_t want = (n_tiles + FUSED_WAVES - 1) / FUSED_WAVES;
-  int64_t cap = (int64_t)cu_count() * (one_per_cu ? 1 : per_cu);
-  if (want < 1) want = 1;
-  return (int)(want < cap ? want : cap);
+  return capped_grid((n_tiles + FUSED_WAVES - 1) / FUSED_WAVES, one_per_cu ? 1 : per_cu);
 }
 // External-adjoint pass (pinn_jet_backward): one workgroup per TILE up to the same cap.  With the kernel's workgroup-major
 // wave numbering (fused_kernel.h, EPI_ADJ) a single wave per workgroup has work while n_tiles <= grid, so every gradient
 // copy is added to in program order and the call is bit-reproducible for N <= 16 x grid.
-int adj_grid_for(int64_t n_tiles, bool one_per_cu, int per_cu = 2) {
-  const int64_t cap = (int64_t)cu_count() * (one_per_cu ? 1 : per_cu);
-  const int64_t want = n_tiles < 1 ? 1 : n_tiles;
-  return (int)(want < cap ? want : cap);
-}
+int adj_grid_for(int64_t n_tiles, bool one_per_cu, int per_cu = 2) { return capped_grid(n_tiles, one_per_cu ? 1 : per_cu); }
+// the cooperative kernel: one workgroup per tile, at most one per CU for a gradient pass (it fills the LDS), else two
+int coop_grid_for(int64_t n_tiles, bool grad) { return capped_grid(n_tiles, grad ? 1 : 2); }
 
 struct WsLayout {
   int64_t wp, wtp, bp, scratch, wg_sums, wg_grads, total;
   int max_grid;
 };
-int64_t al(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 // lean (pinn_residual_fields: a forward-only pass that spills nothing, sums nothing and has no gradient copies): the
 // packed weights only — the answer no longer depends on N.
 WsLayout ws_layout(const Net& n, const Geo& g, int64_t N, bool lean = false) {
   WsLayout w;
   const int64_t n_tiles = (N + 15) / 16;
-  w.max_grid = grid_for(n_tiles, false, g.WP == 16 ? FUSED_W16_WAVES : 2);
-  {   // the cooperative kernel launches one workgroup per tile (up to 2 per CU)
-    const int64_t cap = 2 * (int64_t)cu_count();
-    const int64_t coop_grid = n_tiles < cap ? n_tiles : cap;
-    if (coop_grid > w.max_grid) w.max_grid = (int)coop_grid;
-  }
-  {   // ... and so does the external-adjoint pass, up to the tile kernel's own cap
-    const int adj_grid = adj_grid_for(n_tiles, false, g.WP == 16 ? FUSED_W16_WAVES : 2);
-    if (adj_grid > w.max_grid) w.max_grid = adj_grid;
-  }
+  // the largest grid any pass launches: the tile kernel's; the cooperative kernel's, one workgroup per tile (up to 2 per CU);
+  // the external-adjoint pass's, also one per tile, up to the tile kernel's own cap
+  const int per_cu = tile_wgs_per_cu(g.WP);
+  w.max_grid = std::max({grid_for(n_tiles, false, per_cu), coop_grid_for(n_tiles, false), adj_grid_for(n_tiles, false, per_cu)});
   int64_t off = 0;
-  w.wp = off; off += al((int64_t)g.PW * 4);
-  w.wtp = off; off += al((int64_t)g.PW * 4);
-  w.bp = off; off += al((int64_t)g.PB * 4);
+  w.wp = off; off += align256((int64_t)g.PW * 4);
+  w.wtp = off; off += align256((int64_t)g.PW * 4);
+  w.bp = off; off += align256((int64_t)g.PB * 4);
   int64_t scratch_bytes = (int64_t)w.max_grid * FUSED_WAVES * n.L * g.slot_floats_k4 * 4;
   if (batch_supported(n, g)) {   // the batch kernel's slots: T tiles x (L - 1) layers x K1 <= 4 x KS x 64 floats per wave
     int64_t b = 0;      // (one workspace serves the K1 = 3 and K1 = 4 instances: the larger of the two)
@@ -137,10 +132,10 @@ WsLayout ws_layout(const Net& n, const Geo& g, int64_t N, bool lean = false) {
     if (b > scratch_bytes) scratch_bytes = b;
   }
   if (lean) scratch_bytes = 0;
-  w.scratch = off; off += al(scratch_bytes);
-  w.wg_sums = off; off += al(lean ? 0 : (int64_t)w.max_grid * MAX_SUMS * 4);
+  w.scratch = off; off += align256(scratch_bytes);
+  w.wg_sums = off; off += align256(lean ? 0 : (int64_t)w.max_grid * MAX_SUMS * 4);
   const int64_t copies = lean ? 0 : w.max_grid;   // one (padded) gradient copy per workgroup, in LDS or — too large for it — here
-  w.wg_grads = off; off += al(copies * g.PP * 4);
+  w.wg_grads = off; off += align256(copies * g.PP * 4);
   w.total = off;
   return w;
 }
@@ -189,24 +184,10 @@ __global__ void k_pack(Net n, int WP, const float* __restrict__ params, float* _
   }
 }
 
-__global__ void k_reduce_sums(const float* __restrict__ wg_sums, int grid, int col0, int nt, float* __restrict__ out) {
-  const int t = col0 + blockIdx.x;
-  __shared__ double red[256];
-  double v = 0.0;
-  for (int b = threadIdx.x; b < grid; b += 256) v += (double)wg_sums[(int64_t)b * MAX_SUMS + t];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && blockIdx.x < nt) out[blockIdx.x] = (float)red[0];
-}
-
-// grad_flat[real index] += sum over copies of the padded per-workgroup gradients.  64 parameters x
+// k_reduce_grads: grad_flat[real index] += sum over copies of the padded per-workgroup gradients.  64 parameters x
 // 4 copy groups per block; each thread adds its group's copies in index order and the 4 partial sums
 // are combined in a fixed order, so the result does not depend on scheduling.
-// a thread's share of the copies, added in index order; the loads of eight copies are issued together (one memory
+// sum_copies: a thread's share of the copies, added in index order; the loads of eight copies are issued together (one memory
 // round trip per eight instead of per copy: 59 -> 12 us on the 768 copies of the 10x10 net) — the ORDER of the
 // additions, and with it the result, is unchanged
 __device__ __forceinline__ float sum_copies(const float* __restrict__ wg, int64_t PP, int pidx, int c0, int c1) {
@@ -223,52 +204,73 @@ __device__ __forceinline__ float sum_copies(const float* __restrict__ wg, int64_
   return s;
 }
 
-__global__ void k_reduce_grads(Net n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
-                               float* __restrict__ grad, int flags) {
+// Where flat parameter i lives in the padded arrays: its layer l, PADDED row / col (bias: row only), the layer's offset wo
+// into the padded weights, and its index pidx into a padded, fragment-native gradient copy (fused_kernel.h, GradSink).
+struct ParamSlot { int64_t i; int l, row, col, wo, pidx; bool is_w; };
+__device__ __forceinline__ ParamSlot param_slot(const Net& n, int WP, int PW, int flags, int64_t i) {
   const int rmajor = (flags & PACK_RMAJOR) != 0;   // [r][lane] inside a 16x16 block (bwgrad_flush, BSINK_ATOMIC)
+  ParamSlot p;
+  p.i = i; p.l = n.layer_of(i);
+  const int64_t r = i - n.w_off(p.l);
+  const int in_d = n.in_dim(p.l), out_d = n.out_dim(p.l);
+  p.wo = (p.l == 0) ? 0 : WP * 16 + (p.l - 1) * WP * WP;
+  p.is_w = r < (int64_t)in_d * out_d;
+  if (p.is_w) {
+    p.row = unit_at((int)(r / in_d), row_permuted(flags, p.l, n.L)); p.col = unit_at((int)(r % in_d), col_permuted(flags, p.l));
+    const int ntn = ((p.l == 0) ? 16 : WP) / 16;
+    const int blk = (p.row >> 4) * ntn + (p.col >> 4), ln = ((p.row & 15) >> 2) * 16 + (p.col & 15);
+    p.pidx = rmajor ? p.wo + (blk * 4 + (p.row & 3)) * 64 + ln : p.wo + (blk * 64 + ln) * 4 + (p.row & 3);
+  } else {
+    p.row = unit_at((int)(r - (int64_t)in_d * out_d), row_permuted(flags, p.l, n.L)); p.col = 0;
+    p.pidx = PW + p.l * WP + p.row;
+  }
+  return p;
+}
+// This pass's gradient of flat parameter blockIdx.x * 64 + (threadIdx.x & 63), summed over the copies: each of the four
+// 64-thread groups adds its share of the copies, the four partial sums are combined in a fixed order.  Called by all 256
+// threads of a block; `owner` is true in the one thread per parameter (first group, i < n_params) that holds the result:
+// only there are g (the gradient) and at (where the parameter lives) meaningful.
+struct ParamGrad { bool owner; float g; ParamSlot at; };
+__device__ __forceinline__ ParamGrad grad_of_param(const Net& n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
+                                                   int flags) {
   __shared__ float part[4][64];
   const int lane_p = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int64_t i = (int64_t)blockIdx.x * 64 + lane_p;
+  ParamGrad r = {};
   float s = 0.f;
   if (i < n.n_params()) {
-    const int l = n.layer_of(i);
-    const int64_t off = n.w_off(l);
-    const int64_t r = i - off;
-    const int in_d = n.in_dim(l), out_d = n.out_dim(l);
-    const int inP = (l == 0) ? 16 : WP;
-    const int wo = (l == 0) ? 0 : WP * 16 + (l - 1) * WP * WP;
-    int pidx;
-    if (r < (int64_t)in_d * out_d) {   // fragment-native block layout (fused_kernel.h, GradSink)
-      const int row = unit_at((int)(r / in_d), row_permuted(flags, l, n.L)), col = unit_at((int)(r % in_d), col_permuted(flags, l)), ntn = inP / 16;
-      const int blk = (row >> 4) * ntn + (col >> 4), ln = ((row & 15) >> 2) * 16 + (col & 15);
-      pidx = rmajor ? wo + (blk * 4 + (row & 3)) * 64 + ln : wo + (blk * 64 + ln) * 4 + (row & 3);
-    } else pidx = PW + l * WP + unit_at((int)(r - (int64_t)in_d * out_d), row_permuted(flags, l, n.L));
+    r.at = param_slot(n, WP, PW, flags, i);
     const int per = (copies + 3) / 4;
     const int c0 = grp * per, c1 = (c0 + per < copies) ? c0 + per : copies;
-    s = sum_copies(wg, PP, pidx, c0, c1);
+    s = sum_copies(wg, PP, r.at.pidx, c0, c1);
   }
   part[grp][lane_p] = s;
   __syncthreads();
-  if (grp == 0 && i < n.n_params()) grad[i] += (part[0][lane_p] + part[1][lane_p]) + (part[2][lane_p] + part[3][lane_p]);
+  r.owner = grp == 0 && i < n.n_params();
+  if (r.owner) r.g = (part[0][lane_p] + part[1][lane_p]) + (part[2][lane_p] + part[3][lane_p]);
+  return r;
+}
+
+__global__ void k_reduce_grads(Net n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
+                               float* __restrict__ grad, int flags) {
+  const ParamGrad r = grad_of_param(n, WP, wg, copies, PP, PW, flags);
+  if (r.owner) grad[r.at.i] += r.g;
 }
 
 // One kernel for everything that follows the fused pass in an Adam iteration (pinn_loss_grad_adam_step): the
-// gradient reduction of k_reduce_grads (same partial sums, same order: bit-identical), torch.optim.Adam's update
-// (k_adam's arithmetic, pinn_abi.hip) on the parameter it just summed, the refreshed entries of the packed W / W^T / b
-// the next pass reads (k_pack's mapping, inverted: padding entries stay zero), and — last block — the loss sums of
-// k_reduce_sums.  Five launches of ~4.7 us each become one at the reference's own problem sizes (N_res = 243).
+// gradient reduction of k_reduce_grads (grad_of_param), torch.optim.Adam's update (k_adam's adam_update, reduce_adam.h) on
+// the parameter it just summed, the refreshed entries of the packed W / W^T / b the next pass reads (k_pack's mapping,
+// inverted: padding entries stay zero), and — last block — the loss sums of k_reduce_sums (column_sum).  Five launches of
+// ~4.7 us each become one at the reference's own problem sizes (N_res = 243).
 __global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
                               const float* __restrict__ wg_sums, int grid, int n_terms, float* __restrict__ term_sums,
                               int n_cols, float* __restrict__ col_sums, float* __restrict__ grad,
                               float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
-                              float* __restrict__ Wp, float* __restrict__ WTp, float* __restrict__ Bp,
-                              float w1, float b2, float w2, float eps, float step_size, float bc2_sqrt,
+                              float* __restrict__ Wp, float* __restrict__ WTp, float* __restrict__ Bp, AdamScalars c,
                               int n_loss_rows, const float* __restrict__ loss_rows, float* __restrict__ losses,
                               int row_cols, int flags) {
+  if (blockIdx.x == gridDim.x - 1) {          // loss sums
 #pragma clang fp contract(off)
-  const int rmajor = (flags & PACK_RMAJOR) != 0;
-  if (blockIdx.x == gridDim.x - 1) {          // loss sums: double, fixed order (k_reduce_sums)
-    __shared__ double red[256];
     // [col sums (row_cols of them) | term sums], for the optional weighted losses.  row_cols is the CALLER's column
     // count — the stride of loss_rows (pinn_hip.h) — also when this pass carried no fidelity columns (n_cols = 0:
     // a residual-only request with n_res == N): their sums are then zeros, not a shifted layout.
@@ -276,18 +278,10 @@ __global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int c
     if (threadIdx.x < 2 * PINN_MAX_ROLES + 8) ssum[threadIdx.x] = 0.0;
     __syncthreads();
     for (int j = 0; j < n_terms + n_cols; ++j) {
-      const int t = j < n_terms ? j : MSE_SUM0 + (j - n_terms);
-      double a = 0.0;
-      for (int b = threadIdx.x; b < grid; b += 256) a += (double)wg_sums[(int64_t)b * MAX_SUMS + t];
-      red[threadIdx.x] = a;
-      __syncthreads();
-      for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-      }
+      const float sum = (float)column_sum(wg_sums, grid, MAX_SUMS, j < n_terms ? j : MSE_SUM0 + (j - n_terms));
       if (threadIdx.x == 0) {
-        if (j < n_terms) { term_sums[j] = (float)red[0]; ssum[row_cols + j] = (double)(float)red[0]; }
-        else { col_sums[j - n_terms] = (float)red[0]; ssum[j - n_terms] = (double)(float)red[0]; }
+        if (j < n_terms) { term_sums[j] = sum; ssum[row_cols + j] = (double)sum; }
+        else { col_sums[j - n_terms] = sum; ssum[j - n_terms] = (double)sum; }
       }
       __syncthreads();
     }
@@ -298,47 +292,18 @@ __global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int c
     }
     return;
   }
-  __shared__ float part[4][64];
-  const int lane_p = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int64_t i = (int64_t)blockIdx.x * 64 + lane_p;
-  float s = 0.f;
-  int l = 0, row = 0, col = 0, wo = 0, in_d = 1, out_d = 1;
-  bool is_w = false;
-  if (i < n.n_params()) {
-    l = n.layer_of(i);
-    const int64_t r = i - n.w_off(l);
-    in_d = n.in_dim(l); out_d = n.out_dim(l);
-    const int inP = (l == 0) ? 16 : WP;
-    wo = (l == 0) ? 0 : WP * 16 + (l - 1) * WP * WP;
-    int pidx;
-    is_w = r < (int64_t)in_d * out_d;
-    if (is_w) {   // fragment-native block layout (fused_kernel.h, GradSink); row / col: PADDED indices from here on
-      row = unit_at((int)(r / in_d), row_permuted(flags, l, n.L)); col = unit_at((int)(r % in_d), col_permuted(flags, l));
-      const int ntn = inP / 16;
-      const int blk = (row >> 4) * ntn + (col >> 4), ln = ((row & 15) >> 2) * 16 + (col & 15);
-      pidx = rmajor ? wo + (blk * 4 + (row & 3)) * 64 + ln : wo + (blk * 64 + ln) * 4 + (row & 3);
-    } else { row = unit_at((int)(r - (int64_t)in_d * out_d), row_permuted(flags, l, n.L)); pidx = PW + l * WP + row; }
-    const int per = (copies + 3) / 4;
-    const int c0 = grp * per, c1 = (c0 + per < copies) ? c0 + per : copies;
-    s = sum_copies(wg, PP, pidx, c0, c1);
-  }
-  part[grp][lane_p] = s;
-  __syncthreads();
-  if (grp == 0 && i < n.n_params()) {
-    const float gi = (part[0][lane_p] + part[1][lane_p]) + (part[2][lane_p] + part[3][lane_p]);
-    grad[i] = gi;
-    const float mi = m[i] + w1 * (gi - m[i]);
-    float vi = v[i] * b2;
-    vi = vi + (w2 * gi) * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float pn = params[i] - step_size * (mi / denom);
+  const ParamGrad r = grad_of_param(n, WP, wg, copies, PP, PW, flags);
+  if (r.owner) {
+    const ParamSlot& p = r.at;
+    const int64_t i = p.i;
+    grad[i] = r.g;
+    const float pn = adam_update(params[i], r.g, m[i], v[i], c);
     params[i] = pn;
-    if (is_w) {
-      const int inP = (l == 0) ? 16 : WP, outP = (l == n.L) ? 16 : WP;
-      Wp[wo + row * inP + col] = pn;
-      WTp[wo + col * outP + row] = pn;
-    } else Bp[l * WP + row] = pn;
+    if (p.is_w) {
+      const int inP = (p.l == 0) ? 16 : WP, outP = (p.l == n.L) ? 16 : WP;
+      Wp[p.wo + p.row * inP + p.col] = pn;
+      WTp[p.wo + p.col * outP + p.row] = pn;
+    } else Bp[p.l * WP + p.row] = pn;
   }
 }
 
@@ -368,7 +333,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   P.d_in = n.d_in; P.d_out = n.d_out; P.L = n.L; P.act = n.act;
   for (int j = 0; j < PINN_MAX_DIRS; ++j) P.dir_col[j] = n.dir_col[j];
   P.N = N; P.n_tiles = (N + 15) / 16;
-  P.n_split = rq ? rq->n_split : -1;
+  P.n_split = -1;
   P.X = X;
   P.Wp = (const float*)(base + w.wp); P.WTp = (const float*)(base + w.wtp); P.Bp = (const float*)(base + w.bp);
   P.scratch = (float*)(base + w.scratch);
@@ -379,31 +344,11 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   P.PW = g.PW; P.PB = g.PB;
   P.acc_lds = (grad && fits_lds(g)) ? 1 : 0;
   P.lds_acc_floats = P.acc_lds ? g.PP : 0;
-  if (rq) {
-    P.loss_kind = rq->kind == 0 ? 1 : (rq->kind == 1 ? 2 : 3);
-    if (P.loss_kind & 1) {
-      P.scale = rq->scale;
-      P.residual_id = rq->spec.residual_id;
-      for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = rq->spec.out_col[j];
-      for (int d = 0; d < PINN_MAX_DIRS; ++d) P.q_of[d] = 1 + rq->spec.dir_of[d];
-      P.thr = rq->spec.param[0]; P.anchor = rq->spec.param[1];
-      P.xcol = n.dir_col[rq->spec.dir_of[0]];
-    } else {
-      for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = -1;
-    }
-    if (P.loss_kind & 2) {
-      P.n_cols = rq->n_cols; P.T = rq->T; P.mse_scale = rq->mse_scale;
-      for (int j = 0; j < PINN_MAX_ROLES; ++j) P.mse_col[j] = j < rq->n_cols ? rq->out_col[j] : -1;
-    }
-  }
+  if (rq) set_loss(P, n, *rq);
   if (adj) { P.gY = adj->gY; P.gdY = adj->gdY; }
   if (fld) {   // the residual's roles as a residual loss sets them; nothing else of a loss request
     P.Y = fld->fields; P.dY = nullptr;   // (fused_kernel.h, FusedParams: the field instances' output array)
-    P.residual_id = fld->spec.residual_id;
-    for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = fld->spec.out_col[j];
-    for (int d = 0; d < PINN_MAX_DIRS; ++d) P.q_of[d] = 1 + fld->spec.dir_of[d];
-    P.thr = fld->spec.param[0]; P.anchor = fld->spec.param[1];
-    P.xcol = n.dir_col[fld->spec.dir_of[0]];
+    set_residual_roles(P, n, fld->spec);
   }
   // (the field epilogue exists in the tile kernel only: every kernel choice of desc.engine lands there; the external-adjoint
   // one in the tile and in the batch kernel)
@@ -424,12 +369,9 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   // 8x64 gradient kernels fill the register file and most of LDS (1 workgroup per CU); the narrow
   // networks' kernels fit 2 waves per SIMD, which hides their per-layer latencies
   const bool one_per_cu = grad && P.acc_lds && !(g.WP <= 32 && 2 * (int64_t)lds <= LDS_LIMIT);
-  int grid = grid_for(P.n_tiles, one_per_cu, g.WP == 16 && FUSED_W16_WAVES * (int64_t)lds <= LDS_LIMIT ? FUSED_W16_WAVES : 2);
-  if (adj && !batch) grid = adj_grid_for(P.n_tiles, one_per_cu, g.WP == 16 && FUSED_W16_WAVES * (int64_t)lds <= LDS_LIMIT ? FUSED_W16_WAVES : 2);
-  if (coop) {   // one workgroup per tile, at most one per CU (gradient kernels fill the LDS)
-    const int64_t cap = (int64_t)cu_count() * (grad ? 1 : 2);
-    grid = (int)(P.n_tiles < cap ? (P.n_tiles < 1 ? 1 : P.n_tiles) : cap);
-  }
+  const int per_cu = tile_wgs_per_cu(g.WP) * (int64_t)lds <= LDS_LIMIT ? tile_wgs_per_cu(g.WP) : 2;
+  int grid = adj && !batch ? adj_grid_for(P.n_tiles, one_per_cu, per_cu) : grid_for(P.n_tiles, one_per_cu, per_cu);
+  if (coop) grid = coop_grid_for(P.n_tiles, grad);
 
   if (batch) {   // one workgroup per CU, one wave per SIMD; slots of T tiles x (L - 1) layers per wave
     const int T = batch_T_for(g, n.K1, P.n_tiles);
@@ -516,17 +458,14 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
                        (const float*)P.wg_grads, n_copies, g.PP, g.PW, (const float*)P.wg_sums, grid,
                        (P.loss_kind & 1) ? rq->n_terms : 0, rq->sums, (P.loss_kind & 2) ? rq->n_cols : 0, rq->mse_sums,
                        rq->grad, adam->params, adam->m, adam->v, (float*)(base + w.wp), (float*)(base + w.wtp),
-                       (float*)(base + w.bp), adam->w1, adam->b2, adam->w2, adam->eps, adam->step_size, adam->bc2_sqrt,
-                       adam->n_loss_rows, adam->loss_rows, adam->losses, rq->n_cols, perm | (rmajor ? PACK_RMAJOR : 0));
+                       (float*)(base + w.bp), adam->c, adam->n_loss_rows, adam->loss_rows, adam->losses, rq->n_cols, perm | (rmajor ? PACK_RMAJOR : 0));
     return check_launch("fused finish + adam");
   }
   if (rq) {
     if (P.loss_kind & 1)
-      hipLaunchKernelGGL(k_reduce_sums, dim3(rq->n_terms), dim3(256), 0, s, (const float*)P.wg_sums, grid, 0,
-                         rq->n_terms, rq->sums);
+      reduce_sums(P.wg_sums, grid, MAX_SUMS, 0, rq->n_terms, rq->sums, s);
     if (P.loss_kind & 2)
-      hipLaunchKernelGGL(k_reduce_sums, dim3(rq->n_cols), dim3(256), 0, s, (const float*)P.wg_sums, grid, MSE_SUM0,
-                         rq->n_cols, rq->mse_sums);
+      reduce_sums(P.wg_sums, grid, MAX_SUMS, MSE_SUM0, rq->n_cols, rq->mse_sums, s);
     if (grad) {
       const int copies = n_copies;
       const int64_t np = n.n_params();

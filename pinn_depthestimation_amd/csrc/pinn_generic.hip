@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "common.h"
 #include "residuals.h"
+#include "reduce_adam.h"
 
 namespace pinn {
 
@@ -281,23 +282,6 @@ __global__ void k_mse(const float* __restrict__ y, int d_out, int64_t N, MseMap 
   block_reduce_store<PINN_MAX_ROLES>(sq, partial);
 }
 
-__global__ void k_reduce_partials(const float* __restrict__ partial, int64_t nblocks, int nt_stride, int nt,
-                                  float* __restrict__ out) {
-  // one block per term; fixed summation order -> deterministic
-  const int t = blockIdx.x;
-  if (t >= nt) return;
-  __shared__ double red[256];
-  double v = 0.0;
-  for (int64_t b = threadIdx.x; b < nblocks; b += 256) v += (double)partial[b * nt_stride + t];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[t] = (float)red[0];
-}
-
 // G[c][o][n] from row-major gY (N,d_out) / gdY (k,N,d_out)
 template <int K1>
 __global__ void k_seed_adjoint(const float* __restrict__ gY, const float* __restrict__ gdY, int d_out, int64_t N,
@@ -333,7 +317,6 @@ inline int maxdim(const Net& n) {
   if (n.d_out > m) m = n.d_out;
   return m;
 }
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 struct Layout {
   int64_t act_off[1024 + 2];  // a_0 .. a_L, then out
@@ -429,16 +412,15 @@ int run_loss(const Net& n, const LossReq& rq, const float* params, const float* 
     else if (id == PINN_RES_CONTINUITY_ONLY) LAUNCH_RES(ResContinuity, 1, n.dir_col[rq.spec.dir_of[0]]);
     else { set_error("unknown residual_id %d", id); return PINN_ERR_INVALID; }
 #undef LAUNCH_RES
-    hipLaunchKernelGGL(k_reduce_partials, dim3(rq.n_terms), dim3(256), 0, s, (const float*)partial, lo.nblocks,
-                       nt_stride, rq.n_terms, rq.sums);
+    // (one block per term, fixed summation order: deterministic)
+    reduce_sums(partial, lo.nblocks, nt_stride, 0, rq.n_terms, rq.sums, s);
   }
   if (rq.kind == 1 || rq.kind == 2) {   // fidelity columns; adds into G (pre-zeroed / after the residual's writes)
     MseMap mm; mm.n_cols = rq.n_cols;
     for (int j = 0; j < PINN_MAX_ROLES; ++j) mm.out_col[j] = j < rq.n_cols ? rq.out_col[j] : 0;
     if (want_grad) hipLaunchKernelGGL(k_mse<true>, dim3(grid), dim3(TPB), 0, s, out, n.d_out, N, mm, rq.T, rq.mse_scale, G, partial, n0);
     else hipLaunchKernelGGL(k_mse<false>, dim3(grid), dim3(TPB), 0, s, out, n.d_out, N, mm, rq.T, rq.mse_scale, G, partial, n0);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(rq.n_cols), dim3(256), 0, s, (const float*)partial, lo.nblocks,
-                       PINN_MAX_ROLES, rq.n_cols, rq.mse_sums);
+    reduce_sums(partial, lo.nblocks, PINN_MAX_ROLES, 0, rq.n_cols, rq.mse_sums, s);
   }
   rc = check_launch("generic loss");
   if (rc || !want_grad) return rc;

@@ -420,8 +420,6 @@ __global__ void k2_unseed(const float* __restrict__ out, int d_out, int64_t N, i
 }
 
 // ---- workspace ---------------------------------------------------------------------
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 struct Layout2 {
   int64_t Nc;            // points per chunk
   int64_t act_off[1026]; // post-activation jets a_0 .. a_L (a_0 = the seeds)

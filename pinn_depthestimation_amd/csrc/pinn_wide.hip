@@ -2,6 +2,7 @@
 // point loop, per-layer launches.  Kernels: wide_kernel.h.
 #include <type_traits>
 #include "chain_kernel.h"
+#include "reduce_adam.h"
 
 namespace pinn {
 
@@ -17,7 +18,6 @@ WGeo wgeo(const Net& n) {
   g.PB = n.L * g.WP + 16;
   return g;
 }
-int64_t al256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 // bytes between the 1 KB pieces of a packed weight slab (k_chain_pack): all slabs' piece i, rounded up to 64 KB, + 4 KB
 int64_t chain_plane_bytes(int nh, int NTW) {
   const int64_t slabs = (int64_t)(nh > 0 ? nh : 1) * NTW * 1024;
@@ -57,12 +57,12 @@ WLayout wlayout(const Net& n, const WGeo& g, int64_t N) {
   w.chunk_pts = cp; w.chunk_tiles = cp / 16; w.n_chunks = (npad + cp - 1) / cp;
   w.grid = cus();
   int64_t off = 0;
-  w.wp = off; off += al256((int64_t)g.PW * 4);
-  w.wtp = off; off += al256((int64_t)g.PW * 4);
-  w.bp = off; off += al256((int64_t)g.PB * 4);
-  w.wp16 = off; off += al256((int64_t)g.PW * 2);
-  w.wtp16 = off; off += al256((int64_t)g.PW * 2);
-  w.act_stride = al256(w.chunk_tiles * K1 * g.NTW * 256 * 4);
+  w.wp = off; off += align256((int64_t)g.PW * 4);
+  w.wtp = off; off += align256((int64_t)g.PW * 4);
+  w.bp = off; off += align256((int64_t)g.PB * 4);
+  w.wp16 = off; off += align256((int64_t)g.PW * 2);
+  w.wtp16 = off; off += align256((int64_t)g.PW * 2);
+  w.act_stride = align256(w.chunk_tiles * K1 * g.NTW * 256 * 4);
   w.act = w.gA = w.gB = w.gZ = 0;
   w.wf = w.wtf = w.jA = w.jZ = w.jGL = w.jG1 = w.jet_stride = 0;
   if (!chain) {
@@ -73,15 +73,15 @@ WLayout wlayout(const Net& n, const WGeo& g, int64_t N) {
     const int64_t frag = chain_plane_bytes(n.L - 1, g.NTW) * g.NTW;          // hi + lo bf16 per hidden matrix: 2 NS = NTW piece planes
     w.wf = off; off += frag;
     w.wtf = off; off += frag;
-    w.jet_stride = al256(w.chunk_tiles * K1 * g.NTW * 256 * 2);
+    w.jet_stride = align256(w.chunk_tiles * K1 * g.NTW * 256 * 2);
     w.jA = off; off += w.jet_stride * n.L;
     w.jZ = off; off += w.jet_stride * (n.L > 1 ? n.L - 1 : 0);
     w.jGL = off; off += w.jet_stride;
     if (n.L > 1) { w.jG1 = off; off += w.jet_stride; }
     else w.jG1 = w.jGL;                                  // no hidden matrix: abar_1 is abar_L
   }
-  w.gout = off; off += al256(w.chunk_tiles * K1 * 256 * 4);
-  w.sums = off; off += al256(w.n_chunks * SUM_ROWS_PER_CU * w.grid * MAX_SUMS * 4);   // one row of loss partials per workgroup
+  w.gout = off; off += align256(w.chunk_tiles * K1 * 256 * 4);
+  w.sums = off; off += align256(w.n_chunks * SUM_ROWS_PER_CU * w.grid * MAX_SUMS * 4);   // one row of loss partials per workgroup
   w.total = off;
   return w;
 }
@@ -111,18 +111,6 @@ __global__ void k_wide_pack(Net n, int WP, const float* __restrict__ params, flo
     if (l >= n.L) { l = n.L; o = i - n.L * WP; }
     Bp[i] = (o < n.out_dim(l)) ? params[n.b_off(l) + o] : 0.f;
   }
-}
-
-__global__ void k_wide_reduce_sums(const float* __restrict__ wg_sums, int64_t rows, int col0, int nt,
-                                   float* __restrict__ out) {
-  const int t = col0 + blockIdx.x;
-  __shared__ double red[256];
-  double v = 0.0;
-  for (int64_t b = threadIdx.x; b < rows; b += 256) v += (double)wg_sums[b * MAX_SUMS + t];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s]; __syncthreads(); }
-  if (threadIdx.x == 0 && blockIdx.x < nt) out[blockIdx.x] = (float)red[0];
 }
 
 // Hidden matrices W_1 .. W_{L-1} -> MFMA fragment order for the chain kernels (chain_kernel.h), hi + lo bf16:
@@ -170,25 +158,9 @@ int run_w(const Net& n, const WGeo& g, bool grad, const LossReq* rq, const float
   P.d_in = n.d_in; P.d_out = n.d_out; P.L = n.L; P.act = n.act;
   for (int j = 0; j < PINN_MAX_DIRS; ++j) P.dir_col[j] = n.dir_col[j];
   P.N = N; P.X = X; P.Y = Y; P.dY = dY;
-  P.n_split = rq ? rq->n_split : -1;
+  P.n_split = -1;
   P.wg_sums = (float*)(base + w.sums);
-  if (rq) {
-    P.loss_kind = rq->kind == 0 ? 1 : (rq->kind == 1 ? 2 : 3);
-    if (P.loss_kind & 1) {
-      P.scale = rq->scale;
-      P.residual_id = rq->spec.residual_id;
-      for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = rq->spec.out_col[j];
-      for (int d = 0; d < PINN_MAX_DIRS; ++d) P.q_of[d] = 1 + rq->spec.dir_of[d];
-      P.thr = rq->spec.param[0]; P.anchor = rq->spec.param[1];
-      P.xcol = n.dir_col[rq->spec.dir_of[0]];
-    } else {
-      for (int j = 0; j < PINN_MAX_ROLES; ++j) P.out_col[j] = -1;
-    }
-    if (P.loss_kind & 2) {
-      P.n_cols = rq->n_cols; P.T = rq->T; P.mse_scale = rq->mse_scale;
-      for (int j = 0; j < PINN_MAX_ROLES; ++j) P.mse_col[j] = j < rq->n_cols ? rq->out_col[j] : -1;
-    }
-  }
+  if (rq) set_loss(P, n, *rq);
   const float* Wp = (const float*)(base + w.wp);
   const float* WTp = (const float*)(base + w.wtp);
   const float* Bp = (const float*)(base + w.bp);
@@ -371,11 +343,9 @@ int run_w(const Net& n, const WGeo& g, bool grad, const LossReq* rq, const float
   if (rc) return rc;
   if (rq) {
     if (P.loss_kind & 1)
-      hipLaunchKernelGGL(k_wide_reduce_sums, dim3(rq->n_terms), dim3(256), 0, s, (const float*)P.wg_sums,
-                         (int64_t)w.n_chunks * SUM_ROWS_PER_CU * w.grid, 0, rq->n_terms, rq->sums);
+      reduce_sums(P.wg_sums, (int64_t)w.n_chunks * SUM_ROWS_PER_CU * w.grid, MAX_SUMS, 0, rq->n_terms, rq->sums, s);
     if (P.loss_kind & 2)
-      hipLaunchKernelGGL(k_wide_reduce_sums, dim3(rq->n_cols), dim3(256), 0, s, (const float*)P.wg_sums,
-                         (int64_t)w.n_chunks * SUM_ROWS_PER_CU * w.grid, MSE_SUM0, rq->n_cols, rq->mse_sums);
+      reduce_sums(P.wg_sums, (int64_t)w.n_chunks * SUM_ROWS_PER_CU * w.grid, MAX_SUMS, MSE_SUM0, rq->n_cols, rq->mse_sums, s);
   }
   return check_launch("wide reductions");
 }
