@@ -158,7 +158,12 @@ typedef struct pinn_residual_spec {
                                       are ignored, whatever they hold) */
   int32_t dir_of[PINN_MAX_DIRS];   /* index into desc.dir_col of each direction role (entries beyond the residual's
                                       directions are ignored) */
-  int32_t flags;                   /* bit0: 1 = "corrected" radiation stress (unused; E==0 bug-compatible, physics.py:106) */
+  int32_t flags;                   /* bit 0 with residual_id == PINN_RES_PHYSICS_EQUATION: the corrected radiation stress,
+                                      E = rho g Hrms^2 / 8, Sxx = E (2n + 1/2), Syy = E n, n = kh / sinh 2kh, in place of
+                                      the reference's E == 0 (physics.py:106); same roles, directions, terms and fields.
+                                      Honoured by every entry that takes a spec (engine rules: pinn_residual_loss_grad
+                                      and pinn_residual_fields below).  Bit 0 on the other residuals and all other bits
+                                      are ignored. */
   float param[4];                  /* continuity_only: param[0]=threshold (25.5), param[1]=anchor (0.75) */
 } pinn_residual_spec;
 
@@ -168,6 +173,13 @@ int32_t pinn_version(void);
  * the kernels apply (host evaluation of the same function; for tests and for callers that want the mask). */
 int32_t pinn_dropout_keep(uint32_t seed, int32_t layer, int32_t feature, int64_t point, float p);
 const char* pinn_last_error(void);
+
+/* The corrected physics_equation residual (spec.flags bit 0) at ONE point, evaluated on the host by the very functions the
+ * kernels call (for tests and for callers that want to check a jet by hand; no device is touched).
+ * v[c * 6 + r]: c = 0 the value, 1 the x-derivative, 2 the y-derivative of role r = h, U, V, eta_mean, Hrms, k.
+ * fields <- (fc, fx, fy).  g[c * 6 + r] <- sum_t scale[t] * d(field_t^2) / dv; with scale or g NULL only the fields are
+ * formed and g is left alone.  At kh = 0 the stress ratio takes its limit (n = 1/2, n' = 0, n'' = -2/3). */
+int32_t pinn_pe_corrected_point(const float v[18], const float scale[3], float fields[3], float g[18]);
 
 /* P = sum_l (in_l*out_l + out_l), layers = [d_in] + [width]*n_hidden + [d_out] (train.py:56) */
 int32_t pinn_param_count(const pinn_desc* desc, int64_t* count);
@@ -236,7 +248,17 @@ int32_t pinn_jet2_backward(const pinn_desc* desc, const float* params, const flo
                            const float* gY, const float* gdY, const float* gd2Y, float* grad_flat,
                            void* ws, int64_t ws_bytes, void* stream);
 
-/* term_sums[t] = sum over points of (residual field t)^2  (device, n_terms floats, overwritten) */
+/* term_sums[t] = sum over points of (residual field t)^2  (device, n_terms floats, overwritten)
+ * Corrected radiation stress (spec.flags bit 0 on physics_equation) — the rule of every loss entry that takes a spec
+ * (pinn_residual_loss, pinn_residual_loss_grad, pinn_residual_mse_loss_grad, pinn_residual_mse_split_loss_grad,
+ * pinn_loss_grad_adam_step, pinn_adam_loop): the request runs on the engine the descriptor selects, or is refused with
+ * PINN_ERR_UNSUPPORTED and the word "corrected" in pinn_last_error(); it is never moved to another engine (pinn_query_workspace
+ * does not see the spec).  GENERIC: any shape, tanh or LeakyReLU, dropout, k = 2 or 3.  FUSED: tanh, k = 2, dropout_p == 0 — on
+ * the batch kernel where a gradient request of that shape runs there, else on the tile kernel (also under FUSED_COOP and at
+ * the small N where the cooperative kernel would serve the plain residual: it has no such instance); the split request is
+ * one pass at every width.  LeakyReLU and k = 3 on FUSED are refused (use GENERIC).  Every descriptor whose engine comes out
+ * as WIDE — width 65..256 under AUTO or WIDE, bf16 — is refused (use GENERIC).  With dropout_p > 0 AUTO runs the generic
+ * engine (the fused dropout instances do not carry the corrected residual) and FUSED is refused. */
 int32_t pinn_residual_loss(const pinn_desc* desc, const pinn_residual_spec* spec,
                            const float* params, const float* X, int64_t N,
                            float* term_sums, void* ws, int64_t ws_bytes, void* stream);
@@ -252,7 +274,11 @@ int32_t pinn_residual_loss(const pinn_desc* desc, const pinn_residual_spec* spec
  * area in the workspace, 65536 points at a time, then one point-wise fp32 kernel per chunk (the precision mode belongs to
  * the jet).  AUTO: the MFMA path where FUSED would be served, else the staged one on the engine AUTO picks for
  * pinn_forward_jet.  With dropout_p > 0 (staged path only) the mask's point index restarts at every chunk.
- * The call has a workspace of its own (pinn_query_workspace answers what it always did). */
+ * The call has a workspace of its own (pinn_query_workspace answers what it always did).
+ * Corrected radiation stress (spec.flags bit 0 on physics_equation): k must be 2.  AUTO and FUSED run the tile kernel's own
+ * field instances where FUSED serves fields and the network is tanh; LeakyReLU under FUSED is refused ("corrected" in the
+ * message), under AUTO it is staged like every GENERIC and WIDE request.  pinn_query_fields_workspace takes the spec and
+ * answers for the path the call will take. */
 #define PINN_NS_FIELDS 3
 #define PINN_PE_FIELDS 3
 #define PINN_CF_FIELDS 2

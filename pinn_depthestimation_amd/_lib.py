@@ -60,6 +60,7 @@ _SIGNATURES = {
     "pinn_version": (C.c_int32, []),
     "pinn_last_error": (C.c_char_p, []),
     "pinn_dropout_keep": (C.c_int32, [C.c_uint32, C.c_int32, C.c_int32, C.c_int64, C.c_float]),
+    "pinn_pe_corrected_point": (C.c_int32, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "pinn_param_count": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(C.c_int64)]),
     "pinn_query_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_forward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),

@@ -423,9 +423,20 @@ class _FusedResidual(torch.autograd.Function):
         return (None, None, None, *_split_flat(ctx.model, ctx.grad * g))
 
 
-def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequence[torch.Tensor]):
+def _corrected_is_served(model, handle) -> bool:
+    """Whether the engine AUTO picks for this forward call serves the corrected radiation stress (pinn_hip.h): the
+    fused engine for tanh networks at most 64 wide with two differentiated inputs, the generic one under dropout."""
+    if float(handle.drop[0]) > 0.0:
+        return True
+    return (max(model.layer_sizes[1:-1]) <= 64 and model.init_type == "xavier" and len(handle.grad_cols) == 2
+            and model.layer_sizes[0] <= 16 and model.layer_sizes[-1] <= 16)
+
+
+def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequence[torch.Tensor], corrected: bool = False):
     """Return the fused loss tensor if every argument is recognisably (input column of /
-    output column of) one DNN.forward call, else None."""
+    output column of) one DNN.forward call, else None.  corrected=True (physics_equation only): the corrected
+    radiation stress, hard-wired in the kernels (ResidualSpec.corrected); None as well where the engine that would run
+    the call does not serve it."""
     handle = None
     out_col: List[int] = []
     for o in out_vars:
@@ -444,6 +455,10 @@ def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequenc
         if j is None:
             return None
         dir_of.append(j)
-    spec = ResidualSpec(name, tuple(out_col), tuple(dir_of))
+    if corrected and name != "physics_equation":
+        raise PinnError(f"corrected=True is the radiation stress of physics_equation; residual {name!r} has none")
+    spec = ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected))
     model = handle.model
+    if corrected and not _corrected_is_served(model, handle):
+        return None
     return _FusedResidual.apply(model, handle, spec, *model._ordered_params())

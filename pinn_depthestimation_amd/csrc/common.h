@@ -60,6 +60,11 @@ __host__ __device__ inline uint32_t dropout_threshold(float p) {
 // torch.optim.Adam's scalars, formed in double as Python forms them and cast to fp32 once (adam_scalars, reduce_adam.h)
 struct AdamScalars { float w1, b2, w2, eps, step_size, bc2_sqrt; };   // 1 - b1, b2, 1 - b2, eps, lr / bc1, sqrt(bc2)
 
+// pinn_residual_spec.flags bit 0 on PINN_RES_PHYSICS_EQUATION (the corrected radiation stress, residuals.h:
+// ResPhysicsEquationCorrected) travels inside the library as a residual id of its own: check_spec (pinn_abi.hip) writes it
+// into the NORMALISED spec, no caller can pass it and pinn_hip.h does not know it.
+constexpr int RES_PE_CORRECTED = 5;
+
 // what a loss call asks the engines for
 // torch.optim.Adam's update folded into the kernel that finishes a loss + gradient pass (pinn_loss_grad_adam_step)
 struct AdamReq {
@@ -121,6 +126,8 @@ int fused_jet_backward(const Net& n, const float* params, const float* X, int64_
 
 // pinn_residual_fields on the tile kernel (fused_kernel.h, EPI_FIELD): fields (NF, N) of the residual in `spec`
 bool fused_fields_supports(const Net& n);
+// ... and whether the fused engine serves a corrected-radiation-stress loss request (RES_PE_CORRECTED); if not, why not
+const char* fused_corrected_refusal(const Net& n);
 int64_t fused_fields_workspace_bytes(const Net& n);
 int fused_residual_fields(const Net& n, const pinn_residual_spec& spec, const float* params, const float* X, int64_t N,
                           float* fields, void* ws, int64_t ws_bytes, hipStream_t s);

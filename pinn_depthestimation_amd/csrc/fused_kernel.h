@@ -664,7 +664,11 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 // comes from the caller (load_adjoint below) and loss_epilogue is not called at all.
 // EPI_FIELD (pinn_residual_fields): forward only — the residual's signed field values of every point are stored
 // (field_epilogue below) and nothing else happens: no sums, no Y / dY stores, no adjoint, no reverse sweep.
-constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5;
+// EPI_PEC: the loss epilogue with the residual family fixed to ResPhysicsEquationCorrected (pec_epilogue below): serves what
+// EPI_GENERIC serves (residual, residual + fidelity columns, split mode) but stores no Y / dY.  EPI_FIELD_PEC: EPI_FIELD
+// for that residual.  Both are compile-time choices with translation units of their own (pinn_fused_pec_wXX.hip,
+// pinn_fused_batch_pec_wXX_k3.hip), so the generic epilogues do not grow by a branch.
+constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5, EPI_PEC = 6, EPI_FIELD_PEC = 7;
 
 // The mirror of the generic epilogue's Y / dY store: lane (p, q), register r of G[c][0] is output o = 4q + r of point pt;
 // G[0] <- gY, G[c] <- gdY row c - 1.  Zero for o >= d_out, for the invalid points of the last tile and for a null array.
@@ -718,13 +722,44 @@ __device__ __forceinline__ void field_epilogue(const FusedParams& P, const f4 (&
   }
 }
 
+// EPI_PEC: loss_epilogue_impl's generic part (below) with ONE residual family and without the output stores — the split
+// rule and the fidelity columns are its lines, repeated here because that function must stay as the compiler sees it today.
+template <int K1, bool GRAD, bool SPLIT>
+__device__ __forceinline__ void pec_epilogue(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
+                                             float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
+                                             const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
+                                             int64_t ptc, bool valid, int p, int q) {
+  static_assert(K1 == 3, "EPI_PEC: K1 = 1 + the residual's two directions");
+#pragma unroll
+  for (int c = 0; c < K1; ++c) G[c][0] = f4{0.f, 0.f, 0.f, 0.f};
+  const bool valid_r = SPLIT ? (valid && pt < P.n_split) : valid;
+  const bool valid_m = SPLIT ? (valid && pt >= P.n_split) : valid;
+  if (P.loss_kind & 1) residual_tile<ResPhysicsEquationCorrected, K1, GRAD>(P, out, G, sums, sm, tb, valid_r, false, p, q);
+  if (P.loss_kind & 2) {
+    float gm[1][PINN_MAX_ROLES];
+#pragma unroll
+    for (int j = 0; j < PINN_MAX_ROLES; ++j) {
+      gm[0][j] = 0.f;
+      if (j < P.n_cols) {
+        const float y = gather_out(out[0][0], P.mse_col[j], p);
+        const int64_t trow = SPLIT ? (valid_m ? ptc - P.n_split : 0) : ptc;
+        const float d = P.T[trow * P.n_cols + j] - y;                 // train.py:141 (true - pred)
+        if (valid_m && q == 0) sums[MSE_SUM0 + j] += d * d;
+        if (GRAD) gm[0][j] = -2.f * P.mse_scale[j] * d;
+      }
+    }
+    if constexpr (GRAD) scatter_adjoint<K1, 1, PINN_MAX_ROLES, true>(tb, gm, sm_mse, G, valid_m, p, q);
+  }
+}
+
 template <int K1, bool GRAD, bool SPLIT, int EPI = EPI_GENERIC>
 __device__ __forceinline__ void loss_epilogue_impl(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
                                               float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
                                               const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
                                               int64_t ptc, bool valid, int p, int q, bool primary = true) {
   static_assert(EPI != EPI_ADJ, "EPI_ADJ has no epilogue: k_fused calls load_adjoint instead");
-  static_assert(EPI != EPI_FIELD, "EPI_FIELD has its own epilogue: k_fused calls field_epilogue instead");
+  static_assert(EPI != EPI_FIELD && EPI != EPI_FIELD_PEC, "EPI_FIELD has its own epilogue: k_fused calls field_epilogue instead");
+  static_assert(EPI != EPI_PEC, "EPI_PEC has its own epilogue: loss_epilogue calls pec_epilogue instead");
   // EPI != 0: an epilogue specialised to ONE residual family, residual loss only, no output stores.
   // The generic epilogue keeps every family, the fidelity columns and the Y/dY stores behind runtime
   // switches; at width 64 that costs 146 spilled SGPRs (372 v_readlane per tile) against 4 with the
@@ -803,13 +838,19 @@ __device__ __forceinline__ void loss_epilogue(const FusedParams& P, const f4 (&o
                                               float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
                                               const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
                                               int64_t ptc, bool valid, int p, int q, bool primary = true) {
-  if constexpr (SPLIT_OK && EPI == EPI_GENERIC) {
+  if constexpr (EPI == EPI_PEC) {     // (primary: the cooperative kernel's, which has no such instance)
+    if constexpr (SPLIT_OK) {
+      if (P.n_split >= 0) { pec_epilogue<K1, GRAD, true>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q); return; }
+    }
+    pec_epilogue<K1, GRAD, false>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+    return;
+  } else if constexpr (SPLIT_OK && EPI == EPI_GENERIC) {
     if (P.n_split >= 0) {
       loss_epilogue_impl<K1, GRAD, true>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q, primary);
       return;
     }
   }
-  loss_epilogue_impl<K1, GRAD, false, EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q, primary);
+  if constexpr (EPI != EPI_PEC) loss_epilogue_impl<K1, GRAD, false, EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q, primary);
 }
 
 // Diagnostic build only (-DPINN_DIAG): s_memtime stamps per phase, printed by wave 0 of block 0.
@@ -839,6 +880,8 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
   static_assert(!DROP || (ACT == PINN_ACT_TANH && KRO == 0), "dropout instances: tanh, natural unit order");
   static_assert(EPI != EPI_ADJ || (GRAD && KRO == 0 && !DROP), "external-adjoint instances: gradient pass, natural unit order, no dropout");
   static_assert(EPI != EPI_FIELD || (!GRAD && !LDSACC && KRO == 0 && !DROP), "field instances: forward only, natural unit order, no dropout");
+  static_assert(EPI != EPI_FIELD_PEC || (!GRAD && !LDSACC && KRO == 0 && !DROP && K1 == 3), "field instances: forward only, natural unit order, no dropout");
+  static_assert(EPI != EPI_PEC || (KRO == 0 && !DROP && K1 == 3 && ACT == PINN_ACT_TANH), "corrected-residual instances: tanh, k = 2, natural unit order, no dropout");
   constexpr bool IO1 = KRO > 0;
   constexpr int KRI = IO1 ? 1 : 4;          // k-steps of the first layer's contraction (d_in <= 4 when IO1)
   constexpr int KRL = IO1 ? KRO : 4;        // k-steps of the output layer's reverse contraction
@@ -969,7 +1012,8 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
 
     // ---- outputs / loss -----------------------------------------------------------------------
     if constexpr (EPI == EPI_FIELD) field_epilogue<K1>(P, out, pt, ptc, valid, p, q);
-    else if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+    else if constexpr (EPI == EPI_FIELD_PEC) field_tile<ResPhysicsEquationCorrected, K1>(P, out, pt, valid, false, p, q);
+    else if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64 || EPI == EPI_PEC), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
 
     PINN_STAMP(2);
     // ---- reverse sweep ------------------------------------------------------------------------
@@ -1019,7 +1063,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
   }
 #endif
 
-  if constexpr (EPI == EPI_FIELD) return;   // nothing to reduce: the fields are already where they belong
+  if constexpr (EPI == EPI_FIELD || EPI == EPI_FIELD_PEC) return;   // nothing to reduce: the fields are already where they belong
   // ---- per-workgroup reductions ------------------------------------------------------------------
 #pragma unroll
   for (int j = 0; j < MAX_SUMS; ++j) {
@@ -1050,5 +1094,11 @@ int launch_fused_adj(int K1, const FusedParams& P, int grid, size_t lds_bytes, h
 // field instances: pinn_fused_field.inc, one translation unit per WP (pinn_fused_field_wXX.hip)
 template <int WP>
 int launch_fused_field(int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+// corrected-radiation-stress instances (EPI_PEC loss, EPI_FIELD_PEC fields; K1 = 3, tanh): pinn_fused_pec.inc, one
+// translation unit per WP (pinn_fused_pec_wXX.hip)
+template <int WP>
+int launch_fused_pec(bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+template <int WP>
+int launch_fused_field_pec(const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 
 }  // namespace pinn

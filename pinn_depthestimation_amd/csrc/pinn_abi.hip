@@ -6,6 +6,7 @@
 #include <vector>
 #include "common.h"
 #include "reduce_adam.h"
+#include "residuals.h"
 
 namespace pinn {
 
@@ -169,10 +170,35 @@ static int64_t engine_workspace_bytes(int engine, const Net& n, int64_t N) {
        : engine == PINN_ENGINE_WIDE ? wide_workspace_bytes(n, N) : generic_workspace_bytes(n, N);
 }
 
+// A request with the corrected radiation stress (spec.flags bit 0 -> RES_PE_CORRECTED, check_spec) is served on the engine
+// pick_engine chose for the descriptor (*e) or refused with the reason — never moved to another engine, whose workspace
+// pinn_query_workspace (which does not see the spec) may not have covered.  The one exception: with dropout_p > 0 the fused
+// dropout instances count as absent and AUTO runs the generic engine, which the query of a dropout descriptor covers
+// already (its forward calls run there).  Pure host logic: nothing touches a device before a refusal.
+static int corrected_engine(const pinn_desc* desc, const Net& n, const LossReq& rq, int* e) {
+  if (rq.kind == 1 || rq.spec.residual_id != RES_PE_CORRECTED) return PINN_OK;
+  if (*e == PINN_ENGINE_WIDE) {
+    set_error("the corrected radiation stress (spec.flags bit 0) is not implemented on the wide engine (width 65..256, "
+              "bf16 operands): width %d, precision %d; use engine GENERIC in fp32", n.W, n.prec);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (*e == PINN_ENGINE_FUSED && n.drop_p > 0.f && asked_engine(desc) == PINN_ENGINE_AUTO) *e = PINN_ENGINE_GENERIC;
+  if (*e == PINN_ENGINE_FUSED) {
+    if (const char* why = fused_corrected_refusal(n)) {
+      set_error("the corrected radiation stress (spec.flags bit 0) %s (activation %d, k %d, dropout_p %g)", why, n.act, n.k,
+                (double)n.drop_p);
+      return PINN_ERR_UNSUPPORTED;
+    }
+  }
+  return PINN_OK;
+}
+
 // runs rq on the engine pick_engine() chooses for it
 static int run_loss(const pinn_desc* desc, const Net& n, bool want_grad, const LossReq& rq, const float* params,
                     const float* X, int64_t N, void* ws, int64_t ws_bytes, void* stream) {
-  int rc; const int e = pick_engine(desc, n, want_grad, &rc); if (rc) return rc;
+  int rc; int e = pick_engine(desc, n, want_grad, &rc);
+  if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
+  if (rc) return rc;
   const hipStream_t s = (hipStream_t)stream;
   return e == PINN_ENGINE_FUSED ? fused_loss(n, rq, params, X, N, ws, ws_bytes, s)
        : e == PINN_ENGINE_WIDE ? wide_loss(n, rq, params, X, N, ws, ws_bytes, s)
@@ -212,6 +238,8 @@ static int residual_n_fields(int id) { const ResidualInfo* r = residual_info(id)
 // real role sat there, and the output adjoint of that column was read from beyond the roles' rows.
 static int check_spec(const Net& n, const pinn_residual_spec* sp, pinn_residual_spec* norm) {
   if (!sp) { set_error("spec is NULL"); return PINN_ERR_INVALID; }
+  // (RES_PE_CORRECTED, the library's own id of the corrected physics_equation, is no id a caller may pass: the table
+  // holds the four public ones)
   const ResidualInfo* ri = residual_info(sp->residual_id);
   if (!ri) { set_error("unknown residual_id %d", sp->residual_id); return PINN_ERR_INVALID; }
   const int nr = ri->roles, nd = ri->dirs;
@@ -228,6 +256,8 @@ static int check_spec(const Net& n, const pinn_residual_spec* sp, pinn_residual_
   *norm = *sp;
   for (int r = nr; r < PINN_MAX_ROLES; ++r) norm->out_col[r] = -1;
   for (int d = nd; d < PINN_MAX_DIRS; ++d) norm->dir_of[d] = -1;
+  // flags bit 0 on physics_equation: the corrected radiation stress, carried as an id of its own from here on
+  if (sp->residual_id == PINN_RES_PHYSICS_EQUATION && (sp->flags & 1)) norm->residual_id = RES_PE_CORRECTED;
   return PINN_OK;
 }
 
@@ -257,6 +287,20 @@ int32_t pinn_dropout_keep(uint32_t seed, int32_t layer, int32_t feature, int64_t
   return dropout_bits(seed, (uint32_t)layer, (uint32_t)feature, (uint64_t)point) >= dropout_threshold(p) ? 1 : 0;
 }
 const char* pinn_last_error(void) { return g_err; }
+
+int32_t pinn_pe_corrected_point(const float v[18], const float scale[3], float fields[3], float g[18]) {
+  typedef ResPhysicsEquationCorrected R;
+  if (!v || !fields) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
+  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], sq[R::NT];
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
+  R::fields(jet, *reinterpret_cast<float (*)[R::NF]>(fields));
+  if (!scale || !g) return PINN_OK;
+  R::eval<true>(jet, scale, gj, sq);
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
+  return PINN_OK;
+}
 
 int32_t pinn_param_count(const pinn_desc* desc, int64_t* count) {
   Net n; int rc = make_net(desc, &n); if (rc) return rc;
@@ -465,7 +509,9 @@ int32_t pinn_loss_grad_adam_step(const pinn_desc* desc, const pinn_residual_spec
   rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
   if (n_res == N) { rq.kind = 0; rq.n_split = -1; }      // residual term only
   else { rq.kind = 2; rq.n_split = n_res < 0 ? -1 : n_res; }
-  const int e = pick_engine(desc, n, true, &rc); if (rc) return rc;
+  int e = pick_engine(desc, n, true, &rc);
+  if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
+  if (rc) return rc;
   if (e != PINN_ENGINE_FUSED || !fused_supports_adam(n, rq, N)) {
     set_error("pinn_loss_grad_adam_step: needs a one-pass request on the fused engine (use the loss call + pinn_adam_step)");
     return PINN_ERR_UNSUPPORTED;
@@ -519,14 +565,22 @@ static int fields_plan(const pinn_desc* desc, const pinn_residual_spec* spec, in
                        FieldsPlan* pl) {
   int rc = make_net(desc, n); if (rc) return rc;
   rc = check_spec(*n, spec, nspec); if (rc) return rc;
-  if (n->k != residual_dirs(nspec->residual_id)) {
-    set_error("pinn_residual_fields: the network carries k = %d tangent directions, residual %d has %d (k must equal the "
-              "residual's number of directions)", n->k, nspec->residual_id, residual_dirs(nspec->residual_id));
+  const bool corrected = nspec->residual_id == RES_PE_CORRECTED;
+  if (n->k != residual_dirs(spec->residual_id)) {
+    set_error("pinn_residual_fields: the network carries k = %d tangent directions, residual %d%s has %d (k must equal the "
+              "residual's number of directions)", n->k, spec->residual_id, corrected ? " (corrected radiation stress)" : "",
+              residual_dirs(spec->residual_id));
     return PINN_ERR_UNSUPPORTED;
   }
   if (N < 1) { set_error("pinn_residual_fields: N = %lld, need at least one point", (long long)N); return PINN_ERR_INVALID; }
   const int asked = asked_engine(desc);
-  const bool fused_ok = fused_fields_supports(*n);
+  // (the corrected radiation stress: the tile kernel's EPI_FIELD_PEC instances, tanh only; everything else is staged)
+  if (corrected && asked == PINN_ENGINE_FUSED && fused_fields_supports(*n) && fused_corrected_refusal(*n)) {
+    set_error("pinn_residual_fields on the fused engine: the corrected radiation stress (spec.flags bit 0) %s; engine AUTO "
+              "runs this request through the forward jet", fused_corrected_refusal(*n));
+    return PINN_ERR_UNSUPPORTED;
+  }
+  const bool fused_ok = fused_fields_supports(*n) && !(corrected && fused_corrected_refusal(*n));
   if (asked == PINN_ENGINE_FUSED && !fused_ok) {
     const char* why = n->drop_p > 0.f ? "dropout_p > 0 has no field kernel"
                     : n->prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only"

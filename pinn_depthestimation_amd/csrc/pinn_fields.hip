@@ -62,6 +62,7 @@ int fields_from_jet(const Net& net, const pinn_residual_spec& spec, const float*
   switch (spec.residual_id) {
     case PINN_RES_NAVIER_STOKES: hipLaunchKernelGGL(k_fields_from_jet<ResNavierStokes>, grid, block, 0, s, P); break;
     case PINN_RES_PHYSICS_EQUATION: hipLaunchKernelGGL(k_fields_from_jet<ResPhysicsEquation>, grid, block, 0, s, P); break;
+    case RES_PE_CORRECTED: hipLaunchKernelGGL(k_fields_from_jet<ResPhysicsEquationCorrected>, grid, block, 0, s, P); break;
     default: hipLaunchKernelGGL(k_fields_from_jet<ResContinuity>, grid, block, 0, s, P); break;
   }
   return check_launch("fields from jet");

@@ -12,7 +12,15 @@ int launch_fused_drop64(int K1, const FusedParams& P, int grid, size_t lds, hipS
 int launch_fused_plain(int WP, const FusedParams& P, int cus, hipStream_t s);                      // pinn_fused_plain.hip
 int64_t fused_plain_min_tiles(int WP, int cus);
 
+// batch kernel instances (defined at the end of this file)
+template <int WP>
+int launch_fused_batch_pec(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s);
+
 namespace {
+
+// a loss request with the corrected radiation stress (common.h, RES_PE_CORRECTED): its own kernel instances (EPI_PEC), on
+// the tile and on the batch kernel, never on the cooperative one
+bool is_pec(const LossReq* rq) { return rq && rq->kind != 1 && rq->spec.residual_id == RES_PE_CORRECTED; }
 
 int padded_width(int W) { return W <= 16 ? 16 : (W <= 32 ? 32 : 64); }
 
@@ -352,8 +360,12 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   }
   // (the field epilogue exists in the tile kernel only: every kernel choice of desc.engine lands there; the external-adjoint
   // one in the tile and in the batch kernel)
+  const bool pec = is_pec(rq), fpec = fld && fld->spec.residual_id == RES_PE_CORRECTED;
+  if ((pec || fpec) && fused_corrected_refusal(n)) {
+    set_error("fused engine: the corrected radiation stress %s", fused_corrected_refusal(n)); return PINN_ERR_UNSUPPORTED;
+  }
   const bool batch = !fld && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
-  const bool coop = !adj && !fld && !batch && use_coop(n, g, grad, N);
+  const bool coop = !adj && !fld && !batch && !pec && use_coop(n, g, grad, N);   // (FUSED_COOP with it: the tile kernel)
   if (coop) {
     P.acc_lds = grad ? 1 : 0;
     P.lds_acc_floats = grad ? g.PP : 0;
@@ -409,6 +421,11 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   int rc;
   if (fld) {   // forward-only grid (grid_for above, grad == false), natural unit order (perm == 0), no reductions;
                // no dynamic LDS: these instances touch neither the pads nor the gradient copy
+    if (fpec) switch (g.WP) {
+      case 16: return launch_fused_field_pec<16>(P, grid, 0, s);
+      case 32: return launch_fused_field_pec<32>(P, grid, 0, s);
+      default: return launch_fused_field_pec<64>(P, grid, 0, s);
+    }
     switch (g.WP) {
       case 16: rc = launch_fused_field<16>(n.K1, P, grid, 0, s); break;
       case 32: rc = launch_fused_field<32>(n.K1, P, grid, 0, s); break;
@@ -442,6 +459,15 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     // pinn_forward on enough points to give every wave the chip holds a pass of four tiles: the plain forward's own
     // kernel, one weight fetch per 64 points (pinn_fused_plain.hip)
     rc = launch_fused_plain(g.WP, P, cu_count(), s);
+  }
+  else if (pec) {           // EPI_PEC instances: pinn_fused_batch_pec_wXX_k3.hip / pinn_fused_pec_wXX.hip
+    if (batch) rc = g.WP == 16 ? launch_fused_batch_pec<16>(n.W, n.d_in, P, grid, lds, s)
+                               : launch_fused_batch_pec<32>(n.W, n.d_in, P, grid, lds, s);
+    else switch (g.WP) {
+      case 16: rc = launch_fused_pec<16>(grad, P, grid, lds, s); break;
+      case 32: rc = launch_fused_pec<32>(grad, P, grid, lds, s); break;
+      default: rc = launch_fused_pec<64>(grad, P, grid, lds, s); break;
+    }
   }
   else if (batch) rc = g.WP == 16 ? launch_fused_batch<16>(n.W, n.d_in, n.K1, P, grid, lds, s)
                              : launch_fused_batch<32>(n.W, n.d_in, n.K1, P, grid, lds, s);
@@ -496,6 +522,15 @@ int launch_fused_batch_adj(int W, int d_in, int K1, const FusedParams& P, int gr
 }
 template int launch_fused_batch_adj<16>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
 template int launch_fused_batch_adj<32>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
+// ... and the corrected-radiation-stress loss instances (EPI_PEC, K1 = 3): pinn_fused_batch_pec_w{16,32}_k3.hip
+template <int WP, int K1>
+int launch_fused_batch_pec_k(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s);
+template <int WP>
+int launch_fused_batch_pec(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s) {
+  return launch_fused_batch_pec_k<WP, 3>(W, d_in, P, grid, lds, s);
+}
+template int launch_fused_batch_pec<16>(int, int, const FusedParams&, int, size_t, hipStream_t);
+template int launch_fused_batch_pec<32>(int, int, const FusedParams&, int, size_t, hipStream_t);
 bool fused_batch_has_kernel(int WP, int W, int d_in, int K1, int act) {
   return (WP == 16 || WP == 32) && W >= 1 && d_in <= 8 && (K1 == 3 || K1 == 4) && act == PINN_ACT_TANH;
 }
@@ -531,6 +566,14 @@ bool fused_fields_supports(const Net& n) {
   return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && (n.K1 == 3 || n.K1 == 4) && fused_supports(t, false);
 }
 
+// The corrected radiation stress (EPI_PEC / EPI_FIELD_PEC instances): tanh, k = 2, no dropout.  nullptr = served.
+const char* fused_corrected_refusal(const Net& n) {
+  if (n.act != PINN_ACT_TANH) return "has no LeakyReLU instance on the fused engine: use engine GENERIC";
+  if (n.K1 != 3) return "has fused instances for k = 2 networks only: use engine GENERIC";
+  if (n.drop_p > 0.f) return "has no dropout instance on the fused engine: use engine AUTO or GENERIC";
+  return nullptr;
+}
+
 int64_t fused_fields_workspace_bytes(const Net& n) {
   if (!fused_fields_supports(n)) return -1;
   return ws_layout(n, geo_of(n), 1, true).total;
@@ -548,7 +591,7 @@ bool fused_supports_adam(const Net& n, const LossReq& rq, int64_t N) {
   if (!rq.grad || !fused_supports(n, true)) return false;
   if (rq.kind == 2 && rq.n_split >= 0) {
     const Geo g = geo_of(n);
-    if (g.WP == 64 && !use_coop(n, g, true, N)) return false;
+    if (g.WP == 64 && !is_pec(&rq) && !use_coop(n, g, true, N)) return false;   // (EPI_PEC carries the split code at every width)
   }
   return true;
 }
@@ -578,8 +621,9 @@ int fused_loss(const Net& n, const LossReq& rq, const float* params, const float
     // request that would run on the width-64 tile kernel (large N, where a second launch is noise)
     // is served as two passes on the same stream: residual on the collocation points, then the
     // fidelity columns on the rest with the k = 0 network.
+    // (the corrected residual's width-64 instances carry the split code: they are not the register-starved generic ones)
     const Geo g = geo_of(n);
-    if (g.WP == 64 && !use_coop(n, g, grad, N)) {
+    if (g.WP == 64 && !is_pec(&rq) && !use_coop(n, g, grad, N)) {
       LossReq r0 = rq; r0.kind = 0; r0.n_split = -1;
       int rc = PINN_OK;
       if (rq.n_split > 0) rc = fused_loss(n, r0, params, X, rq.n_split, ws, ws_bytes, s);

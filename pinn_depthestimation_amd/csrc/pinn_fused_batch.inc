@@ -7,11 +7,13 @@
 #include <type_traits>
 #include "fused_batch_kernel.h"
 
+// An includer that sets BATCH_EPI to anything else (EPI_PEC: pinn_fused_batch_pec_w*_k3.hip, launch_fused_batch_pec_k) names
+// its launcher and its launch-error text itself: BATCH_LAUNCH, BATCH_WHAT.
 #ifndef BATCH_EPI
 #define BATCH_EPI EPI_GENERIC
 #define BATCH_LAUNCH launch_fused_batch_k
 #define BATCH_WHAT "fused batch kernel"
-#else
+#elif !defined(BATCH_LAUNCH)
 #define BATCH_LAUNCH launch_fused_batch_adj_k
 #define BATCH_WHAT "fused batch kernel (external adjoint)"
 #endif

@@ -408,6 +408,7 @@ int run_loss(const Net& n, const LossReq& rq, const float* params, const float* 
   } while (0)
     if (id == PINN_RES_NAVIER_STOKES) LAUNCH_RES(ResNavierStokes, 0, 0);
     else if (id == PINN_RES_PHYSICS_EQUATION) LAUNCH_RES(ResPhysicsEquation, 0, 0);
+    else if (id == RES_PE_CORRECTED) LAUNCH_RES(ResPhysicsEquationCorrected, 0, 0);      // (spec.flags bit 0: common.h)
     else if (id == PINN_RES_CONTINUITY_FTEMP) LAUNCH_RES(ResContinuity, 0, 0);
     else if (id == PINN_RES_CONTINUITY_ONLY) LAUNCH_RES(ResContinuity, 1, n.dir_col[rq.spec.dir_of[0]]);
     else { set_error("unknown residual_id %d", id); return PINN_ERR_INVALID; }

@@ -129,6 +129,112 @@ struct ResPhysicsEquation {
   }
 };
 
+// physics_equation with the radiation stress physics.py:106-109 evidently meant (the package's
+// physics.physics_equation(..., corrected=True)): E = rho g Hrms^2 / 8, Sxx = E (2n + 1/2), Syy = E n, n = kh / sinh 2kh.
+// Same roles and directions as ResPhysicsEquation; selected by pinn_residual_spec.flags bit 0, never by an id of its own.
+//   fx = U U_x + V U_y + G eta_x + D (tbx + d Sxx / dx),   fy likewise with d Syy / dy
+// __host__ __device__: pinn_pe_corrected_point (pinn_abi.hip) evaluates the very same functions on the host.
+struct ResPhysicsEquationCorrected {
+  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3;
+  // n(s) = s / sinh 2s with n1 = dn/ds = (S - 2sC) / S^2 and n2 = d2n/ds2 = 4 (s S^2 - C S + 2s) / S^3 (S = sinh 2s,
+  // C = cosh 2s).  Formed from t = exp(-2|s|): 1/S = 2t / (1 - t^2), C/S = (1 + t^2) / (1 - t^2) — nothing overflows,
+  // however large |s| (t underflows to 0 and with it n, n1, n2) — and by parity (n, n2 even, n1 odd).  Below |s| = 1/4
+  // both closed forms cancel (1 - 2s C/S ~ -4/3 s^2), so there the Taylor series of 2s / sinh 2s through s^12 takes
+  // over: first dropped term of n2 is 1e-8 at the threshold; the closed n2 loses a factor 30 (3e-6) just above it.
+  // At s = 0 the limits (1/2, 0, -2/3).
+  __host__ __device__ static inline void ratio(float s, float& n, float& n1, float& n2) {
+    const float a = fabsf(s);
+    if (a < 0.25f) {
+      constexpr float A1 = (float)(-1.0 / 3.0), A2 = (float)(7.0 / 45.0), A3 = (float)(-62.0 / 945.0),
+                      A4 = (float)(127.0 / 4725.0), A5 = (float)(-146.0 / 13365.0), A6 = (float)(2828954.0 / 638512875.0);
+      const float u = s * s;
+      n = fmaf(fmaf(fmaf(fmaf(fmaf(fmaf(A6, u, A5), u, A4), u, A3), u, A2), u, A1), u, 0.5f);
+      n1 = s * fmaf(fmaf(fmaf(fmaf(fmaf(12.f * A6, u, 10.f * A5), u, 8.f * A4), u, 6.f * A3), u, 4.f * A2), u, 2.f * A1);
+      n2 = fmaf(fmaf(fmaf(fmaf(fmaf(132.f * A6, u, 90.f * A5), u, 56.f * A4), u, 30.f * A3), u, 12.f * A2), u, 2.f * A1);
+    } else {
+      const float t = expf(-2.f * a), t2 = t * t;
+      const float id = 1.0f / (1.f - t2);
+      const float iS = 2.f * t * id, ct = (1.f + t2) * id;      // 1 / sinh 2a, coth 2a
+      n = a * iS;
+      const float m1 = iS * (1.f - 2.f * a * ct);
+      n1 = s < 0.f ? -m1 : m1;
+      n2 = 4.f * iS * (a - ct + 2.f * a * (iS * iS));
+    }
+  }
+  // everything eval and fields share
+  struct Mid { float D, tbx, tby, E, n, n1, n2, s_x, s_y, E_x, E_y, Sx, Sy; };
+  __host__ __device__ static inline Mid mid(const float (&v)[1 + ND][NR]) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3], R = v[0][4], K = v[0][5];
+    const float h_x = v[1][0], R_x = v[1][4], K_x = v[1][5];
+    const float h_y = v[2][0], R_y = v[2][4], K_y = v[2][5];
+    const float RHO = 1025.f;
+    const float RC = (float)(1025 * 0.002);
+    const float C_E = (float)(1025 * 9.81 / 8.0);     // rho g / 8
+    Mid m;
+    m.tbx = (RC * U) * fabsf(U);
+    m.tby = (RC * V) * fabsf(V);
+    m.D = 1.0f / (RHO * (eta + h));
+    m.E = C_E * R * R;
+    m.E_x = 2.f * C_E * R * R_x; m.E_y = 2.f * C_E * R * R_y;
+    m.s_x = K_x * h + K * h_x; m.s_y = K_y * h + K * h_y;
+    ratio(K * h, m.n, m.n1, m.n2);
+    m.Sx = m.E_x * (2.f * m.n + 0.5f) + 2.f * m.E * m.n1 * m.s_x;   // d Sxx / dx
+    m.Sy = m.E_y * m.n + m.E * m.n1 * m.s_y;                        // d Syy / dy
+    return m;
+  }
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+    const float U = v[0][1], V = v[0][2];
+    const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
+    const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
+    const float G = 9.81f;
+    const Mid m = mid(v);
+    f[0] = U_x + V_y;
+    f[1] = U * U_x + V * U_y + G * e_x + m.D * (m.tbx + m.Sx);
+    f[2] = U * V_x + V * V_y + G * e_y + m.D * (m.tby + m.Sy);
+  }
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* scale,
+                                              float (&g)[1 + ND][NR], float (&sq)[NT]) {
+    float f[NF];
+    fields(v, f);
+    sq[0] = f[0] * f[0]; sq[1] = f[1] * f[1]; sq[2] = f[2] * f[2];
+    if (GRAD) {
+      const float h = v[0][0], U = v[0][1], V = v[0][2], R = v[0][4], K = v[0][5];
+      const float h_x = v[1][0], U_x = v[1][1], V_x = v[1][2], R_x = v[1][4], K_x = v[1][5];
+      const float h_y = v[2][0], U_y = v[2][1], V_y = v[2][2], R_y = v[2][4], K_y = v[2][5];
+      const float G = 9.81f, RHO = 1025.f;
+      const float RC = (float)(1025 * 0.002);
+      const float C_E = (float)(1025 * 9.81 / 8.0);
+      const Mid m = mid(v);
+      const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
+      const float ax = rx * m.D, ay = ry * m.D;
+      const float dD = -RHO * m.D * m.D;             // d D / d(eta+h)
+      const float gS = dD * (rx * (m.tbx + m.Sx) + ry * (m.tby + m.Sy));
+      const float ds = ax * (2.f * m.E_x * m.n1 + 2.f * m.E * m.n2 * m.s_x) + ay * (m.E_y * m.n1 + m.E * m.n2 * m.s_y);   // adjoint of s = kh
+      const float gsx = 2.f * ax * m.E * m.n1, gsy = ay * m.E * m.n1;   // adjoints of s_x, s_y
+      const float nn = 2.f * m.n + 0.5f;
+      g[0][0] = gS + ds * K + gsx * K_x + gsy * K_y;
+      g[0][1] = rx * (U_x + m.D * RC * 2.f * fabsf(U)) + ry * V_x;
+      g[0][2] = rx * U_y + ry * (V_y + m.D * RC * 2.f * fabsf(V));
+      g[0][3] = gS;
+      g[0][4] = ax * (2.f * C_E * R_x * nn + 4.f * C_E * R * m.n1 * m.s_x) + ay * (2.f * C_E * R_y * m.n + 2.f * C_E * R * m.n1 * m.s_y);
+      g[0][5] = ds * h + gsx * h_x + gsy * h_y;
+      g[1][0] = gsx * K;       // d/dh_x
+      g[1][1] = rc + rx * U;   // d/dU_x
+      g[1][2] = ry * U;        // d/dV_x
+      g[1][3] = rx * G;        // d/deta_x
+      g[1][4] = 2.f * ax * C_E * R * nn;   // d/dHrms_x
+      g[1][5] = gsx * h;       // d/dk_x
+      g[2][0] = gsy * K;
+      g[2][1] = rx * V;
+      g[2][2] = rc + ry * V;
+      g[2][3] = ry * G;
+      g[2][4] = 2.f * ay * C_E * R * m.n;
+      g[2][5] = gsy * h;
+    }
+  }
+};
+
 // physics.py:37-47 continuity_ftemp(x, y, h, U, V); physics.py:18-33 continuity_only
 // roles: outputs h=0 U=1 V=2; directions x=0 y=1.
 // fc = d(hU)/dx + d(hV)/dy.  continuity_only adds (h - anchor)^2 on the points

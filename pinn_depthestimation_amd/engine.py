@@ -91,6 +91,7 @@ class ResidualSpec:
     dir_of: Tuple[int, ...]           # per direction role: index into NetDesc.grad_cols
     threshold: float = 25.5           # physics.py:26
     anchor: float = 0.75              # physics.py:27
+    corrected: bool = False           # physics_equation only: the corrected radiation stress (pinn_residual_spec.flags bit 0)
 
     @property
     def residual_id(self) -> int:
@@ -112,16 +113,19 @@ class ResidualSpec:
             s.out_col[r] = self.out_col[r] if r < len(self.out_col) else 0
         for d in range(_lib.PINN_MAX_DIRS):
             s.dir_of[d] = self.dir_of[d] if d < len(self.dir_of) else 0
-        s.flags = 0
+        s.flags = 1 if self.corrected else 0
         s.param[0], s.param[1] = self.threshold, self.anchor
         return s
 
     @staticmethod
     def from_names(name: str, input_names: Sequence[str], grad_cols: Sequence[int],
-                   output_names: Sequence[str]) -> "ResidualSpec":
-        """Map config variable names (config data_residual.inputs / outputs) onto roles."""
+                   output_names: Sequence[str], corrected: bool = False) -> "ResidualSpec":
+        """Map config variable names (config data_residual.inputs / outputs) onto roles.  corrected=True (physics_equation
+        only): E = rho g Hrms^2 / 8 in place of the reference's E == 0, as physics.physics_equation(corrected=True)."""
         if name not in RESIDUAL_ROLES:
             raise PinnError(f"unknown residual {name!r}; known: {sorted(RESIDUAL_ROLES)}")
+        if corrected and name != "physics_equation":
+            raise PinnError(f"corrected=True is the radiation stress of physics_equation; residual {name!r} has none")
         _, out_roles, dir_roles = RESIDUAL_ROLES[name]
         out_col = []
         for r in out_roles:
@@ -136,7 +140,7 @@ class ResidualSpec:
             if col not in grad_cols:
                 raise PinnError(f"input {r!r} must have requires_grad 'true' for residual {name}")
             dir_of.append(list(grad_cols).index(col))
-        return ResidualSpec(name, tuple(out_col), tuple(dir_of))
+        return ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected))
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -324,7 +328,7 @@ class Engine:
     def fields_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual_fields (pinn_query_fields_workspace), cached apart from workspace()'s."""
         e = self.desc.engine if engine is None else engine
-        key = ("fields", e, spec.residual_id, N)
+        key = ("fields", e, spec.residual_id, spec.corrected, N)
         need = self._ws_need.get(key)
         if need is None:
             c_need = C.c_int64()
@@ -452,7 +456,7 @@ class Engine:
         ws = self.workspace(N)
         tok = self._packed_tok
         packed_valid = (tok is not None and tok[0] is ws and tok[1] == params.data_ptr() and tok[2] == params._version
-                        and tok[3] == params_token and tok[4] == (N, int(n_res), nc))     # (the request picks the kernel, and with it the packed layout)
+                        and tok[3] == params_token and tok[4] == (N, int(n_res), nc, spec.residual_id, spec.corrected))     # (the request picks the kernel, and with it the packed layout)
         self._packed_tok = None
         st = _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0 if lrs is not None else float(lr), float(beta1), float(beta2),
                                 float(eps), 1 if packed_valid else 0, n_rows, _ptr(loss_rows), _ptr(losses))
@@ -469,7 +473,7 @@ class Engine:
         if rc == _lib.ERR_UNSUPPORTED:
             return False
         check(rc, "pinn_loss_grad_adam_step" if lrs is None else "pinn_adam_loop")
-        self._packed_tok = (ws, params.data_ptr(), params._version, params_token, (N, int(n_res), nc))
+        self._packed_tok = (ws, params.data_ptr(), params._version, params_token, (N, int(n_res), nc, spec.residual_id, spec.corrected))
         return True
 
     def invalidate_packed(self):

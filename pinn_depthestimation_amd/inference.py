@@ -20,6 +20,7 @@ import torch
 from . import operations as op
 from . import physics
 from .config import PinnConfig, load_config
+from ._lib import PinnError
 from .dnn import DNN
 from .engine import ACTIVATION_OF_INIT, RESIDUAL_ROLES, Engine, NetDesc, ResidualSpec
 
@@ -29,7 +30,9 @@ FIELD_NAMES = {"Navier_Stokes": ("fc", "fm_x", "fm_y"), "physics_equation": ("fc
 
 
 class Tester:
-    def __init__(self, model, config, device="cuda", residual: Optional[str] = None):
+    def __init__(self, model, config, device="cuda", residual: Optional[str] = None, corrected: bool = False):
+        """corrected (physics_equation only): residual_fields and the physics-only fine-tune use the corrected radiation
+        stress (ResidualSpec.corrected, physics.physics_equation_corrected)."""
         self.config: PinnConfig = config if isinstance(config, PinnConfig) else load_config(config)
         self.device = torch.device(device)
         self.model = self.load_model(model)
@@ -41,6 +44,9 @@ class Tester:
         self.test_output_vars = list(outs.keys()) if isinstance(outs, dict) else list(outs)
         self.nx, self.ny = dt.get("nx"), dt.get("ny")
         self.residual = residual or self.config.default_residual()
+        self.corrected = bool(corrected)
+        if self.corrected and self.residual != "physics_equation":
+            raise PinnError(f"corrected=True is the radiation stress of physics_equation; residual {self.residual!r} has none")
         self.init_optimizers()
         self.last_loss = None
 
@@ -70,7 +76,7 @@ class Tester:
 
     def _residual_loss(self):
         _, out_roles, dir_roles = RESIDUAL_ROLES[self.residual]
-        fn = getattr(physics, self.residual)
+        fn = physics.physics_equation_corrected if self.corrected else getattr(physics, self.residual)
         return fn(*[getattr(self, k) for k in dir_roles], *[getattr(self, k) for k in out_roles])
 
     def test(self, test_input_data, input_min_max: Optional[dict] = None, perform_optimization: Optional[bool] = None):
@@ -114,7 +120,7 @@ class Tester:
         data = torch.as_tensor(np.asarray(test_input_data)).float().to(self.device).contiguous()
         names = list(self.test_input_vars)
         grad_cols = tuple(i for i, k in enumerate(names) if "true" in self.test_input_vars[k].get("requires_grad", []))
-        spec = ResidualSpec.from_names(self.residual, names, grad_cols, self.test_output_vars)
+        spec = ResidualSpec.from_names(self.residual, names, grad_cols, self.test_output_vars, corrected=self.corrected)
         key = (tuple(self.model.layer_sizes), grad_cols)
         if getattr(self, "_fields_engine_key", None) != key:
             self._fields_engine = Engine(NetDesc.from_layers(self.model.layer_sizes, grad_cols,

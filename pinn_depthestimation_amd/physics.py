@@ -96,3 +96,15 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False):
         mom_x = mom_x + inv_depth * d(E * (2 * ratio + 0.5), x)
         mom_y = mom_y + inv_depth * d(E * ratio, y)
     return _mean_sq(mass, mom_x, mom_y)
+
+
+def physics_equation_corrected(x, y, h, U, V, eta_mean, Hrms, k):
+    """physics_equation(..., corrected=True) hard-wired: where the arguments are the input and output columns of one
+    DNN.forward call (and the engine serves it: tanh, width <= 64), loss and d loss / d theta come from ONE kernel with
+    the corrected radiation stress in its epilogue (ResidualSpec.corrected) instead of forward jet + torch autograd +
+    jet_backward.  Otherwise the formula itself, physics_equation(..., corrected=True): the same loss.  One difference:
+    at kh = 0 the kernels take the limit of kh / sinh 2kh and its derivatives, where the formula gives NaN."""
+    fused = fused_residual("physics_equation", (x, y), (h, U, V, eta_mean, Hrms, k), corrected=True)
+    if fused is not None:
+        return fused
+    return physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=True)

@@ -179,7 +179,11 @@ class PINN:
                  dnn: Optional[DNN] = None, engine: int = 0, mat_dump_iter: Optional[int] = None,
                  mat_dump_path: str = "data_at50k.mat", residual_batch: Optional[int] = None, seed: int = 1234,
                  log_flush_every: int = 100, lbfgs_impl: str = "flat", precision: int = 0, fold_adam: bool = True,
-                 resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0):
+                 resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0,
+                 corrected: bool = False):
+        """corrected (or the config key loss.corrected_radiation_stress; physics_equation only): train on the corrected
+        radiation stress, E = rho g Hrms^2 / 8, hard-wired in the kernels (ResidualSpec.corrected) — every path that takes
+        the spec follows: the merged launch, the folded Adam runs, residual_fields and resample="rad"."""
         cfg = config if isinstance(config, PinnConfig) else load_config(config)
         self.config, self.device = cfg, torch.device(device)
         self.reducer = reducer or Reducer()
@@ -193,7 +197,9 @@ class PINN:
         P = self.theta.numel()
 
         residual = residual or cfg.default_residual()
-        self.spec = ResidualSpec.from_names(residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs)
+        self.corrected = bool(corrected) or bool(cfg.raw.get("loss", {}).get("corrected_radiation_stress", False))
+        self.spec = ResidualSpec.from_names(residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs,
+                                            corrected=self.corrected)       # (PinnError on any other residual)
         # i-th fidelity output is compared with output column i (train.py:137-138, train_newmethod.py:129-131)
         self.fid_cols = list(range(len(cfg.fidelity_outputs)))
         if cfg.variant == "newmethod":
