@@ -20,6 +20,8 @@
  *                           fused with loss.backward() (train.py:154,191)
  *   pinn_residual_fields    the same four residuals' signed per-point fields (physics.py:81-83, 113-115, 20-23, 27-28),
  *                           before they are squared and averaged: residual maps, adaptive resampling
+ *   pinn_residual2_loss_grad  Navier_Stokes / physics_equation with the lateral-mixing term nu * lap(U) in the momentum
+ *                           equations (nested compute_gradient, physics.py:6-15) fused with loss.backward()
  *   pinn_mse_loss_grad      train.py:131-141 (weighted fidelity MSE) + backward
  *   pinn_residual_mse_loss_grad  train_newmethod.py:122-159 (both on one forward) + backward
  *   pinn_residual_mse_split_loss_grad  train.py:131-157 (fidelity set + collocation set, one launch)
@@ -58,7 +60,7 @@
  *     term_scale, col_scale, loss_rows, grad of pinn_adam_step, data / grids / minmax, g, s, y; S, Y, M in
  *     pinn_lbfgs_direction; rows of S, Y other than `slot` and entries of M outside row and column `slot` in
  *     pinn_lbfgs_push.
- *   - grad_flat is += in pinn_jet_backward, pinn_jet2_backward, pinn_residual_loss_grad, pinn_mse_loss_grad,
+ *   - grad_flat is += in pinn_jet_backward, pinn_jet2_backward, pinn_residual_loss_grad, pinn_residual2_loss_grad, pinn_mse_loss_grad,
  *     pinn_residual_mse_loss_grad and pinn_residual_mse_split_loss_grad (the caller zeroes it, or accumulates several
  *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step and pinn_adam_loop.  Y, dY, d2Y, fields,
  *     term_sums, col_sums, losses, X_out, n_rows_out, out2 and d are overwritten, whatever they held.
@@ -247,6 +249,53 @@ int32_t pinn_forward_jet2(const pinn_desc* desc, const float* params, const floa
 int32_t pinn_jet2_backward(const pinn_desc* desc, const float* params, const float* X, int64_t N,
                            const float* gY, const float* gdY, const float* gd2Y, float* grad_flat,
                            void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- lateral mixing nu * lap(U): the first hard-wired residual on the second-order jets -----------------------------
+ * (added under ABI version 4, as the fields entries were: no existing entry, struct or constant changed)
+ * With L_a = a_xx + a_yy and nu >= 0 the momentum fields become
+ *   Navier_Stokes:     fm_x = (physics.py:82) - nu L_u,   fm_y = (physics.py:83) - nu L_v        (fc unchanged)
+ *   physics_equation:  fx   = (physics.py:114) - nu L_U,  fy   = (physics.py:115) - nu L_V       (plain and flags bit 0)
+ * The derivatives are with respect to the network's inputs AS IT SEES THEM: in the reference's pipeline those are
+ * normalised to [-1, 1] (operations.py:4-8), so nu is in those units.  nu == 0 is valid and gives the first-order residual.
+ *
+ * pinn_residual2_point: one point on the host, by the very functions the kernel calls (no device is touched).
+ * v[c * NR + r]: c = 0 the value, 1 + d the derivative along direction role d, of role r (NR = 4 roles and 3 directions
+ * for Navier_Stokes, 6 and 2 for physics_equation); lap = (L_u, L_v) resp. (L_U, L_V).  fields <- (fc, f_x, f_y).
+ * With scale, g and glap all given: g[c * NR + r] <- sum_t scale[t] d(field_t^2) / dv and glap <- the adjoints of lap,
+ * (-nu rx, -nu ry) with rx = 2 scale[1] f_x, ry = 2 scale[2] f_y: the adjoint of the pairs (x, x) and (y, y) of the two
+ * momentum roles; every other second-order adjoint is zero.  Any of the three NULL: fields only.
+ * Continuity residuals: PINN_ERR_UNSUPPORTED ("no second-order term"). */
+int32_t pinn_residual2_point(int32_t residual_id, int32_t flags, float nu, const float* v, const float lap[2],
+                             const float* scale, float* fields, float* g, float glap[2]);
+
+/* pinn_residual2_loss_grad: term_sums[t] <- sum over points of (shifted field t)^2 (n_terms floats, overwritten);
+ * fields, if not NULL, (n_fields, N) <- the signed shifted fields (overwritten); grad_flat, if not NULL,
+ * (P,) += sum_t term_scale[t] d term_sums[t] / d theta (NULL: no backward sweep; term_scale may then be NULL too).
+ * term_scale is a DEVICE array as in pinn_residual_loss_grad.  N = 0 zeroes term_sums and touches nothing else.
+ * Per chunk of points the call runs the forward layer kernels of pinn_forward_jet2 ONCE, one point-wise residual kernel
+ * that writes the adjoint of every channel and output column in the workspace layout, and the backward layer kernels of
+ * pinn_jet2_backward: no copy out of or into the workspace, no second forward.  All k (k + 1) / 2 pairs ride along.
+ * The workspace is the call's own (pinn_query_residual2_workspace); large point sets run in chunks as for jet2.
+ * Rules, decided before any device work, the same for the query (which takes no nu):
+ *   nu negative or not finite                    PINN_ERR_INVALID
+ *   desc->k != the residual's directions         PINN_ERR_UNSUPPORTED  (3 for Navier_Stokes, 2 for physics_equation)
+ *   continuity_ftemp / continuity_only           PINN_ERR_UNSUPPORTED, "no second-order term" in the message
+ *   GENERIC                                      any shape, tanh or LeakyReLU, dropout (the mask function of jet2)
+ *   FUSED and its sub-values                     the MFMA layer kernels and an MFMA weight gradient: fp32, every layer at
+ *                                                most 64 wide, no dropout; otherwise PINN_ERR_UNSUPPORTED with the two
+ *                                                messages of pinn_forward_jet2
+ *   AUTO                                         MFMA where served, else generic
+ *   WIDE, PINN_PREC_BF16                         PINN_ERR_UNSUPPORTED
+ * Reproducibility.  term_sums and fields: bit-reproducible on both paths (per-workgroup partial sums, then the fixed-order
+ * double reduction of every loss entry).  grad_flat: both weight-gradient kernels add with float atomics, so two runs
+ * differ in the last bits once more than one workgroup adds to an element: on the MFMA path from 65 points of a chunk
+ * on, on the generic path from 513 points on; below that size the gradient is bit-reproducible too. */
+int32_t pinn_query_residual2_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes);
+int32_t pinn_residual2_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, float nu,
+                                 const float* term_scale, const float* params, const float* X, int64_t N,
+                                 float* term_sums, float* fields /* NULL or (n_fields, N) */,
+                                 float* grad_flat /* NULL: no backward sweep */,
+                                 void* ws, int64_t ws_bytes, void* stream);
 
 /* term_sums[t] = sum over points of (residual field t)^2  (device, n_terms floats, overwritten)
  * Corrected radiation stress (spec.flags bit 0 on physics_equation) — the rule of every loss entry that takes a spec

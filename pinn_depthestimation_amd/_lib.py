@@ -75,6 +75,11 @@ _SIGNATURES = {
     "pinn_query_fields_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_residual_fields": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int64, _P,
                                          _P, C.c_int64, _P]),
+    "pinn_residual2_point": (C.c_int32, [C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pinn_query_residual2_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.POINTER(C.c_int64)]),
+    "pinn_residual2_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_float, _P, _P, _P,
+                                             C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
     "pinn_residual_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P,
                                             C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "pinn_mse_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, _P, C.c_int64, C.c_int32,

@@ -413,7 +413,10 @@ class _FusedResidual(torch.autograd.Function):
                                  torch.tensor(0.0, device=flat.device)])      # 1/0 -> inf -> NaN, as the
         else:                                                                 # reference's mean of empty
             scale = torch.full((spec.n_terms,), 1.0 / N, device=flat.device)
-        sums = eng.residual_loss_grad(spec, scale, flat, handle.X, grad)
+        if spec.nu != 0:      # the lateral-mixing term: the second-order entry, one call as well
+            sums = eng.residual2_loss_grad(spec, scale, flat, handle.X, grad)
+        else:
+            sums = eng.residual_loss_grad(spec, scale, flat, handle.X, grad)
         ctx.model, ctx.grad = model, grad
         return (sums * scale).sum()
 
@@ -432,11 +435,14 @@ def _corrected_is_served(model, handle) -> bool:
             and model.layer_sizes[0] <= 16 and model.layer_sizes[-1] <= 16)
 
 
-def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequence[torch.Tensor], corrected: bool = False):
+def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequence[torch.Tensor], corrected: bool = False,
+                   nu: float = 0.0):
     """Return the fused loss tensor if every argument is recognisably (input column of /
     output column of) one DNN.forward call, else None.  corrected=True (physics_equation only): the corrected
     radiation stress, hard-wired in the kernels (ResidualSpec.corrected); None as well where the engine that would run
-    the call does not serve it."""
+    the call does not serve it.  nu != 0 (Navier_Stokes, physics_equation): the lateral-mixing term -nu lap(U), hard-wired
+    on the second-order jets (pinn_residual2_loss_grad: any shape, tanh or LeakyReLU, dropout, plain or corrected); None
+    where the forward call differentiates other inputs than the residual's directions."""
     handle = None
     out_col: List[int] = []
     for o in out_vars:
@@ -457,8 +463,18 @@ def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequenc
         dir_of.append(j)
     if corrected and name != "physics_equation":
         raise PinnError(f"corrected=True is the radiation stress of physics_equation; residual {name!r} has none")
-    spec = ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected))
+    nu = float(nu)
+    if nu != 0:
+        if name not in ("Navier_Stokes", "physics_equation"):
+            raise PinnError(f"nu is the lateral mixing of a momentum equation; residual {name!r} has none")
+        if not (nu > 0.0 and nu != float("inf")):
+            raise PinnError(f"nu = {nu}: the eddy viscosity must be finite and >= 0")
+    spec = ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected), nu=nu)
     model = handle.model
+    if nu != 0:
+        if len(handle.grad_cols) != len(dir_of) or len(set(dir_of)) != len(dir_of):
+            return None
+        return _FusedResidual.apply(model, handle, spec, *model._ordered_params())
     if corrected and not _corrected_is_served(model, handle):
         return None
     return _FusedResidual.apply(model, handle, spec, *model._ordered_params())

@@ -108,6 +108,14 @@ int jet2_forward(const Net& n, bool mfma, const float* params, const float* X, i
 int jet2_backward(const Net& n, bool mfma, const float* params, const float* X, int64_t N, const float* gY,
                   const float* gdY, const float* gd2Y, float* grad, void* ws, int64_t ws_bytes, hipStream_t s);
 
+// pinn_residual2_loss_grad (pinn_jet2.hip): the residual with the lateral-mixing term nu * lap(U) on the second-order jets,
+// forward chunk -> k2_residual -> backward chunk; mfma = the MFMA layer kernels and k2m_wgrad, else the VALU kernels and
+// k2_wgrad.  spec is normalised (check_spec) and names a residual with a momentum equation; fields and grad may be null.
+int64_t residual2_workspace_bytes(const Net& n, int64_t N);
+int residual2_loss_grad(const Net& n, bool mfma, const pinn_residual_spec& spec, float nu, const float* scale,
+                        const float* params, const float* X, int64_t N, float* sums, float* fields, float* grad,
+                        void* ws, int64_t ws_bytes, hipStream_t s);
+
 // fused MFMA engine (pinn_fused.hip)
 bool fused_supports(const Net& n, bool want_grad);
 bool fused_supports_adam(const Net& n, const LossReq& rq, int64_t N);   // one-pass requests only

@@ -688,4 +688,89 @@ int32_t pinn_jet2_backward(const pinn_desc* desc, const float* params, const flo
   return jet2_backward(n, mfma, params, X, N, gY, gdY, gd2Y, grad_flat, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- the lateral-mixing term nu * lap(U) on the second-order jets ------------------------------------------------------
+// the three residuals with a momentum equation, on the host: the very functions k2_residual calls (residuals.h)
+extern "C++" {
+template <class B>
+static void residual2_point(float nu, const float* v, const float* lap, const float* scale, float* fields, float* g,
+                            float* glap) {
+  typedef Residual2<B> R;
+  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], f[R::NF], gl[2];
+  const float l2[2] = {lap[0], lap[1]};
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
+  if (!scale || !g || !glap) {
+    R::fields(jet, l2, nu, f);
+  } else {
+    R::template eval<true>(jet, l2, nu, scale, f, gj, gl);
+    for (int c = 0; c <= R::ND; ++c)
+      for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
+    glap[0] = gl[0]; glap[1] = gl[1];
+  }
+  for (int t = 0; t < R::NF; ++t) fields[t] = f[t];
+}
+}  // extern "C++"
+
+static int check_nu(float nu) {
+  if (!(nu >= 0.f) || !isfinite(nu)) { set_error("nu = %g: the eddy viscosity must be finite and >= 0", (double)nu); return PINN_ERR_INVALID; }
+  return PINN_OK;
+}
+
+int32_t pinn_residual2_point(int32_t residual_id, int32_t flags, float nu, const float* v, const float lap[2],
+                             const float* scale, float* fields, float* g, float glap[2]) {
+  int rc = check_nu(nu); if (rc) return rc;
+  if (!v || !lap || !fields) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
+  switch (residual_id) {
+    case PINN_RES_NAVIER_STOKES: residual2_point<Res2NavierStokes>(nu, v, lap, scale, fields, g, glap); return PINN_OK;
+    case PINN_RES_PHYSICS_EQUATION:
+      if (flags & 1) residual2_point<Res2PhysicsEquationCorrected>(nu, v, lap, scale, fields, g, glap);
+      else residual2_point<Res2PhysicsEquation>(nu, v, lap, scale, fields, g, glap);
+      return PINN_OK;
+    case PINN_RES_CONTINUITY_FTEMP: case PINN_RES_CONTINUITY_ONLY:
+      set_error("residual %d has no momentum equation: no second-order term", residual_id);
+      return PINN_ERR_UNSUPPORTED;
+    default: set_error("unknown residual_id %d", residual_id); return PINN_ERR_INVALID;
+  }
+}
+
+// validation shared by the query and the call (no HIP call before it has passed)
+static int residual2_plan(const pinn_desc* desc, const pinn_residual_spec* spec, Net* n, pinn_residual_spec* nspec, bool* mfma) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  rc = check_spec(*n, spec, nspec); if (rc) return rc;
+  if (spec->residual_id == PINN_RES_CONTINUITY_FTEMP || spec->residual_id == PINN_RES_CONTINUITY_ONLY) {
+    set_error("pinn_residual2_loss_grad: residual %d has no momentum equation: no second-order term", spec->residual_id);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (n->k != residual_dirs(spec->residual_id)) {
+    set_error("pinn_residual2_loss_grad: the network carries k = %d tangent directions, residual %d has %d (k must equal the "
+              "residual's number of directions)", n->k, spec->residual_id, residual_dirs(spec->residual_id));
+    return PINN_ERR_UNSUPPORTED;
+  }
+  return jet2_net(desc, n, mfma);
+}
+
+int32_t pinn_query_residual2_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
+  Net n; pinn_residual_spec nspec; bool mfma;
+  int rc = residual2_plan(desc, spec, &n, &nspec, &mfma); if (rc) return rc;
+  if (!bytes || N < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
+  const int64_t b = residual2_workspace_bytes(n, N);
+  if (b < 0) { set_error("too many layers for the jet2 kernels"); return PINN_ERR_UNSUPPORTED; }
+  *bytes = b;
+  return PINN_OK;
+}
+
+int32_t pinn_residual2_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, float nu, const float* term_scale,
+                                 const float* params, const float* X, int64_t N, float* term_sums, float* fields,
+                                 float* grad_flat, void* ws, int64_t ws_bytes, void* stream) {
+  Net n; pinn_residual_spec nspec; bool mfma;
+  int rc = residual2_plan(desc, spec, &n, &nspec, &mfma); if (rc) return rc;
+  rc = check_nu(nu); if (rc) return rc;
+  if (!params || (!X && N > 0) || N < 0 || !term_sums || (grad_flat && !term_scale)) {
+    set_error("NULL pointer argument"); return PINN_ERR_INVALID;
+  }
+  if (N == 0) { (void)hipMemsetAsync(term_sums, 0, residual_terms(spec->residual_id) * sizeof(float), (hipStream_t)stream); return PINN_OK; }
+  return residual2_loss_grad(n, mfma, nspec, nu, term_scale, params, X, N, term_sums, fields, grad_flat, ws, ws_bytes,
+                             (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -23,6 +23,7 @@
 // The sweep needs the pre-activation jets of every hidden layer as well as the post-activation ones, about
 // 2 C sum(widths) 4 bytes per point: requests larger than JET2_WS_BUDGET run in point chunks.
 #include "common.h"
+#include "reduce_adam.h"
 #include "residuals.h"
 
 namespace pinn {
@@ -381,6 +382,206 @@ __global__ void k2_wgrad(const float* __restrict__ zb, const float* __restrict__
   if (blockIdx.x == 0 && ti == 0 && o0 + to < out_dim) atomicAdd(&db[o0 + to], accb);
 }
 
+// The same sums on v_mfma_f32_16x16x4_f32 for layers up to 64 x 64 (pinn_residual2_loss_grad's MFMA path):
+//   D[16 outputs x 16 inputs] += A[16 outputs x 4 points] B[4 points x 16 inputs],  A = zbar rows, B = a_in rows.
+// Points are contiguous in the workspace rows, so lane (m = lane & 15, q = lane >> 4) loads the four points 4q .. 4q + 3 of
+// row m with one 16-byte load, for A and for B alike, and feeds element j of both to k-step j: step j contracts points
+// {4q' + j}, the four steps together the tile's 16 points, in an order both operands share.  A wave keeps all OT x IT
+// accumulator tiles of the layer (at most 16 tiles = 64 registers) plus OT tiles for db (channel 0 against a constant-one
+// B operand), walks its slice of the chunk's points over all C channels, and the four waves of a workgroup are summed in
+// LDS before ONE float atomicAdd per element and workgroup (the memory-side atomic units are the scarce
+// resource).  Atomics: two runs differ in the last bits, like k2_wgrad.
+// Rows are Nc floats apart: when Nc % 4 != 0 they are not 16-byte aligned and every element is loaded on its own, under
+// its own bound; with Nc % 4 == 0 a group of four lies wholly inside or wholly outside the chunk.  Points past Nc and
+// rows past the layer's dimensions enter as exact zeros.
+// The slice (points per wave, a multiple of 16) trades parallelism against atomics: k2m_slice() below.
+template <int OT, int IT>
+__global__ __launch_bounds__(256) void k2m_wgrad(const float* __restrict__ zb, const float* __restrict__ a_in, int C,
+                                                 int in_dim, int out_dim, int64_t Nc, int slice,
+                                                 float* __restrict__ dW, float* __restrict__ db) {
+  constexpr int NTILE = OT * IT + OT;             // dW tiles, then the db tiles
+  __shared__ float red[2][NTILE * 4][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, m = lane & 15, q = lane >> 4;
+  const int64_t begin = ((int64_t)blockIdx.x * 4 + wave) * slice;
+  const int64_t end = begin + slice < Nc ? begin + slice : Nc;
+  const bool vec = (Nc & 3) == 0;
+  f32x4 acc[NTILE];
+#pragma unroll
+  for (int t = 0; t < NTILE; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int64_t nb = begin; nb < end; nb += 16) {
+    const int64_t n4 = nb + 4 * q;
+    for (int c = 0; c < C; ++c) {
+      f32x4 za[OT], aa[IT];
+#pragma unroll
+      for (int t = 0; t < OT; ++t) {
+        const int o = t * 16 + m;
+        const float* row = zb + ((int64_t)c * out_dim + o) * Nc;
+        za[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (o < out_dim) {
+          if (vec) {
+            if (n4 < Nc) za[t] = *reinterpret_cast<const f32x4*>(row + n4);
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (n4 + j < Nc) za[t][j] = row[n4 + j];
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < IT; ++t) {
+        const int i = t * 16 + m;
+        const float* row = a_in + ((int64_t)c * in_dim + i) * Nc;
+        aa[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (i < in_dim) {
+          if (vec) {
+            if (n4 < Nc) aa[t] = *reinterpret_cast<const f32x4*>(row + n4);
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (n4 + j < Nc) aa[t][j] = row[n4 + j];
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int to = 0; to < OT; ++to)
+#pragma unroll
+          for (int ti = 0; ti < IT; ++ti)
+            acc[to * IT + ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[to][j], aa[ti][j], acc[to * IT + ti], 0, 0, 0);
+      if (c == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int to = 0; to < OT; ++to)
+            acc[OT * IT + to] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[to][j], 1.f, acc[OT * IT + to], 0, 0, 0);
+      }
+    }
+  }
+  // waves 2, 3 -> LDS; waves 0, 1 add them; waves 0, 1 -> LDS; every thread sums the two copies of its elements
+  if (wave >= 2) {
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave - 2][t * 4 + r][lane] = acc[t][r];
+  }
+  __syncthreads();
+  if (wave < 2) {
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[t][r] += red[wave][t * 4 + r][lane];
+  }
+  __syncthreads();
+  if (wave < 2) {
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][t * 4 + r][lane] = acc[t][r];
+  }
+  __syncthreads();
+  // element (t, r) of lane (m', q') is D[4 q' + r][m'] of tile t: output to * 16 + 4 q' + r, input ti * 16 + m'
+  for (int e = threadIdx.x; e < NTILE * 4 * 64; e += 256) {
+    const int l = e & 63, tr = e >> 6, t = tr >> 2, r = tr & 3;
+    const int mm = l & 15, qq = l >> 4;
+    const float val = red[0][tr][l] + red[1][tr][l];
+    if (t < OT * IT) {
+      const int o = (t / IT) * 16 + 4 * qq + r, i = (t % IT) * 16 + mm;
+      if (o < out_dim && i < in_dim) atomicAdd(&dW[(int64_t)o * in_dim + i], val);
+    } else {
+      const int o = (t - OT * IT) * 16 + 4 * qq + r;
+      if (mm == 0 && o < out_dim) atomicAdd(&db[o], val);
+    }
+  }
+}
+
+// Residual with the lateral-mixing term on the chunk's output jets (pinn_residual2_loss_grad): one thread per point.
+struct Res2Params {
+  const float* out;     // lo.out: [channel][output column][point of the chunk]
+  float* G;             // lo.g0: the adjoint of every channel and output column (written when want_grad)
+  float* fields;        // NULL or (NF, N)
+  float* partial;       // rows of NT partial sums, one per workgroup; this launch writes rows row0 + blockIdx.x
+  const float* scale;   // device term_scale (want_grad)
+  int64_t Nc, n0, N, row0;
+  int d_out, want_grad;
+  int out_col[PINN_MAX_ROLES];
+  int dir_ch[PINN_MAX_DIRS];   // channel of direction role d: 1 + spec.dir_of[d]
+  int ch_xx, ch_yy;            // channels of the pairs (x, x) and (y, y), x and y as the DESCRIPTOR's direction indices
+  float nu;
+};
+
+template <class Res, int K>
+__global__ __launch_bounds__(TPB) void k2_residual(const Res2Params P) {
+  constexpr int C = J2<K>::C, NR = Res::NR, ND = Res::ND, NT = Res::NT, NF = Res::NF;
+  typedef Residual2<Res> R2;
+  __shared__ float red[NT][TPB];
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float f[NF];
+#pragma unroll
+  for (int t = 0; t < NF; ++t) f[t] = 0.f;
+  if (n < P.Nc) {
+    const int64_t Nc = P.Nc;
+    float v[1 + ND][NR], g[1 + ND][NR], lap[2], glap[2];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int o = P.out_col[r];
+      v[0][r] = P.out[(int64_t)o * Nc + n];
+#pragma unroll
+      for (int d = 0; d < ND; ++d) v[1 + d][r] = P.out[((int64_t)P.dir_ch[d] * P.d_out + o) * Nc + n];
+    }
+    const int ou = P.out_col[Res::RU], ov = P.out_col[Res::RV];
+    lap[0] = P.out[((int64_t)P.ch_xx * P.d_out + ou) * Nc + n] + P.out[((int64_t)P.ch_yy * P.d_out + ou) * Nc + n];
+    lap[1] = P.out[((int64_t)P.ch_xx * P.d_out + ov) * Nc + n] + P.out[((int64_t)P.ch_yy * P.d_out + ov) * Nc + n];
+    R2::fields(v, lap, P.nu, f);      // (once, outside the branch: the same bits with and without a gradient request)
+    if (P.want_grad) R2::adjoint(v, f, P.nu, P.scale, g, glap);
+    if (P.fields) {
+#pragma unroll
+      for (int t = 0; t < NF; ++t) P.fields[(int64_t)t * P.N + P.n0 + n] = f[t];
+    }
+    if (P.want_grad) {
+      // columns that carry no role: zeros in every channel
+      for (int o = 0; o < P.d_out; ++o) {
+        bool has = false;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) has = has || P.out_col[r] == o;
+        if (has) continue;
+#pragma unroll
+        for (int c = 0; c < C; ++c) P.G[((int64_t)c * P.d_out + o) * Nc + n] = 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int o = P.out_col[r];
+        P.G[(int64_t)o * Nc + n] = g[0][r];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {       // first-order channel 1 + i: the direction role that rides it, if any
+          float a = 0.f;
+#pragma unroll
+          for (int d = 0; d < ND; ++d) if (P.dir_ch[d] == 1 + i) a = g[1 + d][r];
+          P.G[((int64_t)(1 + i) * P.d_out + o) * Nc + n] = a;
+        }
+        const float gl = r == Res::RU ? glap[0] : r == Res::RV ? glap[1] : 0.f;
+#pragma unroll
+        for (int c = 1 + K; c < C; ++c) {
+          float a = 0.f;
+          if (c == P.ch_xx) a += gl;
+          if (c == P.ch_yy) a += gl;
+          P.G[((int64_t)c * P.d_out + o) * Nc + n] = a;
+        }
+      }
+    }
+  }
+  // per-block partial sums of the squares, in a fixed order
+#pragma unroll
+  for (int t = 0; t < NT; ++t) red[t][threadIdx.x] = f[t] * f[t];
+  __syncthreads();
+  for (int s = TPB / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) red[t][threadIdx.x] += red[t][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < NT) P.partial[(P.row0 + blockIdx.x) * NT + threadIdx.x] = red[threadIdx.x][0];
+}
+
 // G[c][o][n] of the chunk from row-major gY (N, d_out), gdY (K, N, d_out), gd2Y (P, N, d_out); NULL = 0
 template <int K>
 __global__ void k2_seed_adjoint(const float* __restrict__ gY, const float* __restrict__ gdY,
@@ -491,9 +692,44 @@ void run_fwd_chunk(const Net& n, const float* params, const float* X, int64_t n0
   }
 }
 
+// Points per wave of k2m_wgrad: the chunk spread over about K2M_GROUPS workgroups of four waves, in whole 16-point tiles,
+// between 16 and 128.  Measured on MI355X with fixed slices of 16 / 32 / 64 / 128: the 8 x 64 chunk (23 040
+// points, 64 MFMAs per tile and channel) wants the shortest slice, 90.6 / 97.5 / 123.4 / 180.1 ms per 2^20-point call — its
+// few workgroups leave SIMDs idle long before the atomics count; 10 x 10 at 2^20 points, chunks of about 180 000 (4 MFMAs per tile and
+// channel) wants the longest, 17.9 / 12.1 / 9.2 / 8.3 ms — there every workgroup's flush of atomics is the cost.  The rule
+// below is a compromise, not an optimum: it gives the 8 x 64 chunk 16 points per wave (its best) and the 10 x 10 chunks
+// 48 (9.9 ms where a fixed 128 measured 8.3).
+constexpr int64_t K2M_GROUPS = 1024;
+inline int k2m_slice(int64_t Nc) {
+  const int64_t tiles = (Nc + 4 * K2M_GROUPS * 16 - 1) / (4 * K2M_GROUPS * 16);
+  return (int)(tiles < 1 ? 16 : tiles > 8 ? 128 : tiles * 16);
+}
+
+// k2m_wgrad for one layer (both dimensions at most 64)
+void launch_k2m_wgrad(const float* zb, const float* a_in, int C, int in_dim, int out_dim, int64_t Nc, float* dW,
+                      float* db, hipStream_t s) {
+  const int slice = k2m_slice(Nc);
+  const dim3 grid((unsigned)((Nc + 4 * slice - 1) / (4 * slice))), block(256);
+#define K2M_WG(OTv, ITv) \
+  hipLaunchKernelGGL((k2m_wgrad<OTv, ITv>), grid, block, 0, s, zb, a_in, C, in_dim, out_dim, Nc, slice, dW, db)
+  switch (tiles16(out_dim) * 8 + tiles16(in_dim)) {
+    case 1 * 8 + 1: K2M_WG(1, 1); break;
+    case 1 * 8 + 2: K2M_WG(1, 2); break;
+    case 1 * 8 + 4: K2M_WG(1, 4); break;
+    case 2 * 8 + 1: K2M_WG(2, 1); break;
+    case 2 * 8 + 2: K2M_WG(2, 2); break;
+    case 2 * 8 + 4: K2M_WG(2, 4); break;
+    case 4 * 8 + 1: K2M_WG(4, 1); break;
+    case 4 * 8 + 2: K2M_WG(4, 2); break;
+    default: K2M_WG(4, 4); break;
+  }
+#undef K2M_WG
+}
+
+// mfma_wgrad: the weight gradient on k2m_wgrad instead of k2_wgrad (pinn_residual2_loss_grad's MFMA path only)
 template <int K>
 void run_bwd_chunk(const Net& n, const float* params, int64_t n0, char* ws, const Layout2& lo, int64_t Nc,
-                   float* grad, bool mfma, hipStream_t s) {
+                   float* grad, bool mfma, hipStream_t s, bool mfma_wgrad = false) {
   constexpr int C = J2<K>::C;
   const unsigned grid = (unsigned)((Nc + TPB - 1) / TPB);
   float* gcur = (float*)(ws + lo.g0);
@@ -516,9 +752,14 @@ void run_bwd_chunk(const Net& n, const float* params, int64_t n0, char* ws, cons
       hipLaunchKernelGGL(k2_bwd_layer<K>, dim3(grid), dim3(TPB), 0, s, Wl, in_dim, out_dim, gcur, zh, gnext, Nc, n0,
                          hid ? 1 : 0, n.act, gin, dr);
     }
-    dim3 wg((in_dim + 15) / 16, (out_dim + 15) / 16, (unsigned)((Nc + WG_CHUNK - 1) / WG_CHUNK));
-    hipLaunchKernelGGL(k2_wgrad, wg, dim3(256), 0, s, (const float*)gcur, (const float*)(ws + lo.act_off[l]), C,
-                       in_dim, out_dim, Nc, grad + n.w_off(l), grad + n.b_off(l));
+    if (mfma_wgrad) {
+      launch_k2m_wgrad(gcur, (const float*)(ws + lo.act_off[l]), C, in_dim, out_dim, Nc, grad + n.w_off(l),
+                       grad + n.b_off(l), s);
+    } else {
+      dim3 wg((in_dim + 15) / 16, (out_dim + 15) / 16, (unsigned)((Nc + WG_CHUNK - 1) / WG_CHUNK));
+      hipLaunchKernelGGL(k2_wgrad, wg, dim3(256), 0, s, (const float*)gcur, (const float*)(ws + lo.act_off[l]), C,
+                         in_dim, out_dim, Nc, grad + n.w_off(l), grad + n.b_off(l));
+    }
     float* t = gcur; gcur = gnext; gnext = t;
   }
 }
@@ -587,6 +828,78 @@ int jet2_backward(const Net& n, bool mfma, const float* params, const float* X, 
     }
   });
   return check_launch(mfma ? "MFMA jet2_backward" : "generic jet2_backward");
+}
+
+// ---- pinn_residual2_loss_grad: forward chunk, k2_residual, backward chunk — no unseed, no seed_adjoint, one forward ----
+// Workspace: the jet2 layout, then one row of partial sums per k2_residual workgroup of every chunk.
+namespace {
+constexpr int RES2_NT = 3;
+int64_t residual2_rows(int64_t N, int64_t Nc) {   // workgroups of k2_residual over all chunks (a bound when N % Nc != 0)
+  const int64_t chunks = (N + Nc - 1) / Nc;
+  return chunks * ((Nc + TPB - 1) / TPB);
+}
+
+template <class Res, int K>
+void run_residual2(const Net& n, const pinn_residual_spec& sp, float nu, const float* scale, const float* params,
+                   const float* X, int64_t N, float* fields, float* grad, char* w, const Layout2& lo, float* partial,
+                   bool mfma, hipStream_t s, int64_t* rows) {
+  Res2Params P;
+  P.out = (const float*)(w + lo.out); P.G = (float*)(w + lo.g0); P.fields = fields; P.partial = partial; P.scale = scale;
+  P.N = N; P.d_out = n.d_out; P.want_grad = grad ? 1 : 0; P.nu = nu;
+  for (int r = 0; r < PINN_MAX_ROLES; ++r) P.out_col[r] = sp.out_col[r];
+  for (int d = 0; d < PINN_MAX_DIRS; ++d) P.dir_ch[d] = 1 + sp.dir_of[d];
+  const int ix = sp.dir_of[Res::DX], iy = sp.dir_of[Res::DY];
+  P.ch_xx = 1 + K + pair_index(ix, ix, K);
+  P.ch_yy = 1 + K + pair_index(iy, iy, K);
+  int64_t row0 = 0;
+  for (int64_t n0 = 0; n0 < N; n0 += lo.Nc) {
+    const int64_t Nc = N - n0 < lo.Nc ? N - n0 : lo.Nc;
+    const unsigned grid = (unsigned)((Nc + TPB - 1) / TPB);
+    run_fwd_chunk<K>(n, params, X, n0, w, lo, Nc, mfma, s);
+    P.Nc = Nc; P.n0 = n0; P.row0 = row0;
+    hipLaunchKernelGGL((k2_residual<Res, K>), dim3(grid), dim3(TPB), 0, s, P);
+    row0 += grid;
+    if (grad) run_bwd_chunk<K>(n, params, n0, w, lo, Nc, grad, mfma, s, mfma);
+  }
+  *rows = row0;
+}
+}  // namespace
+
+int64_t residual2_workspace_bytes(const Net& n, int64_t N) {
+  Layout2 lo;
+  const int64_t Np = N > 0 ? N : 1;
+  if (!make_layout2(n, Np, &lo)) return -1;
+  return lo.total + align256(residual2_rows(Np, lo.Nc) * RES2_NT * 4);
+}
+
+// spec: normalised (check_spec), a residual with a momentum equation, n.k == its number of directions
+int residual2_loss_grad(const Net& n, bool mfma, const pinn_residual_spec& spec, float nu, const float* scale,
+                        const float* params, const float* X, int64_t N, float* sums, float* fields, float* grad,
+                        void* ws, int64_t ws_bytes, hipStream_t s) {
+  Layout2 lo;
+  if (!make_layout2(n, N, &lo)) { set_error("too many layers for the jet2 kernels"); return PINN_ERR_UNSUPPORTED; }
+  const int64_t need = lo.total + align256(residual2_rows(N, lo.Nc) * RES2_NT * 4);
+  if (!ws || ws_bytes < need) {
+    set_error("workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  char* w = (char*)ws;
+  float* partial = (float*)(w + lo.total);
+  int64_t rows = 0;
+  switch (spec.residual_id) {
+    case PINN_RES_NAVIER_STOKES:
+      run_residual2<Res2NavierStokes, 3>(n, spec, nu, scale, params, X, N, fields, grad, w, lo, partial, mfma, s, &rows);
+      break;
+    case PINN_RES_PHYSICS_EQUATION:
+      run_residual2<Res2PhysicsEquation, 2>(n, spec, nu, scale, params, X, N, fields, grad, w, lo, partial, mfma, s, &rows);
+      break;
+    case RES_PE_CORRECTED:
+      run_residual2<Res2PhysicsEquationCorrected, 2>(n, spec, nu, scale, params, X, N, fields, grad, w, lo, partial, mfma, s, &rows);
+      break;
+    default: set_error("residual %d has no second-order term", spec.residual_id); return PINN_ERR_UNSUPPORTED;
+  }
+  reduce_sums(partial, rows, RES2_NT, 0, RES2_NT, sums, s);
+  return check_launch(mfma ? "MFMA residual2_loss_grad" : "generic residual2_loss_grad");
 }
 
 }  // namespace pinn

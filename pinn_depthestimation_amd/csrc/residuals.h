@@ -278,6 +278,164 @@ struct ResContinuity {
   }
 };
 
+// ---- second order: lateral mixing nu * lap(U) in the momentum equations --------------------------------------------
+// The momentum fields of Navier_Stokes and physics_equation (plain and corrected) with the eddy-viscosity closure
+//   fm_x -> fm_x - nu (u_xx + u_yy),   fm_y -> fm_y - nu (v_xx + v_yy)        (fc unchanged)
+// written on the first-order jet v[1 + ND][NR] plus the two Laplacians lap = (L_u, L_v) of the momentum roles: the
+// caller forms them from whatever pair layout it carries.  Adjoint: the first-order one with rx = 2 scale[1] fx and
+// ry = 2 scale[2] fy of the SHIFTED fields, and glap = (-nu rx, -nu ry), which the caller puts on the (x, x) and (y, y)
+// pairs of role u and of role v; every other second-order adjoint is zero.
+// Each base restates its residual's first-order formulas as __host__ __device__ code (pinn_residual2_point runs them on
+// the host) split into fields1 and adjoint1(rc, rx, ry); the first-order structs above are left as they are.
+struct Res2NavierStokes {   // ResNavierStokes' roles and directions; u = role 2, v = role 3, x = direction 1, y = direction 2
+  static constexpr int NR = 4, ND = 3, NT = 3, NF = 3, RU = 2, RV = 3, DX = 1, DY = 2;
+  __host__ __device__ static inline void fields1(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
+    const float z_t = v[1][1], u_t = v[1][2], w_t = v[1][3];
+    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
+    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
+    const float G = 9.81f;
+    const float CB = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78));
+    const float H = h + z;
+    const float Hx = h_x + z_x, Hy = h_y + z_y;
+    const float hu_x = Hx * u + H * u_x;
+    const float hv_y = Hy * w + H * w_y;
+    const float Fbr_x = CB * Hx * H, Fbr_y = CB * Hy * H;
+    f[0] = z_t + hu_x + hv_y;                                // physics.py:81
+    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;        // physics.py:82
+    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;        // physics.py:83
+  }
+  __host__ __device__ static inline void adjoint1(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
+                                                  float (&g)[1 + ND][NR]) {
+    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
+    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
+    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
+    const float G = 9.81f;
+    const float CB = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78));
+    const float H = h + z;
+    const float Hx = h_x + z_x, Hy = h_y + z_y;
+    const float gh = rc * (u_x + w_y) + CB * (rx * Hx + ry * Hy);
+    g[0][0] = gh; g[0][1] = gh;
+    g[0][2] = rc * Hx + rx * u_x + ry * w_x;
+    g[0][3] = rc * Hy + rx * u_y + ry * w_y;
+    g[1][0] = 0.f; g[1][1] = rc; g[1][2] = rx; g[1][3] = ry;
+    const float ghx = rc * u + rx * CB * H;
+    g[2][0] = ghx; g[2][1] = ghx + rx * G;
+    g[2][2] = rc * H + rx * u; g[2][3] = ry * u;
+    const float ghy = rc * w + ry * CB * H;
+    g[3][0] = ghy; g[3][1] = ghy + ry * G;
+    g[3][2] = rx * w; g[3][3] = rc * H + ry * w;
+  }
+};
+
+struct Res2PhysicsEquation {   // ResPhysicsEquation's roles and directions (E == 0, physics.py:106); U = role 1, V = role 2
+  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3, RU = 1, RV = 2, DX = 0, DY = 1;
+  __host__ __device__ static inline void fields1(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
+    const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
+    const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
+    const float G = 9.81f, RHO = 1025.f;
+    const float RC = (float)(1025 * 0.002);
+    const float tbx = (RC * U) * fabsf(U);
+    const float tby = (RC * V) * fabsf(V);
+    const float D = 1.0f / (RHO * (eta + h));
+    f[0] = U_x + V_y;                                        // physics.py:113
+    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;            // physics.py:114
+    f[2] = U * V_x + V * V_y + G * e_y + D * tby;            // physics.py:115
+  }
+  __host__ __device__ static inline void adjoint1(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
+                                                  float (&g)[1 + ND][NR]) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
+    const float U_x = v[1][1], V_x = v[1][2];
+    const float U_y = v[2][1], V_y = v[2][2];
+    const float G = 9.81f, RHO = 1025.f;
+    const float RC = (float)(1025 * 0.002);
+    const float tbx = (RC * U) * fabsf(U);
+    const float tby = (RC * V) * fabsf(V);
+    const float D = 1.0f / (RHO * (eta + h));
+    for (int c = 0; c < 1 + ND; ++c)
+      for (int r = 0; r < NR; ++r) g[c][r] = 0.f;
+    const float dD = -RHO * D * D;             // d D / d(eta+h)
+    const float gS = dD * (rx * tbx + ry * tby);
+    g[0][0] = gS; g[0][3] = gS;
+    g[0][1] = rx * (U_x + D * RC * 2.f * fabsf(U)) + ry * V_x;
+    g[0][2] = rx * U_y + ry * (V_y + D * RC * 2.f * fabsf(V));
+    g[1][1] = rc + rx * U;   // d/dU_x
+    g[1][2] = ry * U;        // d/dV_x
+    g[1][3] = rx * G;        // d/deta_x
+    g[2][1] = rx * V;        // d/dU_y
+    g[2][2] = rc + ry * V;   // d/dV_y
+    g[2][3] = ry * G;        // d/deta_y
+  }
+};
+
+struct Res2PhysicsEquationCorrected {   // ResPhysicsEquationCorrected: its own fields and mid, its adjoint on given (rc, rx, ry)
+  typedef ResPhysicsEquationCorrected R1;
+  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3, RU = 1, RV = 2, DX = 0, DY = 1;
+  __host__ __device__ static inline void fields1(const float (&v)[1 + ND][NR], float (&f)[NF]) { R1::fields(v, f); }
+  __host__ __device__ static inline void adjoint1(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
+                                                  float (&g)[1 + ND][NR]) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2], R = v[0][4], K = v[0][5];
+    const float h_x = v[1][0], U_x = v[1][1], V_x = v[1][2], R_x = v[1][4], K_x = v[1][5];
+    const float h_y = v[2][0], U_y = v[2][1], V_y = v[2][2], R_y = v[2][4], K_y = v[2][5];
+    const float G = 9.81f, RHO = 1025.f;
+    const float RC = (float)(1025 * 0.002);
+    const float C_E = (float)(1025 * 9.81 / 8.0);
+    const R1::Mid m = R1::mid(v);
+    const float ax = rx * m.D, ay = ry * m.D;
+    const float dD = -RHO * m.D * m.D;             // d D / d(eta+h)
+    const float gS = dD * (rx * (m.tbx + m.Sx) + ry * (m.tby + m.Sy));
+    const float ds = ax * (2.f * m.E_x * m.n1 + 2.f * m.E * m.n2 * m.s_x) + ay * (m.E_y * m.n1 + m.E * m.n2 * m.s_y);   // adjoint of s = kh
+    const float gsx = 2.f * ax * m.E * m.n1, gsy = ay * m.E * m.n1;   // adjoints of s_x, s_y
+    const float nn = 2.f * m.n + 0.5f;
+    g[0][0] = gS + ds * K + gsx * K_x + gsy * K_y;
+    g[0][1] = rx * (U_x + m.D * RC * 2.f * fabsf(U)) + ry * V_x;
+    g[0][2] = rx * U_y + ry * (V_y + m.D * RC * 2.f * fabsf(V));
+    g[0][3] = gS;
+    g[0][4] = ax * (2.f * C_E * R_x * nn + 4.f * C_E * R * m.n1 * m.s_x) + ay * (2.f * C_E * R_y * m.n + 2.f * C_E * R * m.n1 * m.s_y);
+    g[0][5] = ds * h + gsx * h_x + gsy * h_y;
+    g[1][0] = gsx * K;       // d/dh_x
+    g[1][1] = rc + rx * U;   // d/dU_x
+    g[1][2] = ry * U;        // d/dV_x
+    g[1][3] = rx * G;        // d/deta_x
+    g[1][4] = 2.f * ax * C_E * R * nn;   // d/dHrms_x
+    g[1][5] = gsx * h;       // d/dk_x
+    g[2][0] = gsy * K;
+    g[2][1] = rx * V;
+    g[2][2] = rc + ry * V;
+    g[2][3] = ry * G;
+    g[2][4] = 2.f * ay * C_E * R * m.n;
+    g[2][5] = gsy * h;
+  }
+};
+
+// f <- the shifted fields; with GRAD also g <- sum_t scale[t] d(f_t^2) / dv and glap <- (-nu rx, -nu ry)
+template <class B>
+struct Residual2 {
+  static constexpr int NR = B::NR, ND = B::ND, NT = B::NT, NF = B::NF;
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const float (&lap)[2], float nu,
+                                                float (&f)[NF]) {
+    B::fields1(v, f);
+    f[1] = f[1] - nu * lap[0];
+    f[2] = f[2] - nu * lap[1];
+  }
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float (&lap)[2], float nu,
+                                              const float* scale, float (&f)[NF], float (&g)[1 + ND][NR],
+                                              float (&glap)[2]) {
+    fields(v, lap, nu, f);
+    if (GRAD) adjoint(v, f, nu, scale, g, glap);
+  }
+  // the adjoint from fields already formed (k2_residual: one copy of the field arithmetic, with or without a gradient)
+  __host__ __device__ static inline void adjoint(const float (&v)[1 + ND][NR], const float (&f)[NF], float nu,
+                                                 const float* scale, float (&g)[1 + ND][NR], float (&glap)[2]) {
+    const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
+    B::adjoint1(v, rc, rx, ry, g);
+    glap[0] = -nu * rx;
+    glap[1] = -nu * ry;
+  }
+};
+
 // ---- activations (dnn.py:18-21) ------------------------------------------------
 // tanh: odd minimax polynomial below 0.625 (relative error ~1e-7), the
 // exponential form above; abs error <= ~1.5e-7 everywhere in fp32.

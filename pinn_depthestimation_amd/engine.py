@@ -92,10 +92,18 @@ class ResidualSpec:
     threshold: float = 25.5           # physics.py:26
     anchor: float = 0.75              # physics.py:27
     corrected: bool = False           # physics_equation only: the corrected radiation stress (pinn_residual_spec.flags bit 0)
+    nu: float = 0.0                   # lateral mixing -nu lap(U) in the momentum equations (Navier_Stokes, physics_equation), in
+                                      # the units of the network's inputs; travels BESIDE the C struct (pinn_residual2_loss_grad)
 
     @property
     def residual_id(self) -> int:
         return RESIDUAL_ROLES[self.name][0]
+
+    def first_order(self, what: str) -> "ResidualSpec":
+        """self, for a first-order entry: raises instead of silently dropping the second-order term."""
+        if self.nu != 0:
+            raise PinnError(f"{what} evaluates the first-order residual and would drop nu = {self.nu}: use residual2_loss_grad")
+        return self
 
     @property
     def n_terms(self) -> int:
@@ -119,13 +127,19 @@ class ResidualSpec:
 
     @staticmethod
     def from_names(name: str, input_names: Sequence[str], grad_cols: Sequence[int],
-                   output_names: Sequence[str], corrected: bool = False) -> "ResidualSpec":
+                   output_names: Sequence[str], corrected: bool = False, nu: float = 0.0) -> "ResidualSpec":
         """Map config variable names (config data_residual.inputs / outputs) onto roles.  corrected=True (physics_equation
-        only): E = rho g Hrms^2 / 8 in place of the reference's E == 0, as physics.physics_equation(corrected=True)."""
+        only): E = rho g Hrms^2 / 8 in place of the reference's E == 0, as physics.physics_equation(corrected=True).
+        nu (Navier_Stokes, physics_equation): the lateral-mixing term -nu lap(U) in the momentum equations."""
         if name not in RESIDUAL_ROLES:
             raise PinnError(f"unknown residual {name!r}; known: {sorted(RESIDUAL_ROLES)}")
         if corrected and name != "physics_equation":
             raise PinnError(f"corrected=True is the radiation stress of physics_equation; residual {name!r} has none")
+        nu = float(nu)
+        if not (nu >= 0.0 and nu != float("inf")):
+            raise PinnError(f"nu = {nu}: the eddy viscosity must be finite and >= 0")
+        if nu != 0 and name not in ("Navier_Stokes", "physics_equation"):
+            raise PinnError(f"nu is the lateral mixing of a momentum equation; residual {name!r} has none")
         _, out_roles, dir_roles = RESIDUAL_ROLES[name]
         out_col = []
         for r in out_roles:
@@ -140,7 +154,7 @@ class ResidualSpec:
             if col not in grad_cols:
                 raise PinnError(f"input {r!r} must have requires_grad 'true' for residual {name}")
             dir_of.append(list(grad_cols).index(col))
-        return ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected))
+        return ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected), nu=nu)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -317,6 +331,7 @@ class Engine:
         return grad
 
     def residual_loss(self, spec: ResidualSpec, params, X, engine=None) -> torch.Tensor:
+        spec.first_order("residual_loss")
         N = X.shape[0]
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
         sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
@@ -327,6 +342,7 @@ class Engine:
 
     def fields_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual_fields (pinn_query_fields_workspace), cached apart from workspace()'s."""
+        spec.first_order("fields_workspace")
         e = self.desc.engine if engine is None else engine
         key = ("fields", e, spec.residual_id, spec.corrected, N)
         need = self._ws_need.get(key)
@@ -346,6 +362,7 @@ class Engine:
         (pinn_residual_fields); sum over points of row t squared is residual_loss's term_sums[t].  engine=None is the
         descriptor's engine: AUTO runs the MFMA tile kernel's field instances where they exist (width <= 64, fp32, no
         dropout) and the forward jet plus a point-wise kernel otherwise; FUSED is refused where AUTO would fall back."""
+        spec.first_order("residual_fields")
         N = X.shape[0]
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
         out = torch.empty(spec.n_fields, N, dtype=torch.float32, device=X.device)
@@ -357,6 +374,7 @@ class Engine:
     def residual_loss_grad(self, spec: ResidualSpec, term_scale: torch.Tensor, params, X, grad: torch.Tensor,
                            engine=None, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
         """grad += sum_t term_scale[t] * d(term_sums[t])/d(params); returns term_sums (device)."""
+        spec.first_order("residual_loss_grad")
         N = X.shape[0]
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
         self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
@@ -367,6 +385,44 @@ class Engine:
                                                _ptr(term_scale), _ptr(params), _ptr(X), N, _ptr(sums),
                                                _ptr(grad), _ptr(ws), ws.numel())
         return sums
+
+    def residual2_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
+        """Workspace of residual2_loss_grad (pinn_query_residual2_workspace), cached apart from the others."""
+        e = self.desc.engine if engine is None else engine
+        key = ("res2", e, spec.residual_id, N)
+        need = self._ws_need.get(key)
+        if need is None:
+            c_need = C.c_int64()
+            check(self.lib.pinn_query_residual2_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
+                  "pinn_query_residual2_workspace")
+            need = self._ws_need[key] = c_need.value
+        ws = self._ws.get(("res2", e))
+        if ws is None or ws.numel() < need:
+            self._ws[("res2", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def residual2_loss_grad(self, spec: ResidualSpec, term_scale: Optional[torch.Tensor], params, X,
+                            grad: Optional[torch.Tensor] = None, fields: bool = False,
+                            sums: Optional[torch.Tensor] = None, engine=None):
+        """The residual with the lateral-mixing term -spec.nu lap(U) in its momentum equations, on the second-order jets
+        (pinn_residual2_loss_grad): returns term_sums, or (term_sums, fields (n_fields, N)) with fields=True; with `grad`
+        also grad += sum_t term_scale[t] * d(term_sums[t])/d(params).  grad=None runs no backward sweep (term_scale may
+        then be None).  spec.nu == 0 gives the first-order residual.  engine=None is the descriptor's: AUTO runs the MFMA
+        kernels where every layer is at most 64 wide (fp32, no dropout) and the generic ones otherwise."""
+        N = X.shape[0]
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        if grad is not None:
+            self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
+        if sums is None:
+            sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
+        else:
+            self._chk(sums, "sums", (spec.n_terms,))
+        out = torch.empty(spec.n_fields, N, dtype=torch.float32, device=X.device) if fields else None
+        ws = self.residual2_workspace(spec, N, engine)
+        self._run("pinn_residual2_loss_grad", self.lib.pinn_residual2_loss_grad, C.byref(self._d(engine)),
+                  C.byref(spec.c_struct()), C.c_float(spec.nu), _ptr(term_scale) if grad is not None else None, _ptr(params),
+                  _ptr(X), N, _ptr(sums), _ptr(out), _ptr(grad), _ptr(ws), ws.numel())
+        return (sums, out) if fields else sums
 
     def mse_loss_grad(self, params, X, T: torch.Tensor, out_col: Sequence[int],
                       col_scale: Optional[torch.Tensor], grad: Optional[torch.Tensor], engine=None,
@@ -386,6 +442,7 @@ class Engine:
     def residual_mse_loss_grad(self, spec: ResidualSpec, term_scale, T: torch.Tensor, out_col: Sequence[int],
                                col_scale, params, X, grad, engine=None, term_sums=None, col_sums=None):
         """One pass over one point set: PDE residual + fidelity columns (train_newmethod.py:122-159)."""
+        spec.first_order("residual_mse_loss_grad")
         N, nc = X.shape[0], len(out_col)
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in)); self._chk(T, "T", (N, nc))
         self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
@@ -406,6 +463,7 @@ class Engine:
                                      col_sums=None):
         """train.py:131-157 in one launch: X = [n_res collocation points ; fidelity points], T = the
         fidelity targets (N - n_res, n_cols)."""
+        spec.first_order("residual_mse_split_loss_grad")
         N, nc = X.shape[0], len(out_col)
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in)); self._chk(T, "T", (N - n_res, nc))
         self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
@@ -438,6 +496,7 @@ class Engine:
         `.data` (dnn.DNN's Linear weights, `p.data = flat[...]`) have counters of their own, so a caller whose buffer
         is aliased that way passes a token that changes whenever any alias is written (DNN.write_token(): the
         Parameters' version counters); writes no counter sees (`p.data.mul_()`) need invalidate_packed()."""
+        spec.first_order("loss_grad_adam_step")
         N, nc = X.shape[0], len(out_col)
         lrs = [float(x) for x in lr] if isinstance(lr, (list, tuple)) else None
         self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))

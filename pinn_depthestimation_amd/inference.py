@@ -30,9 +30,13 @@ FIELD_NAMES = {"Navier_Stokes": ("fc", "fm_x", "fm_y"), "physics_equation": ("fc
 
 
 class Tester:
-    def __init__(self, model, config, device="cuda", residual: Optional[str] = None, corrected: bool = False):
+    def __init__(self, model, config, device="cuda", residual: Optional[str] = None, corrected: bool = False,
+                 eddy_viscosity: float = 0.0):
         """corrected (physics_equation only): residual_fields and the physics-only fine-tune use the corrected radiation
-        stress (ResidualSpec.corrected, physics.physics_equation_corrected)."""
+        stress (ResidualSpec.corrected, physics.physics_equation_corrected).
+        eddy_viscosity (Navier_Stokes, physics_equation): nu of the lateral-mixing term -nu lap(U) in the momentum
+        equations, in the units of the network's inputs (normalised to [-1, 1] in the reference's pipeline); residual_fields
+        and the fine-tune residual both carry it."""
         self.config: PinnConfig = config if isinstance(config, PinnConfig) else load_config(config)
         self.device = torch.device(device)
         self.model = self.load_model(model)
@@ -47,6 +51,11 @@ class Tester:
         self.corrected = bool(corrected)
         if self.corrected and self.residual != "physics_equation":
             raise PinnError(f"corrected=True is the radiation stress of physics_equation; residual {self.residual!r} has none")
+        self.eddy_viscosity = float(eddy_viscosity)
+        if not (self.eddy_viscosity >= 0.0 and self.eddy_viscosity != float("inf")):
+            raise PinnError(f"eddy_viscosity = {self.eddy_viscosity}: must be finite and >= 0")
+        if self.eddy_viscosity != 0 and self.residual not in ("Navier_Stokes", "physics_equation"):
+            raise PinnError(f"eddy_viscosity is the lateral mixing of a momentum equation; residual {self.residual!r} has none")
         self.init_optimizers()
         self.last_loss = None
 
@@ -76,8 +85,12 @@ class Tester:
 
     def _residual_loss(self):
         _, out_roles, dir_roles = RESIDUAL_ROLES[self.residual]
+        args = [getattr(self, k) for k in dir_roles] + [getattr(self, k) for k in out_roles]
+        if self.eddy_viscosity != 0:
+            kw = {"corrected": True} if self.corrected else {}
+            return getattr(physics, self.residual)(*args, nu=self.eddy_viscosity, **kw)
         fn = physics.physics_equation_corrected if self.corrected else getattr(physics, self.residual)
-        return fn(*[getattr(self, k) for k in dir_roles], *[getattr(self, k) for k in out_roles])
+        return fn(*args)
 
     def test(self, test_input_data, input_min_max: Optional[dict] = None, perform_optimization: Optional[bool] = None):
         data = torch.as_tensor(np.asarray(test_input_data)).float().to(self.device)
@@ -120,13 +133,17 @@ class Tester:
         data = torch.as_tensor(np.asarray(test_input_data)).float().to(self.device).contiguous()
         names = list(self.test_input_vars)
         grad_cols = tuple(i for i, k in enumerate(names) if "true" in self.test_input_vars[k].get("requires_grad", []))
-        spec = ResidualSpec.from_names(self.residual, names, grad_cols, self.test_output_vars, corrected=self.corrected)
+        spec = ResidualSpec.from_names(self.residual, names, grad_cols, self.test_output_vars, corrected=self.corrected,
+                                       nu=self.eddy_viscosity)
         key = (tuple(self.model.layer_sizes), grad_cols)
         if getattr(self, "_fields_engine_key", None) != key:
             self._fields_engine = Engine(NetDesc.from_layers(self.model.layer_sizes, grad_cols,
                                                              ACTIVATION_OF_INIT[self.model.init_type]), self.device)
             self._fields_engine_key = key
-        F = self._fields_engine.residual_fields(spec, self.model.flat_params(), data)
+        if spec.nu != 0:
+            F = self._fields_engine.residual2_loss_grad(spec, None, self.model.flat_params(), data, grad=None, fields=True)[1]
+        else:
+            F = self._fields_engine.residual_fields(spec, self.model.flat_params(), data)
         out = F.cpu().numpy()
         if self.nx and self.ny and data.shape[0] == self.nx * self.ny:
             for i, k in enumerate(names):

@@ -55,10 +55,20 @@ def continuity_ftemp(x, y, h, U, V):
     return _mean_sq(_continuity_field(x, y, h, U, V))
 
 
-def Navier_Stokes(t, x, y, h, z, u, v):
+def _laplacian(a, x, y):
+    d = compute_gradient
+    return d(d(a, x), x) + d(d(a, y), y)
+
+
+def Navier_Stokes(t, x, y, h, z, u, v, nu=0.0):
     """physics.py:50-88 — unsteady shallow-water continuity + x/y momentum with the
-    wave-breaking force 3/16 g gamma_b^2 d(h+z)/dx (h+z); friction terms are zero."""
-    fused = fused_residual("Navier_Stokes", (t, x, y), (h, z, u, v))
+    wave-breaking force 3/16 g gamma_b^2 d(h+z)/dx (h+z); friction terms are zero.
+
+    nu > 0 (an extension, not reference behaviour) adds lateral mixing, -nu (u_xx + u_yy) and -nu (v_xx + v_yy), to the two
+    momentum equations.  The derivatives are with respect to the network's inputs as it sees them: in the reference's
+    pipeline those are normalised to [-1, 1], so nu is in those units.  Where the arguments are the columns of one
+    DNN.forward call the term is hard-wired (pinn_residual2_loss_grad); otherwise nested compute_gradient evaluates it."""
+    fused = fused_residual("Navier_Stokes", (t, x, y), (h, z, u, v), nu=nu)
     if fused is not None:
         return fused
     d = compute_gradient
@@ -68,10 +78,13 @@ def Navier_Stokes(t, x, y, h, z, u, v):
     mass = d(z, t) + d(depth * u, x) + d(depth * v, y)
     mom_x = d(u, t) + u * d(u, x) + v * d(u, y) + g * d(z, x) + cb * d(depth, x) * depth
     mom_y = d(v, t) + u * d(v, x) + v * d(v, y) + g * d(z, y) + cb * d(depth, y) * depth
+    if nu != 0:
+        mom_x = mom_x - nu * _laplacian(u, x, y)
+        mom_y = mom_y - nu * _laplacian(v, x, y)
     return _mean_sq(mass, mom_x, mom_y)
 
 
-def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False):
+def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0):
     """physics.py:91-120 — steady wave-averaged continuity + momentum with quadratic bottom
     friction.  Default is bug-compatible: the reference's E = 1/8**rho*g*Hrms**2 (physics.py:106)
     is exactly 0.0, so the radiation-stress gradients vanish and Hrms, k do not enter.
@@ -79,8 +92,17 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False):
     corrected=True (an extension, not reference behaviour) evaluates what the line evidently
     meant, E = 1/8 * rho * g * Hrms**2, with Sxx = E (2kh/sinh(2kh) + 1/2), Syy = E kh/sinh(2kh)
     (physics.py:107-109); it is written with compute_gradient like any user residual: the forward jet and the
-    parameter gradient (pinn_jet_backward) both run on the MFMA tile kernel, torch autograd evaluates the formula between."""
-    if not corrected:
+    parameter gradient (pinn_jet_backward) both run on the MFMA tile kernel, torch autograd evaluates the formula between.
+
+    nu > 0 (an extension as well) adds lateral mixing, -nu (U_xx + U_yy) and -nu (V_xx + V_yy), to the two momentum
+    equations, plain or corrected: the standard closure of the wave-averaged balance.  nu is in the units of the network's
+    inputs (normalised to [-1, 1] in the reference's pipeline).  Hard-wired (pinn_residual2_loss_grad) where the arguments
+    are the columns of one DNN.forward call, nested compute_gradient otherwise."""
+    if nu != 0:
+        fused = fused_residual("physics_equation", (x, y), (h, U, V, eta_mean, Hrms, k), corrected=corrected, nu=nu)
+        if fused is not None:
+            return fused
+    elif not corrected:
         fused = fused_residual("physics_equation", (x, y), (h, U, V, eta_mean, Hrms, k))
         if fused is not None:
             return fused
@@ -95,6 +117,9 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False):
         ratio = k * h / torch.sinh(2 * k * h)
         mom_x = mom_x + inv_depth * d(E * (2 * ratio + 0.5), x)
         mom_y = mom_y + inv_depth * d(E * ratio, y)
+    if nu != 0:
+        mom_x = mom_x - nu * _laplacian(U, x, y)
+        mom_y = mom_y - nu * _laplacian(V, x, y)
     return _mean_sq(mass, mom_x, mom_y)
 
 

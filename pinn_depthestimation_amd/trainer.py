@@ -79,7 +79,27 @@ class HipEvaluator:
 
     MERGE_MAX_FID = 2048   # fidelity points ride through the jet kernel (4x their own work): only when few
 
+    def _call_nu(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
+        """The residual with the lateral-mixing term (spec.nu != 0): Engine.residual2_loss_grad on the collocation points,
+        the fidelity term a separate mse_loss_grad (also where both terms share one point set)."""
+        drop = self.eng_drop is not None and self.training
+        e = self.eng_drop if drop else self.eng
+        if Xf is not None and Xf.shape[0] > 0:
+            if drop:
+                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
+        else:
+            fid_sums.zero_()
+        if Xr is not None and Xr.shape[0] > 0:
+            if drop:
+                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            e.residual2_loss_grad(self.spec, res_scale, theta, Xr, grad, sums=res_sums)
+        else:
+            res_sums.zero_()
+
     def __call__(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
+        if self.spec.nu != 0:
+            return self._call_nu(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
         if self.eng_drop is not None and self.training:
             # the reference runs the network twice per loss_func call (train.py:133,148): two forward passes, two
             # masks — one fresh seed per pass, from torch's CPU generator
@@ -129,6 +149,8 @@ class HipEvaluator:
         (Engine.loss_grad_adam_step); False — nothing done — otherwise: the caller then runs __call__ + adam_step."""
         if (self.eng_drop is not None and self.training) or Xr is None or Xr.shape[0] == 0:
             return False
+        if self.spec.nu != 0:     # the second-order residual is layer kernels per chunk, not one pass: the classic path
+            return False
         has_fid = Xf is not None and Xf.shape[0] > 0
         if not has_fid:
             if fid_sums.numel():       # (a configuration with fidelity outputs but no fidelity points: classic path)
@@ -167,6 +189,8 @@ class HipEvaluator:
 
     def residual_fields(self, theta, X):
         """(n_fields, N) signed residual fields at the rows of X, in eval mode: the engine without dropout, as predict."""
+        if self.spec.nu != 0:     # the shifted fields, from the entry the loss runs on (no backward sweep)
+            return self.eng.residual2_loss_grad(self.spec, None, theta, X, grad=None, fields=True)[1]
         return self.eng.residual_fields(self.spec, theta, X)
 
 
@@ -180,10 +204,14 @@ class PINN:
                  mat_dump_path: str = "data_at50k.mat", residual_batch: Optional[int] = None, seed: int = 1234,
                  log_flush_every: int = 100, lbfgs_impl: str = "flat", precision: int = 0, fold_adam: bool = True,
                  resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0,
-                 corrected: bool = False):
+                 corrected: bool = False, eddy_viscosity: float = 0.0):
         """corrected (or the config key loss.corrected_radiation_stress; physics_equation only): train on the corrected
         radiation stress, E = rho g Hrms^2 / 8, hard-wired in the kernels (ResidualSpec.corrected) — every path that takes
-        the spec follows: the merged launch, the folded Adam runs, residual_fields and resample="rad"."""
+        the spec follows: the merged launch, the folded Adam runs, residual_fields and resample="rad".
+        eddy_viscosity (or the config key loss.eddy_viscosity; Navier_Stokes and physics_equation): nu of the lateral-mixing
+        term -nu lap(U) in the momentum equations (ResidualSpec.nu), in the units of the network's inputs — normalised to
+        [-1, 1] in the reference's pipeline.  The residual then runs on Engine.residual2_loss_grad, the fidelity term
+        as a separate call; Adam iterations take the classic path; residual_fields and resample="rad" see the shifted fields."""
         cfg = config if isinstance(config, PinnConfig) else load_config(config)
         self.config, self.device = cfg, torch.device(device)
         self.reducer = reducer or Reducer()
@@ -198,8 +226,9 @@ class PINN:
 
         residual = residual or cfg.default_residual()
         self.corrected = bool(corrected) or bool(cfg.raw.get("loss", {}).get("corrected_radiation_stress", False))
+        self.eddy_viscosity = float(eddy_viscosity) if eddy_viscosity else float(cfg.raw.get("loss", {}).get("eddy_viscosity", 0.0))
         self.spec = ResidualSpec.from_names(residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs,
-                                            corrected=self.corrected)       # (PinnError on any other residual)
+                                            corrected=self.corrected, nu=self.eddy_viscosity)   # (PinnError on any other residual)
         # i-th fidelity output is compared with output column i (train.py:137-138, train_newmethod.py:129-131)
         self.fid_cols = list(range(len(cfg.fidelity_outputs)))
         if cfg.variant == "newmethod":
