@@ -26,6 +26,8 @@
  *   pinn_residual_mse_loss_grad  train_newmethod.py:122-159 (both on one forward) + backward
  *   pinn_residual_mse_split_loss_grad  train.py:131-157 (fidelity set + collocation set, one launch)
  *   pinn_lbfgs_push / pinn_lbfgs_direction  torch.optim.LBFGS's two-loop recursion (train.py:116-125,200)
+ *   pinn_lbfgs_loop         torch.optim.LBFGS.step(closure) with the strong-Wolfe line search (train.py:116-125,195-200): runs of
+ *                           evaluations enqueued by one call, every decision taken on the device
  *   pinn_adam_step          torch.optim.Adam.step as called at train.py:192
  *   pinn_loss_grad_adam_step  train.py:189-193 (loss_func + backward + Adam.step) in two launches
  *   pinn_adam_loop          train.py:188-193, n iterations of the above enqueued by one call
@@ -64,6 +66,8 @@
  *     pinn_residual_mse_loss_grad and pinn_residual_mse_split_loss_grad (the caller zeroes it, or accumulates several
  *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step and pinn_adam_loop.  Y, dY, d2Y, fields,
  *     term_sums, col_sums, losses, X_out, n_rows_out, out2 and d are overwritten, whatever they held.
+ *   - pinn_lbfgs_loop: writes params (P), trace (n_slots x PINN_LBFGS_TRACE_COLS) and state (the bytes pinn_query_lbfgs_loop
+ *     states) at those extents only; `state` is the one buffer whose content a call relies on (pinn_lbfgs_loop_init arms it).
  *   - N = 0 where it is accepted: the sums are zeroed, grad_flat and the workspace are not touched.
  */
 #ifndef PINN_HIP_H
@@ -454,6 +458,114 @@ int32_t pinn_lbfgs_push(float* S, float* Y, double* M, int32_t m, int64_t P, int
 int32_t pinn_lbfgs_direction(const float* S, const float* Y, const double* M, int32_t m, int64_t P,
                              int32_t head, int32_t k, const float* g, double H, float* d,
                              double* tmp, float* coef, float* q, void* stream);
+
+/* ---- device-resident L-BFGS: runs of strong-Wolfe evaluations enqueued by one call -----------------------------------
+ * (added under ABI version 4, as the fields and residual2 entries were: no existing entry, struct or constant changed)
+ * torch.optim.LBFGS.step(closure) with line_search_fn = "strong_wolfe" (train.py:116-125,200) without the host in it.
+ * HIP has no device-side launch, so the host enqueues a fixed sequence of SLOTS and the device decides what each means:
+ *     slot:  x_trial = x + t d                       (t, d on the device; x is `params`)
+ *            loss + gradient pass at x_trial          (the very host code of the loss entries, params = x_trial: whatever
+ *                                                      engine the descriptor selects)
+ *            controller: one step of the strong-Wolfe state machine
+ *              CONTINUE  next trial t, the gradient filed in its pool row; the accept kernels exit at once
+ *              ACCEPT    x += t* d, s, y, the stopping tests, ring push (only when y.s > 1e-10), H = y.s / y.y,
+ *                        d = -H_k g (the six-launch recursion of pinn_lbfgs_direction), gtd = g.d, t = lr, search re-armed
+ *              STOP      the done flag with a reason; every later slot is inert
+ * The first slot after pinn_lbfgs_loop_init is the evaluation at t = 0 (torch's orig_loss).  Every slot is a useful
+ * evaluation: a line search of three evaluations takes three slots.
+ *
+ * The line search is torch's _strong_wolfe (torch/optim/lbfgs.py) restated branch for branch as a resumable state machine
+ * (csrc/lbfgs_line_search.h: one source for host and device), c1 = 1e-4, c2 = 0.9, its own tolerance_change = 1e-9, and it
+ * returns the LOW end of the bracket as torch does.  pinn_lbfgs_ls_init / pinn_lbfgs_ls_step run the very functions the
+ * controller kernel calls, on the host; no device is touched.  The state carries no vectors, only rows of a four-row
+ * gradient pool: row 0 holds the gradient of the iterate, g_slot_for_new says where the caller files the gradient of the
+ * trial about to be evaluated, g_acc_slot which row holds the gradient of the accepted point.
+ * Known deviation: lbfgs.FlatLBFGS hands _strong_wolfe a Python-float loss and fp32 0-dim tensors for g.d, so part of its
+ * scalar arithmetic is fp32; here every scalar (g.d, y.s, y.y, |g|_1, the whole line search) is fp64, formed from
+ * per-workgroup partial sums combined in a fixed order.  Same algorithm, same branches; a decision can flip at a rounding
+ * boundary.  The loss value is the fp32 number float(loss) would have been (double accumulation, one rounding). */
+#define PINN_LS_EVALUATE 0   /* evaluate f and g.d at st->t, file the gradient in row st->g_slot_for_new, call ls_step again */
+#define PINN_LS_DONE 1       /* st->t_acc, st->f_acc, st->g_acc_slot */
+#define PINN_LS_POOL_ROWS 4
+typedef struct pinn_ls_state {
+  double f0, gtd0, d_norm;           /* the point t = 0 and max|d| */
+  double t;                          /* the trial step to evaluate (EVALUATE) */
+  double t_prev, f_prev, gtd_prev;   /* bracketing phase: the previous point */
+  double br_t[2], br_f[2], br_gtd[2];/* the bracket */
+  double t_acc, f_acc;               /* DONE: the accepted step and its loss */
+  int32_t phase;                     /* 0 bracketing, 1 zoom, 2 done */
+  int32_t ls_iter, max_ls, n_evals;
+  int32_t low_pos, high_pos, insuf_progress, br_n;
+  int32_t g_prev_slot, br_slot[2];   /* pool rows of the previous point and of the bracket ends */
+  int32_t g_slot_for_new, g_acc_slot;
+} pinn_ls_state;
+int32_t pinn_lbfgs_ls_init(pinn_ls_state* st, double f0, double gtd0, double t0, double d_norm, int32_t max_ls);
+int32_t pinn_lbfgs_ls_step(pinn_ls_state* st, double f_new, double gtd_new);   /* PINN_LS_EVALUATE / PINN_LS_DONE, < 0: error */
+
+typedef struct pinn_lbfgs_opts {
+  double lr, tolerance_grad, tolerance_change;
+  int32_t max_iter, max_eval, history_size;
+} pinn_lbfgs_opts;
+
+/* what a slot did (trace column 2) and why the loop stopped (trace column 6, ctrl.reason) */
+#define PINN_LBFGS_ACT_INERT 0      /* the done flag was up: nothing evaluated, nothing written but this trace row */
+#define PINN_LBFGS_ACT_CONTINUE 1   /* a trial inside a line search */
+#define PINN_LBFGS_ACT_ACCEPT 2     /* the line search ended at this evaluation: iterate updated */
+#define PINN_LBFGS_ACT_INITIAL 3    /* the evaluation at t = 0 */
+#define PINN_LBFGS_STOP_NONE 0
+#define PINN_LBFGS_STOP_GRADIENT 1  /* max|g| <= tolerance_grad */
+#define PINN_LBFGS_STOP_STEP 2      /* max|s| <= tolerance_change */
+#define PINN_LBFGS_STOP_LOSS 3      /* |f - f_prev| < tolerance_change */
+#define PINN_LBFGS_STOP_MAX_ITER 4
+#define PINN_LBFGS_STOP_MAX_EVAL 5
+#define PINN_LBFGS_STOP_DIRECTION 6 /* g.d > -tolerance_change */
+
+/* The control block: the first bytes of `state`.  The host may read it after its own synchronisation; it writes it only
+ * through pinn_lbfgs_loop_init. */
+typedef struct pinn_lbfgs_ctrl {
+  int32_t phase;       /* 0: the next slot is the evaluation at t = 0; 1: inside a line search */
+  int32_t done;        /* 1: stopped, every later slot is inert */
+  int32_t reason;      /* PINN_LBFGS_STOP_* */
+  int32_t action;      /* PINN_LBFGS_ACT_* of the slot in flight (the accept kernels read it) */
+  int32_t head, k, slot, m;          /* the ring: oldest row, pairs in use, row of the last push, history_size */
+  int32_t n_iter, n_evals, max_iter, max_eval;
+  int32_t push;        /* this accept stores a pair */
+  int32_t file_row, acc_row;         /* pool rows: of the gradient just evaluated, of the accepted point */
+  int32_t n_slots;     /* slots run since init, inert ones included */
+  int64_t P;
+  double t;            /* the trial step of the next slot */
+  double f, gtd, d_norm, H;          /* at the iterate: loss, g.d, max|d|, initial scaling */
+  double f_prev;       /* prev_loss of torch */
+  double t_acc, gmax;  /* of the last accept */
+  double lr, tolerance_grad, tolerance_change;
+  pinn_ls_state ls;
+} pinn_lbfgs_ctrl;
+
+/* trace: (n_slots, PINN_LBFGS_TRACE_COLS) doubles, overwritten.  Per slot: 0 evaluation index (1-based), 1 iteration index
+ * (after the slot), 2 action, 3 the step t evaluated, 4 its loss f, 5 g_new.d, 6 stop reason (0: none), 7 accepted step t*,
+ * 8 its loss, 9 max|g| at the accepted point (7..9: ACCEPT and INITIAL rows, else 0), 10 .. 10 + n_loss_rows the weighted
+ * losses of this evaluation, zeros up to column 17.  Inert slots: zeros. */
+#define PINN_LBFGS_TRACE_COLS 18
+
+/* ws_bytes: the pass's workspace (pinn_query_workspace's answer); state_bytes: control block, d, x_trial, g_new, the
+ * four-row gradient pool, prev_g, s, y, q (P floats each), S and Y (history_size x P floats each), M (history_size^2
+ * doubles), the recursion's scratch and the reduction partials — every region on a 256-byte boundary. */
+int32_t pinn_query_lbfgs_loop(const pinn_desc* desc, int64_t N, int32_t history_size, int64_t* ws_bytes, int64_t* state_bytes);
+/* zeroes the state (S and Y with it) and arms the control block; P is the descriptor's parameter count */
+int32_t pinn_lbfgs_loop_init(void* state, int64_t state_bytes, int64_t P, const pinn_lbfgs_opts* opts, void* stream);
+/* n_slots slots.  X, n_res, T, n_cols, out_col, the scales and loss_rows as in pinn_loss_grad_adam_step (loss_rows:
+ * (n_loss_rows, n_cols + n_terms), 1 <= n_loss_rows <= 8); total_row names the row that is the objective.
+ * params is x: it holds the ACCEPTED iterate whenever a call returns; trial weights never reach it.  The state carries
+ * over between calls: two calls of n slots are one call of 2n.  trace may be NULL.
+ * Refused before any device work: history_size (of the query) outside 1..256, n_slots < 0, null pointers, a state smaller
+ * than the query's -> PINN_ERR_INVALID / PINN_ERR_WORKSPACE; dropout_p > 0 -> PINN_ERR_UNSUPPORTED (a seed per forward pass
+ * has no place in a fixed schedule); every refusal the loss request itself would get, with its own message.
+ * Reproducible wherever the pass is: no float atomics, every reduction is per-workgroup partials combined in a fixed order. */
+int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale, const float* T,
+                        int32_t n_cols, const int32_t* out_col, const float* col_scale, float* params, const float* X,
+                        int64_t N, int64_t n_res, int32_t n_loss_rows, const float* loss_rows, int32_t total_row,
+                        void* state, int64_t state_bytes, int32_t n_slots, double* trace,
+                        void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- staging of the collocation points on the device (train.py:246-277, operations.py:4-30) --------------------
  * The reference loads each input variable as a (ny, nx) float64 grid (scipy.io.loadmat), subsamples it with

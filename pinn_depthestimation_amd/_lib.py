@@ -48,6 +48,44 @@ class PinnAdamState(C.Structure):
     ]
 
 
+class PinnLsState(C.Structure):
+    """pinn_ls_state: torch's _strong_wolfe as a resumable state machine (csrc/lbfgs_line_search.h)."""
+    _fields_ = [
+        ("f0", C.c_double), ("gtd0", C.c_double), ("d_norm", C.c_double), ("t", C.c_double),
+        ("t_prev", C.c_double), ("f_prev", C.c_double), ("gtd_prev", C.c_double),
+        ("br_t", C.c_double * 2), ("br_f", C.c_double * 2), ("br_gtd", C.c_double * 2),
+        ("t_acc", C.c_double), ("f_acc", C.c_double),
+        ("phase", C.c_int32), ("ls_iter", C.c_int32), ("max_ls", C.c_int32), ("n_evals", C.c_int32),
+        ("low_pos", C.c_int32), ("high_pos", C.c_int32), ("insuf_progress", C.c_int32), ("br_n", C.c_int32),
+        ("g_prev_slot", C.c_int32), ("br_slot", C.c_int32 * 2), ("g_slot_for_new", C.c_int32), ("g_acc_slot", C.c_int32),
+    ]
+
+
+class PinnLbfgsOpts(C.Structure):
+    _fields_ = [("lr", C.c_double), ("tolerance_grad", C.c_double), ("tolerance_change", C.c_double),
+                ("max_iter", C.c_int32), ("max_eval", C.c_int32), ("history_size", C.c_int32)]
+
+
+class PinnLbfgsCtrl(C.Structure):
+    """pinn_lbfgs_ctrl: the first bytes of the device L-BFGS loop's state."""
+    _fields_ = [
+        ("phase", C.c_int32), ("done", C.c_int32), ("reason", C.c_int32), ("action", C.c_int32),
+        ("head", C.c_int32), ("k", C.c_int32), ("slot", C.c_int32), ("m", C.c_int32),
+        ("n_iter", C.c_int32), ("n_evals", C.c_int32), ("max_iter", C.c_int32), ("max_eval", C.c_int32),
+        ("push", C.c_int32), ("file_row", C.c_int32), ("acc_row", C.c_int32), ("n_slots", C.c_int32),
+        ("P", C.c_int64),
+        ("t", C.c_double), ("f", C.c_double), ("gtd", C.c_double), ("d_norm", C.c_double), ("H", C.c_double),
+        ("f_prev", C.c_double), ("t_acc", C.c_double), ("gmax", C.c_double),
+        ("lr", C.c_double), ("tolerance_grad", C.c_double), ("tolerance_change", C.c_double),
+        ("ls", PinnLsState),
+    ]
+
+
+LS_EVALUATE, LS_DONE, LS_POOL_ROWS = 0, 1, 4
+LBFGS_ACT_INERT, LBFGS_ACT_CONTINUE, LBFGS_ACT_ACCEPT, LBFGS_ACT_INITIAL = 0, 1, 2, 3
+LBFGS_STOP_REASONS = {0: None, 1: "gradient", 2: "step", 3: "loss change", 4: "max_iter", 5: "max_eval", 6: "direction"}
+LBFGS_TRACE_COLS = 18
+
 ERR_INVALID, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -2, -3
 
 
@@ -93,6 +131,13 @@ _SIGNATURES = {
     "pinn_lbfgs_push": (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
     "pinn_lbfgs_direction": (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_double, _P,
                                          _P, _P, _P, _P]),
+    "pinn_lbfgs_ls_init": (C.c_int32, [C.POINTER(PinnLsState), C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32]),
+    "pinn_lbfgs_ls_step": (C.c_int32, [C.POINTER(PinnLsState), C.c_double, C.c_double]),
+    "pinn_query_lbfgs_loop": (C.c_int32, [C.POINTER(PinnDesc), C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pinn_lbfgs_loop_init": (C.c_int32, [_P, C.c_int64, C.c_int64, C.POINTER(PinnLbfgsOpts), _P]),
+    "pinn_lbfgs_loop": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int32, C.POINTER(C.c_int32),
+                                    _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int32,
+                                    _P, _P, C.c_int64, _P]),
     "pinn_nanminmax_f64": (C.c_int32, [_P, C.c_int64, _P, _P, C.c_int64, _P]),
     "pinn_stage_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "pinn_stage_grid_columns": (C.c_int32, [C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P,

@@ -7,6 +7,8 @@
 #include "common.h"
 #include "reduce_adam.h"
 #include "residuals.h"
+#include "lbfgs_loop.h"
+#include "lbfgs_line_search.h"
 
 namespace pinn {
 
@@ -547,8 +549,113 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, co
   return PINN_OK;
 }
 
+// ---- device-resident L-BFGS (pinn_hip.h; kernels: pinn_lbfgs_loop.hip, line search: lbfgs_line_search.h) ---------------
+int32_t pinn_lbfgs_ls_init(pinn_ls_state* st, double f0, double gtd0, double t0, double d_norm, int32_t max_ls) {
+  if (!st) { set_error("pinn_lbfgs_ls_init: state is NULL"); return PINN_ERR_INVALID; }
+  return ls_init(st, f0, gtd0, t0, d_norm, max_ls);
+}
+
+int32_t pinn_lbfgs_ls_step(pinn_ls_state* st, double f_new, double gtd_new) {
+  if (!st) { set_error("pinn_lbfgs_ls_step: state is NULL"); return PINN_ERR_INVALID; }
+  if (st->phase < 0 || st->phase > 2 || st->g_slot_for_new < 1 || st->g_slot_for_new >= PINN_LS_POOL_ROWS) {
+    set_error("pinn_lbfgs_ls_step: the state was not armed by pinn_lbfgs_ls_init"); return PINN_ERR_INVALID;
+  }
+  return ls_step(st, f_new, gtd_new);
+}
+
+// what the query, the init and the loop share: the descriptor's network, refused with dropout
+static int lbfgs_loop_net(const char* who, const pinn_desc* desc, Net* n) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  if (n->drop_p > 0.f) {
+    set_error("%s: dropout_p > 0 is not supported (a seed per forward pass has no place in a fixed schedule of slots)", who);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  return PINN_OK;
+}
+static int lbfgs_history_ok(const char* who, int32_t m) {
+  if (m < 1 || m > LBL_MAX_M) { set_error("%s: history_size = %d outside 1..%d", who, m, LBL_MAX_M); return PINN_ERR_INVALID; }
+  return PINN_OK;
+}
+
+int32_t pinn_query_lbfgs_loop(const pinn_desc* desc, int64_t N, int32_t history_size, int64_t* ws_bytes, int64_t* state_bytes) {
+  Net n; int rc = lbfgs_loop_net("pinn_query_lbfgs_loop", desc, &n); if (rc) return rc;
+  rc = lbfgs_history_ok("pinn_query_lbfgs_loop", history_size); if (rc) return rc;
+  if (!ws_bytes || !state_bytes || N < 1) { set_error("pinn_query_lbfgs_loop: bad arguments"); return PINN_ERR_INVALID; }
+  rc = pinn_query_workspace(desc, N, ws_bytes); if (rc) return rc;
+  *state_bytes = lbl_layout(n.n_params(), history_size).total;
+  return PINN_OK;
+}
+
+int32_t pinn_lbfgs_loop_init(void* state, int64_t state_bytes, int64_t P, const pinn_lbfgs_opts* opts, void* stream) {
+  if (!state || !opts || P < 1) { set_error("pinn_lbfgs_loop_init: NULL pointer argument or P < 1"); return PINN_ERR_INVALID; }
+  int rc = lbfgs_history_ok("pinn_lbfgs_loop_init", opts->history_size); if (rc) return rc;
+  if (opts->max_iter < 0 || opts->max_eval < 1 || !(opts->lr > 0.0)) {
+    set_error("pinn_lbfgs_loop_init: max_iter = %d, max_eval = %d, lr = %g", opts->max_iter, opts->max_eval, opts->lr);
+    return PINN_ERR_INVALID;
+  }
+  const int64_t need = lbl_layout(P, opts->history_size).total;
+  if (state_bytes < need) {
+    set_error("pinn_lbfgs_loop_init: state too small: need %lld bytes, got %lld", (long long)need, (long long)state_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  return lbl_init(state, state_bytes, P, *opts, (hipStream_t)stream);
+}
+
+int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale, const float* T,
+                        int32_t n_cols, const int32_t* out_col, const float* col_scale, float* params, const float* X,
+                        int64_t N, int64_t n_res, int32_t n_loss_rows, const float* loss_rows, int32_t total_row,
+                        void* state, int64_t state_bytes, int32_t n_slots, double* trace,
+                        void* ws, int64_t ws_bytes, void* stream) {
+  Net n; int rc = lbfgs_loop_net("pinn_lbfgs_loop", desc, &n); if (rc) return rc;
+  if (!spec) { set_error("pinn_lbfgs_loop: NULL pointer argument"); return PINN_ERR_INVALID; }
+  pinn_residual_spec nspec; rc = check_spec(n, spec, &nspec); if (rc) return rc;
+  if (!params || !X || N < 1 || !term_scale || !state || !loss_rows) { set_error("pinn_lbfgs_loop: NULL pointer argument or N < 1"); return PINN_ERR_INVALID; }
+  if (n_slots < 0) { set_error("pinn_lbfgs_loop: n_slots = %d", n_slots); return PINN_ERR_INVALID; }
+  if (n_res > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_res, (long long)N); return PINN_ERR_INVALID; }
+  if (n_cols < 0 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 0..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
+  if (n_cols == 0 && n_res != N) { set_error("no fidelity columns: n_res must equal N"); return PINN_ERR_INVALID; }
+  if (n_cols > 0 && (!out_col || !col_scale || (!T && n_res != N))) { set_error("pinn_lbfgs_loop: NULL pointer argument"); return PINN_ERR_INVALID; }
+  if (n_loss_rows < 1 || n_loss_rows > 8 || total_row < 0 || total_row >= n_loss_rows) {
+    set_error("pinn_lbfgs_loop: n_loss_rows = %d outside 1..8 or total_row = %d outside it", n_loss_rows, total_row);
+    return PINN_ERR_INVALID;
+  }
+  const int64_t P = n.n_params();
+  const int64_t need = lbl_layout(P, 1).total;      // (the history's share was checked by pinn_lbfgs_loop_init, which knows m)
+  if (state_bytes < need) {
+    set_error("pinn_lbfgs_loop: state too small: need at least %lld bytes, got %lld", (long long)need, (long long)state_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  const LblPtrs p = lbl_ptrs(state, params, P);
+  LossReq rq; memset(&rq, 0, sizeof(rq));
+  rq.spec = nspec; rq.scale = term_scale; rq.n_terms = residual_terms(spec->residual_id);
+  rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = p.sums; rq.sums = p.sums + n_cols; rq.grad = p.gnew;
+  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
+  if (n_res == N) { rq.kind = 0; rq.n_split = -1; }      // residual term only
+  else { rq.kind = 2; rq.n_split = n_res < 0 ? -1 : n_res; }
+  {   // the refusals of the loss request itself, before anything is launched
+    int e = pick_engine(desc, n, true, &rc);
+    if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
+    if (rc) return rc;
+    const int64_t ws_need = engine_workspace_bytes(e, n, N);
+    if (ws_need < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
+    if (!ws || ws_bytes < ws_need) {
+      set_error("workspace too small: need %lld bytes, got %lld", (long long)ws_need, (long long)ws_bytes);
+      return PINN_ERR_WORKSPACE;
+    }
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  for (int32_t i = 0; i < n_slots; ++i) {
+    rc = lbl_before_pass(p, n_cols + rq.n_terms, s); if (rc) return rc;
+    rc = run_loss(desc, n, true, rq, p.xt, X, N, ws, ws_bytes, stream); if (rc) return rc;
+    rc = lbl_after_pass(p, n_cols, rq.n_terms, n_loss_rows, loss_rows, total_row,
+                        trace ? trace + (int64_t)i * PINN_LBFGS_TRACE_COLS : nullptr, s);
+    if (rc) return rc;
+  }
+  return PINN_OK;
+}
+
 // ---- per-point residual fields -------------------------------------------------------------------------------------
-// Two paths.  The fused tile kernel's field instances (one launch, nothing staged) where fused_fields_supports(); for
+// Two paths. The fused tile kernel's field instances (one launch, nothing staged) where fused_fields_supports(); for
 // every other request the descriptor's own pinn_forward_jet into a staging area, FIELDS_CHUNK points at a time (fixed:
 // the staging stays bounded however large the pool), followed by the point-wise kernel of pinn_fields.hip.
 // AUTO: the first where it applies, else the second.  FUSED (and sub-values): the first or refused, as pinn_jet_backward.

@@ -535,6 +535,49 @@ class Engine:
         self._packed_tok = (ws, params.data_ptr(), params._version, params_token, (N, int(n_res), nc, spec.residual_id, spec.corrected))
         return True
 
+    # ---- the device-resident L-BFGS loop (pinn_lbfgs_loop) ------------------------------------------------------------
+    def lbfgs_loop_query(self, N: int, history_size: int) -> Tuple[int, int]:
+        """(workspace bytes, state bytes) of lbfgs_loop on N points with this history size (pinn_query_lbfgs_loop)."""
+        ws, st = C.c_int64(), C.c_int64()
+        with torch.cuda.device(self._index()):      # the pass's workspace depends on the device's CU count
+            check(self.lib.pinn_query_lbfgs_loop(C.byref(self._d()), int(N), int(history_size), C.byref(ws), C.byref(st)),
+                  "pinn_query_lbfgs_loop")
+        return ws.value, st.value
+
+    def lbfgs_loop_init(self, state: torch.Tensor, lr, max_iter, max_eval, history_size, tolerance_grad, tolerance_change):
+        """Zeroes `state` (uint8, at least the query's state bytes) and arms its control block (pinn_lbfgs_loop_init)."""
+        o = _lib.PinnLbfgsOpts(float(lr), float(tolerance_grad), float(tolerance_change), int(max_iter), int(max_eval),
+                               int(history_size))
+        self._run("pinn_lbfgs_loop_init", self.lib.pinn_lbfgs_loop_init, _ptr(state), state.numel(), self.n_params, C.byref(o))
+
+    def lbfgs_loop(self, spec: ResidualSpec, term_scale, params, X, n_res: int, loss_rows: torch.Tensor, total_row: int,
+                   state: torch.Tensor, n_slots: int, trace: Optional[torch.Tensor] = None, T: Optional[torch.Tensor] = None,
+                   out_col: Sequence[int] = (), col_scale=None, ws: Optional[torch.Tensor] = None):
+        """n_slots slots of the device-resident L-BFGS loop (pinn_lbfgs_loop): every slot one loss + gradient evaluation
+        and one step of the strong-Wolfe state machine, decided on the device.  X, n_res, T, out_col and the scales as
+        loss_grad_adam_step; loss_rows (rows x (len(out_col) + n_terms)), total_row the objective's row.  `params` holds the
+        accepted iterate whenever the enqueued work has run; trace (n_slots, LBFGS_TRACE_COLS) float64, optional."""
+        spec.first_order("lbfgs_loop")
+        N, nc = X.shape[0], len(out_col)
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        self._chk(term_scale, "term_scale", (spec.n_terms,))
+        self._chk(loss_rows, "loss_rows", (loss_rows.shape[0], nc + spec.n_terms))
+        if nc:
+            self._chk(col_scale, "col_scale", (nc,))
+            if n_res != N:
+                self._chk(T, "T", (N - n_res if n_res >= 0 else N, nc))
+        if trace is not None and (trace.dtype != torch.float64 or not trace.is_contiguous()
+                                  or tuple(trace.shape) != (n_slots, _lib.LBFGS_TRACE_COLS) or trace.device != params.device):
+            raise PinnError(f"trace must be a contiguous float64 ({n_slots}, {_lib.LBFGS_TRACE_COLS}) tensor on {params.device}")
+        if state.dtype != torch.uint8 or not state.is_contiguous() or state.device != params.device:
+            raise PinnError("state must be a contiguous uint8 tensor on the engine's device")
+        if ws is None:
+            ws = self.workspace(N)
+        oc = (C.c_int32 * max(nc, 1))(*out_col)
+        self._run("pinn_lbfgs_loop", self.lib.pinn_lbfgs_loop, C.byref(self._d()), C.byref(spec.c_struct()), _ptr(term_scale),
+                  _ptr(T), nc, oc, _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), loss_rows.shape[0], _ptr(loss_rows),
+                  int(total_row), _ptr(state), state.numel(), int(n_slots), _ptr(trace), _ptr(ws), ws.numel())
+
     def invalidate_packed(self):
         """Forget the packed copy of the parameters left in the workspace by loss_grad_adam_step: the next call re-packs.
         For writers torch's version counters cannot see (a `.data` view written in place, a raw pointer)."""

@@ -229,3 +229,120 @@ class FlatLBFGS(_TorchLBFGS):
 
         state.update(d=d, t=t, hist=hist, H_diag=H, prev_flat_grad=prev_g, prev_loss=prev_loss)
         return orig_loss
+
+
+class DeviceLBFGS:
+    """torch.optim.LBFGS.step(closure) with strong-Wolfe line search, run on the device (Engine.lbfgs_loop,
+    pinn_lbfgs_loop): runs of RUN evaluations enqueued by one call, every decision — line search, stopping tests, ring
+    bookkeeping, direction — taken by kernels.  Not a torch.optim.Optimizer: there is no closure to call; the loss request
+    (point set, scales, loss rows) is fixed at construction.  The host reads the control block once per run and stops
+    when the done flag is up.  `params` (the flat fp32 parameter tensor) holds the accepted iterate after every run."""
+
+    RUN = 64
+
+    @staticmethod
+    def check_options(lr, max_iter, max_eval, history_size, tolerance_grad, tolerance_change, line_search_fn):
+        """The options as torch.optim.LBFGS takes them, or PinnError with what the device loop does not do."""
+        from types import SimpleNamespace
+        from ._lib import PinnError
+        flat = '; use lbfgs_impl="flat"'
+        if line_search_fn != "strong_wolfe":
+            raise PinnError(f"the device L-BFGS loop runs the strong_wolfe line search only (line_search_fn={line_search_fn!r})" + flat)
+        if not 1 <= int(history_size) <= 256:
+            raise PinnError(f"the device L-BFGS loop serves history_size 1..256 (got {history_size})" + flat)
+        if int(max_iter) < 0:
+            raise PinnError(f"max_iter={max_iter} must be >= 0" + flat)
+        if max_eval is None:
+            max_eval = int(max_iter) * 5 // 4          # torch.optim.LBFGS.__init__
+        return SimpleNamespace(lr=float(lr), max_iter=int(max_iter), max_eval=int(max_eval), history_size=int(history_size),
+                               tolerance_grad=float(tolerance_grad), tolerance_change=float(tolerance_change))
+
+    def __init__(self, engine, spec, params, X, n_res, term_scale, loss_rows, total_row, T=None, out_col=(), col_scale=None,
+                 lr=1.0, max_iter=20, max_eval=None, history_size=100, tolerance_grad=1e-7, tolerance_change=1e-9,
+                 line_search_fn="strong_wolfe"):
+        from . import _lib
+        self._lib = _lib
+        self.opts = self.check_options(lr, max_iter, max_eval, history_size, tolerance_grad, tolerance_change, line_search_fn)
+        self.engine, self.spec, self.params, self.X, self.n_res = engine, spec, params, X, int(n_res)
+        self.term_scale, self.loss_rows, self.total_row = term_scale, loss_rows, int(total_row)
+        self.T, self.out_col, self.col_scale = T, tuple(out_col), col_scale
+        ws_bytes, state_bytes = engine.lbfgs_loop_query(X.shape[0], self.opts.history_size)
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=params.device)
+        self.state = torch.empty(state_bytes, dtype=torch.uint8, device=params.device)
+        self.traces = []             # one (slots, LBFGS_TRACE_COLS) float64 CPU tensor per run
+        self.reset()
+
+    def reset(self):
+        o = self.opts
+        self.engine.lbfgs_loop_init(self.state, o.lr, o.max_iter, o.max_eval, o.history_size, o.tolerance_grad, o.tolerance_change)
+        self.traces = []
+        self._ctrl = None
+
+    def enqueue(self, n_slots: int) -> torch.Tensor:
+        """n_slots more slots; returns their trace (device tensor; nothing is synchronised)."""
+        trace = torch.empty(n_slots, self._lib.LBFGS_TRACE_COLS, dtype=torch.float64, device=self.params.device)
+        self.engine.lbfgs_loop(self.spec, self.term_scale, self.params, self.X, self.n_res, self.loss_rows, self.total_row,
+                               self.state, n_slots, trace, T=self.T, out_col=self.out_col, col_scale=self.col_scale, ws=self.ws)
+        self._ctrl = None
+        return trace
+
+    def run(self, n_slots: int) -> torch.Tensor:
+        """enqueue(n_slots), then the trace on the host (one synchronisation) with the control block re-read."""
+        tr = self.enqueue(n_slots).cpu()
+        self.traces.append(tr)
+        self.ctrl()
+        return tr
+
+    def ctrl(self):
+        """The control block (pinn_lbfgs_ctrl) as the device holds it now (synchronises)."""
+        if self._ctrl is None:
+            import ctypes
+            n = ctypes.sizeof(self._lib.PinnLbfgsCtrl)
+            self._ctrl = self._lib.PinnLbfgsCtrl.from_buffer_copy(self.state[:n].cpu().numpy().tobytes())
+        return self._ctrl
+
+    @property
+    def x_trial(self) -> torch.Tensor:
+        """The weights of the last evaluation (x + t d), a view into the state: d and x_trial follow the control block,
+        each region on a 256-byte boundary (include/pinn_hip.h, pinn_query_lbfgs_loop)."""
+        import ctypes
+        a = lambda v: (v + 255) // 256 * 256
+        P = self.params.numel()
+        off = a(ctypes.sizeof(self._lib.PinnLbfgsCtrl)) + a(4 * P)
+        return self.state[off:off + 4 * P].view(torch.float32)
+
+    def step(self, before_run=None, after_run=None):
+        """Runs until the done flag is up.  before_run(evaluations so far) -> an upper limit for the slots of the next run;
+        after_run(trace of the run, CPU) is called after each."""
+        while not self.done:
+            # an inert slot still runs its pass, so a run never holds more slots than the iterations left need at the
+            # least (one evaluation each) nor more than the evaluation budget allows (a line search may overrun it by one)
+            c, o = self.ctrl(), self.opts
+            n = max(1, min(self.RUN, o.max_iter - c.n_iter + 1, o.max_eval + 1 - c.n_evals))
+            if before_run is not None:
+                n = max(1, min(n, int(before_run(self.func_evals))))
+            tr = self.run(n)
+            if after_run is not None:
+                after_run(tr)
+        return self
+
+    @property
+    def done(self) -> bool:
+        return bool(self.ctrl().done)
+
+    @property
+    def n_iter(self) -> int:
+        return self.ctrl().n_iter
+
+    @property
+    def func_evals(self) -> int:
+        return self.ctrl().n_evals
+
+    @property
+    def stop_reason(self):
+        return self._lib.LBFGS_STOP_REASONS[self.ctrl().reason]
+
+    @property
+    def trace(self) -> torch.Tensor:
+        """Every slot run so far, (slots, LBFGS_TRACE_COLS) float64 on the CPU."""
+        return torch.cat(self.traces) if self.traces else torch.zeros(0, self._lib.LBFGS_TRACE_COLS, dtype=torch.float64)

@@ -24,7 +24,7 @@ from ._lib import PinnError
 from .config import PinnConfig, load_config
 from .dnn import DNN
 from .engine import ACTIVATION_OF_INIT, Engine, NetDesc, ResidualSpec
-from .lbfgs import FlatLBFGS
+from .lbfgs import DeviceLBFGS, FlatLBFGS
 from .parallel import Reducer
 
 
@@ -51,6 +51,25 @@ def rad_score(fields: torch.Tensor, k: float, c: float) -> torch.Tensor:
     ek = eps.pow(k)
     m = ek.mean()
     return torch.where(m > 0, ek / m, torch.zeros_like(ek)) + c
+
+
+def device_lbfgs_refusal(reducer_active, residual_batch, eddy_viscosity, custom_evaluator, line_search_fn, dropout_rate=0.0):
+    """Why lbfgs_impl="device" cannot run this configuration (None: it can).  The device loop enqueues a fixed schedule of
+    evaluations of ONE loss request; whatever needs the host, a second call or fresh randomness per evaluation is out."""
+    flat = '; use lbfgs_impl="flat"'
+    if reducer_active:
+        return "lbfgs_impl=\"device\" does not run under data parallelism (the all-reduce of every evaluation is issued by the host)" + flat
+    if residual_batch is not None:
+        return "lbfgs_impl=\"device\" does not run with residual_batch (a mini-batch is drawn by the host for every evaluation)" + flat
+    if eddy_viscosity:
+        return "lbfgs_impl=\"device\" does not run with eddy_viscosity > 0 (the second-order residual is two calls per evaluation)" + flat
+    if custom_evaluator:
+        return "lbfgs_impl=\"device\" runs the library's own loss pass, not a custom evaluator" + flat
+    if line_search_fn != "strong_wolfe":
+        return f"lbfgs_impl=\"device\" runs the strong_wolfe line search only (line_search_fn={line_search_fn!r})" + flat
+    if dropout_rate and dropout_rate > 0:
+        return "lbfgs_impl=\"device\" does not run with dropout (a seed per forward pass has no place in a fixed schedule)" + flat
+    return None
 
 
 def _as_f32(a, device) -> Optional[torch.Tensor]:
@@ -215,6 +234,14 @@ class PINN:
         cfg = config if isinstance(config, PinnConfig) else load_config(config)
         self.config, self.device = cfg, torch.device(device)
         self.reducer = reducer or Reducer()
+        if lbfgs_impl not in ("flat", "torch", "device"):
+            raise PinnError(f"lbfgs_impl={lbfgs_impl!r}: use 'flat', 'torch' or 'device'")
+        if lbfgs_impl == "device":       # decided before anything touches a device
+            nu = float(eddy_viscosity) if eddy_viscosity else float(cfg.raw.get("loss", {}).get("eddy_viscosity", 0.0))
+            why = device_lbfgs_refusal(self.reducer.active, residual_batch, nu, evaluator is not None,
+                                       cfg.lbfgs["line_search_fn"], cfg.dropout_rate)
+            if why:
+                raise PinnError(why)
         self.fold_adam, self._adam_folded, self._folded_iters, self._run_losses = bool(fold_adam), False, 0, None
         self._fold_refused = None   # key of the (evaluator, point sets) whose folded request the engine has refused
         self.layers = cfg.layers                                           # train.py:52-56
@@ -292,7 +319,9 @@ class PINN:
         self.resample, self.rad_every, self.rad_k, self.rad_c = resample, int(rad_every), float(rad_k), float(rad_c)
         self._rad_score, self._rad_cdf, self._rad_at = None, None, None
         self.mat_dump_iter, self.mat_dump_path = mat_dump_iter, mat_dump_path
-        self.lbfgs_impl = lbfgs_impl     # "flat": lbfgs.FlatLBFGS (batched recursion); "torch": torch.optim.LBFGS
+        self.lbfgs_impl = lbfgs_impl     # "flat": lbfgs.FlatLBFGS (batched recursion); "torch": torch.optim.LBFGS;
+                                         # "device": lbfgs.DeviceLBFGS (whole runs of evaluations decided on the device)
+        self.device_lbfgs = None
         self.iter = 0                                                      # train.py:73
         self.adam_maxit = cfg.adam["max_it"]
         self.log_dir, self.log_every, self.checkpoint_every = log_dir, max(int(log_every), 1), checkpoint_every
@@ -311,6 +340,11 @@ class PINN:
         self._adam_step = 0
         self._sched_steps = 0
         self.theta_param = torch.nn.Parameter(self.theta)       # shares storage with every Linear weight
+        if self.lbfgs_impl == "device":      # built by train(): it binds the point sets and the loss rows
+            self.optimizer_LBFGS = None
+            DeviceLBFGS.check_options(lb["learning_rate"], lb["max_it"], lb.get("max_evaluation"), lb["history_size"],
+                                      lb["tolerance_grad"], lb["tolerance_change"], lb["line_search_fn"])
+            return
         lbfgs_cls = FlatLBFGS if self.lbfgs_impl == "flat" else torch.optim.LBFGS
         self.optimizer_LBFGS = lbfgs_cls(
             [self.theta_param], lr=lb["learning_rate"], max_iter=lb["max_it"], max_eval=lb.get("max_evaluation"),
@@ -557,8 +591,68 @@ class PINN:
         self.dnn.train()
         self.train_adam(self.adam_maxit)
         if self.config.lbfgs["max_it"] > 0:
-            self.optimizer_LBFGS.step(self.closure)                                # ONE step, train.py:200
+            if self.lbfgs_impl == "device":
+                self.train_lbfgs_device()
+            else:
+                self.optimizer_LBFGS.step(self.closure)                            # ONE step, train.py:200
         self.flush_log()
+
+    def train_lbfgs_device(self):
+        """The L-BFGS stage (train.py:200) through lbfgs.DeviceLBFGS: runs of up to DeviceLBFGS.RUN evaluations enqueued by
+        one call each.  self.iter advances by one per evaluation (train.py:160) and every evaluation's three losses go
+        into the log ring from the trace.  A run is cut so that an evaluation due a checkpoint (or the prediction dump) is
+        its LAST slot: x_trial then still holds that evaluation's weights and the host saves from there — the
+        reference's "weights of the evaluation, saved from inside loss_func" (train.py:175-179)."""
+        self.theta = self.dnn.flat_params()
+        self._ensure_loss_mat()
+        lb = self.config.lbfgs
+        has_fid = self.Xf is not None and self.Xf.shape[0] > 0
+        nc = self._fid_sums.numel()
+        if has_fid and self.Xf is self.Xr:
+            X, n_res = self.Xr, -1
+        elif has_fid:
+            X, n_res = self.evaluator._merged(self.Xr, self.Xf), self.Xr.shape[0]
+        else:
+            X, n_res = self.Xr, self.Xr.shape[0]
+        opt = self.device_lbfgs = DeviceLBFGS(
+            self.evaluator.eng, self.spec, self.theta, X, n_res, self._res_scale, self._loss_mat, 2,
+            T=self.Tf if has_fid else None, out_col=self.fid_cols if nc else (), col_scale=self._fid_scale if nc else None,
+            lr=lb["learning_rate"], max_iter=lb["max_it"], max_eval=lb.get("max_evaluation"), history_size=lb["history_size"],
+            tolerance_grad=lb["tolerance_grad"], tolerance_change=lb["tolerance_change"], line_search_fn=lb["line_search_fn"])
+
+        def due(it):       # evaluation number `it` (1-based, self.iter after it) needs the host right after it
+            return self._checkpoint_due(it) or (self.mat_dump_iter is not None and it - 1 == self.mat_dump_iter)
+
+        def before_run(_evals):
+            for i in range(1, DeviceLBFGS.RUN + 1):
+                if due(self.iter + i):
+                    return i
+            return DeviceLBFGS.RUN
+
+        def after_run(tr):
+            acts = tr[:, 2]
+            k = int((acts != 0).sum())               # evaluations of this run: inert slots follow a stop
+            rows = tr[:k, 10:13].to(torch.float32)
+            for i in range(k):
+                it = self.iter + 1 + i
+                if it % self.log_every == 0 or it % 1000 == 0:
+                    self._ring[len(self._ring_iters)].copy_(rows[i])
+                    self._ring_iters.append(it)
+                    if len(self._ring_iters) == self._ring.shape[0]:
+                        self.flush_log()
+            self.iter += k
+            if k:
+                self.last = tuple(rows[k - 1].to(self.device))
+            if k == tr.shape[0] and due(self.iter):      # the run's last slot was this evaluation: x_trial holds its weights
+                keep = self.theta.clone()
+                self.theta.copy_(opt.x_trial)
+                if self.mat_dump_iter is not None and self.iter - 1 == self.mat_dump_iter:
+                    self.dump_predictions(self.mat_dump_path)
+                if self._checkpoint_due(self.iter):
+                    self.save_checkpoint(f"model_{self.iter}.pth")
+                self.theta.copy_(keep)
+
+        opt.step(before_run, after_run)
 
     def residual_fields(self, X=None) -> torch.Tensor:
         """The residual's signed per-point fields (n_fields, N) at X (default: this rank's collocation shard), in
