@@ -429,6 +429,67 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec,
                        const pinn_adam_state* adam, int32_t n_iters, const double* lr,
                        void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- ensembles: M networks of one shape in one launch --------------------------------------------------------------
+ * (added under ABI version 4, as the fields entries were: no existing entry, struct or constant changed)
+ * A deep ensemble or a seed sweep trains M networks of the same descriptor on a problem that fills a few workgroups of the
+ * chip.  These entries run all M members through ONE launch of the fused tile kernel's ensemble instances (a 2-D grid:
+ * gx workgroups per member x M members) and one finishing launch, whatever M is.  Member m gets the arithmetic of the
+ * single-network entry on params[m]; what differs is the number of workgroups per member (gx, below) and with it the order
+ * of the partial sums.
+ * Layout: params, grad_flat (and the Adam moments m, v) are (M, P) row-major; term_sums (M, n_terms), col_sums (M, n_cols),
+ * adam->losses (M, n_loss_rows) — in pinn_ensemble_adam_loop (n_iters, M, n_loss_rows).  term_scale, col_scale, out_col,
+ * spec and adam->loss_rows are shared by all members.
+ * flags: PINN_ENSEMBLE_OWN_X — X is (M, N, d_in), member m reads its own point set; PINN_ENSEMBLE_OWN_T — T is per member,
+ * (M, rows, n_cols) with rows = N - n_res (split), N (n_res < 0).  Otherwise X (N, d_in) and T are shared.
+ * n_res: as pinn_loss_grad_adam_step — n_res == N residual term only (T may be NULL, n_cols may be 0; col_sums, if given,
+ * is zeroed), 0 <= n_res < N the split request, n_res < 0 both terms on every point.
+ * Served: engine AUTO, FUSED or FUSED_TILE (always the tile kernel, at every N), fp32, tanh, width <= 64, d_in and
+ * d_out <= 16, dropout_p == 0, k = 2 or 3.  Refused with PINN_ERR_UNSUPPORTED and the reason in pinn_last_error(), decided
+ * before any device work (nothing is launched): engine GENERIC, WIDE, FUSED_COOP, FUSED_BATCH; bf16; width > 64;
+ * LeakyReLU; dropout_p > 0; the corrected radiation stress ("corrected" in the message); k other than 2 or 3; the split
+ * request at padded width 64 (hidden width 33..64: the tile kernel carries no split code there).
+ * M < 1 or M > 65535: PINN_ERR_INVALID.  M = 1 is valid.  N >= 1.
+ * Grid: gx = the single-network tile-kernel grid for N points, clamped to max(1, cap / M) with cap the tile kernel's own
+ * workgroup cap for the shape (CUs x workgroups per CU); beyond M = cap, gx = 1 and the M workgroups queue.
+ * The workspace is the entries' own: pinn_ensemble_query_workspace (it grows with M). */
+#define PINN_ENSEMBLE_OWN_X 1
+#define PINN_ENSEMBLE_OWN_T 2
+#define PINN_ENSEMBLE_MAX_MEMBERS 65535
+int32_t pinn_ensemble_query_workspace(const pinn_desc* desc, int32_t M, int64_t N, int64_t* bytes);
+/* *gx = workgroups per member, *copy_in_lds = 1 if a workgroup's gradient copy lives in LDS, 0 if in the workspace.
+ * Refused as the calls are, as far as the descriptor alone decides.  Host logic only: no device is needed (without one
+ * the answer is that of a 256-CU device). */
+int32_t pinn_ensemble_plan(const pinn_desc* desc, int32_t M, int64_t N, int32_t* gx, int32_t* copy_in_lds);
+/* Member m: term_sums[m] / col_sums[m] <- the sums of pinn_residual_loss_grad / pinn_residual_mse_split_loss_grad /
+ * pinn_residual_mse_loss_grad (by n_res) at params[m]; grad_flat[m] += the weighted gradient.  Three launches (pack, pass,
+ * finish) and a zero-fill where the gradient copies live in the workspace. */
+int32_t pinn_ensemble_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M,
+                                const float* term_scale, const float* T, int32_t n_cols,
+                                const int32_t* out_col, const float* col_scale,
+                                const float* params, const float* X, int64_t N, int64_t n_res, int32_t flags,
+                                float* term_sums, float* col_sums, float* grad_flat,
+                                void* ws, int64_t ws_bytes, void* stream);
+/* pinn_loss_grad_adam_step for M members: two launches per iteration, whatever M is.  pinn_adam_state is reused with
+ * m, v of (M, P) and losses of (M, n_loss_rows); one step count, learning rate and set of betas for all members.
+ * grad_flat (M, P) is OVERWRITTEN.  adam->packed_valid: as in pinn_loss_grad_adam_step, for the M packed copies (the
+ * previous call on this `ws` was this function with the same desc, M and request, and nothing has written params since). */
+int32_t pinn_ensemble_adam_step(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M,
+                                const float* term_scale, const float* T, int32_t n_cols,
+                                const int32_t* out_col, const float* col_scale,
+                                float* params, const float* X, int64_t N, int64_t n_res, int32_t flags,
+                                float* term_sums, float* col_sums, float* grad_flat,
+                                const pinn_adam_state* adam, void* ws, int64_t ws_bytes, void* stream);
+/* pinn_adam_loop for M members: n_iters iterations, 2 n_iters launches, enqueued by one call.  Iteration i uses step
+ * adam->step + i and lr[i] (HOST array, shared by all members) and writes its weighted losses to
+ * adam->losses + i * M * n_loss_rows. */
+int32_t pinn_ensemble_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M,
+                                const float* term_scale, const float* T, int32_t n_cols,
+                                const int32_t* out_col, const float* col_scale,
+                                float* params, const float* X, int64_t N, int64_t n_res, int32_t flags,
+                                float* term_sums, float* col_sums, float* grad_flat,
+                                const pinn_adam_state* adam, int32_t n_iters, const double* lr,
+                                void* ws, int64_t ws_bytes, void* stream);
+
 /* torch.optim.Adam single-tensor update on flat buffers (amsgrad off, weight_decay 0,
  * maximize off): m,v are exp_avg / exp_avg_sq; step is the 1-based step count;
  * lr is a host double (StepLR changes it between steps, train.py:193); the scalar

@@ -150,7 +150,19 @@ _SIGNATURES = {
     "pinn_adam_loop": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int32,
                                    C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P,
                                    C.POINTER(PinnAdamState), C.c_int32, C.POINTER(C.c_double), _P, C.c_int64, _P]),
+    "pinn_ensemble_query_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "pinn_ensemble_plan": (C.c_int32, [C.POINTER(PinnDesc), C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pinn_ensemble_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int32, _P, _P, C.c_int32,
+                                            C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P,
+                                            _P, C.c_int64, _P]),
+    "pinn_ensemble_adam_step": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int32, _P, _P, C.c_int32,
+                                            C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P,
+                                            C.POINTER(PinnAdamState), _P, C.c_int64, _P]),
+    "pinn_ensemble_adam_loop": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int32, _P, _P, C.c_int32,
+                                            C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P,
+                                            C.POINTER(PinnAdamState), C.c_int32, C.POINTER(C.c_double), _P, C.c_int64, _P]),
 }
+ENSEMBLE_OWN_X, ENSEMBLE_OWN_T, ENSEMBLE_MAX_MEMBERS = 1, 2, 65535      # pinn_hip.h: PINN_ENSEMBLE_*
 
 _lib = None
 

@@ -124,6 +124,15 @@ int fused_forward(const Net& n, const float* params, const float* X, int64_t N, 
                   void* ws, int64_t ws_bytes, hipStream_t s);
 int fused_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N,
                void* ws, int64_t ws_bytes, hipStream_t s);
+// Ensembles (pinn_ensemble_*): M networks of one shape through the tile kernel's ensemble instances (fused_kernel.h,
+// k_fused_ens), one launch for all members.  rq (and rq.adam) hold the BASE pointers of the (M, .) arrays: params, grad, m, v
+// (M, P); sums (M, n_terms); mse_sums (M, n_cols); losses (M, n_loss_rows).  flags: PINN_ENSEMBLE_OWN_X / _OWN_T.
+// fused_ensemble_refusal: why the request has no ensemble kernel, or nullptr (pure host logic).
+const char* fused_ensemble_refusal(const Net& n, const LossReq& rq);
+// the per-member grid gx, whether a workgroup's gradient copy lives in LDS, and the workspace of M members on N points
+void fused_ensemble_plan(const Net& n, int M, int64_t N, int* gx, int* copy_in_lds, int64_t* ws_bytes);
+int fused_ensemble_loss(const Net& n, const LossReq& rq, int M, int flags, const float* params, const float* X, int64_t N,
+                        void* ws, int64_t ws_bytes, hipStream_t s);
 // pinn_jet_backward on the tile kernel (fused_kernel.h, EPI_ADJ): grad += d/dtheta [sum(gY * Y) + sum(gdY * dY)]
 bool fused_jet_backward_supports(const Net& n);
 // which fused kernel a served pinn_jet_backward request runs: PINN_ENGINE_FUSED_TILE or PINN_ENGINE_FUSED_BATCH (pure host

@@ -549,6 +549,122 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, co
   return PINN_OK;
 }
 
+// ---- ensembles (pinn_hip.h; kernels: fused_kernel.h k_fused_ens, pinn_fused.hip) ------------------------------------------
+// What the query, the plan and the calls share: the descriptor's network, M, and the refusals the descriptor alone decides.
+// Pure host logic.
+static int ensemble_net(const char* who, const pinn_desc* desc, int32_t M, Net* n) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  if (M < 1 || M > PINN_ENSEMBLE_MAX_MEMBERS) {
+    set_error("%s: M = %d outside 1..%d", who, M, PINN_ENSEMBLE_MAX_MEMBERS); return PINN_ERR_INVALID;
+  }
+  const int asked = asked_engine(desc);
+  if (asked == PINN_ENGINE_GENERIC || asked == PINN_ENGINE_WIDE) {
+    set_error("%s: engine %s has no ensemble kernel (use engine AUTO, FUSED or FUSED_TILE)", who,
+              asked == PINN_ENGINE_GENERIC ? "GENERIC" : "WIDE");
+    return PINN_ERR_UNSUPPORTED;
+  }
+  LossReq none; memset(&none, 0, sizeof(none)); none.kind = 1;      // (no spec, no split: the descriptor's part of the rule)
+  if (const char* why = fused_ensemble_refusal(*n, none)) { set_error("%s: %s", who, why); return PINN_ERR_UNSUPPORTED; }
+  return PINN_OK;
+}
+
+int32_t pinn_ensemble_query_workspace(const pinn_desc* desc, int32_t M, int64_t N, int64_t* bytes) {
+  Net n; int rc = ensemble_net("pinn_ensemble_query_workspace", desc, M, &n); if (rc) return rc;
+  if (!bytes || N < 1) { set_error("pinn_ensemble_query_workspace: bytes is NULL or N < 1"); return PINN_ERR_INVALID; }
+  fused_ensemble_plan(n, M, N, nullptr, nullptr, bytes);
+  return PINN_OK;
+}
+
+int32_t pinn_ensemble_plan(const pinn_desc* desc, int32_t M, int64_t N, int32_t* gx, int32_t* copy_in_lds) {
+  Net n; int rc = ensemble_net("pinn_ensemble_plan", desc, M, &n); if (rc) return rc;
+  if (!gx || !copy_in_lds || N < 1) { set_error("pinn_ensemble_plan: NULL pointer argument or N < 1"); return PINN_ERR_INVALID; }
+  int g = 0, c = 0;
+  fused_ensemble_plan(n, M, N, &g, &c, nullptr);
+  *gx = g; *copy_in_lds = c;
+  return PINN_OK;
+}
+
+// adam == nullptr: pinn_ensemble_loss_grad (grad +=); else the folded update (grad overwritten)
+static int32_t ensemble_impl(const char* who, const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M,
+                             const float* term_scale, const float* T, int32_t n_cols, const int32_t* out_col,
+                             const float* col_scale, const float* params, float* params_rw, const float* X, int64_t N,
+                             int64_t n_res, int32_t flags, float* term_sums, float* col_sums, float* grad_flat,
+                             const pinn_adam_state* adam, void* ws, int64_t ws_bytes, void* stream) {
+  Net n; int rc = ensemble_net(who, desc, M, &n); if (rc) return rc;
+  if (!spec) { set_error("%s: spec is NULL", who); return PINN_ERR_INVALID; }
+  pinn_residual_spec nspec; rc = check_spec(n, spec, &nspec); if (rc) return rc;
+  if (N < 1) { set_error("%s: N = %lld, need at least one point", who, (long long)N); return PINN_ERR_INVALID; }
+  if (n_res > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_res, (long long)N); return PINN_ERR_INVALID; }
+  if (n_cols < 0 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 0..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
+  if (n_cols == 0 && n_res != N) { set_error("no fidelity columns: n_res must equal N"); return PINN_ERR_INVALID; }
+  if (flags & ~(PINN_ENSEMBLE_OWN_X | PINN_ENSEMBLE_OWN_T)) { set_error("%s: unknown flags 0x%x", who, flags); return PINN_ERR_INVALID; }
+  LossReq rq; memset(&rq, 0, sizeof(rq));
+  rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums; rq.n_terms = residual_terms(spec->residual_id);
+  rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
+  if (n_res == N) { rq.kind = 0; rq.n_split = -1; }      // residual term only
+  else { rq.kind = 2; rq.n_split = n_res < 0 ? -1 : n_res; }
+  // the request's refusals (corrected radiation stress, the split request at width 64), before the pointers are looked at
+  if (const char* why = fused_ensemble_refusal(n, rq)) { set_error("%s: %s", who, why); return PINN_ERR_UNSUPPORTED; }
+  if (!params || !X || !term_sums || !term_scale || !grad_flat) { set_error("%s: NULL pointer argument", who); return PINN_ERR_INVALID; }
+  if (n_cols > 0 && (!out_col || !col_scale || !col_sums || (!T && n_res != N))) { set_error("%s: NULL pointer argument", who); return PINN_ERR_INVALID; }
+  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
+  AdamReq a;
+  if (adam) {
+    if (!adam->m || !adam->v || adam->step < 1) { set_error("%s: bad adam state", who); return PINN_ERR_INVALID; }
+    if (adam->n_loss_rows < 0 || adam->n_loss_rows > 8 || (adam->n_loss_rows > 0 && (!adam->loss_rows || !adam->losses))) {
+      set_error("bad loss_rows arguments"); return PINN_ERR_INVALID;
+    }
+    a.params = params_rw; a.m = adam->m; a.v = adam->v;
+    a.c = adam_scalars(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step);
+    a.packed_valid = adam->packed_valid != 0;
+    a.n_loss_rows = adam->n_loss_rows; a.loss_rows = adam->loss_rows; a.losses = adam->losses;
+    rq.adam = &a;
+  }
+  int64_t need = 0;
+  fused_ensemble_plan(n, M, N, nullptr, nullptr, &need);
+  if (!ws || ws_bytes < need) {
+    set_error("workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  if (rq.kind == 0 && n_cols > 0) (void)hipMemsetAsync(col_sums, 0, (size_t)M * n_cols * sizeof(float), (hipStream_t)stream);
+  return fused_ensemble_loss(n, rq, M, flags, params, X, N, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int32_t pinn_ensemble_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M, const float* term_scale,
+                                const float* T, int32_t n_cols, const int32_t* out_col, const float* col_scale,
+                                const float* params, const float* X, int64_t N, int64_t n_res, int32_t flags,
+                                float* term_sums, float* col_sums, float* grad_flat, void* ws, int64_t ws_bytes, void* stream) {
+  return ensemble_impl("pinn_ensemble_loss_grad", desc, spec, M, term_scale, T, n_cols, out_col, col_scale, params, nullptr, X,
+                       N, n_res, flags, term_sums, col_sums, grad_flat, nullptr, ws, ws_bytes, stream);
+}
+
+int32_t pinn_ensemble_adam_step(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M, const float* term_scale,
+                                const float* T, int32_t n_cols, const int32_t* out_col, const float* col_scale, float* params,
+                                const float* X, int64_t N, int64_t n_res, int32_t flags, float* term_sums, float* col_sums,
+                                float* grad_flat, const pinn_adam_state* adam, void* ws, int64_t ws_bytes, void* stream) {
+  if (!adam) { set_error("pinn_ensemble_adam_step: adam is NULL"); return PINN_ERR_INVALID; }
+  return ensemble_impl("pinn_ensemble_adam_step", desc, spec, M, term_scale, T, n_cols, out_col, col_scale, params, params, X, N,
+                       n_res, flags, term_sums, col_sums, grad_flat, adam, ws, ws_bytes, stream);
+}
+
+int32_t pinn_ensemble_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M, const float* term_scale,
+                                const float* T, int32_t n_cols, const int32_t* out_col, const float* col_scale, float* params,
+                                const float* X, int64_t N, int64_t n_res, int32_t flags, float* term_sums, float* col_sums,
+                                float* grad_flat, const pinn_adam_state* adam, int32_t n_iters, const double* lr, void* ws,
+                                int64_t ws_bytes, void* stream) {
+  if (!adam || !lr || n_iters < 0) { set_error("pinn_ensemble_adam_loop: bad arguments"); return PINN_ERR_INVALID; }
+  for (int32_t i = 0; i < n_iters; ++i) {
+    pinn_adam_state st = *adam;
+    st.step = adam->step + i; st.lr = lr[i];
+    st.packed_valid = (i > 0 || adam->packed_valid) ? 1 : 0;
+    if (adam->n_loss_rows > 0 && adam->losses) st.losses = adam->losses + (int64_t)i * M * adam->n_loss_rows;
+    const int32_t rc = pinn_ensemble_adam_step(desc, spec, M, term_scale, T, n_cols, out_col, col_scale, params, X, N, n_res,
+                                               flags, term_sums, col_sums, grad_flat, &st, ws, ws_bytes, stream);
+    if (rc) return rc;      // (refusals come from the first iteration, before anything is launched)
+  }
+  return PINN_OK;
+}
+
 // ---- device-resident L-BFGS (pinn_hip.h; kernels: pinn_lbfgs_loop.hip, line search: lbfgs_line_search.h) ---------------
 int32_t pinn_lbfgs_ls_init(pinn_ls_state* st, double f0, double gtd0, double t0, double d_norm, int32_t max_ls) {
   if (!st) { set_error("pinn_lbfgs_ls_init: state is NULL"); return PINN_ERR_INVALID; }

@@ -159,10 +159,9 @@ constexpr int PACK_PERM = 1, PACK_RMAJOR = 2, PACK_IN = 4, PACK_OUT = 8;
 __host__ __device__ inline bool row_permuted(int flags, int l, int L) { return l < L ? (flags & PACK_PERM) != 0 : (flags & PACK_OUT) != 0; }
 __host__ __device__ inline bool col_permuted(int flags, int l) { return (flags & PACK_PERM) != 0 || (l == 0 && (flags & PACK_IN) != 0); }
 
-// flat torch-layout parameters -> padded row-major W, padded transposed W, padded bias
-__global__ void k_pack(Net n, int WP, const float* __restrict__ params, float* __restrict__ Wp,
-                       float* __restrict__ WTp, float* __restrict__ Bp, int PW, int PB, int flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+// flat torch-layout parameters -> padded row-major W, padded transposed W, padded bias: entry i of each
+__device__ __forceinline__ void pack_entry(const Net& n, int WP, const float* __restrict__ params, float* __restrict__ Wp,
+                                           float* __restrict__ WTp, float* __restrict__ Bp, int PW, int PB, int flags, int i) {
   if (i < PW) {
     // which layer block does padded index i fall in?
     int l, rem;
@@ -190,6 +189,17 @@ __global__ void k_pack(Net n, int WP, const float* __restrict__ params, float* _
     o = unit_at(o, row_permuted(flags, l, n.L));
     Bp[i] = (o < n.out_dim(l)) ? params[n.b_off(l) + o] : 0.f;
   }
+}
+__global__ void k_pack(Net n, int WP, const float* __restrict__ params, float* __restrict__ Wp,
+                       float* __restrict__ WTp, float* __restrict__ Bp, int PW, int PB, int flags) {
+  pack_entry(n, WP, params, Wp, WTp, Bp, PW, PB, flags, blockIdx.x * blockDim.x + threadIdx.x);
+}
+// ... of every member of an ensemble (grid.y = M): params (M, P), the packed arrays M x PW / PW / PB floats
+__global__ void k_pack_ens(Net n, int WP, const float* __restrict__ params, float* __restrict__ Wp,
+                           float* __restrict__ WTp, float* __restrict__ Bp, int PW, int PB, int flags) {
+  const int64_t mem = blockIdx.y;
+  pack_entry(n, WP, params + mem * n.n_params(), Wp + mem * PW, WTp + mem * PW, Bp + mem * PB, PW, PB, flags,
+             blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // k_reduce_grads: grad_flat[real index] += sum over copies of the padded per-workgroup gradients.  64 parameters x
@@ -265,41 +275,38 @@ __global__ void k_reduce_grads(Net n, int WP, const float* __restrict__ wg, int 
   if (r.owner) grad[r.at.i] += r.g;
 }
 
-// One kernel for everything that follows the fused pass in an Adam iteration (pinn_loss_grad_adam_step): the
-// gradient reduction of k_reduce_grads (grad_of_param), torch.optim.Adam's update (k_adam's adam_update, reduce_adam.h) on
-// the parameter it just summed, the refreshed entries of the packed W / W^T / b the next pass reads (k_pack's mapping,
-// inverted: padding entries stay zero), and — last block — the loss sums of k_reduce_sums (column_sum).  Five launches of
-// ~4.7 us each become one at the reference's own problem sizes (N_res = 243).
-__global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
-                              const float* __restrict__ wg_sums, int grid, int n_terms, float* __restrict__ term_sums,
-                              int n_cols, float* __restrict__ col_sums, float* __restrict__ grad,
-                              float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
-                              float* __restrict__ Wp, float* __restrict__ WTp, float* __restrict__ Bp, AdamScalars c,
-                              int n_loss_rows, const float* __restrict__ loss_rows, float* __restrict__ losses,
-                              int row_cols, int flags) {
-  if (blockIdx.x == gridDim.x - 1) {          // loss sums
+// The two parts of k_finish_adam (below), shared with the ensemble's finishing kernels:
+// the loss sums' block: term_sums / col_sums <- the fixed-order column sums of the workgroups' partial sums and, optionally,
+// the weighted losses.  Called by all 256 threads of ONE block.
+__device__ __forceinline__ void finish_sums(const float* __restrict__ wg_sums, int grid, int n_terms, float* __restrict__ term_sums,
+                                            int n_cols, float* __restrict__ col_sums, int n_loss_rows,
+                                            const float* __restrict__ loss_rows, float* __restrict__ losses, int row_cols) {
 #pragma clang fp contract(off)
-    // [col sums (row_cols of them) | term sums], for the optional weighted losses.  row_cols is the CALLER's column
-    // count — the stride of loss_rows (pinn_hip.h) — also when this pass carried no fidelity columns (n_cols = 0:
-    // a residual-only request with n_res == N): their sums are then zeros, not a shifted layout.
-    __shared__ double ssum[2 * PINN_MAX_ROLES + 8];
-    if (threadIdx.x < 2 * PINN_MAX_ROLES + 8) ssum[threadIdx.x] = 0.0;
+  // [col sums (row_cols of them) | term sums], for the optional weighted losses.  row_cols is the CALLER's column
+  // count — the stride of loss_rows (pinn_hip.h) — also when this pass carried no fidelity columns (n_cols = 0:
+  // a residual-only request with n_res == N): their sums are then zeros, not a shifted layout.
+  __shared__ double ssum[2 * PINN_MAX_ROLES + 8];
+  if (threadIdx.x < 2 * PINN_MAX_ROLES + 8) ssum[threadIdx.x] = 0.0;
+  __syncthreads();
+  for (int j = 0; j < n_terms + n_cols; ++j) {
+    const float sum = (float)column_sum(wg_sums, grid, MAX_SUMS, j < n_terms ? j : MSE_SUM0 + (j - n_terms));
+    if (threadIdx.x == 0) {
+      if (j < n_terms) { term_sums[j] = sum; ssum[row_cols + j] = (double)sum; }
+      else { col_sums[j - n_terms] = sum; ssum[j - n_terms] = (double)sum; }
+    }
     __syncthreads();
-    for (int j = 0; j < n_terms + n_cols; ++j) {
-      const float sum = (float)column_sum(wg_sums, grid, MAX_SUMS, j < n_terms ? j : MSE_SUM0 + (j - n_terms));
-      if (threadIdx.x == 0) {
-        if (j < n_terms) { term_sums[j] = sum; ssum[row_cols + j] = (double)sum; }
-        else { col_sums[j - n_terms] = sum; ssum[j - n_terms] = (double)sum; }
-      }
-      __syncthreads();
-    }
-    if ((int)threadIdx.x < n_loss_rows) {
-      double a = 0.0;
-      for (int j = 0; j < row_cols + n_terms; ++j) a += (double)loss_rows[threadIdx.x * (row_cols + n_terms) + j] * ssum[j];
-      losses[threadIdx.x] = (float)a;
-    }
-    return;
   }
+  if ((int)threadIdx.x < n_loss_rows) {
+    double a = 0.0;
+    for (int j = 0; j < row_cols + n_terms; ++j) a += (double)loss_rows[threadIdx.x * (row_cols + n_terms) + j] * ssum[j];
+    losses[threadIdx.x] = (float)a;
+  }
+}
+// a parameter block: the gradient of the block's 64 parameters, Adam's update on them, the refreshed packed entries
+__device__ __forceinline__ void finish_adam_params(const Net& n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
+                                                   float* __restrict__ grad, float* __restrict__ params, float* __restrict__ m,
+                                                   float* __restrict__ v, float* __restrict__ Wp, float* __restrict__ WTp,
+                                                   float* __restrict__ Bp, const AdamScalars& c, int flags) {
   const ParamGrad r = grad_of_param(n, WP, wg, copies, PP, PW, flags);
   if (r.owner) {
     const ParamSlot& p = r.at;
@@ -313,6 +320,64 @@ __global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int c
       WTp[p.wo + p.col * outP + p.row] = pn;
     } else Bp[p.l * WP + p.row] = pn;
   }
+}
+// One kernel for everything that follows the fused pass in an Adam iteration (pinn_loss_grad_adam_step): the
+// gradient reduction of k_reduce_grads (grad_of_param), torch.optim.Adam's update (k_adam's adam_update, reduce_adam.h) on
+// the parameter it just summed, the refreshed entries of the packed W / W^T / b the next pass reads (k_pack's mapping,
+// inverted: padding entries stay zero), and — last block — the loss sums of k_reduce_sums (column_sum).  Five launches of
+// ~4.7 us each become one at the reference's own problem sizes (N_res = 243).
+__global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
+                              const float* __restrict__ wg_sums, int grid, int n_terms, float* __restrict__ term_sums,
+                              int n_cols, float* __restrict__ col_sums, float* __restrict__ grad,
+                              float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
+                              float* __restrict__ Wp, float* __restrict__ WTp, float* __restrict__ Bp, AdamScalars c,
+                              int n_loss_rows, const float* __restrict__ loss_rows, float* __restrict__ losses,
+                              int row_cols, int flags) {
+  if (blockIdx.x == gridDim.x - 1) {          // loss sums
+    finish_sums(wg_sums, grid, n_terms, term_sums, n_cols, col_sums, n_loss_rows, loss_rows, losses, row_cols);
+    return;
+  }
+  finish_adam_params(n, WP, wg, copies, PP, PW, grad, params, m, v, Wp, WTp, Bp, c, flags);
+}
+
+// The ensemble's finishing kernels, grid (parameter blocks + 1, M): member blockIdx.y's share of every array, then the
+// single-network functions.  gx is the per-member grid of the pass (a gradient copy and a row of partial sums per workgroup); terms_stride / row_cols are
+// the caller's n_terms / n_cols: the row lengths of term_sums / col_sums, also when this pass carried no fidelity columns.
+struct EnsFinish {
+  const float* wg; const float* wg_sums;    // M x gx x PP, M x gx x MAX_SUMS
+  float* term_sums; float* col_sums;        // (M, n_terms), (M, row_cols)
+  float* grad;                              // (M, P)
+};
+__device__ __forceinline__ EnsFinish ens_finish_member(EnsFinish f, const Net& n, int gx, int PP, int n_terms_stride, int row_cols) {
+  const int64_t mem = blockIdx.y;
+  f.wg += mem * gx * PP; f.wg_sums += mem * gx * MAX_SUMS;
+  f.term_sums += mem * n_terms_stride; f.col_sums += mem * row_cols;
+  f.grad += mem * n.n_params();
+  return f;
+}
+// plain (no Adam): sums as k_reduce_sums writes them, grad (M, P) += as k_reduce_grads adds
+__global__ void k_finish_ens(Net n, int WP, EnsFinish f0, int gx, int PP, int PW, int n_terms, int n_cols, int terms_stride,
+                             int row_cols, int flags) {
+  const EnsFinish f = ens_finish_member(f0, n, gx, PP, terms_stride, row_cols);
+  if (blockIdx.x == gridDim.x - 1) {
+    finish_sums(f.wg_sums, gx, n_terms, f.term_sums, n_cols, f.col_sums, 0, nullptr, nullptr, row_cols);
+    return;
+  }
+  const ParamGrad r = grad_of_param(n, WP, f.wg, gx, PP, PW, flags);
+  if (r.owner) f.grad[r.at.i] += r.g;
+}
+__global__ void k_finish_adam_ens(Net n, int WP, EnsFinish f0, int gx, int PP, int PW, int n_terms, int n_cols, int terms_stride,
+                                  int row_cols, float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
+                                  float* __restrict__ Wp, float* __restrict__ WTp, float* __restrict__ Bp, AdamScalars c,
+                                  int n_loss_rows, const float* __restrict__ loss_rows, float* __restrict__ losses, int flags) {
+  const EnsFinish f = ens_finish_member(f0, n, gx, PP, terms_stride, row_cols);
+  const int64_t mem = blockIdx.y, np = n.n_params();
+  if (blockIdx.x == gridDim.x - 1) {
+    finish_sums(f.wg_sums, gx, n_terms, f.term_sums, n_cols, f.col_sums, n_loss_rows, loss_rows, losses + mem * n_loss_rows, row_cols);
+    return;
+  }
+  finish_adam_params(n, WP, f.wg, gx, PP, PW, f.grad, params + mem * np, m + mem * np, v + mem * np, Wp + mem * PW,
+                     WTp + mem * PW, Bp + mem * (PP - PW), c, flags);
 }
 
 // what pinn_jet_backward hands the tile kernel instead of a loss: the caller's output adjoints, and where the gradient goes
@@ -636,6 +701,123 @@ int fused_loss(const Net& n, const LossReq& rq, const float* params, const float
   }
   if (!fused_supports(n, grad)) { set_error("fused engine: no kernel for this request (k = %d, gradient %d)", n.k, (int)grad); return PINN_ERR_UNSUPPORTED; }
   return run(n, grad, &rq, params, X, N, nullptr, nullptr, ws, ws_bytes, s);
+}
+
+// ---- ensembles: M members through one launch of the tile kernel's ensemble instances (fused_kernel.h, k_fused_ens) ------
+namespace {
+
+// The launch geometry of a member is the single-network gradient pass's (run() above: LDS, workgroups per CU), with the
+// grid clamped so that the M members together stay within the tile kernel's workgroup cap for the shape.
+struct EnsPlan {
+  int gx; bool acc_lds; size_t lds;
+  int64_t wp, wtp, bp, scratch, wg_sums, wg_grads, total;   // workspace layout: M members' shares of each region, back to back
+};
+EnsPlan ens_plan(const Net& n, const Geo& g, int M, int64_t N) {
+  EnsPlan e;
+  e.acc_lds = fits_lds(g);
+  e.lds = (size_t)(e.acc_lds ? g.PP : 0) * 4 + (size_t)lds_fixed_bytes();
+  const bool one_per_cu = e.acc_lds && !(g.WP <= 32 && 2 * (int64_t)e.lds <= LDS_LIMIT);
+  // (workgroups per CU: the single-network rule, with the ensemble instances' own waves per SIMD at width 16 — two, so the
+  // else-branch's 2 is what every narrow shape gets; kept in the rule's form so that the two stay comparable)
+  const int wgs = g.WP == 16 ? FUSED_ENS_W16_WAVES : tile_wgs_per_cu(g.WP);
+  const int per_cu = wgs * (int64_t)e.lds <= LDS_LIMIT ? wgs : 2;
+  const int64_t cap = (int64_t)cu_count() * (one_per_cu ? 1 : per_cu);
+  const int64_t most = cap / M > 1 ? cap / M : 1;
+  const int want = grid_for((N + 15) / 16, one_per_cu, per_cu);
+  e.gx = (int)(want < most ? want : most);
+  int64_t off = 0;
+  e.wp = off; off += align256((int64_t)M * g.PW * 4);
+  e.wtp = off; off += align256((int64_t)M * g.PW * 4);
+  e.bp = off; off += align256((int64_t)M * g.PB * 4);
+  e.scratch = off; off += align256((int64_t)M * e.gx * FUSED_WAVES * n.L * n.K1 * g.NTH * 256 * 4);
+  e.wg_sums = off; off += align256((int64_t)M * e.gx * MAX_SUMS * 4);
+  e.wg_grads = off; off += align256((int64_t)M * e.gx * g.PP * 4);
+  e.total = off;
+  return e;
+}
+
+}  // namespace
+
+const char* fused_ensemble_refusal(const Net& n, const LossReq& rq) {
+  if (n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH)
+    return "the ensemble instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
+  if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no ensemble kernel";
+  if (n.W > 64) return "hidden width above 64 has no ensemble kernel";
+  if (n.act != PINN_ACT_TANH) return "LeakyReLU has no ensemble kernel";
+  if (n.drop_p > 0.f) return "dropout_p > 0 has no ensemble kernel";
+  if (rq.kind != 1 && rq.spec.residual_id == RES_PE_CORRECTED) return "the corrected radiation stress (spec.flags bit 0) has no ensemble kernel";
+  if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
+  if (n.d_in > 16 || n.d_out > 16) return "d_in or d_out above 16";
+  if (n.L + 1 > MAX_LOCKS) return "network too deep for the per-layer locks";
+  if (rq.kind == 2 && rq.n_split >= 0 && padded_width(n.W) == 64)
+    return "the split request (0 <= n_res < N) at hidden width 33..64: the tile kernel carries no split code there";
+  return nullptr;
+}
+
+void fused_ensemble_plan(const Net& n, int M, int64_t N, int* gx, int* copy_in_lds, int64_t* ws_bytes) {
+  const EnsPlan e = ens_plan(n, geo_of(n), M, N);
+  if (gx) *gx = e.gx;
+  if (copy_in_lds) *copy_in_lds = e.acc_lds ? 1 : 0;
+  if (ws_bytes) *ws_bytes = e.total;
+}
+
+int fused_ensemble_loss(const Net& n, const LossReq& rq, int M, int flags, const float* params, const float* X, int64_t N,
+                        void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (const char* why = fused_ensemble_refusal(n, rq)) { set_error("fused engine, ensemble: %s", why); return PINN_ERR_UNSUPPORTED; }
+  const Geo g = geo_of(n);
+  const EnsPlan e = ens_plan(n, g, M, N);
+  if (!ws || ws_bytes < e.total) {
+    set_error("workspace too small: need %lld bytes, got %lld", (long long)e.total, (long long)ws_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  char* base = (char*)ws;
+  FusedParams P;
+  memset(&P, 0, sizeof(P));
+  P.d_in = n.d_in; P.d_out = n.d_out; P.L = n.L; P.act = n.act;
+  for (int j = 0; j < PINN_MAX_DIRS; ++j) P.dir_col[j] = n.dir_col[j];
+  P.N = N; P.n_tiles = (N + 15) / 16;
+  P.X = X;
+  P.Wp = (const float*)(base + e.wp); P.WTp = (const float*)(base + e.wtp); P.Bp = (const float*)(base + e.bp);
+  P.scratch = (float*)(base + e.scratch);
+  P.scratch_per_wave = (int64_t)n.L * n.K1 * g.NTH * 256;
+  P.wg_sums = (float*)(base + e.wg_sums);
+  P.wg_grads = (float*)(base + e.wg_grads);
+  P.PW = g.PW; P.PB = g.PB;
+  P.acc_lds = e.acc_lds ? 1 : 0;
+  P.lds_acc_floats = e.acc_lds ? g.PP : 0;
+  set_loss(P, n, rq);
+  // the members' X / T strides: two flag bits in a field the tile kernel does not read (fused_kernel.h, ens_member)
+  P.batch_T = ((flags & PINN_ENSEMBLE_OWN_X) ? ENS_OWN_X : 0) | ((flags & PINN_ENSEMBLE_OWN_T) && (P.loss_kind & 2) ? ENS_OWN_T : 0);
+
+  const AdamReq* adam = rq.adam;
+  const int packN = g.PW > g.PB ? g.PW : g.PB;
+  if (!(adam && adam->packed_valid))
+    hipLaunchKernelGGL(k_pack_ens, dim3((packN + 255) / 256, M), dim3(256), 0, s, n, g.WP, params, (float*)(base + e.wp),
+                       (float*)(base + e.wtp), (float*)(base + e.bp), g.PW, g.PB, 0);
+  if (!e.acc_lds) {   // global gradient copies start from zero
+    if (hipMemsetAsync(P.wg_grads, 0, (size_t)M * e.gx * g.PP * 4, s) != hipSuccess) {
+      set_error("hipMemsetAsync failed"); return PINN_ERR_LAUNCH;
+    }
+  }
+  int rc;
+  switch (g.WP) {
+    case 16: rc = launch_fused_ens<16>(n.K1, P, e.gx, M, e.lds, s); break;
+    case 32: rc = launch_fused_ens<32>(n.K1, P, e.gx, M, e.lds, s); break;
+    default: rc = launch_fused_ens<64>(n.K1, P, e.gx, M, e.lds, s); break;
+  }
+  if (rc) return rc;
+  const int64_t np = n.n_params();
+  const int n_terms = (P.loss_kind & 1) ? rq.n_terms : 0, n_cols = (P.loss_kind & 2) ? rq.n_cols : 0;
+  const EnsFinish f{(const float*)P.wg_grads, (const float*)P.wg_sums, rq.sums, rq.mse_sums, rq.grad};
+  const dim3 fgrid((unsigned)((np + 63) / 64) + 1, M);
+  if (adam) {
+    hipLaunchKernelGGL(k_finish_adam_ens, fgrid, dim3(256), 0, s, n, g.WP, f, e.gx, g.PP, g.PW, n_terms, n_cols, rq.n_terms,
+                       rq.n_cols, adam->params, adam->m, adam->v, (float*)(base + e.wp), (float*)(base + e.wtp),
+                       (float*)(base + e.bp), adam->c, adam->n_loss_rows, adam->loss_rows, adam->losses, 0);
+    return check_launch("fused ensemble finish + adam");
+  }
+  hipLaunchKernelGGL(k_finish_ens, fgrid, dim3(256), 0, s, n, g.WP, f, e.gx, g.PP, g.PW, n_terms, n_cols, rq.n_terms, rq.n_cols, 0);
+  return check_launch("fused ensemble finish");
 }
 
 }  // namespace pinn

@@ -183,6 +183,7 @@ class Engine:
         self._ws: Dict[object, torch.Tensor] = {}
         self._ws_need: Dict[tuple, int] = {}
         self._packed_tok = None      # (workspace, params storage, params version, caller's token) after loss_grad_adam_step
+        self._ens_packed_tok = None  # ... after ensemble_adam_step, for the M packed copies in the ensemble workspace
         self.dropout_seed = 0        # training-mode dropout: the caller sets a fresh seed per forward pass; the
                                      # reverse sweep of that pass must run under the same one (include/pinn_hip.h)
         cnt = C.c_int64()
@@ -215,6 +216,7 @@ class Engine:
         geometry (CU count) and the stream both belong to the device the tensors live on."""
         idx = self._index()
         self._packed_tok = None      # any other call may re-pack the workspace from ITS params argument
+        self._ens_packed_tok = None  # (the ensemble calls' token: the same rule)
         if torch.cuda.current_device() != idx:
             with torch.cuda.device(idx):
                 check(fn(*args, C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)), what)
@@ -578,10 +580,162 @@ class Engine:
                   _ptr(T), nc, oc, _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), loss_rows.shape[0], _ptr(loss_rows),
                   int(total_row), _ptr(state), state.numel(), int(n_slots), _ptr(trace), _ptr(ws), ws.numel())
 
+    # ---- ensembles: M networks of this geometry in one launch (pinn_ensemble_*) ---------------------------------------------
+    def _ensemble_need(self, M: int, N: int) -> Tuple[int, int]:
+        """(return code, workspace bytes) of pinn_ensemble_query_workspace, cached; host logic only."""
+        key = ("ens", int(M), int(N))
+        got = self._ws_need.get(key)
+        if got is None:
+            c_need = C.c_int64()
+            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
+                rc = self.lib.pinn_ensemble_query_workspace(C.byref(self._d()), int(M), int(N), C.byref(c_need))
+            got = (rc, c_need.value)
+            if rc == 0:
+                self._ws_need[key] = got
+        return got
+
+    def ensemble_workspace(self, M: int, N: int) -> torch.Tensor:
+        """Workspace of the ensemble calls for M members on N points (pinn_ensemble_query_workspace), cached apart from
+        workspace()'s.  Raises PinnError with the engine's reason where the ensemble calls are refused."""
+        rc, need = self._ensemble_need(M, N)
+        check(rc, "pinn_ensemble_query_workspace")
+        ws = self._ws.get("ens")
+        if ws is None or ws.numel() < need:
+            self._ws["ens"] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            self._ens_packed_tok = None
+        return ws
+
+    def ensemble_plan(self, M: int, N: int) -> Tuple[int, bool]:
+        """(workgroups per member, whether a workgroup's gradient copy lives in LDS) of an ensemble pass of M members on N
+        points (pinn_ensemble_plan).  Raises PinnError where the ensemble calls are refused.  Host logic only."""
+        gx, lds = C.c_int32(), C.c_int32()
+        with torch.cuda.device(self._index()):
+            check(self.lib.pinn_ensemble_plan(C.byref(self._d()), int(M), int(N), C.byref(gx), C.byref(lds)), "pinn_ensemble_plan")
+        return gx.value, bool(lds.value)
+
+    def ensemble_refusal(self, spec: ResidualSpec, M: int, N: int, n_res: int, n_cols: int) -> Optional[str]:
+        """Why the ensemble calls would refuse this request (None: they serve it), in the engine's own words: the
+        descriptor's part from pinn_ensemble_plan, the request's part (corrected radiation stress, the split request at
+        hidden width 33..64) from pinn_ensemble_loss_grad called WITHOUT arrays — it decides its refusals before it
+        looks at a pointer (pinn_hip.h) and then stops at the NULL arguments.  Host logic only: nothing is launched."""
+        gx, lds = C.c_int32(), C.c_int32()
+        with torch.cuda.device(self._index()):
+            rc = self.lib.pinn_ensemble_plan(C.byref(self._d()), int(M), int(N), C.byref(gx), C.byref(lds))
+            if rc == 0:
+                oc = (C.c_int32 * max(n_cols, 1))(*range(n_cols))
+                rc = self.lib.pinn_ensemble_loss_grad(C.byref(self._d()), C.byref(spec.c_struct()), int(M), None, None, int(n_cols),
+                                                      oc, None, None, None, int(N), int(n_res), 0, None, None, None, None, 0, None)
+        if rc == _lib.ERR_UNSUPPORTED:
+            return self.last_error()
+        if rc not in (0, _lib.ERR_INVALID):
+            check(rc, "pinn_ensemble_loss_grad")
+        if rc == _lib.ERR_INVALID and "NULL pointer" not in self.last_error():
+            raise PinnError(f"ensemble request is invalid: {self.last_error()}")
+        return None
+
+    def _ensemble_args(self, spec, term_scale, params, X, n_res, grad, T, out_col, col_scale, term_sums, col_sums):
+        """Shapes of an ensemble request: (M, N, nc, flags, term_sums, col_sums)."""
+        if params.dim() != 2:
+            raise PinnError(f"params must be (M, {self.n_params}), got {tuple(params.shape)}")
+        M, nc = params.shape[0], len(out_col)
+        own_x = X.dim() == 3
+        N = X.shape[1] if own_x else X.shape[0]
+        self._chk(params, "params", (M, self.n_params)); self._chk(grad, "grad", (M, self.n_params))
+        self._chk(X, "X", (M, N, self.desc.d_in) if own_x else (N, self.desc.d_in))
+        self._chk(term_scale, "term_scale", (spec.n_terms,))
+        flags = _lib.ENSEMBLE_OWN_X if own_x else 0
+        if term_sums is None:
+            term_sums = torch.empty(M, spec.n_terms, dtype=torch.float32, device=params.device)
+        self._chk(term_sums, "term_sums", (M, spec.n_terms))
+        if nc:
+            self._chk(col_scale, "col_scale", (nc,))
+            if col_sums is None:
+                col_sums = torch.empty(M, nc, dtype=torch.float32, device=params.device)
+            self._chk(col_sums, "col_sums", (M, nc))
+            if n_res != N:
+                rows = N - n_res if n_res >= 0 else N
+                if T is not None and T.dim() == 3:
+                    flags |= _lib.ENSEMBLE_OWN_T
+                    self._chk(T, "T", (M, rows, nc))
+                else:
+                    self._chk(T, "T", (rows, nc))
+        return M, N, nc, flags, term_sums, col_sums
+
+    def ensemble_loss_grad(self, spec: ResidualSpec, term_scale, params, X, n_res: int, grad, T: Optional[torch.Tensor] = None,
+                           out_col: Sequence[int] = (), col_scale=None, term_sums=None, col_sums=None):
+        """Loss sums and gradients of M networks in one pass (pinn_ensemble_loss_grad).  params, grad (M, P); X (N, d_in)
+        shared by the members or (M, N, d_in) one point set each; n_res as loss_grad_adam_step (== N residual only, 0 <=
+        n_res < N split, < 0 both terms on every point); T (rows, nc) shared or (M, rows, nc).  grad += the weighted
+        gradient of each member; returns (term_sums (M, n_terms), col_sums (M, nc) or None).  Raises PinnError with the
+        engine's reason, nothing launched, where the request has no ensemble kernel."""
+        spec.first_order("ensemble_loss_grad")
+        M, N, nc, flags, term_sums, col_sums = self._ensemble_args(spec, term_scale, params, X, n_res, grad, T, out_col, col_scale,
+                                                                   term_sums, col_sums)
+        ws = self.ensemble_workspace(M, N)
+        oc = (C.c_int32 * max(nc, 1))(*out_col)
+        self._run("pinn_ensemble_loss_grad", self.lib.pinn_ensemble_loss_grad, C.byref(self._d()), C.byref(spec.c_struct()), M,
+                  _ptr(term_scale), _ptr(T), nc, oc, _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), flags,
+                  _ptr(term_sums), _ptr(col_sums), _ptr(grad), _ptr(ws), ws.numel())
+        return term_sums, col_sums
+
+    def ensemble_adam_step(self, spec: ResidualSpec, term_scale, params, X, n_res: int, grad, m, v, step: int, lr,
+                           T: Optional[torch.Tensor] = None, out_col: Sequence[int] = (), col_scale=None,
+                           term_sums=None, col_sums=None, beta1=0.9, beta2=0.999, eps=1e-8,
+                           loss_rows: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None,
+                           params_token=None) -> bool:
+        """loss_grad_adam_step for M networks: two launches per iteration whatever M is (pinn_ensemble_adam_step; `lr` a
+        sequence: pinn_ensemble_adam_loop, one call for len(lr) iterations).  params, grad, m, v (M, P); term_sums
+        (M, n_terms), col_sums (M, nc); losses (M, rows), with an lr sequence (len(lr), M, rows).  One step count and one
+        learning-rate schedule for all members.  Returns False — nothing launched, the reason in last_error() — where the
+        request has no ensemble kernel.  The packed-weights token is this method's own, under loss_grad_adam_step's rules."""
+        spec.first_order("ensemble_adam_step")
+        lrs = [float(x) for x in lr] if isinstance(lr, (list, tuple)) else None
+        M, N, nc, flags, term_sums, col_sums = self._ensemble_args(spec, term_scale, params, X, n_res, grad, T, out_col, col_scale,
+                                                                   term_sums, col_sums)
+        for t, nme in ((m, "exp_avg"), (v, "exp_avg_sq")):
+            self._chk(t, nme, (M, self.n_params))
+        n_rows = 0
+        if loss_rows is not None:
+            n_rows = loss_rows.shape[0]
+            self._chk(loss_rows, "loss_rows", (n_rows, nc + spec.n_terms))
+            self._chk(losses, "losses", (M, n_rows) if lrs is None else (len(lrs), M, n_rows))
+        rc, _ = self._ensemble_need(M, N)
+        if rc == _lib.ERR_UNSUPPORTED:
+            return False
+        ws = self.ensemble_workspace(M, N)
+        req = (M, N, int(n_res), nc, flags, spec.residual_id, spec.corrected)
+        tok = self._ens_packed_tok
+        packed_valid = (tok is not None and tok[0] is ws and tok[1] == params.data_ptr() and tok[2] == params._version
+                        and tok[3] == params_token and tok[4] == req)
+        self._ens_packed_tok = None
+        st = _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0 if lrs is not None else float(lr), float(beta1), float(beta2),
+                                float(eps), 1 if packed_valid else 0, n_rows, _ptr(loss_rows), _ptr(losses))
+        oc = (C.c_int32 * max(nc, 1))(*out_col)
+        idx = self._index()
+        head = (C.byref(self._d()), C.byref(spec.c_struct()), M, _ptr(term_scale), _ptr(T), nc, oc, _ptr(col_scale),
+                _ptr(params), _ptr(X), N, int(n_res), flags, _ptr(term_sums), _ptr(col_sums), _ptr(grad), C.byref(st))
+        with torch.cuda.device(idx):
+            tail = (_ptr(ws), ws.numel(), C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+            if lrs is None:
+                rc = self.lib.pinn_ensemble_adam_step(*head, *tail)
+            else:
+                rc = self.lib.pinn_ensemble_adam_loop(*head, len(lrs), (C.c_double * len(lrs))(*lrs), *tail)
+        if rc == _lib.ERR_UNSUPPORTED:
+            return False
+        check(rc, "pinn_ensemble_adam_step" if lrs is None else "pinn_ensemble_adam_loop")
+        self._ens_packed_tok = (ws, params.data_ptr(), params._version, params_token, req)
+        return True
+
+    def last_error(self) -> str:
+        """The library's message for the last refused or failed call of this thread (pinn_last_error)."""
+        msg = self.lib.pinn_last_error()
+        return msg.decode() if msg else ""
+
     def invalidate_packed(self):
         """Forget the packed copy of the parameters left in the workspace by loss_grad_adam_step: the next call re-packs.
         For writers torch's version counters cannot see (a `.data` view written in place, a raw pointer)."""
         self._packed_tok = None
+        self._ens_packed_tok = None
 
     def adam_step(self, params, grad, m, v, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8):
         for t, nme in ((params, "params"), (grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):

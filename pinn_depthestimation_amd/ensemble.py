@@ -1,0 +1,232 @@
+"""ensemble — M networks of one configuration trained side by side: a deep ensemble (same data, different
+initialisations) or a seed sweep, for the spread a single trained network of an ill-posed inverse problem cannot give.
+
+The reference's problems fill a few workgroups of the chip (config_CMB.json: 243 collocation + 12 fidelity points on a
+10 x 10 network), so M trainers run one after the other cost M times the launches while most of the chip idles.
+EnsemblePINN keeps all members' parameters in ONE (M, P) buffer and runs an Adam iteration of all of them in two launches
+(Engine.ensemble_adam_step -> pinn_ensemble_adam_loop): member i gets the arithmetic trainer.PINN applies to its own
+network.  Same config schema, loss weights and StepLR schedule as trainer.PINN; one learning-rate schedule and one set of
+loss weights for all members.  An L-BFGS stage runs per member through the single-network trainer: member(i) is a DNN whose
+parameters are views of row i, ready for trainer.PINN(dnn=...) or inference.Tester.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from ._lib import PinnError
+from .config import PinnConfig, load_config
+from .dnn import DNN, init_flat_params
+from .engine import ACTIVATION_OF_INIT, Engine, NetDesc, ResidualSpec
+from .parallel import Reducer
+from .trainer import _as_f32
+
+DEFAULT_SEED = 1234      # trainer.PINN's default seed: member i starts from DEFAULT_SEED + i
+
+
+def member_seeds(members: int, seeds: Optional[Sequence[int]] = None) -> List[int]:
+    """The members' initialisation seeds: `seeds` (one per member, all different) or DEFAULT_SEED + i."""
+    if int(members) < 1:
+        raise PinnError(f"members = {members}: an ensemble has at least one member")
+    if seeds is None:
+        return [DEFAULT_SEED + i for i in range(int(members))]
+    seeds = [int(s) for s in seeds]
+    if len(seeds) != int(members):
+        raise PinnError(f"{len(seeds)} seeds for {members} members")
+    if len(set(seeds)) != len(seeds):
+        raise PinnError("two members share a seed: they would be the same network")
+    return seeds
+
+
+def init_ensemble_params(layers: Sequence[int], init_type: str, seeds: Sequence[int]) -> torch.Tensor:
+    """(M, P) fp32 on the CPU: row i = dnn.init_flat_params(layers, init_type) drawn from a generator seeded with seeds[i]."""
+    return torch.stack([init_flat_params(layers, init_type, torch.Generator().manual_seed(int(s))) for s in seeds])
+
+
+class EnsemblePINN:
+    """M physics-guided networks of one configuration, trained together (see the module docstring).
+
+    fidelity_input / fidelity_true / residual_input as trainer.PINN takes them — shared by all members — or with a
+    leading member axis, (M, N, d): one point set per member (bootstrap resamples, different collocation draws)."""
+
+    MAX_RUN = 256      # iterations enqueued by one call (pinn_ensemble_adam_loop)
+
+    def __init__(self, fidelity_input, fidelity_true, residual_input, config, members: int,
+                 seeds: Optional[Sequence[int]] = None, residual: Optional[str] = None, device="cuda", engine: int = 0,
+                 log_every: int = 1):
+        cfg = config if isinstance(config, PinnConfig) else load_config(config)
+        self.config, self.device = cfg, torch.device(device)
+        self.seeds = member_seeds(members, seeds)
+        self.members = M = len(self.seeds)
+        if Reducer().active:
+            raise PinnError("EnsemblePINN does not run under data parallelism (the members' gradients are finished on the "
+                            "device, no all-reduce in between): train the ensemble in one process")
+        residual = residual or cfg.default_residual()
+        loss = cfg.raw.get("loss", {})
+        if float(loss.get("eddy_viscosity", 0.0)) != 0.0:
+            raise PinnError("EnsemblePINN has no second-order residual (loss.eddy_viscosity): use trainer.PINN per member")
+        self.spec = ResidualSpec.from_names(residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs,
+                                            corrected=bool(loss.get("corrected_radiation_stress", False)))
+        Xr_in = residual_input
+        own = [a is not None and getattr(a, "ndim", 0) == 3 for a in (fidelity_input, fidelity_true, residual_input)]
+        if residual == "continuity_only" and own[2]:
+            raise PinnError("continuity_only divides its anchor term by a data-dependent count (points with x < threshold): "
+                            "with one collocation set per member the count differs by member, and the term scales are shared")
+        same_set = fidelity_input is not None and Xr_in is not None and (fidelity_input is Xr_in or (
+            cfg.variant == "newmethod" and tuple(fidelity_input.shape) == tuple(Xr_in.shape)
+            and torch.equal(_as_f32(fidelity_input, "cpu"), _as_f32(Xr_in, "cpu"))))      # (as trainer.PINN decides it)
+        fid_cols = list(range(len(cfg.fidelity_outputs)))
+        has_fid = fidelity_input is not None and fidelity_input.shape[-2] > 0 and len(fid_cols) > 0
+        self.fid_cols = fid_cols if has_fid else []
+        nr = 0 if Xr_in is None else int(Xr_in.shape[-2])
+        if nr < 1:
+            raise PinnError("EnsemblePINN needs collocation points (residual_input)")
+        nfp = int(fidelity_input.shape[-2]) if has_fid else 0
+        # the request, as trainer.PINN's evaluator forms it: one point set for both terms / collocation points first, then
+        # the fidelity points / the residual alone
+        if has_fid and same_set:
+            self._N, self._n_res = nr, -1
+        elif has_fid:
+            self._N, self._n_res = nr + nfp, nr
+        else:
+            self._N, self._n_res = nr, nr
+        act = ACTIVATION_OF_INIT[cfg.init_type]
+        self.eng = Engine(NetDesc.from_layers(cfg.layers, cfg.grad_cols, act, engine, 0, cfg.dropout_rate), self.device)
+        why = self.eng.ensemble_refusal(self.spec, M, self._N, self._n_res, len(self.fid_cols))
+        if why:
+            raise PinnError(why)
+
+        # ---- data (nothing above touched the device) ----
+        dev = self.device
+        Xf, Tf, Xr = (_as_f32(a, dev) for a in (fidelity_input if has_fid else None, fidelity_true if has_fid else None, Xr_in))
+
+        def per_member(t):
+            return t if t.dim() == 3 else t.unsqueeze(0).expand(M, *t.shape)
+        for t, name in ((Xf, "fidelity_input"), (Tf, "fidelity_true"), (Xr, "residual_input")):
+            if t is not None and t.dim() == 3 and t.shape[0] != M:
+                raise PinnError(f"{name} has {t.shape[0]} member slices for {M} members")
+        if has_fid and same_set:
+            self.X = Xr
+        elif has_fid:
+            if Xf.dim() == 3 or Xr.dim() == 3:
+                self.X = torch.cat([per_member(Xr), per_member(Xf)], 1).contiguous()
+            else:
+                self.X = torch.cat([Xr, Xf], 0).contiguous()
+        else:
+            self.X = Xr
+        self.T = Tf
+        self.n_res, self.n_fid = nr, nfp
+        if cfg.variant == "newmethod":
+            fid_w = [1.0] * len(self.fid_cols)
+        else:
+            fid_w = [cfg.output_weight(k) for k in cfg.fidelity_outputs][:len(self.fid_cols)]
+        self.weight_fidelity, self.weight_residual = cfg.weight_fid, cfg.weight_res
+        nf, nt = len(self.fid_cols), self.spec.n_terms
+        self._fid_unit = torch.tensor(fid_w, dtype=torch.float32, device=dev) / max(nfp, 1)
+        if residual == "continuity_only":
+            xcol = cfg.grad_cols[self.spec.dir_of[0]]
+            cnt = (Xr[:, xcol] < self.spec.threshold).sum().to(torch.float32).reshape(1)
+            self._res_unit = torch.cat([torch.tensor([1.0 / nr], device=dev), 1.0 / cnt, torch.zeros(1, device=dev)])
+        else:
+            self._res_unit = torch.full((nt,), 1.0 / nr, dtype=torch.float32, device=dev)
+        self._fid_scale = (self.weight_fidelity * self._fid_unit).contiguous()
+        self._res_scale = (self.weight_residual * self._res_unit).contiguous()
+        m = torch.zeros(3, nf + nt, dtype=torch.float32, device=dev)      # [fidelity, residual, total] = m @ [fid sums | res sums]
+        m[0, :nf] = self._fid_unit
+        m[1, nf:] = self._res_unit
+        m[2] = self.weight_fidelity * m[0] + self.weight_residual * m[1]
+        self._loss_mat = m.contiguous()
+
+        # ---- parameters and optimiser state ----
+        self.theta = init_ensemble_params(cfg.layers, cfg.init_type, self.seeds).to(dev).contiguous()
+        P = self.theta.shape[1]
+        self.grad = torch.zeros(M, P, dtype=torch.float32, device=dev)
+        self._adam_m, self._adam_v = torch.zeros_like(self.grad), torch.zeros_like(self.grad)
+        self._res_sums = torch.zeros(M, nt, dtype=torch.float32, device=dev)
+        self._fid_sums = torch.zeros(M, nf, dtype=torch.float32, device=dev) if nf else None
+        self._run_losses = torch.zeros(self.MAX_RUN, M, 3, dtype=torch.float32, device=dev)
+        self._members = {}
+        self.iter = self._adam_step = self._sched_steps = 0
+        self.adam_maxit = cfg.adam["max_it"]
+        self.log_every = max(int(log_every), 1)
+        self._history: List[tuple] = []
+        self._pending: List[Tuple[List[int], torch.Tensor]] = []      # (iterations, their (n, M, 3) rows on the device)
+
+    # ---- members ---------------------------------------------------------------------------------------------------
+    def member(self, i: int) -> DNN:
+        """Member i as a dnn.DNN whose Linear parameters are views of row i of `theta`: what it is told to do (trainer.PINN
+        (dnn=...) for an L-BFGS stage, inference.Tester, load_state_dict) happens to the ensemble's own buffer."""
+        i = int(i)
+        if not 0 <= i < self.members:
+            raise PinnError(f"member {i} of an ensemble of {self.members}")
+        dnn = self._members.get(i)
+        if dnn is None:
+            with torch.random.fork_rng(devices=[]):      # (the module's own initial draw is thrown away: leave the caller's stream alone)
+                dnn = DNN(self.config.layers, self.config.dropout_rate, self.config.init_type)
+            row, off = self.theta[i], 0
+            for p in dnn._ordered_params():
+                n = p.numel()
+                p.data = row[off:off + n].view_as(p)
+                off += n
+            dnn._flat = row
+            self._members[i] = dnn
+        return dnn
+
+    def _write_token(self):
+        """Changes when a member's module was written through torch (engine.py, packed-weights token)."""
+        return tuple((i, d.write_token()) for i, d in sorted(self._members.items()))
+
+    # ---- training ----------------------------------------------------------------------------------------------------
+    def train_adam(self, n: int):
+        """n Adam iterations of every member (train.py:188-193 with the StepLR schedule), in runs of at most MAX_RUN
+        iterations enqueued by one call each: two launches per iteration, whatever the number of members."""
+        a = self.config.adam
+        n = int(n)
+        while n > 0:
+            k = min(n, self.MAX_RUN)
+            lrs = [a["learning_rate"] * a["scheduler_gamma"] ** ((self._sched_steps + i) // a["scheduler_step_size"]) for i in range(k)]
+            out = self._run_losses[:k]
+            nf = len(self.fid_cols)
+            ok = self.eng.ensemble_adam_step(self.spec, self._res_scale, self.theta, self.X, self._n_res, self.grad, self._adam_m,
+                                             self._adam_v, self._adam_step + 1, lrs, T=self.T if nf else None,
+                                             out_col=self.fid_cols, col_scale=self._fid_scale if nf else None,
+                                             term_sums=self._res_sums, col_sums=self._fid_sums, loss_rows=self._loss_mat,
+                                             losses=out, params_token=self._write_token())
+            if not ok:
+                raise PinnError(self.eng.last_error())
+            its = [self.iter + 1 + i for i in range(k) if (self.iter + 1 + i) % self.log_every == 0]
+            if its:
+                idx = torch.tensor([it - self.iter - 1 for it in its], device=self.device)
+                self._pending.append((its, out.index_select(0, idx)))
+            self.iter += k
+            self._adam_step += k
+            self._sched_steps += k
+            n -= k
+
+    def train(self):
+        """The Adam stage of the configuration (adam_optimizer.max_it iterations).  The L-BFGS stage is per member:
+        trainer.PINN(..., dnn=self.member(i)).optimizer_LBFGS / train_lbfgs_device."""
+        self.train_adam(self.adam_maxit)
+
+    @property
+    def history(self) -> List[tuple]:
+        """(iteration, fidelity (M,), residual (M,), total (M,)) of every logged iteration: CPU tensors, formed on the
+        device by the finishing kernel (loss_rows) and brought over here, one synchronisation per call."""
+        for its, rows in self._pending:
+            rows = rows.cpu()
+            for j, it in enumerate(its):
+                self._history.append((it, rows[j, :, 0].clone(), rows[j, :, 1].clone(), rows[j, :, 2].clone()))
+        self._pending = []
+        return self._history
+
+    # ---- inference -------------------------------------------------------------------------------------------------------
+    def predict(self, inputs) -> torch.Tensor:
+        """Every member's outputs on a grid: (N, d_in) -> (M, N, d_out), M calls of Engine.forward."""
+        X = _as_f32(inputs, self.device)
+        return torch.stack([self.eng.forward(self.theta[i], X) for i in range(self.members)])
+
+    def predict_stats(self, inputs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(mean, unbiased standard deviation) over the members, each (N, d_out)."""
+        Y = self.predict(inputs)
+        return Y.mean(0), Y.std(0, unbiased=True)
