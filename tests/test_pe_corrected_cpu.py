@@ -9,10 +9,11 @@ import torch
 
 from pinn_depthestimation_amd import NetDesc, ResidualSpec, _lib, engine, physics
 from pinn_depthestimation_amd._lib import (ACT_LEAKY_RELU, ENGINE_AUTO, ENGINE_FUSED, ENGINE_GENERIC, ENGINE_WIDE, ERR_UNSUPPORTED,
-                                           PREC_BF16, PinnError)
+                                           ERR_WORKSPACE, PREC_BF16, PinnError)
 from tests.pe_corrected_util import ROLES, pec_fields, pec_loss
 
 PE_IN, PE_OUT = ("x", "y"), ROLES
+ERR_LAUNCH = -4      # PINN_ERR_LAUNCH (include/pinn_hip.h): a device call failed — never the answer to a refused request
 
 
 def _spec(desc, corrected=True, inputs=PE_IN):
@@ -162,25 +163,29 @@ def test_the_internal_residual_id_is_not_a_public_one():
 _P = C.c_void_p(0x1000)
 
 
-def _loss_calls(desc, spec):
-    """Every loss entry that takes a spec, with fake non-NULL pointers: (name, rc, message)."""
+def _loss_calls(desc, spec, workspace=True):
+    """Every loss entry that takes a spec, with fake non-NULL pointers: (name, rc, message).  For requests that are REFUSED
+    only: a request the engine serves must come with workspace=False (ws = NULL, ws_bytes = 0), which every engine turns
+    down with PINN_ERR_WORKSPACE before its first device call — with a workspace "size" of 2^40 such a request passes
+    validation and packs, launches and memsets on the fake addresses.  N = 64 with n_res = 48 (or both terms on every
+    point): no entry zeroes col_sums ahead of that check, which the n_res == N forms do."""
     lib = _lib.load()
     d, s = desc.c_struct(), spec.c_struct()
     oc = (C.c_int32 * 1)(0)
     st = _lib.PinnAdamState(_P, _P, 1, 1e-3, 0.9, 0.999, 1e-8, 0, 0, None, None)
     lr = (C.c_double * 2)(1e-3, 1e-3)
-    big = 1 << 40
+    ws, big = (_P, 1 << 40) if workspace else (None, 0)
     calls = [
-        ("pinn_residual_loss", lambda: lib.pinn_residual_loss(C.byref(d), C.byref(s), _P, _P, 64, _P, _P, big, None)),
-        ("pinn_residual_loss_grad", lambda: lib.pinn_residual_loss_grad(C.byref(d), C.byref(s), _P, _P, _P, 64, _P, _P, _P, big, None)),
+        ("pinn_residual_loss", lambda: lib.pinn_residual_loss(C.byref(d), C.byref(s), _P, _P, 64, _P, ws, big, None)),
+        ("pinn_residual_loss_grad", lambda: lib.pinn_residual_loss_grad(C.byref(d), C.byref(s), _P, _P, _P, 64, _P, _P, ws, big, None)),
         ("pinn_residual_mse_loss_grad", lambda: lib.pinn_residual_mse_loss_grad(C.byref(d), C.byref(s), _P, _P, 1, oc, _P, _P, _P, 64, _P, _P,
-                                                                                _P, _P, big, None)),
+                                                                                _P, ws, big, None)),
         ("pinn_residual_mse_split_loss_grad", lambda: lib.pinn_residual_mse_split_loss_grad(C.byref(d), C.byref(s), _P, _P, 1, oc, _P, _P, _P, 64,
-                                                                                            48, _P, _P, _P, _P, big, None)),
+                                                                                            48, _P, _P, _P, ws, big, None)),
         ("pinn_loss_grad_adam_step", lambda: lib.pinn_loss_grad_adam_step(C.byref(d), C.byref(s), _P, _P, 1, oc, _P, _P, _P, 64, 48, _P, _P, _P,
-                                                                          C.byref(st), _P, big, None)),
+                                                                          C.byref(st), ws, big, None)),
         ("pinn_adam_loop", lambda: lib.pinn_adam_loop(C.byref(d), C.byref(s), _P, _P, 1, oc, _P, _P, _P, 64, 48, _P, _P, _P, C.byref(st), 2, lr,
-                                                      _P, big, None)),
+                                                      ws, big, None)),
     ]
     return [(name, fn(), lib.pinn_last_error().decode()) for name, fn in calls]
 
@@ -213,9 +218,13 @@ def test_loss_entries_refuse_with_the_reason(case):
         assert rc == ERR_UNSUPPORTED and "corrected" in msg, (case, name, rc, msg)
     if "GENERIC" not in case:
         assert "GENERIC" in msg
-    # the plain residual on the same descriptor is not refused for that reason
+    # the plain residual on the same descriptor is not refused for that reason.  Most of these descriptors SERVE it, so
+    # the calls carry no workspace: they stop at the workspace check (or at another refusal), ahead of any device work
     plain = ResidualSpec.from_names("physics_equation", ("x", "y", "t") if desc.k == 3 else PE_IN, desc.grad_cols, PE_OUT)
-    assert all("corrected" not in m for _, rc, m in _loss_calls(desc, plain) if rc == ERR_UNSUPPORTED)
+    for name, rc, msg in _loss_calls(desc, plain, workspace=False):
+        assert rc in (ERR_WORKSPACE, ERR_UNSUPPORTED), (case, name, rc, msg)
+        assert rc != ERR_LAUNCH, (case, name, msg)
+        assert "corrected" not in msg, (case, name, rc, msg)
 
 
 @pytest.mark.parametrize("case", ["LeakyReLU, FUSED", "k = 3, FUSED"])
