@@ -174,8 +174,12 @@ __global__ void k_wgrad(const float* __restrict__ zb, const float* __restrict__ 
   const int o0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
   const int64_t n_begin = (int64_t)blockIdx.z * chunk;
   const int64_t n_end = (n_begin + chunk < N) ? n_begin + chunk : N;
+  // Two levels: a partial sum per WG_PTS points, added to the running sum once.  One running sum over the whole chunk
+  // (up to 16384 * K1 products of one sign, e.g. the fidelity adjoint times a biased activation) drifted by 4e-5 of the
+  // output layer's dW at 9600 points (tests/test_sweep2_gpu.py, pe_12x12_split_9600).
   float acc = 0.f, accb = 0.f;
   for (int64_t nb = n_begin; nb < n_end; nb += WG_PTS) {
+    float part = 0.f, partb = 0.f;
     for (int e = threadIdx.x; e < K1 * 16 * WG_PTS; e += 256) {
       const int p = e % WG_PTS, f = (e / WG_PTS) % 16, c = e / (WG_PTS * 16);
       const int64_t n = nb + p;
@@ -186,9 +190,10 @@ __global__ void k_wgrad(const float* __restrict__ zb, const float* __restrict__ 
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < K1; ++c)
-      for (int p = 0; p < WG_PTS; ++p) acc = fmaf(zs[c][to][p], as[c][ti][p], acc);
+      for (int p = 0; p < WG_PTS; ++p) part = fmaf(zs[c][to][p], as[c][ti][p], part);
     if (blockIdx.x == 0 && ti == 0)
-      for (int p = 0; p < WG_PTS; ++p) accb += zs[0][to][p];
+      for (int p = 0; p < WG_PTS; ++p) partb += zs[0][to][p];
+    acc += part; accb += partb;
     __syncthreads();
   }
   if (o0 + to < out_dim && i0 + ti < in_dim) atomicAdd(&dW[(int64_t)(o0 + to) * in_dim + i0 + ti], acc);
