@@ -22,6 +22,8 @@
  *                           before they are squared and averaged: residual maps, adaptive resampling
  *   pinn_residual2_loss_grad  Navier_Stokes / physics_equation with the lateral-mixing term nu * lap(U) in the momentum
  *                           equations (nested compute_gradient, physics.py:6-15) fused with loss.backward()
+ *   pinn_residual_coef_loss_grad  Navier_Stokes / physics_equation with gamma_b (physics.py:76) / Cd (physics.py:99) read from a
+ *                           device array, and the gradient with respect to them: the closures as trainable unknowns
  *   pinn_mse_loss_grad      train.py:131-141 (weighted fidelity MSE) + backward
  *   pinn_residual_mse_loss_grad  train_newmethod.py:122-159 (both on one forward) + backward
  *   pinn_residual_mse_split_loss_grad  train.py:131-157 (fidelity set + collocation set, one launch)
@@ -62,7 +64,8 @@
  *     term_scale, col_scale, loss_rows, grad of pinn_adam_step, data / grids / minmax, g, s, y; S, Y, M in
  *     pinn_lbfgs_direction; rows of S, Y other than `slot` and entries of M outside row and column `slot` in
  *     pinn_lbfgs_push.
- *   - grad_flat is += in pinn_jet_backward, pinn_jet2_backward, pinn_residual_loss_grad, pinn_residual2_loss_grad, pinn_mse_loss_grad,
+ *   - grad_flat is += in pinn_jet_backward, pinn_jet2_backward, pinn_residual_loss_grad, pinn_residual2_loss_grad,
+ *     pinn_residual_coef_loss_grad (whose coef_grad is += too; its coef is read-only), pinn_mse_loss_grad,
  *     pinn_residual_mse_loss_grad and pinn_residual_mse_split_loss_grad (the caller zeroes it, or accumulates several
  *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step and pinn_adam_loop.  Y, dY, d2Y, fields,
  *     term_sums, col_sums, losses, X_out, n_rows_out, out2 and d are overwritten, whatever they held.
@@ -300,6 +303,65 @@ int32_t pinn_residual2_loss_grad(const pinn_desc* desc, const pinn_residual_spec
                                  float* term_sums, float* fields /* NULL or (n_fields, N) */,
                                  float* grad_flat /* NULL: no backward sweep */,
                                  void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- runtime closure coefficients: train gamma_b and Cd alongside the network -----------------------------------------
+ * (added under ABI version 4, as the fields and residual2 entries were: no existing entry, struct or constant changed)
+ * The first-order residuals' physical closures as an optional DEVICE array instead of compile-time constants:
+ *   Navier_Stokes                 coef[0] = gamma_b, default 0.78    CB = 3/16 g gamma_b^2 in Fbr_x, Fbr_y (physics.py:76-78)
+ *   physics_equation (plain)      coef[0] = Cd,      default 0.002   tau_b = rho Cd U|U|              (physics.py:99-103)
+ * The continuity residuals have no coefficient (PINN_ERR_UNSUPPORTED, "no coefficient" in the message); neither has the
+ * corrected radiation stress (spec.flags bit 0: PINN_ERR_UNSUPPORTED, "corrected" in the message).
+ * The coefficients are a device array so that an optimiser updates them without a host round trip, as term_scale.  It
+ * follows that NO ENTRY VALIDATES THEIR VALUES: a negative, huge or non-finite coefficient is evaluated as given, and
+ * what it does to the sums and gradients is the caller's business. */
+#define PINN_MAX_COEFS 4
+/* *n <- the number of coefficients of the residual: 1, 1, 0, 0 for the four ids (0 for physics_equation with flags bit 0) */
+int32_t pinn_residual_coef_count(int32_t residual_id, int32_t flags, int32_t* n);
+/* *value <- the default of coefficient j: the constant the other entries have compiled in */
+int32_t pinn_residual_coef_default(int32_t residual_id, int32_t j, float* value);
+
+/* pinn_residual_coef_point: one point on the host, by the very functions the kernels call (no device is touched; coef is a
+ * HOST array here).  v as in pinn_residual2_point: v[c * NR + r], c = 0 the value, 1 + d the derivative along direction
+ * role d, of role r (NR = 4 roles and 3 directions for Navier_Stokes, 6 and 2 for physics_equation).
+ * fields <- (fc, f_x, f_y) with the given coefficient.  With scale, g and gcoef all given: g[c * NR + r] <- sum_t scale[t]
+ * d(field_t^2) / dv and gcoef[j] <- d/d coef[j] sum_t scale[t] field_t^2:
+ *   Navier_Stokes      (rx Hx H + ry Hy H) 3/8 g gamma_b,   H = h + z
+ *   physics_equation   D rho (rx U|U| + ry V|V|),           D = 1 / (rho (eta_mean + h))
+ * with rx = 2 scale[1] f_x, ry = 2 scale[2] f_y.  Any of the three NULL: fields only.
+ * At the default coefficients fields and g equal pinn_residual2_point's at nu = 0 to rounding, not bit for bit: the
+ * products rho Cd and 3/16 g gamma_b^2 are formed in fp32 at run time here and in double at compile time there. */
+int32_t pinn_residual_coef_point(int32_t residual_id, const float* v, const float* coef, const float* scale,
+                                 float* fields, float* g, float* gcoef);
+
+/* pinn_residual_coef_loss_grad: pinn_residual_loss_grad with the residual's coefficients read from `coef` (device, n_coef
+ * floats, read-only; NULL is PINN_ERR_INVALID) and their gradient out of the same pass:
+ *   term_sums (n_terms)  <- sum over points of field_t^2                                   (overwritten)
+ *   grad_flat (P,)       += sum_t term_scale[t] d term_sums[t] / d theta
+ *   coef_grad (n_coef,)  += sum_t term_scale[t] d term_sums[t] / d coef[j]
+ * grad_flat == NULL: forward only (term_scale may then be NULL too, and coef_grad must be).  coef_grad == NULL with
+ * grad_flat given: the coefficient VALUES only (a frozen coefficient).  N = 0 zeroes term_sums and touches nothing else.
+ * The workspace is the call's own (pinn_query_residual_coef_workspace), so that AUTO may move between engines.
+ * Rules, all decided before any device work; the query follows the same rules:
+ *   desc->k != the residual's directions     PINN_ERR_UNSUPPORTED  (3 for Navier_Stokes, 2 for physics_equation)
+ *   continuity_ftemp / continuity_only       PINN_ERR_UNSUPPORTED, "no coefficient" in the message
+ *   spec.flags bit 0 (corrected stress)      PINN_ERR_UNSUPPORTED, "corrected" in the message
+ *   GENERIC                                  any shape, tanh or LeakyReLU, dropout
+ *   FUSED and FUSED_TILE                     the tile kernel's coefficient instances: fp32, tanh, width <= 64, d_in and
+ *                                            d_out <= 16, dropout_p == 0; otherwise PINN_ERR_UNSUPPORTED with the reason
+ *   FUSED_COOP, FUSED_BATCH, WIDE, bf16      PINN_ERR_UNSUPPORTED (no such instances)
+ *   AUTO                                     the tile instances where FUSED is served, else GENERIC
+ * Reproducibility.  term_sums and coef_grad: bit-reproducible from run to run on both engines (the coefficient gradient
+ * is summed per workgroup beside the term sums and takes the same fixed-order double reduction).  A forward-only call
+ * (grad_flat == NULL) returns the very bits of the gradient call's term_sums on the same engine: it runs on that call's
+ * grid, and the fields are formed without fused multiply-adds so that every instance rounds them alike.  grad_flat: as for every
+ * tile-kernel gradient call — several waves share a workgroup's gradient copy, so two runs differ in the last bits once a
+ * workgroup holds more than one tile; on the generic engine the weight gradient adds with float atomics. */
+int32_t pinn_query_residual_coef_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes);
+int32_t pinn_residual_coef_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, const float* coef,
+                                     const float* term_scale, const float* params, const float* X, int64_t N,
+                                     float* term_sums, float* grad_flat /* NULL: no backward sweep */,
+                                     float* coef_grad /* NULL: no coefficient gradient */,
+                                     void* ws, int64_t ws_bytes, void* stream);
 
 /* term_sums[t] = sum over points of (residual field t)^2  (device, n_terms floats, overwritten)
  * Corrected radiation stress (spec.flags bit 0 on physics_equation) — the rule of every loss entry that takes a spec

@@ -12,6 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 PINN_MAX_DIRS = 3
 PINN_MAX_ROLES = 8
+PINN_MAX_COEFS = 4
 
 ACT_TANH, ACT_LEAKY_RELU = 0, 1
 ENGINE_AUTO, ENGINE_GENERIC, ENGINE_FUSED, ENGINE_WIDE = 0, 1, 2, 3
@@ -21,6 +22,7 @@ PREC_F32, PREC_BF16 = 0, 1
 
 RES_NAVIER_STOKES, RES_PHYSICS_EQUATION, RES_CONTINUITY_FTEMP, RES_CONTINUITY_ONLY = 1, 2, 3, 4
 RES_TERMS = {RES_NAVIER_STOKES: 3, RES_PHYSICS_EQUATION: 3, RES_CONTINUITY_FTEMP: 1, RES_CONTINUITY_ONLY: 3}
+RES_COEFS = {RES_NAVIER_STOKES: ("gamma_b",), RES_PHYSICS_EQUATION: ("Cd",), RES_CONTINUITY_FTEMP: (), RES_CONTINUITY_ONLY: ()}   # pinn_residual_coef_*: names, in coef[] order
 RES_FIELDS = {RES_NAVIER_STOKES: 3, RES_PHYSICS_EQUATION: 3, RES_CONTINUITY_FTEMP: 2, RES_CONTINUITY_ONLY: 2}   # pinn_residual_fields' rows
 
 
@@ -118,6 +120,13 @@ _SIGNATURES = {
     "pinn_query_residual2_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_residual2_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_float, _P, _P, _P,
                                              C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
+    "pinn_residual_coef_count": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "pinn_residual_coef_default": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    "pinn_residual_coef_point": (C.c_int32, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pinn_query_residual_coef_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.POINTER(C.c_int64)]),
+    "pinn_residual_coef_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P, _P,
+                                                 C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
     "pinn_residual_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P,
                                             C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "pinn_mse_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, _P, C.c_int64, C.c_int32,

@@ -88,6 +88,9 @@ struct LossReq {
   float* mse_sums;          // device col_sums
   float* grad;          // device flat grad (+=) or null
   const AdamReq* adam;  // fused engine only: grad is OVERWRITTEN with this pass's gradient and the update applied
+  // pinn_residual_coef_loss_grad only (kind 0, no adam; null everywhere else): the residual's closure coefficients, a device
+  // array of n_coef floats, and where their gradient goes (n_coef floats, +=; null = not wanted)
+  const float* coef; float* coef_grad; int n_coef;
 };
 
 // generic engine (pinn_generic.hip)
@@ -151,6 +154,13 @@ int fused_residual_fields(const Net& n, const pinn_residual_spec& spec, const fl
 // ... and from a staged jet (pinn_fields.hip): Y (n, d_out), dY (k, n, d_out) of points [n0, n0 + n) -> fields[f * N + n0 + i]
 int fields_from_jet(const Net& net, const pinn_residual_spec& spec, const float* X, const float* Y, const float* dY,
                     int64_t n, int64_t n0, int64_t N, float* fields, hipStream_t s);
+
+// pinn_residual_coef_loss_grad on the tile kernel's coefficient instances (fused_kernel.h, EPI_COEF): why the fused engine
+// does not serve the descriptor, or nullptr (pure host logic); the workspace of a served call; the call itself (rq.coef set)
+const char* fused_coef_refusal(const Net& n);
+int64_t fused_coef_workspace_bytes(const Net& n, int64_t N);
+int fused_coef_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
+                    int64_t ws_bytes, hipStream_t s);
 
 // wide MFMA engine, 64 < W <= 256 (pinn_wide.hip)
 bool wide_supports(const Net& n);

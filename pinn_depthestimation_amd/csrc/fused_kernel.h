@@ -76,6 +76,8 @@ struct FusedParams {
   uint32_t drop_seed, drop_thresh;   // k_fused<..., DROP = true>: nn.Dropout in training mode (common.h: dropout_bits)
   float drop_scale, drop_keep;       // 1 / (1 - p), 1 - p
   const float* gY;                   // k_fused<..., EPI_ADJ>: the caller's output adjoints, gY (N, d_out) and gdY (K1 - 1, N, d_out)
+                                     // k_fused<..., EPI_COEF>: the residual's coefficients instead (n_coef floats; gdY null) — a
+                                     // member of their own would grow the argument block of every instance (see Y above)
   const float* gdY;                  // in the engine's direction order (row c - 1 belongs to dir_col[c - 1]); either may be null
 };
 
@@ -668,7 +670,12 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 // EPI_GENERIC serves (residual, residual + fidelity columns, split mode) but stores no Y / dY.  EPI_FIELD_PEC: EPI_FIELD
 // for that residual.  Both are compile-time choices with translation units of their own (pinn_fused_pec_wXX.hip,
 // pinn_fused_batch_pec_wXX_k3.hip), so the generic epilogues do not grow by a branch.
-constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5, EPI_PEC = 6, EPI_FIELD_PEC = 7;
+// EPI_COEF (pinn_residual_coef_loss_grad): the EPI_NS / EPI_PE epilogue with the residual's closure coefficient read from
+// a device array (coef_epilogue below) and its gradient summed beside the term sums; translation units of its own too
+// (pinn_fused_coef_wXX.hip).
+constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5, EPI_PEC = 6, EPI_FIELD_PEC = 7,
+              EPI_COEF = 8;
+constexpr int COEF_SUM = 3;   // EPI_COEF: the term slot of [0, MSE_SUM0) that carries gc[0] (PINN_NS_TERMS = PINN_PE_TERMS = 3 leave it free)
 
 // The mirror of the generic epilogue's Y / dY store: lane (p, q), register r of G[c][0] is output o = 4q + r of point pt;
 // G[0] <- gY, G[c] <- gdY row c - 1.  Zero for o >= d_out, for the invalid points of the last tile and for a null array.
@@ -720,6 +727,48 @@ __device__ __forceinline__ void field_epilogue(const FusedParams& P, const f4 (&
     const bool masked = P.residual_id == PINN_RES_CONTINUITY_ONLY && P.X[ptc * P.d_in + P.xcol] < P.thr;
     field_tile<ResContinuity, K1>(P, out, pt, valid, masked, p, q);
   }
+}
+
+// EPI_COEF: residual_tile with a coefficient residual (residuals.h: ResNavierStokesCoef, ResPhysicsEquationCoef).  The
+// coefficients are P.gY (see FusedParams: only the EPI_ADJ instances read it otherwise, and FusedParams must not grow);
+// the point's coefficient gradient gc[0] joins sums[COEF_SUM] under the term sums' own predicate, so it reaches the host
+// side through wg_sums and the fixed-order double reduction and is bit-reproducible as they are.
+template <class RES, int K1, bool GRAD>
+__device__ __forceinline__ void residual_tile_coef(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
+                                                   float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
+                                                   float* __restrict__ tb, bool valid, int p, int q) {
+  constexpr int NR = RES::NR, ND = RES::ND, NT = RES::NT, NC = RES::NC;
+  static_assert(NT <= COEF_SUM && NC == 1, "EPI_COEF: one coefficient, its gradient in the free term slot");
+  float v[1 + ND][NR], g[1 + ND][NR], sq[NT], sc[NT], cf[NC], gc[NC];
+#pragma unroll
+  for (int c = 0; c <= ND; ++c) {
+    const f4 tile = (c == 0) ? out[0][0] : pick_q<K1>(out, P.q_of[c - 1]);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) v[c][r] = gather_out(tile, P.out_col[r], p);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) sc[t] = GRAD ? P.scale[t] : 0.f;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) cf[j] = P.gY[j];
+  RES::template eval<GRAD>(v, cf, sc, g, sq, gc);
+  if (valid && q == 0) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sums[t] += sq[t];
+    if (GRAD) sums[COEF_SUM] += gc[0];
+  }
+  if constexpr (GRAD) scatter_adjoint<K1, 1 + ND, NR>(tb, g, sm, G, valid, p, q);
+}
+// K1 decides the family (the host refuses any other pairing): 4 = Navier-Stokes, 3 = physics_equation.  Residual loss only:
+// no output stores, no fidelity columns, no split.
+template <int K1, bool GRAD>
+__device__ __forceinline__ void coef_epilogue(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
+                                              float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
+                                              float* __restrict__ tb, bool valid, int p, int q) {
+  static_assert(K1 == 3 || K1 == 4, "EPI_COEF: K1 = 1 + the residual's directions");
+#pragma unroll
+  for (int c = 0; c < K1; ++c) G[c][0] = f4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (K1 == 4) residual_tile_coef<ResNavierStokesCoef, K1, GRAD>(P, out, G, sums, sm, tb, valid, p, q);
+  else residual_tile_coef<ResPhysicsEquationCoef, K1, GRAD>(P, out, G, sums, sm, tb, valid, p, q);
 }
 
 // EPI_PEC: loss_epilogue_impl's generic part (below) with ONE residual family and without the output stores — the split
@@ -904,6 +953,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
   static_assert(EPI != EPI_FIELD || (!GRAD && !LDSACC && KRO == 0 && !DROP), "field instances: forward only, natural unit order, no dropout");
   static_assert(EPI != EPI_FIELD_PEC || (!GRAD && !LDSACC && KRO == 0 && !DROP && K1 == 3), "field instances: forward only, natural unit order, no dropout");
   static_assert(EPI != EPI_PEC || (KRO == 0 && !DROP && K1 == 3 && ACT == PINN_ACT_TANH), "corrected-residual instances: tanh, k = 2, natural unit order, no dropout");
+  static_assert(EPI != EPI_COEF || (KRO == 0 && !DROP && (K1 == 3 || K1 == 4) && ACT == PINN_ACT_TANH), "coefficient instances: tanh, k = 2 or 3, natural unit order, no dropout");
 #include "fused_tile_body.inc"
 }
 
@@ -938,6 +988,9 @@ template <int WP>
 int launch_fused_pec(bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 template <int WP>
 int launch_fused_field_pec(const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+// coefficient instances (EPI_COEF; K1 = 3 or 4, tanh): pinn_fused_coef.inc, one translation unit per WP (pinn_fused_coef_wXX.hip)
+template <int WP>
+int launch_fused_coef(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 // ensemble instances (k_fused_ens: grid (gx, M), gradient pass, tanh, K1 = 3 or 4): pinn_fused_ens.inc, one translation unit per WP
 // (pinn_fused_ens_wXX.hip)
 template <int WP>

@@ -272,6 +272,14 @@ void reduce_sums(const float* rows, int64_t n_rows, int stride, int col0, int n,
   hipLaunchKernelGGL(k_reduce_sums, dim3(n), dim3(256), 0, s, rows, n_rows, stride, col0, out);
 }
 
+__global__ void k_reduce_sums_add(const float* __restrict__ rows, int64_t n_rows, int stride, int col0, float* __restrict__ out) {
+  const double v = column_sum(rows, n_rows, stride, col0 + blockIdx.x);
+  if (threadIdx.x == 0) out[blockIdx.x] += (float)v;
+}
+void reduce_sums_add(const float* rows, int64_t n_rows, int stride, int col0, int n, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_reduce_sums_add, dim3(n), dim3(256), 0, s, rows, n_rows, stride, col0, out);
+}
+
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                        float* __restrict__ v, int64_t P, AdamScalars c) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -994,6 +1002,121 @@ int32_t pinn_residual2_loss_grad(const pinn_desc* desc, const pinn_residual_spec
   if (N == 0) { (void)hipMemsetAsync(term_sums, 0, residual_terms(spec->residual_id) * sizeof(float), (hipStream_t)stream); return PINN_OK; }
   return residual2_loss_grad(n, mfma, nspec, nu, term_scale, params, X, N, term_sums, fields, grad_flat, ws, ws_bytes,
                              (hipStream_t)stream);
+}
+
+// ---- runtime closure coefficients: gamma_b of Navier_Stokes, Cd of the plain physics_equation ---------------------------
+// the two residuals with a coefficient, on the host: the very functions the kernels call (residuals.h)
+extern "C++" {
+template <class R>
+static void residual_coef_point(const float* v, const float* coef, const float* scale, float* fields, float* g, float* gcoef) {
+  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], f[R::NF], sq[R::NT], gc[R::NC];
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
+  R::fields(jet, coef, f);
+  for (int t = 0; t < R::NF; ++t) fields[t] = f[t];
+  if (!scale || !g || !gcoef) return;
+  R::template eval<true>(jet, coef, scale, gj, sq, gc);
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
+  for (int j = 0; j < R::NC; ++j) gcoef[j] = gc[j];
+}
+}  // extern "C++"
+
+// 0 = the residual has a coefficient form; else the refusal ("no coefficient" / "corrected" in the message) or INVALID
+static int coef_residual(const char* who, int residual_id, int flags) {
+  switch (residual_id) {
+    case PINN_RES_NAVIER_STOKES: return PINN_OK;
+    case PINN_RES_PHYSICS_EQUATION:
+      if (flags & 1) {
+        set_error("%s: the corrected radiation stress (spec.flags bit 0) has no coefficient form", who);
+        return PINN_ERR_UNSUPPORTED;
+      }
+      return PINN_OK;
+    case PINN_RES_CONTINUITY_FTEMP: case PINN_RES_CONTINUITY_ONLY:
+      set_error("%s: residual %d has no closure: no coefficient", who, residual_id);
+      return PINN_ERR_UNSUPPORTED;
+    default: set_error("unknown residual_id %d", residual_id); return PINN_ERR_INVALID;
+  }
+}
+
+int32_t pinn_residual_coef_count(int32_t residual_id, int32_t flags, int32_t* n) {
+  if (!n) { set_error("n is NULL"); return PINN_ERR_INVALID; }
+  if (!residual_info(residual_id)) { set_error("unknown residual_id %d", residual_id); return PINN_ERR_INVALID; }
+  const bool has = residual_id == PINN_RES_NAVIER_STOKES || (residual_id == PINN_RES_PHYSICS_EQUATION && !(flags & 1));
+  *n = has ? 1 : 0;
+  return PINN_OK;
+}
+
+int32_t pinn_residual_coef_default(int32_t residual_id, int32_t j, float* value) {
+  if (!value) { set_error("value is NULL"); return PINN_ERR_INVALID; }
+  int rc = coef_residual("pinn_residual_coef_default", residual_id, 0); if (rc) return rc;
+  if (j != 0) { set_error("pinn_residual_coef_default: residual %d has 1 coefficient, j = %d", residual_id, j); return PINN_ERR_INVALID; }
+  *value = residual_id == PINN_RES_NAVIER_STOKES ? ResNavierStokesCoef::DEFAULTS[0] : ResPhysicsEquationCoef::DEFAULTS[0];
+  return PINN_OK;
+}
+
+int32_t pinn_residual_coef_point(int32_t residual_id, const float* v, const float* coef, const float* scale, float* fields,
+                                 float* g, float* gcoef) {
+  int rc = coef_residual("pinn_residual_coef_point", residual_id, 0); if (rc) return rc;
+  if (!v || !coef || !fields) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
+  if (residual_id == PINN_RES_NAVIER_STOKES) residual_coef_point<ResNavierStokesCoef>(v, coef, scale, fields, g, gcoef);
+  else residual_coef_point<ResPhysicsEquationCoef>(v, coef, scale, fields, g, gcoef);
+  return PINN_OK;
+}
+
+// validation shared by the query and the call (no HIP call before it has passed); *engine <- PINN_ENGINE_FUSED (the tile
+// kernel's coefficient instances) or PINN_ENGINE_GENERIC
+static int coef_plan(const pinn_desc* desc, const pinn_residual_spec* spec, Net* n, pinn_residual_spec* nspec, int* engine) {
+  const char* who = "pinn_residual_coef_loss_grad";
+  int rc = make_net(desc, n); if (rc) return rc;
+  rc = check_spec(*n, spec, nspec); if (rc) return rc;
+  rc = coef_residual(who, spec->residual_id, spec->flags); if (rc) return rc;
+  if (n->k != residual_dirs(spec->residual_id)) {
+    set_error("%s: the network carries k = %d tangent directions, residual %d has %d (k must equal the residual's number of "
+              "directions)", who, n->k, spec->residual_id, residual_dirs(spec->residual_id));
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (n->prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
+  const int asked = asked_engine(desc);
+  if (asked == PINN_ENGINE_WIDE) { set_error("%s does not run on the wide engine: use engine AUTO, FUSED or GENERIC", who); return PINN_ERR_UNSUPPORTED; }
+  const char* why = fused_coef_refusal(*n);
+  if (asked == PINN_ENGINE_FUSED && why) {
+    set_error("%s on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); engine AUTO or "
+              "GENERIC runs this request on the generic engine", who, why, n->W, n->d_in, n->d_out, n->k, n->act, (double)n->drop_p);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  *engine = (asked != PINN_ENGINE_GENERIC && !why) ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
+  return PINN_OK;
+}
+
+int32_t pinn_query_residual_coef_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
+  Net n; pinn_residual_spec nspec; int e;
+  int rc = coef_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
+  if (!bytes || N < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
+  const int64_t b = e == PINN_ENGINE_FUSED ? fused_coef_workspace_bytes(n, N) : generic_workspace_bytes(n, N);
+  if (b < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
+  *bytes = b;
+  return PINN_OK;
+}
+
+int32_t pinn_residual_coef_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, const float* coef,
+                                     const float* term_scale, const float* params, const float* X, int64_t N,
+                                     float* term_sums, float* grad_flat, float* coef_grad, void* ws, int64_t ws_bytes,
+                                     void* stream) {
+  Net n; pinn_residual_spec nspec; int e;
+  int rc = coef_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
+  if (!coef || !params || (!X && N > 0) || N < 0 || !term_sums || (grad_flat && !term_scale)) {
+    set_error("NULL pointer argument"); return PINN_ERR_INVALID;
+  }
+  if (coef_grad && !grad_flat) { set_error("coef_grad without grad_flat: the coefficient gradient comes out of the gradient pass"); return PINN_ERR_INVALID; }
+  LossReq rq; memset(&rq, 0, sizeof(rq));
+  rq.kind = 0; rq.n_split = -1; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums;
+  rq.grad = grad_flat; rq.n_terms = residual_terms(spec->residual_id);
+  rq.coef = coef; rq.coef_grad = coef_grad; rq.n_coef = 1;
+  const hipStream_t s = (hipStream_t)stream;
+  if (N == 0) { (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), s); return PINN_OK; }
+  return e == PINN_ENGINE_FUSED ? fused_coef_loss(n, rq, params, X, N, ws, ws_bytes, s)
+                                : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
 }
 
 }  // extern "C"

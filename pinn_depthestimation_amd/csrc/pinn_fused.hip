@@ -21,6 +21,9 @@ namespace {
 // a loss request with the corrected radiation stress (common.h, RES_PE_CORRECTED): its own kernel instances (EPI_PEC), on
 // the tile and on the batch kernel, never on the cooperative one
 bool is_pec(const LossReq* rq) { return rq && rq->kind != 1 && rq->spec.residual_id == RES_PE_CORRECTED; }
+// a residual request with runtime closure coefficients (pinn_residual_coef_loss_grad): its own instances of the tile kernel
+// (EPI_COEF), never the batch or the cooperative kernel, natural unit order
+bool is_coef(const LossReq* rq) { return rq && rq->coef != nullptr; }
 
 int padded_width(int W) { return W <= 16 ? 16 : (W <= 32 ? 32 : 64); }
 
@@ -419,6 +422,8 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   P.lds_acc_floats = P.acc_lds ? g.PP : 0;
   if (rq) set_loss(P, n, *rq);
   if (adj) { P.gY = adj->gY; P.gdY = adj->gdY; }
+  const bool coefq = is_coef(rq);
+  if (coefq) P.gY = rq->coef;   // (fused_kernel.h, FusedParams: the coefficient instances' array)
   if (fld) {   // the residual's roles as a residual loss sets them; nothing else of a loss request
     P.Y = fld->fields; P.dY = nullptr;   // (fused_kernel.h, FusedParams: the field instances' output array)
     set_residual_roles(P, n, fld->spec);
@@ -429,8 +434,8 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   if ((pec || fpec) && fused_corrected_refusal(n)) {
     set_error("fused engine: the corrected radiation stress %s", fused_corrected_refusal(n)); return PINN_ERR_UNSUPPORTED;
   }
-  const bool batch = !fld && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
-  const bool coop = !adj && !fld && !batch && !pec && use_coop(n, g, grad, N);   // (FUSED_COOP with it: the tile kernel)
+  const bool batch = !fld && !coefq && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
+  const bool coop = !adj && !fld && !batch && !pec && !coefq && use_coop(n, g, grad, N);   // (FUSED_COOP with it: the tile kernel)
   if (coop) {
     P.acc_lds = grad ? 1 : 0;
     P.lds_acc_floats = grad ? g.PP : 0;
@@ -445,8 +450,12 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
                    : coop ? (size_t)coop_lds_bytes(n, g, grad) : (size_t)P.lds_acc_floats * 4 + (size_t)lds_fixed_bytes();
   // 8x64 gradient kernels fill the register file and most of LDS (1 workgroup per CU); the narrow
   // networks' kernels fit 2 waves per SIMD, which hides their per-layer latencies
-  const bool one_per_cu = grad && P.acc_lds && !(g.WP <= 32 && 2 * (int64_t)lds <= LDS_LIMIT);
-  const int per_cu = tile_wgs_per_cu(g.WP) * (int64_t)lds <= LDS_LIMIT ? tile_wgs_per_cu(g.WP) : 2;
+  // (a forward-only coefficient request takes the GRID of its gradient call — the geometry that call's LDS gives — so that its
+  // per-workgroup partial sums, and with them term_sums, are the gradient call's bit for bit: include/pinn_hip.h)
+  const bool as_grad = grad || coefq;
+  const int64_t lds_geo = coefq && !grad ? (int64_t)(fits_lds(g) ? g.PP : 0) * 4 + lds_fixed_bytes() : (int64_t)lds;
+  const bool one_per_cu = as_grad && (coefq ? fits_lds(g) : P.acc_lds != 0) && !(g.WP <= 32 && 2 * lds_geo <= LDS_LIMIT);
+  const int per_cu = tile_wgs_per_cu(g.WP) * lds_geo <= LDS_LIMIT ? tile_wgs_per_cu(g.WP) : 2;
   int grid = adj && !batch ? adj_grid_for(P.n_tiles, one_per_cu, per_cu) : grid_for(P.n_tiles, one_per_cu, per_cu);
   if (coop) grid = coop_grid_for(P.n_tiles, grad);
 
@@ -457,7 +466,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     P.scratch_per_wave = (int64_t)T * (n.L > 1 ? n.L - 1 : 1) * n.K1 * batch_ks(n) * 64;
   }
   // k_fused<64, ..., KRO > 0>: the specialised-epilogue kernels take inputs / outputs in k-step-major order
-  if (!batch && !coop && n.drop_p == 0.f && g.WP == 64 && grad && P.acc_lds && n.act == PINN_ACT_TANH && P.loss_kind == 1 && !Y && P.n_split < 0 &&
+  if (!batch && !coop && !coefq && n.drop_p == 0.f && g.WP == 64 && grad && P.acc_lds && n.act == PINN_ACT_TANH && P.loss_kind == 1 && !Y && P.n_split < 0 &&
       n.d_in <= 4) {
     const int rid = P.residual_id;
     P.io1 = (n.K1 == 4 && rid == PINN_RES_NAVIER_STOKES && n.d_out <= 4) ||
@@ -525,6 +534,11 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     // kernel, one weight fetch per 64 points (pinn_fused_plain.hip)
     rc = launch_fused_plain(g.WP, P, cu_count(), s);
   }
+  else if (coefq) switch (g.WP) {   // EPI_COEF instances: pinn_fused_coef_wXX.hip
+    case 16: rc = launch_fused_coef<16>(n.K1, grad, P, grid, lds, s); break;
+    case 32: rc = launch_fused_coef<32>(n.K1, grad, P, grid, lds, s); break;
+    default: rc = launch_fused_coef<64>(n.K1, grad, P, grid, lds, s); break;
+  }
   else if (pec) {           // EPI_PEC instances: pinn_fused_batch_pec_wXX_k3.hip / pinn_fused_pec_wXX.hip
     if (batch) rc = g.WP == 16 ? launch_fused_batch_pec<16>(n.W, n.d_in, P, grid, lds, s)
                                : launch_fused_batch_pec<32>(n.W, n.d_in, P, grid, lds, s);
@@ -555,6 +569,8 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   if (rq) {
     if (P.loss_kind & 1)
       reduce_sums(P.wg_sums, grid, MAX_SUMS, 0, rq->n_terms, rq->sums, s);
+    if (coefq && grad && rq->coef_grad)   // the coefficient gradient rode in the free term slot (fused_kernel.h, COEF_SUM)
+      reduce_sums_add(P.wg_sums, grid, MAX_SUMS, COEF_SUM, rq->n_coef, rq->coef_grad, s);
     if (P.loss_kind & 2)
       reduce_sums(P.wg_sums, grid, MAX_SUMS, MSE_SUM0, rq->n_cols, rq->mse_sums, s);
     if (grad) {
@@ -637,6 +653,29 @@ const char* fused_corrected_refusal(const Net& n) {
   if (n.K1 != 3) return "has fused instances for k = 2 networks only: use engine GENERIC";
   if (n.drop_p > 0.f) return "has no dropout instance on the fused engine: use engine AUTO or GENERIC";
   return nullptr;
+}
+
+// Runtime coefficients (EPI_COEF instances): the tile kernel only, fp32, tanh, k = 2 or 3, no dropout.  nullptr = served.
+const char* fused_coef_refusal(const Net& n) {
+  if (n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH)
+    return "the coefficient instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
+  if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no coefficient kernel";
+  if (n.W > 64) return "hidden width above 64 has no coefficient kernel on the fused engine";
+  if (n.act != PINN_ACT_TANH) return "LeakyReLU has no coefficient kernel on the fused engine";
+  if (n.drop_p > 0.f) return "dropout_p > 0 has no coefficient kernel on the fused engine";
+  if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
+  if (n.d_in > 16 || n.d_out > 16) return "d_in or d_out above 16";
+  if (n.L + 1 > MAX_LOCKS) return "network too deep for the per-layer locks";
+  return nullptr;
+}
+int64_t fused_coef_workspace_bytes(const Net& n, int64_t N) {
+  if (fused_coef_refusal(n)) return -1;
+  return ws_layout(n, geo_of(n), N > 0 ? N : 1).total;
+}
+int fused_coef_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
+                    int64_t ws_bytes, hipStream_t s) {
+  if (const char* why = fused_coef_refusal(n)) { set_error("fused engine, coefficients: %s", why); return PINN_ERR_UNSUPPORTED; }
+  return run(n, rq.grad != nullptr, &rq, params, X, N, nullptr, nullptr, ws, ws_bytes, s);
 }
 
 int64_t fused_fields_workspace_bytes(const Net& n) {

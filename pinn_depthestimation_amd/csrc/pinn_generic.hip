@@ -264,6 +264,48 @@ __global__ void k_residual(const float* __restrict__ yj, int d_out, int64_t N, R
   block_reduce_store<NT>(sq, partial);
 }
 
+// k_residual for a residual with runtime closure coefficients (residuals.h: ResNavierStokesCoef, ResPhysicsEquationCoef):
+// coef is the device array, and the partial sums carry NC more columns, the point's coefficient gradient gc
+template <class RES, bool GRAD>
+__global__ void k_residual_coef(const float* __restrict__ yj, int d_out, int64_t N, RoleMap rm,
+                                const float* __restrict__ scale, const float* __restrict__ coef, float* __restrict__ G,
+                                float* __restrict__ partial) {
+  constexpr int NR = RES::NR, ND = RES::ND, NT = RES::NT, NC = RES::NC;
+  static_assert(NT + NC <= PINN_MAX_ROLES, "the partial-sum rows hold PINN_MAX_ROLES columns");
+  int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float sq[NT + NC];
+#pragma unroll
+  for (int t = 0; t < NT + NC; ++t) sq[t] = 0.f;
+  if (n < N) {
+    float v[1 + ND][NR], g[1 + ND][NR], st[NT], gc[NC], cf[NC];
+#pragma unroll
+    for (int c = 0; c <= ND; ++c) {
+      const int q = (c == 0) ? 0 : rm.q_of[c - 1];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) v[c][r] = yj[((int64_t)q * d_out + rm.out_col[r]) * N + n];
+    }
+    float sc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sc[t] = GRAD ? scale[t] : 0.f;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) cf[j] = coef[j];
+    RES::template eval<GRAD>(v, cf, sc, g, st, gc);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sq[t] = st[t];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) sq[NT + j] = gc[j];
+    if (GRAD) {
+#pragma unroll
+      for (int c = 0; c <= ND; ++c) {
+        const int q = (c == 0) ? 0 : rm.q_of[c - 1];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) G[((int64_t)q * d_out + rm.out_col[r]) * N + n] = g[c][r];
+      }
+    }
+  }
+  block_reduce_store<NT + NC>(sq, partial);
+}
+
 // fidelity: (true - pred)^2 per column (train.py:141)
 struct MseMap { int n_cols; int out_col[PINN_MAX_ROLES]; };
 template <bool GRAD>
@@ -395,7 +437,29 @@ int run_loss(const Net& n, const LossReq& rq, const float* params, const float* 
   if (want_grad) (void)hipMemsetAsync(G, 0, (size_t)K1 * n.d_out * N * 4, s);
   const int64_t n_res = (rq.kind == 2 && rq.n_split >= 0) ? rq.n_split : N;
   const int64_t n0 = (rq.kind == 2 && rq.n_split >= 0) ? rq.n_split : 0;
-  if (rq.kind == 0 || rq.kind == 2) {
+  if (rq.coef) {   // pinn_residual_coef_loss_grad: a residual request (kind 0) with runtime coefficients
+    RoleMap rm;
+    for (int r = 0; r < PINN_MAX_ROLES; ++r) rm.out_col[r] = rq.spec.out_col[r];
+    for (int d = 0; d < PINN_MAX_DIRS; ++d) rm.q_of[d] = 1 + rq.spec.dir_of[d];
+    const int id = rq.spec.residual_id;
+    int stride = 0;
+#define LAUNCH_COEF(RES)                                                                                          \
+  do {                                                                                                            \
+    stride = RES::NT + RES::NC;                                                                                   \
+    if (want_grad)                                                                                                \
+      hipLaunchKernelGGL((k_residual_coef<RES, true>), dim3(grid), dim3(TPB), 0, s, out, n.d_out, N, rm, rq.scale, \
+                         rq.coef, G, partial);                                                                    \
+    else                                                                                                          \
+      hipLaunchKernelGGL((k_residual_coef<RES, false>), dim3(grid), dim3(TPB), 0, s, out, n.d_out, N, rm, rq.scale, \
+                         rq.coef, G, partial);                                                                    \
+  } while (0)
+    if (id == PINN_RES_NAVIER_STOKES) LAUNCH_COEF(ResNavierStokesCoef);
+    else if (id == PINN_RES_PHYSICS_EQUATION) LAUNCH_COEF(ResPhysicsEquationCoef);
+    else { set_error("residual %d has no coefficient", id); return PINN_ERR_UNSUPPORTED; }
+#undef LAUNCH_COEF
+    reduce_sums(partial, lo.nblocks, stride, 0, rq.n_terms, rq.sums, s);
+    if (want_grad && rq.coef_grad) reduce_sums_add(partial, lo.nblocks, stride, rq.n_terms, rq.n_coef, rq.coef_grad, s);
+  } else if (rq.kind == 0 || rq.kind == 2) {
     int nt_stride = 0;
     RoleMap rm;
     for (int r = 0; r < PINN_MAX_ROLES; ++r) rm.out_col[r] = rq.spec.out_col[r];

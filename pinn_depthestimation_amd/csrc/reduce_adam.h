@@ -25,6 +25,8 @@ __device__ __forceinline__ double column_sum(const float* __restrict__ rows, int
 
 // launches k_reduce_sums (pinn_abi.hip): out[j] = column_sum of column col0 + j, j < n; one block per column
 void reduce_sums(const float* rows, int64_t n_rows, int stride, int col0, int n, float* out, hipStream_t s);
+// ... and its accumulating form (k_reduce_sums_add): out[j] += the same sum (pinn_residual_coef_loss_grad's coef_grad)
+void reduce_sums_add(const float* rows, int64_t n_rows, int stride, int col0, int n, float* out, hipStream_t s);
 
 // torch.optim.Adam, _single_tensor_adam (the path train.py:192 takes on CPU):
 //   exp_avg.lerp_(grad, 1-b1); exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1-b2)

@@ -278,6 +278,126 @@ struct ResContinuity {
   }
 };
 
+// ---- runtime closure coefficients (pinn_residual_coef_loss_grad) -----------------------------------------------------
+// Navier_Stokes and the plain physics_equation with their one physical closure read from an array instead of the literal
+// above: coef[0] = gamma_b (physics.py:76, default 0.78) resp. Cd (physics.py:99, default 0.002).  NC coefficients;
+// gc[j] <- d/d coef[j] sum_t scale[t] field_t^2 at this point (0 without GRAD).  The formulas are the structs' above with
+// CB resp. RC formed in fp32 at run time (there: in double at compile time), so at the defaults the two agree to
+// rounding, not bit for bit.  __host__ __device__: pinn_residual_coef_point runs the very same functions on the host.
+struct ResNavierStokesCoef {
+  static constexpr int NR = 4, ND = 3, NT = 3, NF = 3, NC = 1;
+  static constexpr float DEFAULTS[NC] = {0.78f};
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const float* coef, float (&f)[NF]) {
+#pragma clang fp contract(off)   // the fields round the same way in every instance: the forward-only sums equal the gradient call's bit for bit
+    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
+    const float z_t = v[1][1], u_t = v[1][2], w_t = v[1][3];
+    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
+    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
+    const float G = 9.81f;
+    const float gb = coef[0];
+    const float CB = (float)(3.0 / 16.0 * 9.81) * (gb * gb);   // physics.py:76-78
+    const float H = h + z;
+    const float Hx = h_x + z_x, Hy = h_y + z_y;
+    const float hu_x = Hx * u + H * u_x;
+    const float hv_y = Hy * w + H * w_y;
+    const float Fbr_x = CB * Hx * H, Fbr_y = CB * Hy * H;
+    f[0] = z_t + hu_x + hv_y;                                // physics.py:81
+    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;        // physics.py:82
+    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;        // physics.py:83
+  }
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* coef, const float* scale,
+                                              float (&g)[1 + ND][NR], float (&sq)[NT], float (&gc)[NC]) {
+    float f[NF];
+    fields(v, coef, f);
+    {
+#pragma clang fp contract(off)   // (no fusing of a square into the caller's running sum either)
+      sq[0] = f[0] * f[0]; sq[1] = f[1] * f[1]; sq[2] = f[2] * f[2];
+    }
+    gc[0] = 0.f;
+    if (GRAD) {
+      const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
+      const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
+      const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
+      const float G = 9.81f;
+      const float gb = coef[0];
+      const float CB = (float)(3.0 / 16.0 * 9.81) * (gb * gb);
+      const float H = h + z;
+      const float Hx = h_x + z_x, Hy = h_y + z_y;
+      const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
+      const float gh = rc * (u_x + w_y) + CB * (rx * Hx + ry * Hy);
+      g[0][0] = gh; g[0][1] = gh;
+      g[0][2] = rc * Hx + rx * u_x + ry * w_x;
+      g[0][3] = rc * Hy + rx * u_y + ry * w_y;
+      g[1][0] = 0.f; g[1][1] = rc; g[1][2] = rx; g[1][3] = ry;
+      const float ghx = rc * u + rx * CB * H;
+      g[2][0] = ghx; g[2][1] = ghx + rx * G;
+      g[2][2] = rc * H + rx * u; g[2][3] = ry * u;
+      const float ghy = rc * w + ry * CB * H;
+      g[3][0] = ghy; g[3][1] = ghy + ry * G;
+      g[3][2] = rx * w; g[3][3] = rc * H + ry * w;
+      gc[0] = (rx * Hx * H + ry * Hy * H) * ((float)(3.0 / 8.0 * 9.81) * gb);   // d CB / d gamma_b = 3/8 g gamma_b
+    }
+  }
+};
+
+struct ResPhysicsEquationCoef {   // the plain residual (E == 0, physics.py:106); the corrected stress has no coefficient form
+  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3, NC = 1;
+  static constexpr float DEFAULTS[NC] = {0.002f};
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const float* coef, float (&f)[NF]) {
+#pragma clang fp contract(off)   // the fields round the same way in every instance: the forward-only sums equal the gradient call's bit for bit
+    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
+    const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
+    const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
+    const float G = 9.81f, RHO = 1025.f;
+    const float RC = RHO * coef[0];              // rho*Cd  physics.py:102-103
+    const float tbx = (RC * U) * fabsf(U);
+    const float tby = (RC * V) * fabsf(V);
+    const float D = 1.0f / (RHO * (eta + h));
+    f[0] = U_x + V_y;                                        // physics.py:113
+    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;            // physics.py:114
+    f[2] = U * V_x + V * V_y + G * e_y + D * tby;            // physics.py:115
+  }
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* coef, const float* scale,
+                                              float (&g)[1 + ND][NR], float (&sq)[NT], float (&gc)[NC]) {
+    float f[NF];
+    fields(v, coef, f);
+    {
+#pragma clang fp contract(off)   // (no fusing of a square into the caller's running sum either)
+      sq[0] = f[0] * f[0]; sq[1] = f[1] * f[1]; sq[2] = f[2] * f[2];
+    }
+    gc[0] = 0.f;
+    if (GRAD) {
+      const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
+      const float U_x = v[1][1], V_x = v[1][2];
+      const float U_y = v[2][1], V_y = v[2][2];
+      const float G = 9.81f, RHO = 1025.f;
+      const float RC = RHO * coef[0];
+      const float tbx = (RC * U) * fabsf(U);
+      const float tby = (RC * V) * fabsf(V);
+      const float D = 1.0f / (RHO * (eta + h));
+      const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
+#pragma unroll
+      for (int c = 0; c < 1 + ND; ++c)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) g[c][r] = 0.f;
+      const float dD = -RHO * D * D;             // d D / d(eta+h)
+      const float gS = dD * (rx * tbx + ry * tby);
+      g[0][0] = gS; g[0][3] = gS;
+      g[0][1] = rx * (U_x + D * RC * 2.f * fabsf(U)) + ry * V_x;
+      g[0][2] = rx * U_y + ry * (V_y + D * RC * 2.f * fabsf(V));
+      g[1][1] = rc + rx * U;   // d/dU_x
+      g[1][2] = ry * U;        // d/dV_x
+      g[1][3] = rx * G;        // d/deta_x
+      g[2][1] = rx * V;        // d/dU_y
+      g[2][2] = rc + ry * V;   // d/dV_y
+      g[2][3] = ry * G;        // d/deta_y
+      gc[0] = D * RHO * (rx * (U * fabsf(U)) + ry * (V * fabsf(V)));   // d tau_b / d Cd = rho U|U|
+    }
+  }
+};
+
 // ---- second order: lateral mixing nu * lap(U) in the momentum equations --------------------------------------------
 // The momentum fields of Navier_Stokes and physics_equation (plain and corrected) with the eddy-viscosity closure
 //   fm_x -> fm_x - nu (u_xx + u_yy),   fm_y -> fm_y - nu (v_xx + v_yy)        (fc unchanged)

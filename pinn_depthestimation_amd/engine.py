@@ -114,6 +114,26 @@ class ResidualSpec:
         """Rows of Engine.residual_fields: (fc, fm_x, fm_y) / (fc, fx, fy) / (fc, da)."""
         return RES_FIELDS[self.residual_id]
 
+    @property
+    def coef_names(self) -> Tuple[str, ...]:
+        """The residual's closure coefficients, in the order of residual_coef_loss_grad's coef array: ("gamma_b",) for
+        Navier_Stokes, ("Cd",) for the plain physics_equation, () for everything else (pinn_residual_coef_count)."""
+        return () if self.corrected else _lib.RES_COEFS[self.residual_id]
+
+    @property
+    def n_coefs(self) -> int:
+        return len(self.coef_names)
+
+    @property
+    def coef_defaults(self) -> Tuple[float, ...]:
+        """The constants the other entries have compiled in (pinn_residual_coef_default): 0.78 / 0.002."""
+        out = []
+        for j in range(self.n_coefs):
+            v = C.c_float()
+            check(_lib.load().pinn_residual_coef_default(self.residual_id, j, C.byref(v)), "pinn_residual_coef_default")
+            out.append(float(v.value))
+        return tuple(out)
+
     def c_struct(self) -> PinnResidualSpec:
         s = PinnResidualSpec()
         s.residual_id = self.residual_id
@@ -386,6 +406,55 @@ class Engine:
         self._run("pinn_residual_loss_grad", self.lib.pinn_residual_loss_grad, C.byref(self._d(engine)), C.byref(spec.c_struct()),
                                                _ptr(term_scale), _ptr(params), _ptr(X), N, _ptr(sums),
                                                _ptr(grad), _ptr(ws), ws.numel())
+        return sums
+
+    def residual_coef_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
+        """Workspace of residual_coef_loss_grad (pinn_query_residual_coef_workspace), cached apart from the others."""
+        spec.first_order("residual_coef_workspace")
+        e = self.desc.engine if engine is None else engine
+        key = ("coef", e, spec.residual_id, spec.corrected, N)
+        need = self._ws_need.get(key)
+        if need is None:
+            c_need = C.c_int64()
+            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
+                check(self.lib.pinn_query_residual_coef_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
+                      "pinn_query_residual_coef_workspace")
+            need = self._ws_need[key] = c_need.value
+        ws = self._ws.get(("coef", e))
+        if ws is None or ws.numel() < need:
+            self._ws[("coef", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def residual_coef_loss_grad(self, spec: ResidualSpec, coef: torch.Tensor, term_scale: Optional[torch.Tensor], params, X,
+                                grad: Optional[torch.Tensor] = None, coef_grad: Optional[torch.Tensor] = None,
+                                sums: Optional[torch.Tensor] = None, engine=None) -> torch.Tensor:
+        """residual_loss_grad with the residual's closure coefficients read from the device tensor `coef` (spec.coef_names:
+        gamma_b of Navier_Stokes, Cd of physics_equation) instead of the compiled-in constants (pinn_residual_coef_loss_grad).
+        Returns term_sums; with `grad`, grad += sum_t term_scale[t] d term_sums[t] / d params, and with `coef_grad` as well,
+        coef_grad += the same derivative with respect to coef.  grad=None: forward only (term_scale may then be None).
+        coef_grad=None: the coefficients are values only.  Their VALUES are not checked: they never leave the device.
+        engine=None is the descriptor's: AUTO runs the tile kernel's coefficient instances where they exist (fp32, tanh,
+        width <= 64, no dropout) and the generic engine otherwise."""
+        spec.first_order("residual_coef_loss_grad")
+        N = X.shape[0]
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        if coef is None:
+            raise PinnError("residual_coef_loss_grad: coef is None (use residual_loss_grad for the compiled-in constants)")
+        self._chk(coef, "coef", (max(spec.n_coefs, 1),))
+        if grad is not None:
+            self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
+        if coef_grad is not None:
+            if grad is None:
+                raise PinnError("residual_coef_loss_grad: coef_grad without grad (the coefficient gradient comes out of the gradient pass)")
+            self._chk(coef_grad, "coef_grad", (max(spec.n_coefs, 1),))
+        if sums is None:
+            sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
+        else:
+            self._chk(sums, "sums", (spec.n_terms,))
+        ws = self.residual_coef_workspace(spec, N, engine)
+        self._run("pinn_residual_coef_loss_grad", self.lib.pinn_residual_coef_loss_grad, C.byref(self._d(engine)),
+                  C.byref(spec.c_struct()), _ptr(coef), _ptr(term_scale) if grad is not None else None, _ptr(params), _ptr(X), N,
+                  _ptr(sums), _ptr(grad), _ptr(coef_grad), _ptr(ws), ws.numel())
         return sums
 
     def residual2_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
@@ -737,9 +806,12 @@ class Engine:
         self._packed_tok = None
         self._ens_packed_tok = None
 
-    def adam_step(self, params, grad, m, v, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8):
+    def adam_step(self, params, grad, m, v, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, count: Optional[int] = None):
+        """torch.optim.Adam.step on the flat parameter vector; count: the length of another flat vector to update instead
+        (the trainer's closure coefficients: same kernel, same step count)."""
+        n = self.n_params if count is None else int(count)
         for t, nme in ((params, "params"), (grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
-            self._chk(t, nme, (self.n_params,))
+            self._chk(t, nme, (n,))
         self._packed_tok = None
-        self._run("pinn_adam_step", self.lib.pinn_adam_step, _ptr(params), _ptr(grad), _ptr(m), _ptr(v), self.n_params, step, lr, beta1,
+        self._run("pinn_adam_step", self.lib.pinn_adam_step, _ptr(params), _ptr(grad), _ptr(m), _ptr(v), n, step, lr, beta1,
                                       beta2, eps)

@@ -54,9 +54,13 @@ class EnsemblePINN:
 
     def __init__(self, fidelity_input, fidelity_true, residual_input, config, members: int,
                  seeds: Optional[Sequence[int]] = None, residual: Optional[str] = None, device="cuda", engine: int = 0,
-                 log_every: int = 1):
+                 log_every: int = 1, coefficients=None, trainable_coefficients=()):
         cfg = config if isinstance(config, PinnConfig) else load_config(config)
         self.config, self.device = cfg, torch.device(device)
+        if coefficients or trainable_coefficients or cfg.raw.get("loss", {}).get("coefficients") \
+                or cfg.raw.get("loss", {}).get("trainable_coefficients"):
+            raise PinnError("EnsemblePINN has no runtime closure coefficients (loss.coefficients / loss.trainable_coefficients): "
+                            "the ensemble kernels carry the constants; use trainer.PINN per member")
         self.seeds = member_seeds(members, seeds)
         self.members = M = len(self.seeds)
         if Reducer().active:

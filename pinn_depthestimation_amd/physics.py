@@ -60,20 +60,28 @@ def _laplacian(a, x, y):
     return d(d(a, x), x) + d(d(a, y), y)
 
 
-def Navier_Stokes(t, x, y, h, z, u, v, nu=0.0):
+def Navier_Stokes(t, x, y, h, z, u, v, nu=0.0, gamma_b=None):
     """physics.py:50-88 — unsteady shallow-water continuity + x/y momentum with the
     wave-breaking force 3/16 g gamma_b^2 d(h+z)/dx (h+z); friction terms are zero.
 
     nu > 0 (an extension, not reference behaviour) adds lateral mixing, -nu (u_xx + u_yy) and -nu (v_xx + v_yy), to the two
     momentum equations.  The derivatives are with respect to the network's inputs as it sees them: in the reference's
     pipeline those are normalised to [-1, 1], so nu is in those units.  Where the arguments are the columns of one
-    DNN.forward call the term is hard-wired (pinn_residual2_loss_grad); otherwise nested compute_gradient evaluates it."""
-    fused = fused_residual("Navier_Stokes", (t, x, y), (h, z, u, v), nu=nu)
-    if fused is not None:
-        return fused
+    DNN.forward call the term is hard-wired (pinn_residual2_loss_grad); otherwise nested compute_gradient evaluates it.
+
+    gamma_b (an extension too): the breaker index, a float or a tensor, in place of the reference's 0.78.  When given, the
+    formula below runs with that value (the forward jet and the parameter gradient still on the engine) and, for a tensor
+    that requires grad, torch autograd supplies d loss / d gamma_b.  The kernel-speed route for a trainable gamma_b is
+    Engine.residual_coef_loss_grad (trainer.PINN(trainable_coefficients=("gamma_b",)))."""
+    if gamma_b is None:
+        fused = fused_residual("Navier_Stokes", (t, x, y), (h, z, u, v), nu=nu)
+        if fused is not None:
+            return fused
     d = compute_gradient
     depth = h + z
-    g, gamma_b = 9.81, 0.78
+    g = 9.81
+    if gamma_b is None:
+        gamma_b = 0.78
     cb = 3.0 / 16.0 * g * gamma_b ** 2
     mass = d(z, t) + d(depth * u, x) + d(depth * v, y)
     mom_x = d(u, t) + u * d(u, x) + v * d(u, y) + g * d(z, x) + cb * d(depth, x) * depth
@@ -84,7 +92,7 @@ def Navier_Stokes(t, x, y, h, z, u, v, nu=0.0):
     return _mean_sq(mass, mom_x, mom_y)
 
 
-def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0):
+def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0, Cd=None):
     """physics.py:91-120 — steady wave-averaged continuity + momentum with quadratic bottom
     friction.  Default is bug-compatible: the reference's E = 1/8**rho*g*Hrms**2 (physics.py:106)
     is exactly 0.0, so the radiation-stress gradients vanish and Hrms, k do not enter.
@@ -97,8 +105,14 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0):
     nu > 0 (an extension as well) adds lateral mixing, -nu (U_xx + U_yy) and -nu (V_xx + V_yy), to the two momentum
     equations, plain or corrected: the standard closure of the wave-averaged balance.  nu is in the units of the network's
     inputs (normalised to [-1, 1] in the reference's pipeline).  Hard-wired (pinn_residual2_loss_grad) where the arguments
-    are the columns of one DNN.forward call, nested compute_gradient otherwise."""
-    if nu != 0:
+    are the columns of one DNN.forward call, nested compute_gradient otherwise.
+
+    Cd (an extension too): the drag coefficient, a float or a tensor, in place of the reference's 0.002.  When given, the
+    formula below runs with that value and, for a tensor that requires grad, torch autograd supplies d loss / d Cd; the
+    kernel-speed route is Engine.residual_coef_loss_grad (trainer.PINN(trainable_coefficients=("Cd",)))."""
+    if Cd is not None:
+        pass      # the formula route: the hard-wired kernels carry the constant
+    elif nu != 0:
         fused = fused_residual("physics_equation", (x, y), (h, U, V, eta_mean, Hrms, k), corrected=corrected, nu=nu)
         if fused is not None:
             return fused
@@ -107,7 +121,7 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0):
         if fused is not None:
             return fused
     d = compute_gradient
-    g, rho, cd = 9.81, 1025, 0.002
+    g, rho, cd = 9.81, 1025, (0.002 if Cd is None else Cd)
     inv_depth = 1 / (rho * (eta_mean + h))
     mass = d(U, x) + d(V, y)
     mom_x = U * d(U, x) + V * d(U, y) + g * d(eta_mean, x) + inv_depth * (rho * cd * U * abs(U))

@@ -14,16 +14,18 @@ restores line-by-line behaviour): log.txt has the same lines, just written in ba
 """
 from __future__ import annotations
 
+import json
 import os
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import PinnError
 from .config import PinnConfig, load_config
 from .dnn import DNN
-from .engine import ACTIVATION_OF_INIT, Engine, NetDesc, ResidualSpec
+from .engine import ACTIVATION_OF_INIT, RESIDUAL_ROLES, Engine, NetDesc, ResidualSpec
 from .lbfgs import DeviceLBFGS, FlatLBFGS
 from .parallel import Reducer
 
@@ -53,7 +55,8 @@ def rad_score(fields: torch.Tensor, k: float, c: float) -> torch.Tensor:
     return torch.where(m > 0, ek / m, torch.zeros_like(ek)) + c
 
 
-def device_lbfgs_refusal(reducer_active, residual_batch, eddy_viscosity, custom_evaluator, line_search_fn, dropout_rate=0.0):
+def device_lbfgs_refusal(reducer_active, residual_batch, eddy_viscosity, custom_evaluator, line_search_fn, dropout_rate=0.0,
+                         coefficients=False):
     """Why lbfgs_impl="device" cannot run this configuration (None: it can).  The device loop enqueues a fixed schedule of
     evaluations of ONE loss request; whatever needs the host, a second call or fresh randomness per evaluation is out."""
     flat = '; use lbfgs_impl="flat"'
@@ -69,6 +72,35 @@ def device_lbfgs_refusal(reducer_active, residual_batch, eddy_viscosity, custom_
         return f"lbfgs_impl=\"device\" runs the strong_wolfe line search only (line_search_fn={line_search_fn!r})" + flat
     if dropout_rate and dropout_rate > 0:
         return "lbfgs_impl=\"device\" does not run with dropout (a seed per forward pass has no place in a fixed schedule)" + flat
+    if coefficients:
+        return "lbfgs_impl=\"device\" does not run with runtime closure coefficients (the device loop enqueues the loss entries that carry the constants)" + flat
+    return None
+
+
+def coefficient_refusal(residual, coefficients, trainable, corrected=False, eddy_viscosity=0.0, reducer_active=False,
+                        resample="uniform", custom_evaluator=False):
+    """Why trainer.PINN cannot run this configuration with runtime closure coefficients (None: it can, or none are asked
+    for).  Pure host logic.  coefficients: {name: value}; trainable: names."""
+    coefficients, trainable = dict(coefficients or {}), tuple(trainable or ())
+    if not coefficients and not trainable:
+        return None
+    if residual not in RESIDUAL_ROLES:
+        return f"unknown residual {residual!r}"
+    have = () if corrected else _lib.RES_COEFS[RESIDUAL_ROLES[residual][0]]
+    if corrected:
+        return "the corrected radiation stress has no coefficient form (the corrected kernels carry the constant Cd)"
+    for name in list(coefficients) + list(trainable):
+        if name not in have:
+            return (f"residual {residual!r} has no coefficient {name!r}: " +
+                    (f"it has {', '.join(have)}" if have else "it has no coefficient at all"))
+    if eddy_viscosity:
+        return "runtime coefficients do not run with eddy_viscosity != 0 (the second-order residual carries the constants)"
+    if reducer_active:
+        return "runtime coefficients do not run under data parallelism (the coefficient gradient has no place in the all-reduce)"
+    if resample == "rad":
+        return "runtime coefficients do not run with resample='rad' (the field kernels carry the constants)"
+    if custom_evaluator:
+        return "runtime coefficients need the library's own evaluator, not a custom one"
     return None
 
 
@@ -96,7 +128,11 @@ class HipEvaluator:
         self._cat = None            # [collocation points ; fidelity points], allocated once
         self._cat_src = (None, None)   # the very tensor OBJECTS whose rows _cat currently holds
 
-    MERGE_MAX_FID = 2048   # fidelity points ride through the jet kernel (4x their own work): only when few
+    MERGE_MAX_FID = 2048
+    # runtime closure coefficients (PINN(coefficients=..., trainable_coefficients=...)): the device tensor the residual reads
+    # them from, and where their gradient goes (None: values only — frozen, or nothing trainable); set by the trainer
+    coef = None
+    coef_grad = None   # fidelity points ride through the jet kernel (4x their own work): only when few
 
     def _call_nu(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
         """The residual with the lateral-mixing term (spec.nu != 0): Engine.residual2_loss_grad on the collocation points,
@@ -116,7 +152,30 @@ class HipEvaluator:
         else:
             res_sums.zero_()
 
+    def _call_coef(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
+        """The residual with runtime closure coefficients (self.coef): Engine.residual_coef_loss_grad on the collocation
+        points, the fidelity term a separate mse_loss_grad, as _call_nu.  self.coef_grad, when set, is overwritten with
+        d loss / d coef of this evaluation."""
+        drop = self.eng_drop is not None and self.training
+        e = self.eng_drop if drop else self.eng
+        if self.coef_grad is not None:
+            self.coef_grad.zero_()
+        if Xf is not None and Xf.shape[0] > 0:
+            if drop:
+                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
+        else:
+            fid_sums.zero_()
+        if Xr is not None and Xr.shape[0] > 0:
+            if drop:
+                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            e.residual_coef_loss_grad(self.spec, self.coef, res_scale, theta, Xr, grad, self.coef_grad, sums=res_sums)
+        else:
+            res_sums.zero_()
+
     def __call__(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
+        if self.coef is not None:
+            return self._call_coef(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
         if self.spec.nu != 0:
             return self._call_nu(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
         if self.eng_drop is not None and self.training:
@@ -170,6 +229,8 @@ class HipEvaluator:
             return False
         if self.spec.nu != 0:     # the second-order residual is layer kernels per chunk, not one pass: the classic path
             return False
+        if self.coef is not None:     # the folded iteration runs the entries that carry the constants: the classic path
+            return False
         has_fid = Xf is not None and Xf.shape[0] > 0
         if not has_fid:
             if fid_sums.numel():       # (a configuration with fidelity outputs but no fidelity points: classic path)
@@ -208,6 +269,8 @@ class HipEvaluator:
 
     def residual_fields(self, theta, X):
         """(n_fields, N) signed residual fields at the rows of X, in eval mode: the engine without dropout, as predict."""
+        if self.coef is not None:
+            raise PinnError("residual_fields does not run with runtime closure coefficients: the field kernels carry the constants")
         if self.spec.nu != 0:     # the shifted fields, from the entry the loss runs on (no backward sweep)
             return self.eng.residual2_loss_grad(self.spec, None, theta, X, grad=None, fields=True)[1]
         return self.eng.residual_fields(self.spec, theta, X)
@@ -223,8 +286,17 @@ class PINN:
                  mat_dump_path: str = "data_at50k.mat", residual_batch: Optional[int] = None, seed: int = 1234,
                  log_flush_every: int = 100, lbfgs_impl: str = "flat", precision: int = 0, fold_adam: bool = True,
                  resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0,
-                 corrected: bool = False, eddy_viscosity: float = 0.0):
-        """corrected (or the config key loss.corrected_radiation_stress; physics_equation only): train on the corrected
+                 corrected: bool = False, eddy_viscosity: float = 0.0, coefficients: Optional[dict] = None,
+                 trainable_coefficients: Sequence[str] = ()):
+        """coefficients (or the config key loss.coefficients), e.g. {"Cd": 0.01}: values of the residual's closure coefficients
+        (ResidualSpec.coef_names: gamma_b of Navier_Stokes, Cd of physics_equation) in place of the compiled-in constants.
+        trainable_coefficients (or loss.trainable_coefficients), e.g. ("Cd",): those are unknowns learned with the network —
+        a small device tensor with Adam state of its own, updated with the same step count and schedule (learning rate:
+        adam_optimizer.coefficient_learning_rate, default the network's).  With either set the residual runs on
+        Engine.residual_coef_loss_grad, the fidelity term as a separate call, Adam iterations take the classic path, and the
+        L-BFGS stage holds the coefficients frozen at their Adam-final values.  Refused (coefficient_refusal): lbfgs_impl=
+        "device", data parallelism, eddy_viscosity, corrected, resample="rad", residual_fields(), unknown names.
+        corrected (or the config key loss.corrected_radiation_stress; physics_equation only): train on the corrected
         radiation stress, E = rho g Hrms^2 / 8, hard-wired in the kernels (ResidualSpec.corrected) — every path that takes
         the spec follows: the merged launch, the folded Adam runs, residual_fields and resample="rad".
         eddy_viscosity (or the config key loss.eddy_viscosity; Navier_Stokes and physics_equation): nu of the lateral-mixing
@@ -236,10 +308,20 @@ class PINN:
         self.reducer = reducer or Reducer()
         if lbfgs_impl not in ("flat", "torch", "device"):
             raise PinnError(f"lbfgs_impl={lbfgs_impl!r}: use 'flat', 'torch' or 'device'")
+        # runtime closure coefficients: parsed and refused before anything touches a device
+        loss_cfg = cfg.raw.get("loss", {})
+        coef_in = dict(coefficients) if coefficients else dict(loss_cfg.get("coefficients") or {})
+        coef_tr = tuple(trainable_coefficients) if trainable_coefficients else tuple(loss_cfg.get("trainable_coefficients") or ())
+        nu0 = float(eddy_viscosity) if eddy_viscosity else float(loss_cfg.get("eddy_viscosity", 0.0))
+        why = coefficient_refusal(residual or cfg.default_residual(), coef_in, coef_tr,
+                                  bool(corrected) or bool(loss_cfg.get("corrected_radiation_stress", False)), nu0,
+                                  self.reducer.active, resample, evaluator is not None)
+        if why:
+            raise PinnError(why)
         if lbfgs_impl == "device":       # decided before anything touches a device
             nu = float(eddy_viscosity) if eddy_viscosity else float(cfg.raw.get("loss", {}).get("eddy_viscosity", 0.0))
             why = device_lbfgs_refusal(self.reducer.active, residual_batch, nu, evaluator is not None,
-                                       cfg.lbfgs["line_search_fn"], cfg.dropout_rate)
+                                       cfg.lbfgs["line_search_fn"], cfg.dropout_rate, bool(coef_in or coef_tr))
             if why:
                 raise PinnError(why)
         self.fold_adam, self._adam_folded, self._folded_iters, self._run_losses = bool(fold_adam), False, 0, None
@@ -292,6 +374,19 @@ class PINN:
         self._fid_sums, self._res_sums = self.buf[P:P + nf], self.buf[P + nf:]
         self.evaluator = evaluator or HipEvaluator(cfg.layers, cfg.init_type, cfg.grad_cols, self.spec,
                                                    self.fid_cols, dev, engine, precision, cfg.dropout_rate)
+        # the coefficients: every one of the residual's, given or default, in ResidualSpec.coef_names order
+        self.coef_names: Tuple[str, ...] = self.spec.coef_names if (coef_in or coef_tr) else ()
+        self.trainable_coefficients = tuple(n for n in self.coef_names if n in coef_tr)
+        self._coef = self._coef_grad = self._coef_m = self._coef_v = self._coef_mask = None
+        self._coef_history: List[tuple] = []
+        if self.coef_names:
+            vals = [float(coef_in.get(n, d)) for n, d in zip(self.coef_names, self.spec.coef_defaults)]
+            self._coef = torch.tensor(vals, dtype=torch.float32, device=dev)
+            self.evaluator.coef = self._coef
+            if self.trainable_coefficients:
+                self._coef_grad = torch.zeros_like(self._coef)
+                self._coef_mask = torch.tensor([1.0 if n in coef_tr else 0.0 for n in self.coef_names], dtype=torch.float32, device=dev)
+                self.evaluator.coef_grad = self._coef_grad
 
         # optional resampled collocation mini-batch (the reference is full-batch only):
         # each closure draws `residual_batch` of this rank's points with a device-side generator
@@ -327,7 +422,7 @@ class PINN:
         self.log_dir, self.log_every, self.checkpoint_every = log_dir, max(int(log_every), 1), checkpoint_every
         self._log_fh = None
         self._history: List[tuple] = []
-        self._ring = torch.zeros(max(int(log_flush_every), 1), 3, dtype=torch.float32, device=dev)
+        self._ring = torch.zeros(max(int(log_flush_every), 1), 3 + len(self.coef_names), dtype=torch.float32, device=dev)
         self._ring_iters: List[int] = []
         self.last = None
         self.init_optimizers()
@@ -337,6 +432,8 @@ class PINN:
         a, lb = self.config.adam, self.config.lbfgs
         self._adam_m = torch.zeros_like(self.theta)
         self._adam_v = torch.zeros_like(self.theta)
+        if self._coef_grad is not None:      # the coefficients' own Adam state
+            self._coef_m, self._coef_v = torch.zeros_like(self._coef), torch.zeros_like(self._coef)
         self._adam_step = 0
         self._sched_steps = 0
         self.theta_param = torch.nn.Parameter(self.theta)       # shares storage with every Linear weight
@@ -355,6 +452,17 @@ class PINN:
         """StepLR(step_size, gamma) stepped once per Adam iteration (train.py:109-113,193)."""
         a = self.config.adam
         return a["learning_rate"] * a["scheduler_gamma"] ** (self._sched_steps // a["scheduler_step_size"])
+
+    def current_coefficient_lr(self) -> float:
+        """The coefficients' learning rate: adam_optimizer.coefficient_learning_rate (default: the network's) on the same StepLR."""
+        a = self.config.adam
+        return float(a.get("coefficient_learning_rate", a["learning_rate"])) * a["scheduler_gamma"] ** (self._sched_steps // a["scheduler_step_size"])
+
+    def coefficients(self) -> Dict[str, float]:
+        """The closure coefficients in use, by name (one synchronisation); {} when the compiled-in constants are."""
+        if self._coef is None:
+            return {}
+        return dict(zip(self.coef_names, (float(x) for x in self._coef.cpu().tolist())))
 
     # ---- loss (train.py:128-181) ----------------------------------------------------------------------
     def loss_func(self, _adam=None) -> torch.Tensor:
@@ -382,7 +490,9 @@ class PINN:
         nxt = self.iter + 1
         logged = nxt % self.log_every == 0 or nxt % 1000 == 0
         # the three losses of a logged iteration are computed straight into the device-side ring
-        vec = self._ring[len(self._ring_iters)] if logged else self._loss_vec
+        vec = self._ring[len(self._ring_iters)][:3] if logged else self._loss_vec
+        if logged and self._coef is not None:      # the coefficients this evaluation ran with, beside its losses
+            self._ring[len(self._ring_iters)][3:].copy_(self._coef)
         self._adam_folded = _adam is not None and self.evaluator.adam_iteration(
             self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad, self._fid_sums, self._res_sums,
             *_adam, loss_rows=self._loss_mat, losses=vec, params_token=self.dnn.write_token(self.theta))
@@ -438,13 +548,16 @@ class PINN:
             return
         rows = self._ring[:len(self._ring_iters)].cpu().tolist()
         iters, self._ring_iters = self._ring_iters, []
-        for it, (fid, res, tot) in zip(iters, rows):
-            self._log(it, fid, res, tot)
+        for it, row in zip(iters, rows):
+            self._log(it, row[0], row[1], row[2], row[3:])
         if self._log_fh is not None:
             self._log_fh.flush()
 
-    def _log(self, it: int, fid: float, res: float, tot: float):
+    def _log(self, it: int, fid: float, res: float, tot: float, coefs: Sequence[float] = ()):
         self._history.append((it, fid, res, tot))
+        if coefs:
+            self._coef_history.append((it,) + tuple(coefs))
+        tail = "".join(f", {c:.6e}" for c in coefs)      # the coefficients' values, appended to the log line
         if it % 1000 == 0 and self.reducer.rank == 0:
             print(f"Epoch {it}, Fidelity Loss: {fid:.5e}, Residual Loss: {res:.5e}, Total Loss: {tot:.5e}")
         if self.log_dir is None or self.reducer.rank != 0:
@@ -455,8 +568,8 @@ class PINN:
             new = not os.path.exists(path) or os.stat(path).st_size == 0
             self._log_fh = open(path, "a")
             if new:
-                self._log_fh.write("Epoch, Fidelity Loss, Residual Loss, Total Loss\n")       # train.py:167
-        self._log_fh.write(f"{it}, {fid:.5e}, {res:.5e}, {tot:.5e}\n")                        # train.py:170
+                self._log_fh.write("Epoch, Fidelity Loss, Residual Loss, Total Loss" + "".join(f", {n}" for n in self.coef_names) + "\n")   # train.py:167
+        self._log_fh.write(f"{it}, {fid:.5e}, {res:.5e}, {tot:.5e}{tail}\n")                  # train.py:170
 
     def dump_predictions(self, path: str):
         """savemat of pred_<key> (N,1) float32 for every network output on ALL residual points — the
@@ -469,7 +582,10 @@ class PINN:
         from scipy.io import savemat
         Y = Y.cpu().numpy().astype(np.float32)
         names = self.config.residual_outputs
-        savemat(path, {f"pred_{k}": Y[:, i:i + 1] for i, k in enumerate(names)})
+        out = {f"pred_{k}": Y[:, i:i + 1] for i, k in enumerate(names)}
+        if self._coef is not None:
+            out["coefficients"] = self._coef.cpu().numpy().astype(np.float32).reshape(1, -1)      # in coef_names order
+        savemat(path, out)
         print(f"Data saved to {path} after {self.iter} iterations.")
 
     def save_checkpoint(self, name: str):
@@ -479,6 +595,10 @@ class PINN:
         os.makedirs(self.log_dir, exist_ok=True)
         torch.save(self.dnn, os.path.join(self.log_dir, name))                    # whole module, as train.py:179
         torch.save(self.dnn.state_dict(), os.path.join(self.log_dir, name.replace(".pth", ".state.pth")))
+        if self._coef is not None:
+            with open(os.path.join(self.log_dir, "coefficients.json"), "w") as fh:
+                json.dump({"iteration": self.iter, "coefficients": self.coefficients(),
+                           "trainable": list(self.trainable_coefficients)}, fh)
 
     # ---- training (train.py:185-200) ------------------------------------------------------------------
     def adam_step(self):
@@ -486,6 +606,8 @@ class PINN:
         # One process, no checkpoint inside this iteration (the reference saves the PRE-update weights from inside
         # loss_func, train.py:175-179): the evaluator may fold the update into the pass's last kernel.
         fold = (self._may_fold() and not self._checkpoint_due(self.iter + 1))
+        if self._coef is not None:
+            self.evaluator.coef_grad = self._coef_grad      # (None when nothing is trainable: values only)
         loss = self.loss_func((self._adam_m, self._adam_v, self._adam_step + 1, self.current_lr()) if fold else None)
         self._adam_step += 1
         if fold and not self._adam_folded:
@@ -493,6 +615,11 @@ class PINN:
         if not self._adam_folded:
             self.evaluator.adam_step(self.theta, self.grad, self._adam_m, self._adam_v, self._adam_step,
                                      self.current_lr())
+            if self._coef_grad is not None:      # the coefficients: the same step count and schedule, their own state
+                if len(self.trainable_coefficients) < len(self.coef_names):
+                    self._coef_grad.mul_(self._coef_mask)
+                self.evaluator.eng.adam_step(self._coef, self._coef_grad, self._coef_m, self._coef_v, self._adam_step,
+                                             self.current_coefficient_lr(), count=self._coef.numel())
         else:
             self._folded_iters += 1
         self._sched_steps += 1
@@ -507,7 +634,7 @@ class PINN:
         """The folded iteration is worth asking for: switched on, one process, an evaluator that has it, and the engine
         has not already refused this very request (wide / generic engine, a large split request: the refusal is remembered
         per evaluator and point sets instead of being re-discovered by two refused C calls every iteration)."""
-        return (self.fold_adam and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
+        return (self.fold_adam and self._coef is None and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
                 and self._fold_refused != self._fold_key())
 
     def _foldable_run(self, n: int) -> int:
@@ -583,6 +710,8 @@ class PINN:
 
     def closure(self):
         """train.py:195-199"""
+        if self._coef is not None:      # the L-BFGS stage holds the coefficients frozen: values only, no coefficient gradient
+            self.evaluator.coef_grad = None
         loss = self.loss_func()
         self.theta_param.grad = self.grad.clone()
         return loss
@@ -657,6 +786,8 @@ class PINN:
     def residual_fields(self, X=None) -> torch.Tensor:
         """The residual's signed per-point fields (n_fields, N) at X (default: this rank's collocation shard), in
         eval mode: Navier_Stokes (fc, fm_x, fm_y), physics_equation (fc, fx, fy), continuity (fc, da)."""
+        if self._coef is not None:
+            raise PinnError("residual_fields does not run with runtime closure coefficients: the field kernels carry the constants")
         X = self.Xr if X is None else _as_f32(X, self.device)
         return self.evaluator.residual_fields(self.dnn.flat_params(), X)
 
