@@ -24,6 +24,9 @@
  *                           equations (nested compute_gradient, physics.py:6-15) fused with loss.backward()
  *   pinn_residual_coef_loss_grad  Navier_Stokes / physics_equation with gamma_b (physics.py:76) / Cd (physics.py:99) read from a
  *                           device array, and the gradient with respect to them: the closures as trainable unknowns
+ *   pinn_residual_weighted_loss_grad  the four residuals with one weight per collocation point (and term) on the squares:
+ *                           masks, confidence maps, importance weights, self-adaptive weights; optionally the signed
+ *                           per-point fields out of the same pass
  *   pinn_mse_loss_grad      train.py:131-141 (weighted fidelity MSE) + backward
  *   pinn_residual_mse_loss_grad  train_newmethod.py:122-159 (both on one forward) + backward
  *   pinn_residual_mse_split_loss_grad  train.py:131-157 (fidelity set + collocation set, one launch)
@@ -65,7 +68,8 @@
  *     pinn_lbfgs_direction; rows of S, Y other than `slot` and entries of M outside row and column `slot` in
  *     pinn_lbfgs_push.
  *   - grad_flat is += in pinn_jet_backward, pinn_jet2_backward, pinn_residual_loss_grad, pinn_residual2_loss_grad,
- *     pinn_residual_coef_loss_grad (whose coef_grad is += too; its coef is read-only), pinn_mse_loss_grad,
+ *     pinn_residual_coef_loss_grad (whose coef_grad is += too; its coef is read-only), pinn_residual_weighted_loss_grad
+ *     (whose point_w is read-only and whose fields, if given, are overwritten at (n_fields, N)), pinn_mse_loss_grad,
  *     pinn_residual_mse_loss_grad and pinn_residual_mse_split_loss_grad (the caller zeroes it, or accumulates several
  *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step and pinn_adam_loop.  Y, dY, d2Y, fields,
  *     term_sums, col_sums, losses, X_out, n_rows_out, out2 and d are overwritten, whatever they held.
@@ -362,6 +366,49 @@ int32_t pinn_residual_coef_loss_grad(const pinn_desc* desc, const pinn_residual_
                                      float* term_sums, float* grad_flat /* NULL: no backward sweep */,
                                      float* coef_grad /* NULL: no coefficient gradient */,
                                      void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- per-point weights on the residual's squares ---------------------------------------------------------------------
+ * pinn_residual_weighted_loss_grad: pinn_residual_loss_grad with a weight on every point's squared fields.
+ * Let n_w = min(n_terms, n_fields) of the residual: 3, 3, 1, 2 for Navier_Stokes, physics_equation, continuity_ftemp,
+ * continuity_only.  point_w is a device array (w_rows, N), row-major, read-only:
+ *   w_rows == 1     one weight per point, shared by all weighted terms: w_t[n] = point_w[n]
+ *   w_rows == n_w   row t weights term t:                               w_t[n] = point_w[t * N + n]
+ *   any other w_rows, or point_w == NULL: PINN_ERR_INVALID
+ *   term_sums (n_terms)  <- sum_n w_t[n] f_t[n]^2 for t < n_w, f_t being field t exactly as pinn_residual_fields defines
+ *                           it                                                               (overwritten)
+ *                           continuity_only's third term, the count of points with x < threshold, is NEVER weighted: it
+ *                           is a normaliser, not a loss
+ *   grad_flat (P,)       += sum_t term_scale[t] d term_sums[t] / d theta
+ *   fields               NULL, or (n_fields, N): overwritten with the UNWEIGHTED SIGNED fields, the quantity
+ *                           pinn_residual_fields writes.  The caller forms the gradient with respect to a weight from it:
+ *                           d / d w_t[n] = term_scale[t] f_t[n]^2.  There is no further output.
+ * grad_flat == NULL: forward only (term_scale may then be NULL too); with fields given this is loss plus residual map in
+ * one pass.  N = 0 zeroes term_sums and touches nothing else.  The workspace is the call's own
+ * (pinn_query_residual_weighted_workspace), so that AUTO may move between engines.
+ * NO ENTRY VALIDATES THE WEIGHTS' VALUES, as for the coefficients above: they never leave the device.  A negative or
+ * non-finite weight is evaluated as given.  A zero weight removes its point from the sums and the gradient only if the
+ * point's residual is finite: 0 * inf is NaN.  The lanes of a ragged last tile read the weight of the last point of
+ * the row, never past the row's end.
+ * Rules, all decided before any device work; the query follows the same rules:
+ *   desc->k != the residual's directions     PINN_ERR_UNSUPPORTED
+ *   spec.flags bit 0 (corrected stress)      PINN_ERR_UNSUPPORTED, "corrected" in the message
+ *   GENERIC                                  any shape, tanh or LeakyReLU, dropout
+ *   FUSED and FUSED_TILE                     the tile kernel's weighted instances: fp32, tanh, width <= 64, d_in and
+ *                                            d_out <= 16, dropout_p == 0; otherwise PINN_ERR_UNSUPPORTED with the reason
+ *   FUSED_COOP, FUSED_BATCH, WIDE, bf16      PINN_ERR_UNSUPPORTED (no such instances)
+ *   AUTO                                     the tile instances where FUSED is served, else GENERIC
+ * Reproducibility.  term_sums and fields: bit-reproducible from run to run on both engines (per-workgroup sums, fixed-order
+ * double reduction).  A forward-only call returns the very bits of the gradient call's term_sums on the same engine: it
+ * runs on that call's grid.  grad_flat: as for every tile-kernel gradient call (see pinn_residual_coef_loss_grad). */
+int32_t pinn_query_residual_weighted_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes);
+int32_t pinn_residual_weighted_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec,
+                                         const float* term_scale,
+                                         const float* point_w, int32_t w_rows,
+                                         const float* params, const float* X, int64_t N,
+                                         float* term_sums,
+                                         float* fields    /* NULL or (n_fields, N) */,
+                                         float* grad_flat /* NULL: no backward sweep */,
+                                         void* ws, int64_t ws_bytes, void* stream);
 
 /* term_sums[t] = sum over points of (residual field t)^2  (device, n_terms floats, overwritten)
  * Corrected radiation stress (spec.flags bit 0 on physics_equation) — the rule of every loss entry that takes a spec

@@ -127,6 +127,9 @@ _SIGNATURES = {
     "pinn_query_residual_coef_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_residual_coef_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P, _P,
                                                  C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
+    "pinn_query_residual_weighted_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.POINTER(C.c_int64)]),
+    "pinn_residual_weighted_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int32, _P, _P,
+                                                     C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
     "pinn_residual_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P,
                                             C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "pinn_mse_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, _P, C.c_int64, C.c_int32,

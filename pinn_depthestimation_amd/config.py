@@ -62,6 +62,21 @@ class PinnConfig:
         """config.loss.weight_<key>_loss (train.py:94-95); 1 when the old schema omits it."""
         return float(self.loss_weights.get(f"weight_{key}_loss", 1))
 
+    @property
+    def self_adaptive(self) -> Optional[dict]:
+        """loss.self_adaptive: None (absent or false), or {"init", "mask", "per_term"} with the defaults filled in."""
+        return self_adaptive_options(self.raw.get("loss", {}).get("self_adaptive"))
+
+    @property
+    def rad_importance(self) -> bool:
+        """loss.rad_importance: importance weights on the RAD mini-batch."""
+        return bool(self.raw.get("loss", {}).get("rad_importance", False))
+
+    @property
+    def weight_learning_rate(self) -> float:
+        """adam_optimizer.weight_learning_rate: the self-adaptive weights' rate, default the network's."""
+        return float(self.adam.get("weight_learning_rate", self.adam["learning_rate"]))
+
     def default_residual(self) -> str:
         """The reference hard-codes the residual by import (train.py:17, train_newmethod.py:18);
         pick the one whose argument names the config's variables satisfy."""
@@ -72,6 +87,28 @@ class PinnConfig:
         if "eta_mean" in self.residual_outputs:
             return "physics_equation"
         return "continuity_ftemp"
+
+
+SELF_ADAPTIVE_DEFAULTS = {"init": 1.0, "mask": "square", "per_term": True}
+
+
+def self_adaptive_options(value) -> Optional[dict]:
+    """The self-adaptive weights' options from `true` or an object {"init": 1.0, "mask": "square" | "linear",
+    "per_term": true}; None for an absent or false key.  ValueError on an unknown key or mask."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return dict(SELF_ADAPTIVE_DEFAULTS)
+    if not isinstance(value, dict):
+        raise ValueError(f"self_adaptive = {value!r}: use true or an object with the keys {sorted(SELF_ADAPTIVE_DEFAULTS)}")
+    unknown = sorted(set(value) - set(SELF_ADAPTIVE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"self_adaptive: unknown key(s) {unknown}; known: {sorted(SELF_ADAPTIVE_DEFAULTS)}")
+    out = {**SELF_ADAPTIVE_DEFAULTS, **value}
+    if out["mask"] not in ("square", "linear"):
+        raise ValueError(f"self_adaptive.mask = {out['mask']!r}: use 'square' or 'linear'")
+    out["init"], out["per_term"] = float(out["init"]), bool(out["per_term"])
+    return out
 
 
 def load_config(src) -> PinnConfig:

@@ -91,6 +91,10 @@ struct LossReq {
   // pinn_residual_coef_loss_grad only (kind 0, no adam; null everywhere else): the residual's closure coefficients, a device
   // array of n_coef floats, and where their gradient goes (n_coef floats, +=; null = not wanted)
   const float* coef; float* coef_grad; int n_coef;
+  // pinn_residual_weighted_loss_grad only (kind 0, no adam; null everywhere else): the point weights, a device array
+  // (w_rows, N) with row stride w_stride (0: one row for every term, N: a row per weighted term); n_weighted = the
+  // residual's weighted terms; fields_out: null or the (n_fields, N) array of the unweighted signed fields (overwritten)
+  const float* point_w; int64_t w_stride; int n_weighted; float* fields_out;
 };
 
 // generic engine (pinn_generic.hip)
@@ -161,6 +165,13 @@ const char* fused_coef_refusal(const Net& n);
 int64_t fused_coef_workspace_bytes(const Net& n, int64_t N);
 int fused_coef_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
                     int64_t ws_bytes, hipStream_t s);
+
+// pinn_residual_weighted_loss_grad on the tile kernel's weighted instances (fused_kernel.h, EPI_WEIGHTED): the same three
+// (rq.point_w set)
+const char* fused_weighted_refusal(const Net& n);
+int64_t fused_weighted_workspace_bytes(const Net& n, int64_t N);
+int fused_weighted_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
+                        int64_t ws_bytes, hipStream_t s);
 
 // wide MFMA engine, 64 < W <= 256 (pinn_wide.hip)
 bool wide_supports(const Net& n);

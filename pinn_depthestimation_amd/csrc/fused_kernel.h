@@ -55,6 +55,8 @@ struct FusedParams {
                         // fields' array, field-major (NF, N), and dY is null — a member of its own would change the kernel
                         // argument block of EVERY k_fused instance, and with it the register allocation of the
                         // register-starved width-64 forward kernels (measured: AGPRs 8 -> 4, spilled SGPRs 36 -> 39)
+                        // k_fused<..., EPI_WEIGHTED>: Y is the optional array of the unweighted signed fields, (NF, N) as for
+                        // EPI_FIELD, or null; dY is null
   int loss_kind;        // bit 0: PDE residual, bit 1: fidelity MSE (both: one pass, train_newmethod.py:122-159)
   int residual_id;
   int out_col[PINN_MAX_ROLES];   // residual: output column of each role
@@ -65,6 +67,8 @@ struct FusedParams {
   int mse_col[PINN_MAX_ROLES];   // mse: output column of each target column
   const float* T;            // mse: targets (N, n_cols); split mode: (N - n_split, n_cols)
   int64_t n_split;           // < 0: every loss term on every point; >= 0: residual on points < n_split, mse on the rest
+                             // k_fused<..., EPI_WEIGHTED> (no split, no fidelity term): the row stride of the point weights
+                             // instead, 0 (one row for every term) or N (a row per weighted term)
   const float* mse_scale;    // mse: device column scales
   float* wg_sums;            // [grid][MAX_SUMS]
   float* wg_grads;           // [grid][PP]: acc_lds: written once at kernel end; else the workgroups' live global copies
@@ -78,6 +82,7 @@ struct FusedParams {
   const float* gY;                   // k_fused<..., EPI_ADJ>: the caller's output adjoints, gY (N, d_out) and gdY (K1 - 1, N, d_out)
                                      // k_fused<..., EPI_COEF>: the residual's coefficients instead (n_coef floats; gdY null) — a
                                      // member of their own would grow the argument block of every instance (see Y above)
+                                     // k_fused<..., EPI_WEIGHTED>: the point weights instead, (w_rows, N) row-major (gdY null)
   const float* gdY;                  // in the engine's direction order (row c - 1 belongs to dir_col[c - 1]); either may be null
 };
 
@@ -673,8 +678,11 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 // EPI_COEF (pinn_residual_coef_loss_grad): the EPI_NS / EPI_PE epilogue with the residual's closure coefficient read from
 // a device array (coef_epilogue below) and its gradient summed beside the term sums; translation units of its own too
 // (pinn_fused_coef_wXX.hip).
+// EPI_WEIGHTED (pinn_residual_weighted_loss_grad): the residual epilogue of any first-order family with one weight per point
+// and weighted term (weighted_epilogue below), and an optional store of the signed fields; translation units of its own
+// (pinn_fused_wt_wXX.hip).
 constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5, EPI_PEC = 6, EPI_FIELD_PEC = 7,
-              EPI_COEF = 8;
+              EPI_COEF = 8, EPI_WEIGHTED = 9;
 constexpr int COEF_SUM = 3;   // EPI_COEF: the term slot of [0, MSE_SUM0) that carries gc[0] (PINN_NS_TERMS = PINN_PE_TERMS = 3 leave it free)
 
 // The mirror of the generic epilogue's Y / dY store: lane (p, q), register r of G[c][0] is output o = 4q + r of point pt;
@@ -769,6 +777,66 @@ __device__ __forceinline__ void coef_epilogue(const FusedParams& P, const f4 (&o
   for (int c = 0; c < K1; ++c) G[c][0] = f4{0.f, 0.f, 0.f, 0.f};
   if constexpr (K1 == 4) residual_tile_coef<ResNavierStokesCoef, K1, GRAD>(P, out, G, sums, sm, tb, valid, p, q);
   else residual_tile_coef<ResPhysicsEquationCoef, K1, GRAD>(P, out, G, sums, sm, tb, valid, p, q);
+}
+
+// EPI_WEIGHTED: residual_tile with a weight on every point's squares.  The weights are P.gY, (w_rows, N) row-major with row
+// stride P.n_split (0: one row serves every term; N: row t weights term t), the optional fields array is P.Y (see FusedParams:
+// it must not grow).  Term t < NW = min(terms, fields) takes scale[t] * w_t into the adjoint and w_t * sq[t] into its sum;
+// terms from NW on (continuity_only's point count) go in unweighted.  The weight is read at the CLAMPED point index ptc, so
+// the lanes of a ragged last tile stay inside their row; their sums and adjoints are dropped by `valid` as everywhere.
+template <class RES, int K1, bool GRAD>
+__device__ __forceinline__ void residual_tile_weighted(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
+                                                       float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
+                                                       float* __restrict__ tb, int64_t pt, int64_t ptc, bool valid,
+                                                       bool masked, int p, int q) {
+  constexpr int NR = RES::NR, ND = RES::ND, NT = RES::NT, NF = RES::NF, NW = NT < NF ? NT : NF;
+  float v[1 + ND][NR], g[1 + ND][NR], sq[NT], sc[NT], w[NW];
+#pragma unroll
+  for (int c = 0; c <= ND; ++c) {
+    const f4 tile = (c == 0) ? out[0][0] : pick_q<K1>(out, P.q_of[c - 1]);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) v[c][r] = gather_out(tile, P.out_col[r], p);
+  }
+#pragma unroll
+  for (int t = 0; t < NW; ++t) w[t] = P.gY[(int64_t)t * P.n_split + ptc];
+  // the weighted sums and the field store take the fields formed apart from the adjoint's arithmetic (residuals.h,
+  // isolated_fields): the forward-only and the gradient instance round them alike
+  float f[NF];
+  if constexpr (std::is_same<RES, ResContinuity>::value)
+    isolated_fields<RES>(v, f, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
+  else
+    isolated_fields<RES>(v, f);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) sc[t] = GRAD ? (t < NW ? P.scale[t] * w[t] : P.scale[t]) : 0.f;
+  if constexpr (std::is_same<RES, ResContinuity>::value)
+    RES::template eval<GRAD>(v, sc, g, sq, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
+  else
+    RES::template eval<GRAD>(v, sc, g, sq);
+  if (valid && q == 0) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sums[t] = t < NW ? __fmaf_rn(w[t], f[t] * f[t], sums[t]) : sums[t] + sq[t];
+    if (P.Y != nullptr) {   // the signed fields, as field_tile stores them
+#pragma unroll
+      for (int t = 0; t < NF; ++t) P.Y[(int64_t)t * P.N + pt] = f[t];
+    }
+  }
+  if constexpr (GRAD) scatter_adjoint<K1, 1 + ND, NR>(tb, g, sm, G, valid, p, q);
+}
+// K1 decides the family as for field_epilogue.  Residual loss only: no Y / dY stores, no fidelity columns, no split.
+template <int K1, bool GRAD>
+__device__ __forceinline__ void weighted_epilogue(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
+                                                  float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
+                                                  float* __restrict__ tb, int64_t pt, int64_t ptc, bool valid, int p, int q) {
+  static_assert(K1 == 3 || K1 == 4, "EPI_WEIGHTED: K1 = 1 + the residual's directions");
+#pragma unroll
+  for (int c = 0; c < K1; ++c) G[c][0] = f4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (K1 == 4) residual_tile_weighted<ResNavierStokes, K1, GRAD>(P, out, G, sums, sm, tb, pt, ptc, valid, false, p, q);
+  else if (P.residual_id == PINN_RES_PHYSICS_EQUATION)
+    residual_tile_weighted<ResPhysicsEquation, K1, GRAD>(P, out, G, sums, sm, tb, pt, ptc, valid, false, p, q);
+  else {
+    const bool masked = P.residual_id == PINN_RES_CONTINUITY_ONLY && P.X[ptc * P.d_in + P.xcol] < P.thr;
+    residual_tile_weighted<ResContinuity, K1, GRAD>(P, out, G, sums, sm, tb, pt, ptc, valid, masked, p, q);
+  }
 }
 
 // EPI_PEC: loss_epilogue_impl's generic part (below) with ONE residual family and without the output stores — the split
@@ -954,6 +1022,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
   static_assert(EPI != EPI_FIELD_PEC || (!GRAD && !LDSACC && KRO == 0 && !DROP && K1 == 3), "field instances: forward only, natural unit order, no dropout");
   static_assert(EPI != EPI_PEC || (KRO == 0 && !DROP && K1 == 3 && ACT == PINN_ACT_TANH), "corrected-residual instances: tanh, k = 2, natural unit order, no dropout");
   static_assert(EPI != EPI_COEF || (KRO == 0 && !DROP && (K1 == 3 || K1 == 4) && ACT == PINN_ACT_TANH), "coefficient instances: tanh, k = 2 or 3, natural unit order, no dropout");
+  static_assert(EPI != EPI_WEIGHTED || (KRO == 0 && !DROP && (K1 == 3 || K1 == 4) && ACT == PINN_ACT_TANH), "weighted instances: tanh, k = 2 or 3, natural unit order, no dropout");
 #include "fused_tile_body.inc"
 }
 
@@ -991,6 +1060,9 @@ int launch_fused_field_pec(const FusedParams& P, int grid, size_t lds_bytes, hip
 // coefficient instances (EPI_COEF; K1 = 3 or 4, tanh): pinn_fused_coef.inc, one translation unit per WP (pinn_fused_coef_wXX.hip)
 template <int WP>
 int launch_fused_coef(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+// point-weighted instances (EPI_WEIGHTED; K1 = 3 or 4, tanh): pinn_fused_wt.inc, one translation unit per WP (pinn_fused_wt_wXX.hip)
+template <int WP>
+int launch_fused_wt(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 // ensemble instances (k_fused_ens: grid (gx, M), gradient pass, tanh, K1 = 3 or 4): pinn_fused_ens.inc, one translation unit per WP
 // (pinn_fused_ens_wXX.hip)
 template <int WP>

@@ -133,6 +133,7 @@
     if constexpr (EPI == EPI_FIELD) field_epilogue<K1>(P, out, pt, ptc, valid, p, q);
     else if constexpr (EPI == EPI_FIELD_PEC) field_tile<ResPhysicsEquationCorrected, K1>(P, out, pt, valid, false, p, q);
     else if constexpr (EPI == EPI_COEF) coef_epilogue<K1, GRAD>(P, out, G, sums, sm, tb, valid, p, q);
+    else if constexpr (EPI == EPI_WEIGHTED) weighted_epilogue<K1, GRAD>(P, out, G, sums, sm, tb, pt, ptc, valid, p, q);
     else if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64 || EPI == EPI_PEC), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
 
     PINN_STAMP(2);

@@ -1119,4 +1119,70 @@ int32_t pinn_residual_coef_loss_grad(const pinn_desc* desc, const pinn_residual_
                                 : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
 }
 
+// ---- per-point weights on the residual's squares -------------------------------------------------------------------------
+// validation shared by the query and the call (no HIP call before it has passed), in the order of the header's table;
+// *engine <- PINN_ENGINE_FUSED (the tile kernel's weighted instances) or PINN_ENGINE_GENERIC
+static int weighted_plan(const pinn_desc* desc, const pinn_residual_spec* spec, Net* n, pinn_residual_spec* nspec, int* engine) {
+  const char* who = "pinn_residual_weighted_loss_grad";
+  int rc = make_net(desc, n); if (rc) return rc;
+  rc = check_spec(*n, spec, nspec); if (rc) return rc;
+  if (n->k != residual_dirs(spec->residual_id)) {
+    set_error("%s: the network carries k = %d tangent directions, residual %d has %d (k must equal the residual's number of "
+              "directions)", who, n->k, spec->residual_id, residual_dirs(spec->residual_id));
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (spec->residual_id == PINN_RES_PHYSICS_EQUATION && (spec->flags & 1)) {
+    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no point-weighted form", who);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (n->prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
+  const int asked = asked_engine(desc);
+  if (asked == PINN_ENGINE_WIDE) { set_error("%s does not run on the wide engine: use engine AUTO, FUSED or GENERIC", who); return PINN_ERR_UNSUPPORTED; }
+  const char* why = fused_weighted_refusal(*n);
+  if (asked == PINN_ENGINE_FUSED && why) {
+    set_error("%s on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); engine AUTO or "
+              "GENERIC runs this request on the generic engine", who, why, n->W, n->d_in, n->d_out, n->k, n->act, (double)n->drop_p);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  *engine = (asked != PINN_ENGINE_GENERIC && !why) ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
+  return PINN_OK;
+}
+
+int32_t pinn_query_residual_weighted_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
+  Net n; pinn_residual_spec nspec; int e;
+  int rc = weighted_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
+  if (!bytes || N < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
+  const int64_t b = e == PINN_ENGINE_FUSED ? fused_weighted_workspace_bytes(n, N) : generic_workspace_bytes(n, N);
+  if (b < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
+  *bytes = b;
+  return PINN_OK;
+}
+
+int32_t pinn_residual_weighted_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
+                                         const float* point_w, int32_t w_rows, const float* params, const float* X,
+                                         int64_t N, float* term_sums, float* fields, float* grad_flat, void* ws,
+                                         int64_t ws_bytes, void* stream) {
+  Net n; pinn_residual_spec nspec; int e;
+  int rc = weighted_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
+  const int n_terms = residual_terms(spec->residual_id), n_fields = residual_n_fields(spec->residual_id);
+  const int n_w = n_terms < n_fields ? n_terms : n_fields;
+  if (!point_w) { set_error("pinn_residual_weighted_loss_grad: point_w is NULL"); return PINN_ERR_INVALID; }
+  if (w_rows != 1 && w_rows != n_w) {
+    set_error("pinn_residual_weighted_loss_grad: w_rows = %d, residual %d takes 1 row or %d (one per weighted term)", w_rows,
+              spec->residual_id, n_w);
+    return PINN_ERR_INVALID;
+  }
+  if (!params || (!X && N > 0) || N < 0 || !term_sums || (grad_flat && !term_scale)) {
+    set_error("NULL pointer argument"); return PINN_ERR_INVALID;
+  }
+  LossReq rq; memset(&rq, 0, sizeof(rq));
+  rq.kind = 0; rq.n_split = -1; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums;
+  rq.grad = grad_flat; rq.n_terms = n_terms;
+  rq.point_w = point_w; rq.w_stride = w_rows == 1 ? 0 : N; rq.n_weighted = n_w; rq.fields_out = fields;
+  const hipStream_t s = (hipStream_t)stream;
+  if (N == 0) { (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), s); return PINN_OK; }
+  return e == PINN_ENGINE_FUSED ? fused_weighted_loss(n, rq, params, X, N, ws, ws_bytes, s)
+                                : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
+}
+
 }  // extern "C"

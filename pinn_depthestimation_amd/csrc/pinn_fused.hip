@@ -24,6 +24,9 @@ bool is_pec(const LossReq* rq) { return rq && rq->kind != 1 && rq->spec.residual
 // a residual request with runtime closure coefficients (pinn_residual_coef_loss_grad): its own instances of the tile kernel
 // (EPI_COEF), never the batch or the cooperative kernel, natural unit order
 bool is_coef(const LossReq* rq) { return rq && rq->coef != nullptr; }
+// a residual request with point weights (pinn_residual_weighted_loss_grad): its own instances of the tile kernel too
+// (EPI_WEIGHTED), with the coefficient requests' kernel choice and grid rule
+bool is_weighted(const LossReq* rq) { return rq && rq->point_w != nullptr; }
 
 int padded_width(int W) { return W <= 16 ? 16 : (W <= 32 ? 32 : 64); }
 
@@ -422,8 +425,13 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   P.lds_acc_floats = P.acc_lds ? g.PP : 0;
   if (rq) set_loss(P, n, *rq);
   if (adj) { P.gY = adj->gY; P.gdY = adj->gdY; }
-  const bool coefq = is_coef(rq);
+  const bool wtq = is_weighted(rq);
+  const bool coefq = is_coef(rq) || wtq;   // (everything below that holds for a coefficient request holds for a weighted one)
   if (coefq) P.gY = rq->coef;   // (fused_kernel.h, FusedParams: the coefficient instances' array)
+  if (wtq) {   // (fused_kernel.h, FusedParams: the weighted instances' weights, their row stride and the optional fields array)
+    P.gY = rq->point_w; P.n_split = rq->w_stride;
+    P.Y = rq->fields_out; P.dY = nullptr;
+  }
   if (fld) {   // the residual's roles as a residual loss sets them; nothing else of a loss request
     P.Y = fld->fields; P.dY = nullptr;   // (fused_kernel.h, FusedParams: the field instances' output array)
     set_residual_roles(P, n, fld->spec);
@@ -534,6 +542,11 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     // kernel, one weight fetch per 64 points (pinn_fused_plain.hip)
     rc = launch_fused_plain(g.WP, P, cu_count(), s);
   }
+  else if (wtq) switch (g.WP) {   // EPI_WEIGHTED instances: pinn_fused_wt_wXX.hip
+    case 16: rc = launch_fused_wt<16>(n.K1, grad, P, grid, lds, s); break;
+    case 32: rc = launch_fused_wt<32>(n.K1, grad, P, grid, lds, s); break;
+    default: rc = launch_fused_wt<64>(n.K1, grad, P, grid, lds, s); break;
+  }
   else if (coefq) switch (g.WP) {   // EPI_COEF instances: pinn_fused_coef_wXX.hip
     case 16: rc = launch_fused_coef<16>(n.K1, grad, P, grid, lds, s); break;
     case 32: rc = launch_fused_coef<32>(n.K1, grad, P, grid, lds, s); break;
@@ -569,7 +582,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   if (rq) {
     if (P.loss_kind & 1)
       reduce_sums(P.wg_sums, grid, MAX_SUMS, 0, rq->n_terms, rq->sums, s);
-    if (coefq && grad && rq->coef_grad)   // the coefficient gradient rode in the free term slot (fused_kernel.h, COEF_SUM)
+    if (coefq && !wtq && grad && rq->coef_grad)   // the coefficient gradient rode in the free term slot (fused_kernel.h, COEF_SUM)
       reduce_sums_add(P.wg_sums, grid, MAX_SUMS, COEF_SUM, rq->n_coef, rq->coef_grad, s);
     if (P.loss_kind & 2)
       reduce_sums(P.wg_sums, grid, MAX_SUMS, MSE_SUM0, rq->n_cols, rq->mse_sums, s);
@@ -675,6 +688,30 @@ int64_t fused_coef_workspace_bytes(const Net& n, int64_t N) {
 int fused_coef_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
                     int64_t ws_bytes, hipStream_t s) {
   if (const char* why = fused_coef_refusal(n)) { set_error("fused engine, coefficients: %s", why); return PINN_ERR_UNSUPPORTED; }
+  return run(n, rq.grad != nullptr, &rq, params, X, N, nullptr, nullptr, ws, ws_bytes, s);
+}
+
+// Point weights (EPI_WEIGHTED instances): the coefficient instances' rules — the tile kernel only, fp32, tanh, k = 2 or 3, no
+// dropout — and their workspace.
+const char* fused_weighted_refusal(const Net& n) {
+  if (n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH)
+    return "the weighted instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
+  if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no weighted kernel";
+  if (n.W > 64) return "hidden width above 64 has no weighted kernel on the fused engine";
+  if (n.act != PINN_ACT_TANH) return "LeakyReLU has no weighted kernel on the fused engine";
+  if (n.drop_p > 0.f) return "dropout_p > 0 has no weighted kernel on the fused engine";
+  if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
+  if (n.d_in > 16 || n.d_out > 16) return "d_in or d_out above 16";
+  if (n.L + 1 > MAX_LOCKS) return "network too deep for the per-layer locks";
+  return nullptr;
+}
+int64_t fused_weighted_workspace_bytes(const Net& n, int64_t N) {
+  if (fused_weighted_refusal(n)) return -1;
+  return ws_layout(n, geo_of(n), N > 0 ? N : 1).total;
+}
+int fused_weighted_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
+                        int64_t ws_bytes, hipStream_t s) {
+  if (const char* why = fused_weighted_refusal(n)) { set_error("fused engine, point weights: %s", why); return PINN_ERR_UNSUPPORTED; }
   return run(n, rq.grad != nullptr, &rq, params, X, N, nullptr, nullptr, ws, ws_bytes, s);
 }
 

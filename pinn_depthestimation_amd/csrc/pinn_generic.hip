@@ -264,6 +264,60 @@ __global__ void k_residual(const float* __restrict__ yj, int d_out, int64_t N, R
   block_reduce_store<NT>(sq, partial);
 }
 
+// k_residual with point weights (pinn_residual_weighted_loss_grad): w is (w_rows, N) row-major with row stride w_stride
+// (0: one row for every term, N: row t weights term t).  Term t < NW = min(terms, fields) takes scale[t] * w_t into the
+// adjoint and w_t * sq[t] into its sum; continuity_only's point count goes in unweighted.  fields, if not null, takes the
+// unweighted signed fields, field-major (NF, N).
+template <class RES, bool GRAD>
+__global__ void k_residual_weighted(const float* __restrict__ yj, int d_out, int64_t N, RoleMap rm,
+                                    const float* __restrict__ scale, const float* __restrict__ w, int64_t w_stride,
+                                    const float* __restrict__ X, int d_in, int xcol, int anchor_on, float thr, float anchor,
+                                    float* __restrict__ G, float* __restrict__ partial, float* __restrict__ fields) {
+  constexpr int NR = RES::NR, ND = RES::ND, NT = RES::NT, NF = RES::NF, NW = NT < NF ? NT : NF;
+  int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float sq[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) sq[t] = 0.f;
+  if (n < N) {
+    float v[1 + ND][NR], g[1 + ND][NR], st[NT], wt[NW], f[NF];
+#pragma unroll
+    for (int c = 0; c <= ND; ++c) {
+      const int q = (c == 0) ? 0 : rm.q_of[c - 1];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) v[c][r] = yj[((int64_t)q * d_out + rm.out_col[r]) * N + n];
+    }
+#pragma unroll
+    for (int t = 0; t < NW; ++t) wt[t] = w[(int64_t)t * w_stride + n];
+    float sc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sc[t] = GRAD ? (t < NW ? scale[t] * wt[t] : scale[t]) : 0.f;
+    // (the fields of the sums and of the store: formed apart from the adjoint's arithmetic, residuals.h isolated_fields)
+    if constexpr (std::is_same<RES, ResContinuity>::value) {
+      const bool masked = anchor_on ? (X[n * d_in + xcol] < thr) : false;
+      isolated_fields<RES>(v, f, anchor_on != 0, masked, anchor);
+      RES::template eval<GRAD>(v, sc, g, st, anchor_on != 0, masked, anchor);
+    } else {
+      isolated_fields<RES>(v, f);
+      RES::template eval<GRAD>(v, sc, g, st);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sq[t] = t < NW ? wt[t] * (f[t] * f[t]) : st[t];
+    if (fields) {
+#pragma unroll
+      for (int t = 0; t < NF; ++t) fields[(int64_t)t * N + n] = f[t];
+    }
+    if (GRAD) {
+#pragma unroll
+      for (int c = 0; c <= ND; ++c) {
+        const int q = (c == 0) ? 0 : rm.q_of[c - 1];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) G[((int64_t)q * d_out + rm.out_col[r]) * N + n] = g[c][r];
+      }
+    }
+  }
+  block_reduce_store<NT>(sq, partial);
+}
+
 // k_residual for a residual with runtime closure coefficients (residuals.h: ResNavierStokesCoef, ResPhysicsEquationCoef):
 // coef is the device array, and the partial sums carry NC more columns, the point's coefficient gradient gc
 template <class RES, bool GRAD>
@@ -437,7 +491,32 @@ int run_loss(const Net& n, const LossReq& rq, const float* params, const float* 
   if (want_grad) (void)hipMemsetAsync(G, 0, (size_t)K1 * n.d_out * N * 4, s);
   const int64_t n_res = (rq.kind == 2 && rq.n_split >= 0) ? rq.n_split : N;
   const int64_t n0 = (rq.kind == 2 && rq.n_split >= 0) ? rq.n_split : 0;
-  if (rq.coef) {   // pinn_residual_coef_loss_grad: a residual request (kind 0) with runtime coefficients
+  if (rq.point_w) {   // pinn_residual_weighted_loss_grad: a residual request (kind 0) with point weights
+    RoleMap rm;
+    for (int r = 0; r < PINN_MAX_ROLES; ++r) rm.out_col[r] = rq.spec.out_col[r];
+    for (int d = 0; d < PINN_MAX_DIRS; ++d) rm.q_of[d] = 1 + rq.spec.dir_of[d];
+    const int id = rq.spec.residual_id;
+    int stride = 0;
+#define LAUNCH_WT(RES, ANCH, XCOL)                                                                                  \
+  do {                                                                                                              \
+    stride = RES::NT;                                                                                               \
+    if (want_grad)                                                                                                  \
+      hipLaunchKernelGGL((k_residual_weighted<RES, true>), dim3(grid), dim3(TPB), 0, s, out, n.d_out, N, rm, rq.scale, \
+                         rq.point_w, rq.w_stride, X, n.d_in, XCOL, ANCH, rq.spec.param[0], rq.spec.param[1], G,    \
+                         partial, rq.fields_out);                                                                   \
+    else                                                                                                            \
+      hipLaunchKernelGGL((k_residual_weighted<RES, false>), dim3(grid), dim3(TPB), 0, s, out, n.d_out, N, rm, rq.scale, \
+                         rq.point_w, rq.w_stride, X, n.d_in, XCOL, ANCH, rq.spec.param[0], rq.spec.param[1], G,    \
+                         partial, rq.fields_out);                                                                   \
+  } while (0)
+    if (id == PINN_RES_NAVIER_STOKES) LAUNCH_WT(ResNavierStokes, 0, 0);
+    else if (id == PINN_RES_PHYSICS_EQUATION) LAUNCH_WT(ResPhysicsEquation, 0, 0);
+    else if (id == PINN_RES_CONTINUITY_FTEMP) LAUNCH_WT(ResContinuity, 0, 0);
+    else if (id == PINN_RES_CONTINUITY_ONLY) LAUNCH_WT(ResContinuity, 1, n.dir_col[rq.spec.dir_of[0]]);
+    else { set_error("residual %d has no point-weighted form", id); return PINN_ERR_UNSUPPORTED; }
+#undef LAUNCH_WT
+    reduce_sums(partial, lo.nblocks, stride, 0, rq.n_terms, rq.sums, s);
+  } else if (rq.coef) {   // pinn_residual_coef_loss_grad: a residual request (kind 0) with runtime coefficients
     RoleMap rm;
     for (int r = 0; r < PINN_MAX_ROLES; ++r) rm.out_col[r] = rq.spec.out_col[r];
     for (int d = 0; d < PINN_MAX_DIRS; ++d) rm.q_of[d] = 1 + rq.spec.dir_of[d];

@@ -597,4 +597,29 @@ __device__ inline f2 tanh_f32x2(f2 x) {
             fabsf(x[1]) < 0.625f ? small[1] : copysignf(big[1], x[1])};
 }
 
+// ---- point weights (pinn_residual_weighted_loss_grad) ---------------------------------------------------------------------
+// The value of x behind a barrier the optimiser cannot see through.  The weighted kernels form the fields that go into the
+// sums (and into the optional field store) from opaque copies of the jet and take them out through it again: that piece of
+// arithmetic then has no operand in common with the adjoint's, so it is contracted into fused multiply-adds the same way in
+// the forward-only and in the gradient instance, and a forward-only call returns the gradient call's term sums bit for bit.
+// (Measured without it: eval<false> and eval<true> of ResNavierStokes rounded fc differently in the generic kernel.)
+__device__ __forceinline__ float opaque(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(x));
+#endif
+  return x;
+}
+// the signed fields f[NF] of one point from its jet v, through the barrier on both sides
+template <class RES, class... A>
+__device__ __forceinline__ void isolated_fields(const float (&v)[1 + RES::ND][RES::NR], float (&f)[RES::NF], A... a) {
+  float vb[1 + RES::ND][RES::NR];
+#pragma unroll
+  for (int c = 0; c <= RES::ND; ++c)
+#pragma unroll
+    for (int r = 0; r < RES::NR; ++r) vb[c][r] = opaque(v[c][r]);
+  RES::fields(vb, f, a...);
+#pragma unroll
+  for (int t = 0; t < RES::NF; ++t) f[t] = opaque(f[t]);
+}
+
 }  // namespace pinn

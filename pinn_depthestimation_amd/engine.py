@@ -115,6 +115,12 @@ class ResidualSpec:
         return RES_FIELDS[self.residual_id]
 
     @property
+    def n_weighted_terms(self) -> int:
+        """The terms residual_weighted_loss_grad weights, min(n_terms, n_fields): 3, 3, 1, 2 (continuity_only's third term,
+        the count of points below the threshold, is a normaliser and never weighted)."""
+        return min(self.n_terms, self.n_fields)
+
+    @property
     def coef_names(self) -> Tuple[str, ...]:
         """The residual's closure coefficients, in the order of residual_coef_loss_grad's coef array: ("gamma_b",) for
         Navier_Stokes, ("Cd",) for the plain physics_equation, () for everything else (pinn_residual_coef_count)."""
@@ -456,6 +462,62 @@ class Engine:
                   C.byref(spec.c_struct()), _ptr(coef), _ptr(term_scale) if grad is not None else None, _ptr(params), _ptr(X), N,
                   _ptr(sums), _ptr(grad), _ptr(coef_grad), _ptr(ws), ws.numel())
         return sums
+
+    def residual_weighted_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
+        """Workspace of residual_weighted_loss_grad (pinn_query_residual_weighted_workspace), cached apart from the others."""
+        spec.first_order("residual_weighted_workspace")
+        e = self.desc.engine if engine is None else engine
+        key = ("weighted", e, spec.residual_id, spec.corrected, N)
+        need = self._ws_need.get(key)
+        if need is None:
+            c_need = C.c_int64()
+            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
+                check(self.lib.pinn_query_residual_weighted_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
+                      "pinn_query_residual_weighted_workspace")
+            need = self._ws_need[key] = c_need.value
+        ws = self._ws.get(("weighted", e))
+        if ws is None or ws.numel() < need:
+            self._ws[("weighted", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def residual_weighted_loss_grad(self, spec: ResidualSpec, weights: torch.Tensor, scale: Optional[torch.Tensor], theta, X,
+                                    grad: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None, fields=None,
+                                    engine=None):
+        """residual_loss_grad with a weight on every point's squared fields (pinn_residual_weighted_loss_grad):
+        term_sums[t] = sum_n w_t[n] f_t[n]^2 for the spec.n_weighted_terms first terms.  `weights` is (N,) — one weight per
+        point for every term — or (w_rows, N) with w_rows 1 or spec.n_weighted_terms, contiguous fp32 on the device; its
+        VALUES are not checked.  With `grad`, grad += sum_t scale[t] d term_sums[t] / d theta; grad=None: forward only
+        (scale may then be None).  fields: None, a (n_fields, N) tensor to overwrite with the unweighted signed fields, or
+        True to allocate one.  Returns term_sums, or (term_sums, fields) when fields were asked for."""
+        spec.first_order("residual_weighted_loss_grad")
+        N = X.shape[0]
+        self._chk(theta, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        if weights is None:
+            raise PinnError("residual_weighted_loss_grad: weights is None (use residual_loss_grad for the unweighted sums)")
+        if weights.dim() not in (1, 2) or weights.shape[-1] != N:
+            raise PinnError(f"residual_weighted_loss_grad: weights must be (N,) or (w_rows, N) with N = {N}, got {tuple(weights.shape)}")
+        w_rows = 1 if weights.dim() == 1 else int(weights.shape[0])
+        self._chk(weights, "weights", tuple(weights.shape))
+        if grad is not None:
+            self._chk(grad, "grad", (self.n_params,)); self._chk(scale, "term_scale", (spec.n_terms,))
+        if sums is None:
+            sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
+        else:
+            self._chk(sums, "sums", (spec.n_terms,))
+        if fields is True:
+            fields = torch.empty(spec.n_fields, N, dtype=torch.float32, device=X.device)
+        elif fields is not None and fields is not False:
+            self._chk(fields, "fields", (spec.n_fields, N))
+        else:
+            fields = None
+        ws = self.residual_weighted_workspace(spec, N, engine)
+        # (an empty tensor has no address, and a NULL point_w is refused whatever N: at N = 0, where nothing is read, the sums'
+        # address stands in)
+        wp = _ptr(weights) if N > 0 else _ptr(sums)
+        self._run("pinn_residual_weighted_loss_grad", self.lib.pinn_residual_weighted_loss_grad, C.byref(self._d(engine)),
+                  C.byref(spec.c_struct()), _ptr(scale) if grad is not None else None, wp, w_rows, _ptr(theta), _ptr(X), N,
+                  _ptr(sums), _ptr(fields), _ptr(grad), _ptr(ws), ws.numel())
+        return sums if fields is None else (sums, fields)
 
     def residual2_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual2_loss_grad (pinn_query_residual2_workspace), cached apart from the others."""

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import PinnError
-from .config import PinnConfig, load_config
+from .config import PinnConfig, load_config, self_adaptive_options
 from .dnn import DNN
 from .engine import ACTIVATION_OF_INIT, RESIDUAL_ROLES, Engine, NetDesc, ResidualSpec
 from .lbfgs import DeviceLBFGS, FlatLBFGS
@@ -53,6 +53,62 @@ def rad_score(fields: torch.Tensor, k: float, c: float) -> torch.Tensor:
     ek = eps.pow(k)
     m = ek.mean()
     return torch.where(m > 0, ek / m, torch.zeros_like(ek)) + c
+
+
+def rad_importance_weights(score: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """Importance weights of a mini-batch drawn at `idx` with probability proportional to `score` (rad_indices): one row
+    w_b = mean(score) / score[idx_b], formed in float64 and cast to float32 once.  With p_n = score_n / sum(score) the batch
+    mean of w f^2 is then an unbiased estimate of the pool mean of f^2: sum_n p_n w_n f_n^2 = mean(f^2).  Only drawn points
+    are divided by, and a zero-score point is never drawn."""
+    s64 = score.to(torch.float64)
+    return (s64.mean() / s64.index_select(0, idx)).to(torch.float32).reshape(1, -1).contiguous()
+
+
+def sa_weights(lam: torch.Tensor, mask: str) -> torch.Tensor:
+    """The self-adaptive weights w = m(lambda): lambda^2 ("square") or lambda ("linear")."""
+    return lam * lam if mask == "square" else lam.clone()
+
+
+def sa_weight_grad(lam: torch.Tensor, fields: torch.Tensor, term_scale: torch.Tensor, mask: str) -> torch.Tensor:
+    """The gradient Adam DESCENDS along so that lambda ASCENDS the weighted residual loss sum_t s_t sum_n m(lambda_t[n]) f_t[n]^2:
+    -s_t m'(lambda) f^2, the shape of lambda.  lam is (rows, N): rows == 1 shares one multiplier among the weighted terms
+    (its gradient sums over them), otherwise row t belongs to term t.  fields: the pass's unweighted signed fields
+    (n_fields, N), of which the first n_w = min(len(term_scale), n_fields) are weighted terms."""
+    n_w = min(int(term_scale.numel()), int(fields.shape[0]))
+    sf = term_scale[:n_w].reshape(-1, 1) * fields[:n_w] * fields[:n_w]          # s_t f_t^2, (n_w, N)
+    if lam.shape[0] == 1:
+        sf = sf.sum(0, keepdim=True)
+    elif lam.shape[0] != n_w:
+        raise PinnError(f"sa_weight_grad: lambda has {lam.shape[0]} rows, the residual {n_w} weighted terms")
+    return -(2.0 * lam * sf if mask == "square" else sf)
+
+
+def weighted_refusal(residual_weights=False, self_adaptive=False, rad_importance=False, reducer_active=False, eddy_viscosity=0.0,
+                     coefficients=False, corrected=False, lbfgs_impl="flat", custom_evaluator=False, residual_batch=None,
+                     resample="uniform"):
+    """Why trainer.PINN cannot run this configuration with point weights on the residual — fixed residual_weights, self_adaptive
+    or rad_importance (None: it can, or none is asked for).  Pure host logic, evaluated before anything touches a device."""
+    if not (residual_weights or self_adaptive or rad_importance):
+        return None
+    if reducer_active:
+        return "point weights on the residual do not run under data parallelism (the weights are not sharded with the points)"
+    if eddy_viscosity:
+        return "point weights on the residual do not run with eddy_viscosity != 0 (the second-order residual has no weighted form)"
+    if coefficients:
+        return "point weights on the residual do not run with runtime closure coefficients (the coefficient kernels have no weights)"
+    if corrected:
+        return "point weights on the residual do not run with the corrected radiation stress (the corrected kernels have no weights)"
+    if lbfgs_impl == "device":
+        return "point weights on the residual do not run with lbfgs_impl=\"device\" (the device loop enqueues the unweighted loss entries); use lbfgs_impl=\"flat\""
+    if custom_evaluator:
+        return "point weights on the residual need the library's own evaluator, not a custom one"
+    if rad_importance and resample != "rad":
+        return "rad_importance re-weights the RAD mini-batch: it needs resample='rad'"
+    if self_adaptive and (residual_batch is not None or resample == "rad"):
+        return "self_adaptive does not run with residual_batch or resample='rad' (a multiplier belongs to a point of a fixed set)"
+    if self_adaptive and residual_weights:
+        return "self_adaptive and residual_weights are two sources of the same weights: give one"
+    return None
 
 
 def device_lbfgs_refusal(reducer_active, residual_batch, eddy_viscosity, custom_evaluator, line_search_fn, dropout_rate=0.0,
@@ -133,6 +189,30 @@ class HipEvaluator:
     # them from, and where their gradient goes (None: values only — frozen, or nothing trainable); set by the trainer
     coef = None
     coef_grad = None   # fidelity points ride through the jet kernel (4x their own work): only when few
+    # point weights on the residual (PINN(residual_weights=..., self_adaptive=..., rad_importance=...)): the device tensor
+    # (w_rows, N) matching the collocation points of the call, and where the pass's unweighted signed fields go (None: not
+    # wanted); set by the trainer
+    point_w = None
+    fields_out = None
+
+    def _call_weighted(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
+        """The residual with point weights (self.point_w): Engine.residual_weighted_loss_grad on the collocation points, the
+        fidelity term a separate mse_loss_grad, as _call_coef.  With dropout the engine is eng_drop's (AUTO: generic)."""
+        drop = self.eng_drop is not None and self.training
+        e = self.eng_drop if drop else self.eng
+        if Xf is not None and Xf.shape[0] > 0:
+            if drop:
+                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
+        else:
+            fid_sums.zero_()
+        if Xr is not None and Xr.shape[0] > 0:
+            if drop:
+                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            e.residual_weighted_loss_grad(self.spec, self.point_w, res_scale, theta, Xr, grad, sums=res_sums,
+                                          fields=self.fields_out)
+        else:
+            res_sums.zero_()
 
     def _call_nu(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
         """The residual with the lateral-mixing term (spec.nu != 0): Engine.residual2_loss_grad on the collocation points,
@@ -174,6 +254,8 @@ class HipEvaluator:
             res_sums.zero_()
 
     def __call__(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
+        if self.point_w is not None:
+            return self._call_weighted(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
         if self.coef is not None:
             return self._call_coef(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
         if self.spec.nu != 0:
@@ -231,6 +313,8 @@ class HipEvaluator:
             return False
         if self.coef is not None:     # the folded iteration runs the entries that carry the constants: the classic path
             return False
+        if self.point_w is not None:  # ... and the unweighted ones
+            return False
         has_fid = Xf is not None and Xf.shape[0] > 0
         if not has_fid:
             if fid_sums.numel():       # (a configuration with fidelity outputs but no fidelity points: classic path)
@@ -287,8 +371,21 @@ class PINN:
                  log_flush_every: int = 100, lbfgs_impl: str = "flat", precision: int = 0, fold_adam: bool = True,
                  resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0,
                  corrected: bool = False, eddy_viscosity: float = 0.0, coefficients: Optional[dict] = None,
-                 trainable_coefficients: Sequence[str] = ()):
-        """coefficients (or the config key loss.coefficients), e.g. {"Cd": 0.01}: values of the residual's closure coefficients
+                 trainable_coefficients: Sequence[str] = (), residual_weights=None, self_adaptive=None,
+                 rad_importance: Optional[bool] = None):
+        """residual_weights: fixed weights on the collocation points' squared residuals, (N_res,) or (n_w, N_res) with
+        n_w = ResidualSpec.n_weighted_terms — a mask, a confidence map; set_residual_weights changes them later.  The
+        normaliser stays the point count (res_scale = weight / N), not the sum of the weights.
+        self_adaptive (or the config key loss.self_adaptive): True, or {"init": 1.0, "mask": "square" | "linear", "per_term":
+        True} — one trainable multiplier lambda per collocation point (and weighted term), w = lambda^2 or lambda, raised by one
+        Adam ASCENT step after every Adam pass (McClenny & Braga-Neto) with Adam moments of its own, the network's step count
+        and StepLR factor and the rate adam_optimizer.weight_learning_rate (default the network's); the L-BFGS stage holds the
+        weights frozen.  rad_importance (or loss.rad_importance) with resample="rad": the mini-batch gets the importance weights
+        mean(score) / score[idx], which makes its loss an unbiased estimate of the pool mean.  With any of the three the residual
+        runs on Engine.residual_weighted_loss_grad, the fidelity term as a separate call, and Adam iterations take the classic
+        path.  Refused (weighted_refusal): data parallelism, eddy_viscosity, runtime coefficients, corrected, lbfgs_impl=
+        "device", a custom evaluator; self_adaptive with residual_batch or resample="rad".
+        coefficients (or the config key loss.coefficients), e.g. {"Cd": 0.01}: values of the residual's closure coefficients
         (ResidualSpec.coef_names: gamma_b of Navier_Stokes, Cd of physics_equation) in place of the compiled-in constants.
         trainable_coefficients (or loss.trainable_coefficients), e.g. ("Cd",): those are unknowns learned with the network —
         a small device tensor with Adam state of its own, updated with the same step count and schedule (learning rate:
@@ -316,6 +413,17 @@ class PINN:
         why = coefficient_refusal(residual or cfg.default_residual(), coef_in, coef_tr,
                                   bool(corrected) or bool(loss_cfg.get("corrected_radiation_stress", False)), nu0,
                                   self.reducer.active, resample, evaluator is not None)
+        if why:
+            raise PinnError(why)
+        # point weights on the residual: parsed and refused before anything touches a device
+        if self_adaptive is None or self_adaptive is False:
+            sa_opt = None if self_adaptive is False else cfg.self_adaptive
+        else:
+            sa_opt = self_adaptive_options(self_adaptive)
+        rad_imp = cfg.rad_importance if rad_importance is None else bool(rad_importance)
+        why = weighted_refusal(residual_weights is not None, sa_opt is not None, rad_imp, self.reducer.active, nu0,
+                               bool(coef_in or coef_tr), bool(corrected) or bool(loss_cfg.get("corrected_radiation_stress", False)),
+                               lbfgs_impl, evaluator is not None, residual_batch, resample)
         if why:
             raise PinnError(why)
         if lbfgs_impl == "device":       # decided before anything touches a device
@@ -388,6 +496,21 @@ class PINN:
                 self._coef_mask = torch.tensor([1.0 if n in coef_tr else 0.0 for n in self.coef_names], dtype=torch.float32, device=dev)
                 self.evaluator.coef_grad = self._coef_grad
 
+        # point weights on the residual: fixed (_w_fixed), self-adaptive (_lam -> _w_fixed = m(lambda) every pass) and / or the
+        # RAD mini-batch's importance weights (formed per draw in loss_func)
+        self.self_adaptive, self.rad_importance = sa_opt, rad_imp
+        self._w_fixed = self._lam = self._lam_m = self._lam_v = self._sa_fields = None
+        self._sa_frozen = False
+        self._last_idx = None
+        if residual_weights is not None:
+            self.set_residual_weights(residual_weights)
+        if sa_opt is not None:
+            rows = self.spec.n_weighted_terms if sa_opt["per_term"] else 1
+            self._lam = torch.full((rows, self.n_res), sa_opt["init"], dtype=torch.float32, device=dev)
+            self._w_fixed = sa_weights(self._lam, sa_opt["mask"]).contiguous()
+            self._sa_fields = torch.zeros(self.spec.n_fields, self.n_res, dtype=torch.float32, device=dev)
+            self.evaluator.point_w = self._w_fixed
+
         # optional resampled collocation mini-batch (the reference is full-batch only):
         # each closure draws `residual_batch` of this rank's points with a device-side generator
         self.residual_batch = residual_batch
@@ -434,6 +557,8 @@ class PINN:
         self._adam_v = torch.zeros_like(self.theta)
         if self._coef_grad is not None:      # the coefficients' own Adam state
             self._coef_m, self._coef_v = torch.zeros_like(self._coef), torch.zeros_like(self._coef)
+        if self._lam is not None:            # the self-adaptive multipliers' own Adam state
+            self._lam_m, self._lam_v = torch.zeros_like(self._lam), torch.zeros_like(self._lam)
         self._adam_step = 0
         self._sched_steps = 0
         self.theta_param = torch.nn.Parameter(self.theta)       # shares storage with every Linear weight
@@ -457,6 +582,34 @@ class PINN:
         """The coefficients' learning rate: adam_optimizer.coefficient_learning_rate (default: the network's) on the same StepLR."""
         a = self.config.adam
         return float(a.get("coefficient_learning_rate", a["learning_rate"])) * a["scheduler_gamma"] ** (self._sched_steps // a["scheduler_step_size"])
+
+    def current_weight_lr(self) -> float:
+        """The self-adaptive weights' learning rate: adam_optimizer.weight_learning_rate (default: the network's) on the same StepLR."""
+        a = self.config.adam
+        return self.config.weight_learning_rate * a["scheduler_gamma"] ** (self._sched_steps // a["scheduler_step_size"])
+
+    def set_residual_weights(self, weights):
+        """Fixed weights on the collocation points: (N_res,) or (n_w, N_res) (None: back to the unweighted loss).  Not with
+        self_adaptive, whose weights are m(lambda)."""
+        if self._lam is not None:
+            raise PinnError("set_residual_weights: the weights are the self-adaptive ones, m(lambda)")
+        if weights is None:
+            self._w_fixed = None
+            self.evaluator.point_w = None
+            return
+        w = _as_f32(weights, self.device)
+        w = w.reshape(1, -1) if w.dim() == 1 else w
+        if w.dim() != 2 or w.shape[1] != self.n_res or w.shape[0] not in (1, self.spec.n_weighted_terms):
+            raise PinnError(f"residual_weights must be ({self.n_res},) or ({self.spec.n_weighted_terms}, {self.n_res}), got {tuple(w.shape)}")
+        self._w_fixed = w.contiguous()
+        self.evaluator.point_w = self._w_fixed
+
+    def residual_weights(self) -> Optional[torch.Tensor]:
+        """The weights on the collocation points in use, (w_rows, N_res): the fixed ones, or m(lambda) of the self-adaptive
+        multipliers; None for the unweighted loss."""
+        if self._lam is not None:
+            return sa_weights(self._lam, self.self_adaptive["mask"])
+        return None if self._w_fixed is None else self._w_fixed.clone()
 
     def coefficients(self) -> Dict[str, float]:
         """The closure coefficients in use, by name (one synchronisation); {} when the compiled-in constants are."""
@@ -486,6 +639,17 @@ class PINN:
             else:
                 idx = torch.randint(0, self.Xr.shape[0], (self.residual_batch,), device=self.device, generator=self._gen)
             Xr = self.Xr.index_select(0, idx)
+            self._last_idx = idx
+            if self.rad_importance or self._w_fixed is not None:      # the mini-batch's weights: importance x the fixed ones
+                w = rad_importance_weights(self._rad_score, idx) if self.rad_importance else None
+                if self._w_fixed is not None:
+                    wf = self._w_fixed.index_select(1, idx)
+                    w = wf if w is None else wf * w
+                self.evaluator.point_w = w.contiguous()
+        elif self._lam is not None:
+            # w = m(lambda) of this pass; the L-BFGS stage (closure) holds it and asks for no fields
+            self._w_fixed.copy_(sa_weights(self._lam, self.self_adaptive["mask"]))
+            self.evaluator.fields_out = None if self._sa_frozen else self._sa_fields
         self._ensure_loss_mat()
         nxt = self.iter + 1
         logged = nxt % self.log_every == 0 or nxt % 1000 == 0
@@ -585,6 +749,8 @@ class PINN:
         out = {f"pred_{k}": Y[:, i:i + 1] for i, k in enumerate(names)}
         if self._coef is not None:
             out["coefficients"] = self._coef.cpu().numpy().astype(np.float32).reshape(1, -1)      # in coef_names order
+        if self.residual_weights() is not None:
+            out["residual_weights"] = self.residual_weights().cpu().numpy().astype(np.float32)    # (w_rows, N_res)
         savemat(path, out)
         print(f"Data saved to {path} after {self.iter} iterations.")
 
@@ -599,6 +765,8 @@ class PINN:
             with open(os.path.join(self.log_dir, "coefficients.json"), "w") as fh:
                 json.dump({"iteration": self.iter, "coefficients": self.coefficients(),
                            "trainable": list(self.trainable_coefficients)}, fh)
+        if self.residual_weights() is not None:
+            np.save(os.path.join(self.log_dir, "residual_weights.npy"), self.residual_weights().cpu().numpy().astype(np.float32))
 
     # ---- training (train.py:185-200) ------------------------------------------------------------------
     def adam_step(self):
@@ -608,6 +776,7 @@ class PINN:
         fold = (self._may_fold() and not self._checkpoint_due(self.iter + 1))
         if self._coef is not None:
             self.evaluator.coef_grad = self._coef_grad      # (None when nothing is trainable: values only)
+        self._sa_frozen = False
         loss = self.loss_func((self._adam_m, self._adam_v, self._adam_step + 1, self.current_lr()) if fold else None)
         self._adam_step += 1
         if fold and not self._adam_folded:
@@ -620,6 +789,10 @@ class PINN:
                     self._coef_grad.mul_(self._coef_mask)
                 self.evaluator.eng.adam_step(self._coef, self._coef_grad, self._coef_m, self._coef_v, self._adam_step,
                                              self.current_coefficient_lr(), count=self._coef.numel())
+            if self._lam is not None:            # the multipliers' ascent step from this pass's fields: same step count and schedule
+                g = sa_weight_grad(self._lam, self._sa_fields, self._res_scale, self.self_adaptive["mask"]).contiguous()
+                self.evaluator.eng.adam_step(self._lam.view(-1), g.view(-1), self._lam_m.view(-1), self._lam_v.view(-1),
+                                             self._adam_step, self.current_weight_lr(), count=self._lam.numel())
         else:
             self._folded_iters += 1
         self._sched_steps += 1
@@ -634,8 +807,11 @@ class PINN:
         """The folded iteration is worth asking for: switched on, one process, an evaluator that has it, and the engine
         has not already refused this very request (wide / generic engine, a large split request: the refusal is remembered
         per evaluator and point sets instead of being re-discovered by two refused C calls every iteration)."""
-        return (self.fold_adam and self._coef is None and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
+        return (self.fold_adam and self._coef is None and not self._weighted() and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
                 and self._fold_refused != self._fold_key())
+
+    def _weighted(self) -> bool:
+        return self._w_fixed is not None or self.rad_importance
 
     def _foldable_run(self, n: int) -> int:
         """How many of the next n Adam iterations can be enqueued by ONE call: full batch, one process, nothing the
@@ -712,6 +888,7 @@ class PINN:
         """train.py:195-199"""
         if self._coef is not None:      # the L-BFGS stage holds the coefficients frozen: values only, no coefficient gradient
             self.evaluator.coef_grad = None
+        self._sa_frozen = True          # ... and the self-adaptive weights at their Adam-final values
         loss = self.loss_func()
         self.theta_param.grad = self.grad.clone()
         return loss
