@@ -36,6 +36,8 @@
  *   pinn_adam_step          torch.optim.Adam.step as called at train.py:192
  *   pinn_loss_grad_adam_step  train.py:189-193 (loss_func + backward + Adam.step) in two launches
  *   pinn_adam_loop          train.py:188-193, n iterations of the above enqueued by one call
+ *   pinn_adam_loop_ext      the same for the residual with runtime coefficients or point weights (fixed or self-adaptive):
+ *                           three launches per iteration, the coefficients' / multipliers' Adam step on the device
  *
  * Conventions
  *   - plain C, no exceptions; every function returns 0 on success, <0 on error;
@@ -63,7 +65,7 @@
  *     dY (k, N, d_out), d2Y (P, N, d_out), fields (n_fields, N), term_sums (n_terms), col_sums (n_cols), grad_flat /
  *     m / v / params (P), losses (n_loss_rows, or n_iters x n_loss_rows), out2 (2), n_rows_out (1), d (P), tmp (4m),
  *     coef (2m), q (P); X_out up to its capacity of ceil(ny/ix) * ceil(nx/iy) rows (rows past n_rows_out: unspecified).
- *   - Read-only, never written: params (except by the two Adam entries and pinn_adam_step), X, T, gY, gdY, gd2Y,
+ *   - Read-only, never written: params (except by the Adam entries and pinn_adam_step), X, T, gY, gdY, gd2Y,
  *     term_scale, col_scale, loss_rows, grad of pinn_adam_step, data / grids / minmax, g, s, y; S, Y, M in
  *     pinn_lbfgs_direction; rows of S, Y other than `slot` and entries of M outside row and column `slot` in
  *     pinn_lbfgs_push.
@@ -71,7 +73,7 @@
  *     pinn_residual_coef_loss_grad (whose coef_grad is += too; its coef is read-only), pinn_residual_weighted_loss_grad
  *     (whose point_w is read-only and whose fields, if given, are overwritten at (n_fields, N)), pinn_mse_loss_grad,
  *     pinn_residual_mse_loss_grad and pinn_residual_mse_split_loss_grad (the caller zeroes it, or accumulates several
- *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step and pinn_adam_loop.  Y, dY, d2Y, fields,
+ *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step, pinn_adam_loop and pinn_adam_loop_ext.  Y, dY, d2Y, fields,
  *     term_sums, col_sums, losses, X_out, n_rows_out, out2 and d are overwritten, whatever they held.
  *   - pinn_lbfgs_loop: writes params (P), trace (n_slots x PINN_LBFGS_TRACE_COLS) and state (the bytes pinn_query_lbfgs_loop
  *     states) at those extents only; `state` is the one buffer whose content a call relies on (pinn_lbfgs_loop_init arms it).
@@ -537,6 +539,77 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec,
                        float* term_sums, float* col_sums, float* grad_flat,
                        const pinn_adam_state* adam, int32_t n_iters, const double* lr,
                        void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- device-enqueued Adam runs with closure coefficients or point weights -------------------------------------------------
+ * (added under ABI version 4, as the entries above were: no existing entry, struct or constant changed)
+ * pinn_adam_loop for the two requests it does not carry: the residual with runtime coefficients (pinn_residual_coef_loss_grad)
+ * and the residual with point weights (pinn_residual_weighted_loss_grad), fixed or self-adaptive.  One call enqueues n_iters
+ * iterations; iteration i uses step adam->step + i and the HOST arrays lr[i] (network), lr_coef[i] (coefficients), lr_w[i]
+ * (multipliers) and is, in stream order:
+ *   1. the residual pass: the tile kernel's coefficient / weighted gradient instance on (X, N_res), on the very grid the
+ *      single entry uses — term_sums, coef_grad and fields keep that entry's bit-reproducibility;
+ *   2. the fidelity pass: pinn_mse_loss_grad's pass on its own point set (Xf, T, N_fid), on the kernel that entry would take
+ *      (at hidden width 33..64 under AUTO / FUSED the cooperative kernel while the points are at most one 16-point tile per
+ *      compute unit, else the tile kernel); skipped when N_fid == 0 (col_sums, if given, is then zeroed).  Xf may alias X;
+ *   3. ONE finishing kernel:
+ *        parameter blocks   gradient of parameter p = (fidelity pass's) + (residual pass's), each summed over that pass's own
+ *                           gradient copies in pinn_loss_grad_adam_step's order; grad_flat[p] OVERWRITTEN with it; Adam on
+ *                           params / m / v (pinn_adam_step's arithmetic, bit for bit); packed weights refreshed
+ *        one sums block     term_sums from the residual pass, col_sums from the fidelity pass, the optional weighted losses
+ *                           (adam->loss_rows, row stride n_cols + n_terms, written to adam->losses + i * n_loss_rows);
+ *                           coefficients: coef_log row i <- coef (the values iteration i RAN WITH), coef_grad[c] <- the
+ *                           pass's coefficient gradient (what pinn_residual_coef_loss_grad adds to a zeroed array) times
+ *                           coef_mask[c] if a mask is given, then Adam with lr_coef[i] on coef / coef_m / coef_v in place
+ *        multiplier blocks  self-adaptive weights only, one thread per element (t, n) of lam: from the pass's unweighted
+ *                           signed fields, sf = (term_scale[t] f) f (w_rows == 1: summed over the weighted terms in term
+ *                           order), g = -((2 lam) sf) for sa_mask 0 (w = lam^2) or g = -sf for sa_mask 1 (w = lam), no fused
+ *                           multiply-add; Adam with lr_w[i] DESCENDS along g (lam ascends the loss) on lam / lam_m / lam_v;
+ *                           point_w <- lam_new^2 or lam_new for the next pass
+ * Three launches per iteration, two without fidelity points; a zero-fill per pass where the gradient copies do not fit in
+ * LDS; one packing kernel per call unless adam->packed_valid (the caller's promise, as in pinn_loss_grad_adam_step); with
+ * lam, one kernel per call that forms point_w from lam before the first pass.  adam->lr is ignored.
+ * pinn_adam_extras: exactly one of the two groups.
+ *   coefficients  coef (n_coef, required), coef_grad (NULL: every coefficient frozen — values only, coef is not written and
+ *                 coef_m, coef_v, coef_mask, lr_coef are not read; otherwise coef_m, coef_v and lr_coef are required),
+ *                 coef_mask (NULL: all trainable; else n_coef floats 0 / 1: a 0 entry sees gradient 0 and does not move
+ *                 while its moments are zero), coef_log (NULL or (n_iters, n_coef))
+ *   weights       point_w (w_rows, N_res), w_rows 1 or n_w as in pinn_residual_weighted_loss_grad.  lam == NULL: fixed
+ *                 weights, point_w is read only; fields may be given and is overwritten every iteration.  lam given:
+ *                 lam, lam_m, lam_v (w_rows, N_res), fields (n_fields, N_res) and lr_w are required, sa_mask is 0 or 1.
+ * Rules, all decided before any device work (nothing is launched on a refusal); the query follows the same rules:
+ *   both groups (coef and point_w)              PINN_ERR_UNSUPPORTED  ("no kernel carries both")
+ *   neither group, or extras NULL               PINN_ERR_INVALID      (use pinn_adam_loop)
+ *   the residual request                        served where pinn_residual_coef_loss_grad / pinn_residual_weighted_loss_grad
+ *                                               run the tile kernel: AUTO, FUSED, FUSED_TILE; fp32, tanh, width <= 64, d_in
+ *                                               and d_out <= 16, dropout_p == 0, k = the residual's directions
+ *   GENERIC, WIDE, FUSED_COOP, FUSED_BATCH, bf16, LeakyReLU, width > 64, dropout, k mismatch
+ *                                               PINN_ERR_UNSUPPORTED with the reason (AUTO is NOT moved to the generic engine
+ *                                               here: use the single entries and pinn_adam_step)
+ *   spec.flags bit 0 (corrected stress)         PINN_ERR_UNSUPPORTED, "corrected" in the message
+ *   the continuity residuals with coef          PINN_ERR_UNSUPPORTED, "no coefficient" in the message
+ *   w_rows other than 1 or n_w, sa_mask other than 0 or 1, N_res < 1, N_fid < 0, NULL pointers   PINN_ERR_INVALID
+ *   n_iters == 0                                PINN_OK, nothing launched
+ * n_cols: the fidelity columns, 0..PINN_MAX_ROLES, the row length of col_sums and the column offset of the term sums in
+ * adam->loss_rows also when N_fid == 0.  N_fid > 0 needs n_cols >= 1, Xf, T (N_fid, n_cols), out_col, col_scale, col_sums.
+ * The workspace is the entry's own (pinn_query_adam_ext_workspace: packed weights, one scratch area, and a region of partial
+ * sums and of gradient copies for EACH pass); it grows with N_res and N_fid and is never smaller than the single entries'. */
+typedef struct pinn_adam_extras {
+  /* exactly one of the two groups */
+  float* coef; float* coef_m; float* coef_v; float* coef_grad;   /* (n_coef); coef_grad NULL: all frozen, values only   */
+  const float* coef_mask;                                        /* NULL: all trainable, else (n_coef) 0/1              */
+  float* coef_log;                                               /* NULL or (n_iters, n_coef)                           */
+  float* point_w; int32_t w_rows;                                /* (w_rows, N_res): fixed weights, read only ...       */
+  float* fields;                                                 /* NULL or (n_fields, N_res); required with lam        */
+  float* lam; float* lam_m; float* lam_v; int32_t sa_mask;       /* ... or self-adaptive: point_w is then written (0 lam^2, 1 lam) */
+} pinn_adam_extras;
+int32_t pinn_query_adam_ext_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, const pinn_adam_extras* extras,
+                                      int64_t N_res, int64_t N_fid, int64_t* bytes);
+int32_t pinn_adam_loop_ext(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
+                           const float* Xf, const float* T, int64_t N_fid, int32_t n_cols, const int32_t* out_col,
+                           const float* col_scale, float* params, const float* X, int64_t N_res,
+                           float* term_sums, float* col_sums, float* grad_flat, const pinn_adam_state* adam,
+                           const pinn_adam_extras* extras, int32_t n_iters, const double* lr, const double* lr_coef,
+                           const double* lr_w, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- ensembles: M networks of one shape in one launch --------------------------------------------------------------
  * (added under ABI version 4, as the fields entries were: no existing entry, struct or constant changed)

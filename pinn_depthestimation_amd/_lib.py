@@ -50,6 +50,16 @@ class PinnAdamState(C.Structure):
     ]
 
 
+class PinnAdamExtras(C.Structure):
+    """pinn_adam_extras (pinn_adam_loop_ext): the coefficient group or the weight group, the other left NULL."""
+    _fields_ = [
+        ("coef", C.c_void_p), ("coef_m", C.c_void_p), ("coef_v", C.c_void_p), ("coef_grad", C.c_void_p),
+        ("coef_mask", C.c_void_p), ("coef_log", C.c_void_p),
+        ("point_w", C.c_void_p), ("w_rows", C.c_int32), ("fields", C.c_void_p),
+        ("lam", C.c_void_p), ("lam_m", C.c_void_p), ("lam_v", C.c_void_p), ("sa_mask", C.c_int32),
+    ]
+
+
 class PinnLsState(C.Structure):
     """pinn_ls_state: torch's _strong_wolfe as a resumable state machine (csrc/lbfgs_line_search.h)."""
     _fields_ = [
@@ -162,6 +172,12 @@ _SIGNATURES = {
     "pinn_adam_loop": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int32,
                                    C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P,
                                    C.POINTER(PinnAdamState), C.c_int32, C.POINTER(C.c_double), _P, C.c_int64, _P]),
+    "pinn_query_adam_ext_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.POINTER(PinnAdamExtras),
+                                                  C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "pinn_adam_loop_ext": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P, C.c_int64, C.c_int32,
+                                       C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(PinnAdamState),
+                                       C.POINTER(PinnAdamExtras), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), _P, C.c_int64, _P]),
     "pinn_ensemble_query_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_ensemble_plan": (C.c_int32, [C.POINTER(PinnDesc), C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pinn_ensemble_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int32, _P, _P, C.c_int32,

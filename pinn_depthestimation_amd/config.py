@@ -77,6 +77,12 @@ class PinnConfig:
         """adam_optimizer.weight_learning_rate: the self-adaptive weights' rate, default the network's."""
         return float(self.adam.get("weight_learning_rate", self.adam["learning_rate"]))
 
+    @property
+    def fold_extras(self) -> bool:
+        """adam_optimizer.fold_extras: run Adam iterations with closure coefficients or point weights in device-enqueued
+        runs (trainer.PINN(fold_extras=True)); off unless asked for."""
+        return bool(self.adam.get("fold_extras", False))
+
     def default_residual(self) -> str:
         """The reference hard-codes the residual by import (train.py:17, train_newmethod.py:18);
         pick the one whose argument names the config's variables satisfy."""

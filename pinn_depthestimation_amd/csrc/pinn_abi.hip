@@ -6,6 +6,7 @@
 #include <vector>
 #include "common.h"
 #include "reduce_adam.h"
+#include "adam_ext.h"
 #include "residuals.h"
 #include "lbfgs_loop.h"
 #include "lbfgs_line_search.h"
@@ -1183,6 +1184,120 @@ int32_t pinn_residual_weighted_loss_grad(const pinn_desc* desc, const pinn_resid
   if (N == 0) { (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), s); return PINN_OK; }
   return e == PINN_ENGINE_FUSED ? fused_weighted_loss(n, rq, params, X, N, ws, ws_bytes, s)
                                 : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
+}
+
+// ---- device-enqueued Adam runs with coefficients or point weights (pinn_hip.h; kernels: pinn_fused.hip) -------------------
+// validation shared by the query and the call, in the order of the header's table (no HIP call before it has passed);
+// *coef <- the request carries coefficients (else weights), *n_w <- the residual's weighted terms
+static int adam_ext_plan(const char* who, const pinn_desc* desc, const pinn_residual_spec* spec, const pinn_adam_extras* ex,
+                         int64_t N_res, int64_t N_fid, Net* n, pinn_residual_spec* nspec, bool* coef, int* n_w) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  rc = check_spec(*n, spec, nspec); if (rc) return rc;
+  if (!ex) { set_error("%s: extras is NULL (use pinn_adam_loop for the plain request)", who); return PINN_ERR_INVALID; }
+  if (ex->coef && ex->point_w) {
+    set_error("%s: coefficients and point weights together: no kernel carries both", who); return PINN_ERR_UNSUPPORTED;
+  }
+  if (!ex->coef && !ex->point_w) {
+    set_error("%s: neither coef nor point_w is given (use pinn_adam_loop for the plain request)", who); return PINN_ERR_INVALID;
+  }
+  *coef = ex->coef != nullptr;
+  if (*coef) { rc = coef_residual(who, spec->residual_id, spec->flags); if (rc) return rc; }
+  else if (spec->residual_id == PINN_RES_PHYSICS_EQUATION && (spec->flags & 1)) {
+    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no point-weighted form", who);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (n->k != residual_dirs(spec->residual_id)) {
+    set_error("%s: the network carries k = %d tangent directions, residual %d has %d (k must equal the residual's number of "
+              "directions)", who, n->k, spec->residual_id, residual_dirs(spec->residual_id));
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (n->prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
+  const int asked = asked_engine(desc);
+  if (asked == PINN_ENGINE_GENERIC || asked == PINN_ENGINE_WIDE) {
+    set_error("%s runs on the fused tile kernel only (engine AUTO, FUSED or FUSED_TILE), not on engine %d: use the single "
+              "entries and pinn_adam_step", who, desc->engine);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (const char* why = fused_adam_ext_refusal(*n, *coef)) {
+    set_error("%s: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); use the single entries and "
+              "pinn_adam_step", who, why, n->W, n->d_in, n->d_out, n->k, n->act, (double)n->drop_p);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  const int n_terms = residual_terms(spec->residual_id), n_fields = residual_n_fields(spec->residual_id);
+  *n_w = n_terms < n_fields ? n_terms : n_fields;
+  if (!*coef) {
+    if (ex->w_rows != 1 && ex->w_rows != *n_w) {
+      set_error("%s: w_rows = %d, residual %d takes 1 row or %d (one per weighted term)", who, ex->w_rows, spec->residual_id, *n_w);
+      return PINN_ERR_INVALID;
+    }
+    if (ex->lam && ex->sa_mask != 0 && ex->sa_mask != 1) { set_error("%s: sa_mask = %d (0: w = lam^2, 1: w = lam)", who, ex->sa_mask); return PINN_ERR_INVALID; }
+  }
+  if (N_res < 1 || N_fid < 0) { set_error("%s: N_res = %lld must be >= 1, N_fid = %lld >= 0", who, (long long)N_res, (long long)N_fid); return PINN_ERR_INVALID; }
+  return PINN_OK;
+}
+
+int32_t pinn_query_adam_ext_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, const pinn_adam_extras* extras,
+                                      int64_t N_res, int64_t N_fid, int64_t* bytes) {
+  Net n; pinn_residual_spec nspec; bool coef; int n_w;
+  int rc = adam_ext_plan("pinn_query_adam_ext_workspace", desc, spec, extras, N_res, N_fid, &n, &nspec, &coef, &n_w); if (rc) return rc;
+  if (!bytes) { set_error("bytes is NULL"); return PINN_ERR_INVALID; }
+  *bytes = fused_adam_ext_workspace_bytes(n, N_res, N_fid);
+  return PINN_OK;
+}
+
+int32_t pinn_adam_loop_ext(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
+                           const float* Xf, const float* T, int64_t N_fid, int32_t n_cols, const int32_t* out_col,
+                           const float* col_scale, float* params, const float* X, int64_t N_res,
+                           float* term_sums, float* col_sums, float* grad_flat, const pinn_adam_state* adam,
+                           const pinn_adam_extras* extras, int32_t n_iters, const double* lr, const double* lr_coef,
+                           const double* lr_w, void* ws, int64_t ws_bytes, void* stream) {
+  const char* who = "pinn_adam_loop_ext";
+  Net n; pinn_residual_spec nspec; bool coef; int n_w;
+  int rc = adam_ext_plan(who, desc, spec, extras, N_res, N_fid, &n, &nspec, &coef, &n_w); if (rc) return rc;
+  if (!adam || n_iters < 0) { set_error("%s: bad arguments", who); return PINN_ERR_INVALID; }
+  if (n_iters == 0) return PINN_OK;
+  if (!params || !X || !term_sums || !term_scale || !grad_flat || !adam->m || !adam->v || adam->step < 1 || !lr) {
+    set_error("%s: bad arguments", who); return PINN_ERR_INVALID;
+  }
+  if (n_cols < 0 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 0..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
+  if (N_fid > 0 && (n_cols < 1 || !Xf || !T || !out_col || !col_scale || !col_sums)) {
+    set_error("%s: fidelity points need n_cols >= 1, Xf, T, out_col, col_scale and col_sums", who); return PINN_ERR_INVALID;
+  }
+  if (adam->n_loss_rows < 0 || adam->n_loss_rows > 8 || (adam->n_loss_rows > 0 && (!adam->loss_rows || !adam->losses))) {
+    set_error("bad loss_rows arguments"); return PINN_ERR_INVALID;
+  }
+  if (coef && extras->coef_grad && (!extras->coef_m || !extras->coef_v || !lr_coef)) {
+    set_error("%s: trainable coefficients need coef_m, coef_v and lr_coef", who); return PINN_ERR_INVALID;
+  }
+  if (!coef && extras->lam && (!extras->lam_m || !extras->lam_v || !extras->fields || !lr_w)) {
+    set_error("%s: self-adaptive weights need lam_m, lam_v, fields and lr_w", who); return PINN_ERR_INVALID;
+  }
+  AdamExtReq q; memset(&q, 0, sizeof(q));
+  LossReq& r = q.res;
+  r.kind = 0; r.n_split = -1; r.spec = nspec; r.scale = term_scale; r.sums = term_sums; r.grad = grad_flat;
+  r.n_terms = residual_terms(spec->residual_id);
+  if (coef) { r.coef = extras->coef; r.coef_grad = extras->coef_grad; r.n_coef = 1; }
+  else { r.point_w = extras->point_w; r.w_stride = extras->w_rows == 1 ? 0 : N_res; r.n_weighted = n_w; r.fields_out = extras->fields; }
+  if (N_fid > 0) {
+    LossReq& m = q.fid;
+    m.kind = 1; m.n_split = -1; m.T = T; m.n_cols = n_cols; m.mse_scale = col_scale; m.mse_sums = col_sums; m.grad = grad_flat;
+    rc = set_out_cols(n, n_cols, out_col, &m); if (rc) return rc;
+  }
+  q.Xf = Xf; q.N_fid = N_fid;
+  q.params = params; q.m = adam->m; q.v = adam->v;
+  q.beta1 = adam->beta1; q.beta2 = adam->beta2; q.eps = adam->eps; q.step = adam->step;
+  q.packed_valid = adam->packed_valid != 0;
+  q.n_loss_rows = adam->n_loss_rows; q.loss_rows = adam->loss_rows; q.losses = adam->losses; q.row_cols = n_cols;
+  q.col_sums = col_sums;
+  if (coef) {
+    q.coef = extras->coef; q.coef_m = extras->coef_m; q.coef_v = extras->coef_v; q.coef_grad = extras->coef_grad;
+    q.coef_mask = extras->coef_mask; q.coef_log = extras->coef_log; q.n_coef = 1;
+  } else {
+    q.point_w = extras->point_w; q.w_rows = extras->w_rows; q.lam = extras->lam; q.lam_m = extras->lam_m; q.lam_v = extras->lam_v;
+    q.sa_mask = extras->sa_mask;
+  }
+  q.n_iters = n_iters; q.lr = lr; q.lr_coef = lr_coef; q.lr_w = lr_w;
+  return fused_adam_ext(n, q, X, N_res, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include "fused_coop_kernel.h"
 #include "fused_batch_kernel.h"
 #include "reduce_adam.h"
+#include "adam_ext.h"
 
 namespace pinn {
 
@@ -284,9 +285,12 @@ __global__ void k_reduce_grads(Net n, int WP, const float* __restrict__ wg, int 
 // The two parts of k_finish_adam (below), shared with the ensemble's finishing kernels:
 // the loss sums' block: term_sums / col_sums <- the fixed-order column sums of the workgroups' partial sums and, optionally,
 // the weighted losses.  Called by all 256 threads of ONE block.
-__device__ __forceinline__ void finish_sums(const float* __restrict__ wg_sums, int grid, int n_terms, float* __restrict__ term_sums,
-                                            int n_cols, float* __restrict__ col_sums, int n_loss_rows,
-                                            const float* __restrict__ loss_rows, float* __restrict__ losses, int row_cols) {
+// (finish_sums2: the term sums and the column sums from the partial sums of two different passes — pinn_adam_loop_ext runs
+// the residual and the fidelity points as a pass each; finish_sums below: both from one pass)
+__device__ __forceinline__ void finish_sums2(const float* __restrict__ wg_sums, int grid, const float* __restrict__ wg_sums_c, int grid_c,
+                                             int n_terms, float* __restrict__ term_sums,
+                                             int n_cols, float* __restrict__ col_sums, int n_loss_rows,
+                                             const float* __restrict__ loss_rows, float* __restrict__ losses, int row_cols) {
 #pragma clang fp contract(off)
   // [col sums (row_cols of them) | term sums], for the optional weighted losses.  row_cols is the CALLER's column
   // count — the stride of loss_rows (pinn_hip.h) — also when this pass carried no fidelity columns (n_cols = 0:
@@ -295,7 +299,8 @@ __device__ __forceinline__ void finish_sums(const float* __restrict__ wg_sums, i
   if (threadIdx.x < 2 * PINN_MAX_ROLES + 8) ssum[threadIdx.x] = 0.0;
   __syncthreads();
   for (int j = 0; j < n_terms + n_cols; ++j) {
-    const float sum = (float)column_sum(wg_sums, grid, MAX_SUMS, j < n_terms ? j : MSE_SUM0 + (j - n_terms));
+    const float sum = (float)column_sum(j < n_terms ? wg_sums : wg_sums_c, j < n_terms ? grid : grid_c, MAX_SUMS,
+                                        j < n_terms ? j : MSE_SUM0 + (j - n_terms));
     if (threadIdx.x == 0) {
       if (j < n_terms) { term_sums[j] = sum; ssum[row_cols + j] = (double)sum; }
       else { col_sums[j - n_terms] = sum; ssum[j - n_terms] = (double)sum; }
@@ -308,12 +313,17 @@ __device__ __forceinline__ void finish_sums(const float* __restrict__ wg_sums, i
     losses[threadIdx.x] = (float)a;
   }
 }
-// a parameter block: the gradient of the block's 64 parameters, Adam's update on them, the refreshed packed entries
-__device__ __forceinline__ void finish_adam_params(const Net& n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
-                                                   float* __restrict__ grad, float* __restrict__ params, float* __restrict__ m,
-                                                   float* __restrict__ v, float* __restrict__ Wp, float* __restrict__ WTp,
-                                                   float* __restrict__ Bp, const AdamScalars& c, int flags) {
-  const ParamGrad r = grad_of_param(n, WP, wg, copies, PP, PW, flags);
+__device__ __forceinline__ void finish_sums(const float* __restrict__ wg_sums, int grid, int n_terms, float* __restrict__ term_sums,
+                                            int n_cols, float* __restrict__ col_sums, int n_loss_rows,
+                                            const float* __restrict__ loss_rows, float* __restrict__ losses, int row_cols) {
+  finish_sums2(wg_sums, grid, wg_sums, grid, n_terms, term_sums, n_cols, col_sums, n_loss_rows, loss_rows, losses, row_cols);
+}
+// a parameter block, once its gradient is summed (r, grad_of_param): Adam's update on the block's 64 parameters and the
+// refreshed packed entries
+__device__ __forceinline__ void finish_adam_apply(const Net& n, int WP, const ParamGrad& r,
+                                                  float* __restrict__ grad, float* __restrict__ params, float* __restrict__ m,
+                                                  float* __restrict__ v, float* __restrict__ Wp, float* __restrict__ WTp,
+                                                  float* __restrict__ Bp, const AdamScalars& c) {
   if (r.owner) {
     const ParamSlot& p = r.at;
     const int64_t i = p.i;
@@ -326,6 +336,14 @@ __device__ __forceinline__ void finish_adam_params(const Net& n, int WP, const f
       WTp[p.wo + p.col * outP + p.row] = pn;
     } else Bp[p.l * WP + p.row] = pn;
   }
+}
+// a parameter block: the gradient of the block's 64 parameters, Adam's update on them, the refreshed packed entries
+__device__ __forceinline__ void finish_adam_params(const Net& n, int WP, const float* __restrict__ wg, int copies, int PP, int PW,
+                                                   float* __restrict__ grad, float* __restrict__ params, float* __restrict__ m,
+                                                   float* __restrict__ v, float* __restrict__ Wp, float* __restrict__ WTp,
+                                                   float* __restrict__ Bp, const AdamScalars& c, int flags) {
+  const ParamGrad r = grad_of_param(n, WP, wg, copies, PP, PW, flags);
+  finish_adam_apply(n, WP, r, grad, params, m, v, Wp, WTp, Bp, c);
 }
 // One kernel for everything that follows the fused pass in an Adam iteration (pinn_loss_grad_adam_step): the
 // gradient reduction of k_reduce_grads (grad_of_param), torch.optim.Adam's update (k_adam's adam_update, reduce_adam.h) on
@@ -344,6 +362,96 @@ __global__ void k_finish_adam(Net n, int WP, const float* __restrict__ wg, int c
     return;
   }
   finish_adam_params(n, WP, wg, copies, PP, PW, grad, params, m, v, Wp, WTp, Bp, c, flags);
+}
+
+// ---- pinn_adam_loop_ext: everything that follows the residual pass and the fidelity pass of one iteration --------------------
+// The residual pass (EPI_COEF / EPI_WEIGHTED instance) and the fidelity pass (K1 = 1) each leave a row of partial sums per
+// workgroup and their own gradient copies.  Grid: [parameter blocks | one sums block | multiplier blocks].
+struct ExtFinish {
+  const float* wg_r; int copies_r; const float* sums_r; int grid_r;   // the residual pass
+  const float* wg_f; int copies_f; const float* sums_f; int grid_f;   // the fidelity pass (copies_f == 0: there was none)
+  int param_blocks;
+  int n_terms, n_cols, row_cols;      // n_cols: of the fidelity pass (0 without one); row_cols: the caller's
+  float* term_sums; float* col_sums; float* grad;
+  float* params; float* m; float* v; float* Wp; float* WTp; float* Bp;
+  AdamScalars c;
+  int n_loss_rows; const float* loss_rows; float* losses;
+  // coefficients (n_coef == 0: none)
+  int n_coef; float* coef; float* coef_m; float* coef_v; float* coef_grad; const float* coef_mask; float* coef_log;
+  AdamScalars cc;
+  // self-adaptive multipliers (lam == nullptr: none): lam, lam_m, lam_v, point_w (rows, N); fields (n_fields, N)
+  int rows, n_w, sa_mask; int64_t N;
+  const float* scale; const float* fields; float* lam; float* lam_m; float* lam_v; float* point_w;
+  AdamScalars cw;
+};
+// the self-adaptive weights w = m(lambda) (trainer.sa_weights): lambda^2 (sa_mask 0) or lambda (1)
+__device__ __forceinline__ float sa_weight_of(float lam, int sa_mask) {
+#pragma clang fp contract(off)
+  return sa_mask == 0 ? lam * lam : lam;
+}
+// One multiplier, element e = t * N + n of lam: trainer.sa_weight_grad's arithmetic in its order, contraction off —
+// sf = (s_t f) f, summed over the weighted terms in term order for a shared row; g = -((2 lam) sf) or -sf — then Adam's
+// update along g and the weight of the next pass.
+__device__ __forceinline__ void finish_multiplier(const ExtFinish& f, int64_t e) {
+#pragma clang fp contract(off)
+  const int64_t t = e / f.N, nn = e - t * f.N;
+  float sf;
+  if (f.rows == 1) {
+    sf = 0.f;
+    for (int tt = 0; tt < f.n_w; ++tt) {
+      const float fv = f.fields[(int64_t)tt * f.N + nn];
+      const float st = (f.scale[tt] * fv) * fv;
+      sf = tt == 0 ? st : sf + st;
+    }
+  } else {
+    const float fv = f.fields[e];
+    sf = (f.scale[t] * fv) * fv;
+  }
+  const float lam = f.lam[e];
+  const float gi = f.sa_mask == 0 ? -((2.0f * lam) * sf) : -sf;
+  const float ln = adam_update(lam, gi, f.lam_m[e], f.lam_v[e], f.cw);
+  f.lam[e] = ln;
+  f.point_w[e] = sa_weight_of(ln, f.sa_mask);
+}
+__global__ void k_finish_adam_ext(Net n, int WP, int PP, int PW, ExtFinish f) {
+  const int b = blockIdx.x;
+  if (b < f.param_blocks) {        // gradient = fidelity pass's + residual pass's, Adam, packed entries (natural unit order)
+    ParamGrad r = grad_of_param(n, WP, f.wg_r, f.copies_r, PP, PW, 0);
+    if (f.copies_f > 0) {
+      __syncthreads();             // (grad_of_param's partial sums are read before they are written again)
+      const ParamGrad q = grad_of_param(n, WP, f.wg_f, f.copies_f, PP, PW, 0);
+      if (r.owner) r.g = q.g + r.g;
+    }
+    finish_adam_apply(n, WP, r, f.grad, f.params, f.m, f.v, f.Wp, f.WTp, f.Bp, f.c);
+    return;
+  }
+  if (b == f.param_blocks) {       // loss sums, weighted losses, coefficients
+    finish_sums2(f.sums_r, f.grid_r, f.sums_f, f.grid_f, f.n_terms, f.term_sums, f.n_cols, f.col_sums, f.n_loss_rows,
+                 f.loss_rows, f.losses, f.row_cols);
+    for (int c = 0; c < f.n_coef; ++c) {
+      // (the coefficient gradient rode in the free term slot of the residual pass's partial sums: fused_kernel.h, COEF_SUM)
+      const float cg = (float)column_sum(f.sums_r, f.grid_r, MAX_SUMS, COEF_SUM + c);
+      if (threadIdx.x == 0) {
+        const float cur = f.coef[c];
+        if (f.coef_log) f.coef_log[c] = cur;          // the value this iteration ran with
+        if (f.coef_grad) {
+          float gi = 0.f + cg;                         // what reduce_sums_add adds to a zeroed array
+          if (f.coef_mask) gi = gi * f.coef_mask[c];
+          f.coef_grad[c] = gi;
+          f.coef[c] = adam_update(cur, gi, f.coef_m[c], f.coef_v[c], f.cc);
+        }
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  const int64_t e = (int64_t)(b - f.param_blocks - 1) * 256 + threadIdx.x;
+  if (f.lam && e < (int64_t)f.rows * f.N) finish_multiplier(f, e);
+}
+// before the first pass of a pinn_adam_loop_ext call with multipliers: point_w = m(lambda)
+__global__ void k_sa_weights(const float* __restrict__ lam, float* __restrict__ w, int64_t count, int sa_mask) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < count) w[e] = sa_weight_of(lam[e], sa_mask);
 }
 
 // The ensemble's finishing kernels, grid (parameter blocks + 1, M): member blockIdx.y's share of every array, then the
@@ -398,11 +506,22 @@ struct FieldReq {
   float* fields;
 };
 
+// One pass of pinn_adam_loop_ext: run() launches the gradient pass ALONE — no reduction, no finishing kernel, the packing
+// kernel only if asked — with its scratch, partial sums and gradient copies at the byte offsets the caller names (the
+// caller has checked the workspace against its own layout, fused_adam_ext), and reports what the finishing kernel needs.
+struct PassOnly {
+  int64_t scratch, wg_sums, wg_grads;   // in
+  bool pack;                            // in: the packed weights are not valid yet
+  int grid, n_copies;                   // out: rows of partial sums, gradient copies
+};
+
 int run(const Net& n, bool grad, const LossReq* rq, const float* params, const float* X, int64_t N, float* Y,
-        float* dY, void* ws, int64_t ws_bytes, hipStream_t s, const AdjReq* adj = nullptr, const FieldReq* fld = nullptr) {
+        float* dY, void* ws, int64_t ws_bytes, hipStream_t s, const AdjReq* adj = nullptr, const FieldReq* fld = nullptr,
+        PassOnly* po = nullptr) {
   const Geo g = geo_of(n);
-  const WsLayout w = ws_layout(n, g, N, fld != nullptr);
-  if (!ws || ws_bytes < w.total) {
+  WsLayout w = ws_layout(n, g, N, fld != nullptr);
+  if (po) { w.scratch = po->scratch; w.wg_sums = po->wg_sums; w.wg_grads = po->wg_grads; }
+  if (!po && (!ws || ws_bytes < w.total)) {
     set_error("workspace too small: need %lld bytes, got %lld", (long long)w.total, (long long)ws_bytes);
     return PINN_ERR_WORKSPACE;
   }
@@ -489,7 +608,13 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
 
   const AdamReq* adam = rq ? rq->adam : nullptr;
   const int packN = g.PW > g.PB ? g.PW : g.PB;
-  if (!(adam && adam->packed_valid))
+  // pinn_adam_loop_ext: one packed copy serves its two passes and its finishing kernel, so both must take natural unit order.
+  // An INTERNAL INVARIANT, not a refusal a caller can meet: a coefficient / weighted request never takes the batch kernel or
+  // the KRO > 0 order (coefq above), and a K1 = 1 pass has neither (fused_batch_has_kernel wants K1 = 3 or 4, io1 a residual),
+  // so perm is 0 for both passes by construction.  Should a later kernel choice break that, the call stops here with what it
+  // has enqueued so far instead of finishing an iteration on weights packed in the wrong order.
+  if (po && perm) { set_error("fused engine: a pass of pinn_adam_loop_ext would run in permuted unit order"); return PINN_ERR_UNSUPPORTED; }
+  if (po ? po->pack : !(adam && adam->packed_valid))
     hipLaunchKernelGGL(k_pack, dim3((packN + 255) / 256), dim3(256), 0, s, n, g.WP, params, (float*)(base + w.wp),
                        (float*)(base + w.wtp), (float*)(base + w.bp), g.PW, g.PB, perm);
   // gradient copies the reduction reads: one per workgroup, or the batch kernel's shared atomic copies (register-major)
@@ -570,6 +695,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     default: rc = launch_fused<64>(n.K1, grad, P, grid, lds, s); break;
   }
   if (rc) return rc;
+  if (po) { po->grid = grid; po->n_copies = n_copies; return check_launch("fused pass"); }
   if (adam) {
     const int64_t np = n.n_params();
     hipLaunchKernelGGL(k_finish_adam, dim3((unsigned)((np + 63) / 64) + 1), dim3(256), 0, s, n, g.WP,
@@ -713,6 +839,88 @@ int fused_weighted_loss(const Net& n, const LossReq& rq, const float* params, co
                         int64_t ws_bytes, hipStream_t s) {
   if (const char* why = fused_weighted_refusal(n)) { set_error("fused engine, point weights: %s", why); return PINN_ERR_UNSUPPORTED; }
   return run(n, rq.grad != nullptr, &rq, params, X, N, nullptr, nullptr, ws, ws_bytes, s);
+}
+
+// ---- pinn_adam_loop_ext ---------------------------------------------------------------------------------------------------
+const char* fused_adam_ext_refusal(const Net& n, bool coefficients) {
+  if (const char* why = coefficients ? fused_coef_refusal(n) : fused_weighted_refusal(n)) return why;
+  Net n1 = n; n1.k = 0; n1.K1 = 1;
+  if (!fused_supports(n1, true)) return "the fidelity pass has no fused gradient kernel for this network";
+  return nullptr;
+}
+namespace {
+// The workspace of pinn_adam_loop_ext: the single entries' layout for the larger of the two point sets (packed weights,
+// scratch, and the RESIDUAL pass's partial sums and gradient copies), then the fidelity pass's partial sums and gradient
+// copies.  Every region holds the largest grid any pass on that many points launches (ws_layout).
+struct ExtLayout { WsLayout w; int64_t sums_f, grads_f, total; };
+ExtLayout ext_layout(const Net& n, const Geo& g, int64_t N_res, int64_t N_fid) {
+  ExtLayout e;
+  const int64_t nmax = std::max<int64_t>(std::max(N_res, N_fid), 1);
+  e.w = ws_layout(n, g, nmax);
+  int64_t off = e.w.total;
+  e.sums_f = off; off += align256((int64_t)e.w.max_grid * MAX_SUMS * 4);
+  e.grads_f = off; off += align256((int64_t)e.w.max_grid * g.PP * 4);
+  e.total = off;
+  return e;
+}
+}  // namespace
+int64_t fused_adam_ext_workspace_bytes(const Net& n, int64_t N_res, int64_t N_fid) {
+  return ext_layout(n, geo_of(n), N_res, N_fid).total;
+}
+int fused_adam_ext(const Net& n, const AdamExtReq& q, const float* X, int64_t N_res, void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (const char* why = fused_adam_ext_refusal(n, q.res.coef != nullptr)) {
+    set_error("fused engine, pinn_adam_loop_ext: %s", why); return PINN_ERR_UNSUPPORTED;
+  }
+  const Geo g = geo_of(n);
+  const ExtLayout L = ext_layout(n, g, N_res, q.N_fid);
+  if (!ws || ws_bytes < L.total) {
+    set_error("workspace too small: need %lld bytes, got %lld", (long long)L.total, (long long)ws_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  char* base = (char*)ws;
+  Net n1 = n; n1.k = 0; n1.K1 = 1;   // the fidelity term needs no input derivatives (pinn_mse_loss_grad)
+  const int64_t np = n.n_params();
+  const int64_t n_lam = q.lam ? (int64_t)q.w_rows * N_res : 0;
+  if (q.lam)   // w = m(lambda) of the first pass
+    hipLaunchKernelGGL(k_sa_weights, dim3((unsigned)((n_lam + 255) / 256)), dim3(256), 0, s, (const float*)q.lam, q.point_w,
+                       n_lam, q.sa_mask);
+  if (q.N_fid == 0 && q.row_cols > 0 && q.col_sums) (void)hipMemsetAsync(q.col_sums, 0, q.row_cols * sizeof(float), s);
+  ExtFinish f;
+  memset(&f, 0, sizeof(f));
+  f.param_blocks = (int)((np + 63) / 64);
+  f.n_terms = q.res.n_terms; f.n_cols = q.N_fid > 0 ? q.fid.n_cols : 0; f.row_cols = q.row_cols;
+  f.term_sums = q.res.sums; f.col_sums = q.col_sums; f.grad = q.res.grad;
+  f.params = q.params; f.m = q.m; f.v = q.v;
+  f.Wp = (float*)(base + L.w.wp); f.WTp = (float*)(base + L.w.wtp); f.Bp = (float*)(base + L.w.bp);
+  f.n_loss_rows = q.n_loss_rows; f.loss_rows = q.loss_rows;
+  f.n_coef = q.res.coef ? q.n_coef : 0;
+  f.coef = q.coef; f.coef_m = q.coef_m; f.coef_v = q.coef_v; f.coef_grad = q.coef_grad; f.coef_mask = q.coef_mask;
+  f.rows = q.w_rows; f.n_w = q.res.n_weighted; f.sa_mask = q.sa_mask; f.N = N_res;
+  f.scale = q.res.scale; f.fields = q.res.fields_out; f.lam = q.lam; f.lam_m = q.lam_m; f.lam_v = q.lam_v; f.point_w = q.point_w;
+  const unsigned blocks = (unsigned)f.param_blocks + 1 + (unsigned)((n_lam + 255) / 256);
+  for (int i = 0; i < q.n_iters; ++i) {
+    PassOnly pr = {L.w.scratch, L.w.wg_sums, L.w.wg_grads, i == 0 && !q.packed_valid, 0, 0};
+    int rc = run(n, true, &q.res, q.params, X, N_res, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pr);
+    if (rc) return rc;
+    // (on whichever kernel pinn_mse_loss_grad would take for these points: the cooperative one at padded width 64 while there
+    // is at most one tile per CU, else the tile kernel — both natural order, one gradient copy and one sums row per workgroup)
+    PassOnly pf = {L.w.scratch, L.sums_f, L.grads_f, false, 0, 0};
+    if (q.N_fid > 0) {
+      rc = run(n1, true, &q.fid, q.params, q.Xf, q.N_fid, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pf);
+      if (rc) return rc;
+    }
+    f.wg_r = (const float*)(base + L.w.wg_grads); f.copies_r = pr.n_copies; f.sums_r = (const float*)(base + L.w.wg_sums); f.grid_r = pr.grid;
+    f.wg_f = (const float*)(base + L.grads_f); f.copies_f = pf.n_copies; f.sums_f = (const float*)(base + L.sums_f); f.grid_f = pf.grid;
+    f.c = adam_scalars(q.lr[i], q.beta1, q.beta2, q.eps, q.step + i);
+    if (f.n_coef && q.coef_grad) f.cc = adam_scalars(q.lr_coef[i], q.beta1, q.beta2, q.eps, q.step + i);
+    if (q.lam) f.cw = adam_scalars(q.lr_w[i], q.beta1, q.beta2, q.eps, q.step + i);
+    f.losses = q.n_loss_rows > 0 ? q.losses + (int64_t)i * q.n_loss_rows : nullptr;
+    f.coef_log = q.coef_log ? q.coef_log + (int64_t)i * f.n_coef : nullptr;
+    hipLaunchKernelGGL(k_finish_adam_ext, dim3(blocks), dim3(256), 0, s, n, g.WP, g.PP, g.PW, f);
+    rc = check_launch("fused finish + adam (ext)");
+    if (rc) return rc;
+  }
+  return PINN_OK;
 }
 
 int64_t fused_fields_workspace_bytes(const Net& n) {

@@ -668,6 +668,116 @@ class Engine:
         self._packed_tok = (ws, params.data_ptr(), params._version, params_token, (N, int(n_res), nc, spec.residual_id, spec.corrected))
         return True
 
+    def adam_loop_ext(self, spec: ResidualSpec, term_scale, params, X, grad, m, v, step: int, lr: Sequence[float],
+                      Xf: Optional[torch.Tensor] = None, T: Optional[torch.Tensor] = None, out_col: Sequence[int] = (),
+                      col_scale=None, term_sums=None, col_sums=None,
+                      coef=None, coef_m=None, coef_v=None, coef_grad=None, coef_mask=None, coef_log=None, lr_coef=None,
+                      point_w=None, fields=None, lam=None, lam_m=None, lam_v=None, sa_mask: str = "square", lr_w=None,
+                      beta1=0.9, beta2=0.999, eps=1e-8, loss_rows: Optional[torch.Tensor] = None,
+                      losses: Optional[torch.Tensor] = None, params_token=None) -> bool:
+        """len(lr) Adam iterations of the residual with closure coefficients (`coef`) or with point weights (`point_w`)
+        enqueued by ONE call (pinn_adam_loop_ext): per iteration the residual pass on X, the fidelity pass on (Xf, T) when Xf
+        is given (Xf may be X itself), and one finishing kernel — gradient, Adam on params / m / v, the sums, the weighted
+        losses (losses[i] = loss_rows @ [col sums | term sums]) and
+          coefficients: coef_log[i] <- coef as iteration i ran with it, coef_grad <- its gradient (times coef_mask), Adam
+            with lr_coef[i] on coef / coef_m / coef_v; coef_grad=None: the coefficients are values only;
+          weights: lam=None — point_w (N,) or (w_rows, N) is fixed and read only (fields, if given, gets every pass's
+            unweighted signed fields); lam given — the self-adaptive multipliers: Adam with lr_w[i] raises lam / lam_m /
+            lam_v (w_rows, N) along the weighted loss and point_w = lam^2 (sa_mask "square") or lam ("linear") is rewritten.
+        grad is OVERWRITTEN with the last iteration's gradient.  Returns False — nothing launched, the reason in
+        last_error() — where the request is not served (engine, precision, activation, width, dropout, corrected, the
+        continuity residuals with coef, both groups).  The packing kernel is skipped under loss_grad_adam_step's rules."""
+        spec.first_order("adam_loop_ext")
+        N, nc = X.shape[0], len(out_col)
+        lrs = [float(x) for x in lr]
+        k = len(lrs)
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        for t, nme in ((grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
+            self._chk(t, nme, (self.n_params,))
+        self._chk(term_scale, "term_scale", (spec.n_terms,)); self._chk(term_sums, "term_sums", (spec.n_terms,))
+        n_fid = 0 if Xf is None else Xf.shape[0]
+        if nc:
+            self._chk(col_sums, "col_sums", (nc,))
+        if n_fid:
+            self._chk(Xf, "Xf", (n_fid, self.desc.d_in)); self._chk(T, "T", (n_fid, nc)); self._chk(col_scale, "col_scale", (nc,))
+        n_rows = 0
+        if loss_rows is not None:
+            n_rows = loss_rows.shape[0]
+            self._chk(loss_rows, "loss_rows", (n_rows, nc + spec.n_terms)); self._chk(losses, "losses", (k, n_rows))
+        ex = _lib.PinnAdamExtras()
+        kind = ("coef" if coef is not None else "") + ("w" if point_w is not None else "") + ("sa" if lam is not None else "")
+        keep = []          # ctypes arrays must outlive the call
+        if coef is not None:
+            nco = max(spec.n_coefs, 1)
+            for t, nme in ((coef, "coef"), (coef_m, "coef_m"), (coef_v, "coef_v"), (coef_grad, "coef_grad"), (coef_mask, "coef_mask")):
+                if t is not None:
+                    self._chk(t, nme, (nco,))
+            if coef_log is not None:
+                self._chk(coef_log, "coef_log", (k, nco))
+            ex.coef, ex.coef_m, ex.coef_v, ex.coef_grad = (t.data_ptr() if t is not None else None for t in (coef, coef_m, coef_v, coef_grad))
+            ex.coef_mask = coef_mask.data_ptr() if coef_mask is not None else None
+            ex.coef_log = coef_log.data_ptr() if coef_log is not None else None
+        if point_w is not None:
+            if point_w.dim() not in (1, 2) or point_w.shape[-1] != N:
+                raise PinnError(f"adam_loop_ext: point_w must be (N,) or (w_rows, N) with N = {N}, got {tuple(point_w.shape)}")
+            self._chk(point_w, "point_w", tuple(point_w.shape))
+            ex.point_w, ex.w_rows = point_w.data_ptr(), (1 if point_w.dim() == 1 else int(point_w.shape[0]))
+            if fields is not None:
+                self._chk(fields, "fields", (spec.n_fields, N)); ex.fields = fields.data_ptr()
+            if lam is not None:
+                if sa_mask not in ("square", "linear"):
+                    raise PinnError(f"adam_loop_ext: sa_mask = {sa_mask!r}: use 'square' or 'linear'")
+                for t, nme in ((lam, "lam"), (lam_m, "lam_m"), (lam_v, "lam_v")):
+                    if t is not None:
+                        self._chk(t, nme, (ex.w_rows, N))
+                ex.lam, ex.lam_m, ex.lam_v = (t.data_ptr() if t is not None else None for t in (lam, lam_m, lam_v))
+                ex.sa_mask = 0 if sa_mask == "square" else 1
+
+        def darr(xs):
+            if xs is None:
+                return None
+            xs = [float(x) for x in xs]
+            if len(xs) != k:
+                raise PinnError(f"adam_loop_ext: {len(xs)} learning rates for {k} iterations")
+            a = (C.c_double * max(k, 1))(*xs); keep.append(a)
+            return a
+
+        idx = self._index()
+        key = ("adamext", kind, spec.residual_id, spec.corrected, N, n_fid)
+        with torch.cuda.device(idx):
+            need = self._ws_need.get(key)
+            if need is None:
+                c_need = C.c_int64()
+                rc = self.lib.pinn_query_adam_ext_workspace(C.byref(self._d()), C.byref(spec.c_struct()), C.byref(ex), N, n_fid,
+                                                            C.byref(c_need))
+                if rc == _lib.ERR_UNSUPPORTED:
+                    return False
+                check(rc, "pinn_query_adam_ext_workspace")
+                need = self._ws_need[key] = c_need.value
+            ws = self._ws.get("adamext")
+            if ws is None or ws.numel() < need:
+                self._ws["adamext"] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            req = ("ext", kind, N, n_fid, nc, spec.residual_id, spec.corrected)
+            tok = self._packed_tok
+            packed_valid = (tok is not None and tok[0] is ws and tok[1] == params.data_ptr() and tok[2] == params._version
+                            and tok[3] == params_token and tok[4] == req)
+            self._packed_tok = None
+            self._ens_packed_tok = None
+            st = _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0, float(beta1), float(beta2), float(eps),
+                                    1 if packed_valid else 0, n_rows, _ptr(loss_rows), _ptr(losses))
+            oc = (C.c_int32 * max(nc, 1))(*out_col)
+            rc = self.lib.pinn_adam_loop_ext(
+                C.byref(self._d()), C.byref(spec.c_struct()), _ptr(term_scale), _ptr(Xf) if n_fid else None,
+                _ptr(T) if n_fid else None, n_fid, nc, oc, _ptr(col_scale) if n_fid else None, _ptr(params), _ptr(X), N,
+                _ptr(term_sums), _ptr(col_sums) if nc else None, _ptr(grad), C.byref(st), C.byref(ex), k, darr(lrs),
+                darr(lr_coef), darr(lr_w), _ptr(ws), ws.numel(), C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return False
+        check(rc, "pinn_adam_loop_ext")
+        if k > 0:
+            self._packed_tok = (ws, params.data_ptr(), params._version, params_token, req)
+        return True
+
     # ---- the device-resident L-BFGS loop (pinn_lbfgs_loop) ------------------------------------------------------------
     def lbfgs_loop_query(self, N: int, history_size: int) -> Tuple[int, int]:
         """(workspace bytes, state bytes) of lbfgs_loop on N points with this history size (pinn_query_lbfgs_loop)."""

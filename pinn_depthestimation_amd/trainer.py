@@ -160,6 +160,32 @@ def coefficient_refusal(residual, coefficients, trainable, corrected=False, eddy
     return None
 
 
+def fold_extras_refusal(fold_extras=False, coefficients=False, weighted=False, rad_importance=False, residual_batch=None,
+                        resample="uniform", dropout_rate=0.0, reducer_active=False, eddy_viscosity=0.0, custom_evaluator=False,
+                        fold_adam=True):
+    """Why Adam iterations with runtime closure coefficients or point weights stay on the classic path although
+    fold_extras is asked for (None: they run as device-enqueued runs, Engine.adam_loop_ext — or there is nothing to decide:
+    the option is off, or the configuration has neither coefficients nor weights).  Nothing is refused outright: the classic
+    path computes the same iteration.  Pure host logic."""
+    if not fold_extras or not (coefficients or weighted or rad_importance):
+        return None
+    if not fold_adam:
+        return "fold_adam is off: every Adam iteration takes the classic path"
+    if reducer_active:
+        return "data parallelism: the all-reduce of every iteration is issued by the host"
+    if eddy_viscosity:
+        return "eddy_viscosity != 0: the second-order residual is layer kernels per chunk, not one pass"
+    if custom_evaluator:
+        return "a custom evaluator: the device-enqueued runs are the library's own"
+    if rad_importance or resample == "rad":
+        return "resample='rad': the host draws and weights a mini-batch for every iteration"
+    if residual_batch is not None:
+        return "residual_batch: the host draws a mini-batch for every iteration"
+    if dropout_rate and dropout_rate > 0:
+        return "dropout: a fresh seed per forward pass has no place in an enqueued run"
+    return None
+
+
 def _as_f32(a, device) -> Optional[torch.Tensor]:
     if a is None:
         return None
@@ -304,17 +330,33 @@ class HipEvaluator:
         self.eng.adam_step(theta, grad, m, v, step, lr)
 
     def adam_iteration(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums, m, v, step, lr,
-                       loss_rows=None, losses=None, params_token=None) -> bool:
+                       loss_rows=None, losses=None, params_token=None, extras=None) -> bool:
         """loss_func + backward + Adam.step (train.py:189-193) in two launches where the engine can
-        (Engine.loss_grad_adam_step); False — nothing done — otherwise: the caller then runs __call__ + adam_step."""
+        (Engine.loss_grad_adam_step); False — nothing done — otherwise: the caller then runs __call__ + adam_step.
+        extras (trainer.PINN(fold_extras=True)): with runtime coefficients or point weights set, the keyword arguments of
+        Engine.adam_loop_ext that belong to them (moments, learning rates, coef_log / the multipliers) — the request then
+        runs as a device-enqueued run of that entry; without it such requests take the classic path."""
         if (self.eng_drop is not None and self.training) or Xr is None or Xr.shape[0] == 0:
             return False
         if self.spec.nu != 0:     # the second-order residual is layer kernels per chunk, not one pass: the classic path
             return False
-        if self.coef is not None:     # the folded iteration runs the entries that carry the constants: the classic path
-            return False
-        if self.point_w is not None:  # ... and the unweighted ones
-            return False
+        if self.coef is not None or self.point_w is not None:
+            # the folded iteration runs the entries that carry the constants and no weights: these requests have a loop entry
+            # of their own, taken only when the trainer asks for it
+            if extras is None:
+                return False
+            single = not isinstance(lr, (list, tuple))
+            has_fid = Xf is not None and Xf.shape[0] > 0
+            kw = dict(extras)
+            if self.coef is not None:
+                kw.update(coef=self.coef, coef_grad=self.coef_grad)
+            else:
+                kw.update(point_w=self.point_w, fields=self.fields_out)
+            return self.eng.adam_loop_ext(self.spec, res_scale, theta, Xr, grad, m, v, step, [lr] if single else lr,
+                                          Xf=Xf if has_fid else None, T=Tf if has_fid else None, out_col=self.fid_cols,
+                                          col_scale=fid_scale, term_sums=res_sums, col_sums=fid_sums, loss_rows=loss_rows,
+                                          losses=losses.reshape(1, -1) if single and losses is not None else losses,
+                                          params_token=params_token, **kw)
         has_fid = Xf is not None and Xf.shape[0] > 0
         if not has_fid:
             if fid_sums.numel():       # (a configuration with fidelity outputs but no fidelity points: classic path)
@@ -372,8 +414,14 @@ class PINN:
                  resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0,
                  corrected: bool = False, eddy_viscosity: float = 0.0, coefficients: Optional[dict] = None,
                  trainable_coefficients: Sequence[str] = (), residual_weights=None, self_adaptive=None,
-                 rad_importance: Optional[bool] = None):
-        """residual_weights: fixed weights on the collocation points' squared residuals, (N_res,) or (n_w, N_res) with
+                 rad_importance: Optional[bool] = None, fold_extras: bool = False):
+        """fold_extras (or the config key adam_optimizer.fold_extras; off unless asked for): Adam iterations with runtime
+        coefficients, fixed residual_weights or self_adaptive weights run as device-enqueued runs (Engine.adam_loop_ext: three
+        launches per iteration, no Python in between; the coefficients, the multipliers and their Adam moments are updated on
+        the device) instead of the classic path.  Checkpoint iterations, mat_dump_iter, residual_batch, resample="rad",
+        dropout, data parallelism and eddy_viscosity keep the classic path (fold_extras_refusal says why;
+        self.fold_extras_why holds the answer); the L-BFGS stage is unchanged.
+        residual_weights: fixed weights on the collocation points' squared residuals, (N_res,) or (n_w, N_res) with
         n_w = ResidualSpec.n_weighted_terms — a mask, a confidence map; set_residual_weights changes them later.  The
         normaliser stays the point count (res_scale = weight / N), not the sum of the weights.
         self_adaptive (or the config key loss.self_adaptive): True, or {"init": 1.0, "mask": "square" | "linear", "per_term":
@@ -433,6 +481,11 @@ class PINN:
             if why:
                 raise PinnError(why)
         self.fold_adam, self._adam_folded, self._folded_iters, self._run_losses = bool(fold_adam), False, 0, None
+        self.fold_extras = bool(fold_extras) or cfg.fold_extras
+        self.fold_extras_why = fold_extras_refusal(self.fold_extras, bool(coef_in or coef_tr), residual_weights is not None or sa_opt is not None,
+                                                   rad_imp, residual_batch, resample, cfg.dropout_rate, self.reducer.active, nu0,
+                                                   evaluator is not None, bool(fold_adam))
+        self._run_coef_log = None
         self._fold_refused = None   # key of the (evaluator, point sets) whose folded request the engine has refused
         self.layers = cfg.layers                                           # train.py:52-56
         self.dnn = dnn if dnn is not None else DNN(cfg.layers, cfg.dropout_rate, cfg.init_type)
@@ -659,7 +712,8 @@ class PINN:
             self._ring[len(self._ring_iters)][3:].copy_(self._coef)
         self._adam_folded = _adam is not None and self.evaluator.adam_iteration(
             self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad, self._fid_sums, self._res_sums,
-            *_adam, loss_rows=self._loss_mat, losses=vec, params_token=self.dnn.write_token(self.theta))
+            *_adam, loss_rows=self._loss_mat, losses=vec, params_token=self.dnn.write_token(self.theta),
+            **({"extras": self._fold_extras_kw(1)} if self._has_extras() else {}))
         if not self._adam_folded:
             self.buf.zero_()
             self.evaluator(self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad,
@@ -774,6 +828,11 @@ class PINN:
         # One process, no checkpoint inside this iteration (the reference saves the PRE-update weights from inside
         # loss_func, train.py:175-179): the evaluator may fold the update into the pass's last kernel.
         fold = (self._may_fold() and not self._checkpoint_due(self.iter + 1))
+        if fold and self._has_extras() and self.mat_dump_iter is not None and self.iter == self.mat_dump_iter:
+            # the prediction dump's iteration takes the classic path.  The plain request folds it (the dump is written at the
+            # start of loss_func either way); with extras the .mat also carries the coefficients / residual_weights, and the
+            # iteration that hands them over is kept the one that has always written that file.  _foldable_run cuts runs here.
+            fold = False
         if self._coef is not None:
             self.evaluator.coef_grad = self._coef_grad      # (None when nothing is trainable: values only)
         self._sa_frozen = False
@@ -807,11 +866,35 @@ class PINN:
         """The folded iteration is worth asking for: switched on, one process, an evaluator that has it, and the engine
         has not already refused this very request (wide / generic engine, a large split request: the refusal is remembered
         per evaluator and point sets instead of being re-discovered by two refused C calls every iteration)."""
-        return (self.fold_adam and self._coef is None and not self._weighted() and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
+        if self._has_extras() and not (self.fold_extras and self.fold_extras_why is None and self.residual_batch is None):
+            return False      # coefficients / point weights: the classic path unless fold_extras is on and applies
+        return (self.fold_adam and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
                 and self._fold_refused != self._fold_key())
 
     def _weighted(self) -> bool:
         return self._w_fixed is not None or self.rad_importance
+
+    def _has_extras(self) -> bool:
+        return self._coef is not None or self._weighted()
+
+    def _fold_extras_kw(self, k: int, coef_log: Optional[torch.Tensor] = None) -> dict:
+        """What Engine.adam_loop_ext needs beside the evaluator's own tensors for the next k iterations: the coefficients'
+        or the multipliers' Adam state and their learning rates on the StepLR schedule (current_coefficient_lr /
+        current_weight_lr at each iteration); coef_log: where the coefficients each iteration ran with go."""
+        a = self.config.adam
+        sched = [a["scheduler_gamma"] ** ((self._sched_steps + i) // a["scheduler_step_size"]) for i in range(k)]
+        if self._coef is not None:
+            kw = {"coef_log": coef_log}
+            if self._coef_grad is not None:
+                base = float(a.get("coefficient_learning_rate", a["learning_rate"]))
+                kw.update(coef_m=self._coef_m, coef_v=self._coef_v, lr_coef=[base * f for f in sched])
+                if len(self.trainable_coefficients) < len(self.coef_names):
+                    kw["coef_mask"] = self._coef_mask
+            return kw
+        if self._lam is not None:
+            return {"lam": self._lam, "lam_m": self._lam_m, "lam_v": self._lam_v, "sa_mask": self.self_adaptive["mask"],
+                    "lr_w": [self.config.weight_learning_rate * f for f in sched]}
+        return {}
 
     def _foldable_run(self, n: int) -> int:
         """How many of the next n Adam iterations can be enqueued by ONE call: full batch, one process, nothing the
@@ -859,19 +942,38 @@ class PINN:
         if self._run_losses is None or self._run_losses.shape[0] < k:
             self._run_losses = torch.zeros(max(k, self.MAX_RUN), 3, dtype=torch.float32, device=self.device)
         out = self._run_losses[:k]
+        ext, clog = {}, None
+        if self._has_extras():       # (fold_extras: _may_fold has said so) the run of Engine.adam_loop_ext
+            if self._coef is not None:
+                self.evaluator.coef_grad = self._coef_grad      # (None when nothing is trainable: values only)
+                if self._run_coef_log is None or self._run_coef_log.shape[0] < k:
+                    self._run_coef_log = torch.zeros(max(k, self.MAX_RUN), len(self.coef_names), dtype=torch.float32, device=self.device)
+                clog = self._run_coef_log[:k]
+            if self._lam is not None:
+                self._sa_frozen = False
+                self.evaluator.fields_out = self._sa_fields
+            ext = {"extras": self._fold_extras_kw(k, clog)}
         if not self.evaluator.adam_iteration(self.theta, self.Xf, self.Tf, self._fid_scale, self.Xr, self._res_scale, self.grad,
                                              self._fid_sums, self._res_sums, self._adam_m, self._adam_v, self._adam_step + 1,
-                                             lrs, loss_rows=self._loss_mat, losses=out, params_token=self.dnn.write_token(self.theta)):
+                                             lrs, loss_rows=self._loss_mat, losses=out, params_token=self.dnn.write_token(self.theta), **ext):
             return False
         if self.log_every == 1:                      # every iteration logged: one copy into the ring
             r0 = len(self._ring_iters)
-            self._ring[r0:r0 + k].copy_(out)
+            if clog is None:
+                self._ring[r0:r0 + k].copy_(out)
+            else:                                    # ... and the coefficients each iteration ran with beside its losses
+                self._ring[r0:r0 + k, :3].copy_(out)
+                self._ring[r0:r0 + k, 3:].copy_(clog)
             self._ring_iters.extend(range(self.iter + 1, self.iter + k + 1))
         else:
             for i in range(k):
                 it = self.iter + 1 + i
                 if it % self.log_every == 0 or it % 1000 == 0:
-                    self._ring[len(self._ring_iters)].copy_(out[i])
+                    if clog is None:
+                        self._ring[len(self._ring_iters)].copy_(out[i])
+                    else:
+                        self._ring[len(self._ring_iters)][:3].copy_(out[i])
+                        self._ring[len(self._ring_iters)][3:].copy_(clog[i])
                     self._ring_iters.append(it)
         self.iter += k
         self._adam_step += k
