@@ -99,6 +99,16 @@ extern "C" {
 /* activation (dnn.py:18-21) */
 #define PINN_ACT_TANH 0        /* init_type == 'xavier'  */
 #define PINN_ACT_LEAKY_RELU 1  /* init_type == 'kaiming', negative_slope 0.01 */
+/* Fourier-feature first layer: a_1 = sin(W_0 x + b_0) on the FIRST hidden layer, tanh on every other hidden layer, the
+   last layer bare (n_hidden == 1: the only hidden layer is the sine).  W_0 and b_0 are the ordinary first-layer
+   parameters of the flat buffer: no struct gains a field.  Served by the generic engine for every first-order request
+   and by the fused tile kernel (AUTO, FUSED, FUSED_TILE) for the plain requests: forward, forward jet with k in {0, 2, 3},
+   the residual / mse / merged / split loss calls and the folded Adam and L-BFGS loops on them.  Requests whose fused
+   kernel has no sine instance (coefficients, point weights, corrected radiation stress, residual fields, pinn_jet_backward,
+   dropout) run on the generic engine under AUTO and are refused under an explicit FUSED*; FUSED_COOP, FUSED_BATCH, WIDE,
+   bf16, the ensemble entries and the second-order entries (jet2 / residual2) are refused with a message that names the
+   sine first layer. */
+#define PINN_ACT_SIN_TANH 2
 
 /* engine selector (0 lets the library pick the fastest kernel that supports the shape) */
 #define PINN_ENGINE_AUTO 0

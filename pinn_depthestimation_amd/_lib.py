@@ -15,6 +15,7 @@ PINN_MAX_ROLES = 8
 PINN_MAX_COEFS = 4
 
 ACT_TANH, ACT_LEAKY_RELU = 0, 1
+ACT_SIN_TANH = 2      # sine on the first hidden layer, tanh on the others (pinn_hip.h: PINN_ACT_SIN_TANH)
 ENGINE_AUTO, ENGINE_GENERIC, ENGINE_FUSED, ENGINE_WIDE = 0, 1, 2, 3
 ENGINE_FUSED_TILE, ENGINE_FUSED_COOP, ENGINE_FUSED_BATCH = 4, 5, 6     # sub-values of ENGINE_FUSED: force one of its kernels (pinn_hip.h)
 ABI_VERSION = 4

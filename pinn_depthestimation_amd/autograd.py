@@ -48,9 +48,12 @@ _ENGINES = {}
 def engine_for(model, grad_cols: Sequence[int], device, drop=(0.0, 0)) -> Engine:
     """The engine for this geometry (cached), with the dropout seed of the CURRENT forward pass set on it:
     drop = (p, seed); every kernel call of one pass, forward and reverse, runs under the pass's own seed."""
-    key = (tuple(model.layer_sizes), tuple(grad_cols), model.init_type, str(device), float(drop[0]))
+    # (DNN.activation_id: the sine first layer is an activation of its own; a stand-in without it goes by its init_type)
+    act = getattr(model, "activation_id", None)
+    act = ACTIVATION_OF_INIT[model.init_type] if act is None else int(act)
+    key = (tuple(model.layer_sizes), tuple(grad_cols), model.init_type, act, str(device), float(drop[0]))
     if key not in _ENGINES:
-        desc = NetDesc.from_layers(model.layer_sizes, grad_cols, ACTIVATION_OF_INIT[model.init_type],
+        desc = NetDesc.from_layers(model.layer_sizes, grad_cols, act,
                                    dropout_p=float(drop[0]))
         _ENGINES[key] = Engine(desc, device)
     eng = _ENGINES[key]

@@ -49,6 +49,10 @@ class PinnConfig:
     grad_cols: Tuple[int, ...] = ()
     trues: List[str] = field(default_factory=list)
     unknowns: List[str] = field(default_factory=list)
+    # layers.first_activation ("sin": a Fourier-feature first layer, dnn.DNN) and layers.fourier_sigma (the standard deviation
+    # of its weights, in the units of the normalised inputs); absent keys mean the reference's network
+    first_activation: Optional[str] = None
+    fourier_sigma: float = 1.0
 
     @property
     def weight_fid(self) -> float:
@@ -139,6 +143,10 @@ def load_config(src) -> PinnConfig:
     cfg = PinnConfig(raw=raw, layers=layers, dropout_rate=float(L.get("dropout_rate", 0.0)),
                      init_type=L.get("init_type", "xavier"), adam=adam, lbfgs=lb,
                      loss_weights=dict(raw.get("loss", {})), variant="train")
+    cfg.first_activation = L.get("first_activation")
+    if cfg.first_activation not in (None, "sin"):
+        raise ValueError(f"layers.first_activation = {cfg.first_activation!r}: use \"sin\" or leave the key out")
+    cfg.fourier_sigma = float(L.get("fourier_sigma", 1.0))
     if "data" in raw and "data_residual" not in raw:          # config_CMB_h.json:33-41
         d = raw["data"]
         cfg.variant = "newmethod"

@@ -341,6 +341,70 @@ __device__ __forceinline__ void activate_adjoint_to(const f4 (&G)[K1][NT], const
     }
 }
 
+// ---- the sine first layer (PINN_ACT_SIN_TANH): layer 0's activation and its adjoint; layers >= 1 take the tanh forms above ----
+// forward: a = sin z, adot_j = cos z * zdot_j.  z_0 is NOT the MFMA chain's fp32 sum: at a Fourier layer's arguments its
+// rounding is the largest error of the whole pass (residuals.h, sincos_f64arg), so the value is formed in double from the
+// unit's row of the padded W_0 (row stride 16) and the point's row of X (d_in terms, vector ALU; the MFMAs carry the
+// tangents, which are columns of W_0 and exact).  q: the lane group, so register r of tile MT is unit 16 MT + 4 q + r.
+template <int NT, int K1>
+__device__ __forceinline__ void activate_sin_to(const f4 (&acc)[K1][NT], const f4 (&bias)[NT], f4 (&a)[K1][NT],
+                                                const float* __restrict__ W0, const float* __restrict__ xrow, int d_in, int q) {
+#pragma unroll
+  for (int MT = 0; MT < NT; ++MT)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float sn, cs;
+      sincos_f64arg(sin_layer_z(W0 + (16 * MT + 4 * q + r) * 16, bias[MT][r], xrow, d_in), sn, cs);
+      a[0][MT][r] = sn;
+#pragma unroll
+      for (int c = 1; c < K1; ++c) a[c][MT][r] = acc[c][MT][r] * cs;
+    }
+}
+// reverse: zbardot_j = cos z * abardot_j ;  zbar = cos z * abar - sin z * sum_j abardot_j * zdot_j.
+// cos z cannot be rebuilt from the stored a_1 = sin z and is not spilled either (a slot per wave more would change ws_layout):
+// z_0 = W_0 x + b_0 is formed AGAIN, at the end of the reverse sweep where only the adjoint G and the output Z are live — W_0
+// and b_0 reloaded, the forward's own double sum (activate_sin_to: z_0 bit for bit).  The tangents zdot_j are the columns
+// dir_col[j] of W_0; they come out of W_0 as the A operand against the unit tangent, one quantity at a time, so that a single
+// temporary tile row is live beside cos z, sin z and the cross sum.  `in` is the layer-0 input jet (input_jet of the body).
+template <int NT, int K1, int KRI>
+__device__ __forceinline__ void sin_adjoint_to(const float* __restrict__ W0, const float* __restrict__ B0, const f4 (&in)[K1][1],
+                                               const f4 (&G)[K1][NT], f4 (&Z)[K1][NT], int p, int q,
+                                               const float* __restrict__ xrow, int d_in) {
+  f4 w0[NT][1];
+  load_w<1, NT>(W0, w0, p, q);
+  f4 bias[NT];
+  load_bias<NT>(B0, bias, q);
+  f4 cz[NT], sz[NT], cross[NT];
+#pragma unroll
+  for (int MT = 0; MT < NT; ++MT) {
+    cross[MT] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float sn, cs;
+      sincos_f64arg(sin_layer_z(W0 + (16 * MT + 4 * q + r) * 16, bias[MT][r], xrow, d_in), sn, cs);
+      sz[MT][r] = sn; cz[MT][r] = cs;
+    }
+  }
+#pragma unroll
+  for (int c = 1; c < K1; ++c) {
+    f4 bv[1][1], zd[1][NT];
+    bv[0][0] = in[c][0];
+    zero_tiles<NT, 1>(zd);
+    gemm_chain<1, NT, 1, KRI>(w0, bv, zd);
+#pragma unroll
+    for (int MT = 0; MT < NT; ++MT)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        cross[MT][r] = fmaf(G[c][MT][r], zd[0][MT][r], cross[MT][r]);
+        Z[c][MT][r] = G[c][MT][r] * cz[MT][r];
+      }
+  }
+#pragma unroll
+  for (int MT = 0; MT < NT; ++MT)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Z[0][MT][r] = fmaf(-sz[MT][r], cross[MT][r], cz[MT][r] * G[0][MT][r]);
+}
+
 template <int NT, int K1>
 __device__ __forceinline__ void spill(float* __restrict__ slot, const f4 (&v)[K1][NT], int lane) {
 #pragma unroll
@@ -1023,6 +1087,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
   static_assert(EPI != EPI_PEC || (KRO == 0 && !DROP && K1 == 3 && ACT == PINN_ACT_TANH), "corrected-residual instances: tanh, k = 2, natural unit order, no dropout");
   static_assert(EPI != EPI_COEF || (KRO == 0 && !DROP && (K1 == 3 || K1 == 4) && ACT == PINN_ACT_TANH), "coefficient instances: tanh, k = 2 or 3, natural unit order, no dropout");
   static_assert(EPI != EPI_WEIGHTED || (KRO == 0 && !DROP && (K1 == 3 || K1 == 4) && ACT == PINN_ACT_TANH), "weighted instances: tanh, k = 2 or 3, natural unit order, no dropout");
+  static_assert(ACT != PINN_ACT_SIN_TANH || (EPI == EPI_GENERIC && KRO == 0 && !DROP && (K1 == 1 || K1 == 3 || K1 == 4)), "sine-first-layer instances: generic epilogue, k = 0, 2 or 3, natural unit order, no dropout");
 #include "fused_tile_body.inc"
 }
 
@@ -1063,6 +1128,10 @@ int launch_fused_coef(int K1, bool grad, const FusedParams& P, int grid, size_t 
 // point-weighted instances (EPI_WEIGHTED; K1 = 3 or 4, tanh): pinn_fused_wt.inc, one translation unit per WP (pinn_fused_wt_wXX.hip)
 template <int WP>
 int launch_fused_wt(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+// sine-first-layer instances (PINN_ACT_SIN_TANH, EPI_GENERIC; K1 = 1, 3 or 4): pinn_fused_sin.inc, one translation unit per WP
+// (pinn_fused_sin_wXX.hip)
+template <int WP>
+int launch_fused_sin(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
 // ensemble instances (k_fused_ens: grid (gx, M), gradient pass, tanh, K1 = 3 or 4): pinn_fused_ens.inc, one translation unit per WP
 // (pinn_fused_ens_wXX.hip)
 template <int WP>

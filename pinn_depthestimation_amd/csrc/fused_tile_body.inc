@@ -6,6 +6,8 @@
   constexpr int KRL = IO1 ? KRO : 4;        // k-steps of the output layer's reverse contraction
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NTH = WP / 16;
+  constexpr bool SIN0 = ACT == PINN_ACT_SIN_TANH;                // sine on hidden layer 0 (fused_kernel.h: activate_sin_to, sin_adjoint_to) ...
+  constexpr int ACT_H = SIN0 ? PINN_ACT_TANH : ACT;              // ... and this activation on every other hidden layer
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int p = lane & 15, q = lane >> 4;
   float* lacc = smem;
@@ -93,7 +95,8 @@
       zero_tiles<NTH, K1>(acc0);
       gemm_chain<1, NTH, K1, KRI>(w0, b0, acc0);
       PINN_STAMP(0);
-      activate_to<ACT, NTH, K1, DROP>(acc0, bias, a, &dl, 0, q);
+      if constexpr (SIN0) activate_sin_to<NTH, K1>(acc0, bias, a, Wp_, P.X + ptc * P.d_in, P.d_in, q);
+      else activate_to<ACT, NTH, K1, DROP>(acc0, bias, a, &dl, 0, q);
     }
     PINN_STAMP(1);
     for (int l = 1; l < L; ++l) {
@@ -105,7 +108,7 @@
       auto sp = [&]() { if (GRAD) spill<NTH, K1>(scr + (l - 1) * SLOT, a, lane); };
       gemm_stream<NTH, NTH, K1>(Wp_ + w_off_p<WP>(l), Wp_ + w_off_p<WP>(l + 1), ws, a, nx, p, q, sp);
       PINN_STAMP(0);
-      activate_to<ACT, NTH, K1, DROP>(nx, bias, a, &dl, l, q);
+      activate_to<ACT_H, NTH, K1, DROP>(nx, bias, a, &dl, l, q);
       PINN_STAMP(1);
     }
     f4 G[K1][1];
@@ -150,7 +153,10 @@
         f4 g[K1][NTH];
         zero_tiles<NTH, K1>(g);
         gemm_chain<1, NTH, K1, KRL>(wtl, G, g);
-        activate_adjoint_to<ACT, NTH, K1, DROP>(g, a, z, &dl, L - 1, q);
+        if constexpr (SIN0) {   // L == 1: the output layer's adjoint feeds the sine adjoint directly
+          if (L == 1) { f4 b1[K1][1]; input_jet(b1); sin_adjoint_to<NTH, K1, KRI>(Wp_, Bp_ + b_off_p<WP>(0), b1, g, z, p, q, P.X + ptc * P.d_in, P.d_in); }
+          else activate_adjoint_to<ACT_H, NTH, K1, DROP>(g, a, z, &dl, L - 1, q);
+        } else activate_adjoint_to<ACT, NTH, K1, DROP>(g, a, z, &dl, L - 1, q);
       }
       for (int l = L - 1; l >= 1; --l) {
         PINN_STAMP(3);
@@ -162,7 +168,10 @@
         PINN_STAMP(6);
         weight_grad<NTH, NTH, K1>(sink, l, w_off_p<WP>(l), P.PW + b_off_p<WP>(l), z, ai, tb, lane);
         PINN_STAMP(5);
-        activate_adjoint_to<ACT, NTH, K1, DROP>(g2, ai, z, &dl, l - 1, q);
+        if constexpr (SIN0) {   // l == 1: the adjoint of layer 0, the sine, from a recomputed z_0
+          if (l == 1) { f4 b1[K1][1]; input_jet(b1); sin_adjoint_to<NTH, K1, KRI>(Wp_, Bp_ + b_off_p<WP>(0), b1, g2, z, p, q, P.X + ptc * P.d_in, P.d_in); }
+          else activate_adjoint_to<ACT_H, NTH, K1, DROP>(g2, ai, z, &dl, l - 1, q);
+        } else activate_adjoint_to<ACT, NTH, K1, DROP>(g2, ai, z, &dl, l - 1, q);
         PINN_STAMP(4);
       }
       {  // layer 0: z = zbar_0, input = (x, unit tangents)

@@ -68,9 +68,9 @@ int make_net(const pinn_desc* d, Net* n) {
     return PINN_ERR_INVALID;
   }
   if (d->k < 0 || d->k > PINN_MAX_DIRS) { set_error("k=%d outside 0..%d", d->k, PINN_MAX_DIRS); return PINN_ERR_INVALID; }
-  if (d->activation != PINN_ACT_TANH && d->activation != PINN_ACT_LEAKY_RELU) {
+  if (d->activation != PINN_ACT_TANH && d->activation != PINN_ACT_LEAKY_RELU && d->activation != PINN_ACT_SIN_TANH) {
     // mirrors the ValueError of dnn.py:23 for an unknown init_type
-    set_error("invalid activation %d (0 = tanh/'xavier', 1 = leaky_relu/'kaiming')", d->activation);
+    set_error("invalid activation %d (0 = tanh/'xavier', 1 = leaky_relu/'kaiming', 2 = sine first layer then tanh)", d->activation);
     return PINN_ERR_INVALID;
   }
   n->d_in = d->d_in; n->d_out = d->d_out; n->L = d->n_hidden; n->W = d->width;
@@ -121,6 +121,12 @@ static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc
     return (asked == PINN_ENGINE_AUTO || asked == PINN_ENGINE_FUSED) && fused_ok ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
   }
   if (n.prec == PINN_PREC_BF16) {   // bf16 operands exist on the wide engine only
+    if (n.act == PINN_ACT_SIN_TANH) {
+      set_error("precision bf16 is implemented on the wide engine only, which has no kernel for the sine first layer "
+                "(activation 2): use precision fp32");
+      *rc = PINN_ERR_UNSUPPORTED;
+      return PINN_ENGINE_WIDE;
+    }
     if ((asked != PINN_ENGINE_AUTO && asked != PINN_ENGINE_WIDE) || !wide_supports(n)) {
       set_error("precision bf16 is implemented on the wide engine (64 < width <= 256, tanh, k in {0,2,3}) only");
       *rc = PINN_ERR_UNSUPPORTED;
@@ -130,7 +136,16 @@ static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc
   if (asked == PINN_ENGINE_GENERIC) return PINN_ENGINE_GENERIC;
   if (asked == PINN_ENGINE_FUSED || asked == PINN_ENGINE_WIDE) {
     const bool ok = asked == PINN_ENGINE_FUSED ? fused_supports(n, want_grad) : wide_supports(n);
-    if (!ok) {
+    if (!ok && n.act == PINN_ACT_SIN_TANH) {
+      // the sine first layer: the tile kernel's own instances only (pinn_fused_sin_wXX.hip)
+      const char* why = asked == PINN_ENGINE_WIDE ? "the wide engine has no kernel for it"
+                      : n.fused_kernel == FUSED_KERNEL_COOP ? "engine FUSED_COOP: the cooperative kernel has no instance for it (use AUTO, FUSED or FUSED_TILE)"
+                      : n.fused_kernel == FUSED_KERNEL_BATCH ? "engine FUSED_BATCH: the batch kernel has no instance for it (use AUTO, FUSED or FUSED_TILE)"
+                      : "the tile kernel's sine instances serve width <= 64, d_in and d_out <= 16, k in {0, 2, 3}, no dropout";
+      set_error("the sine first layer (activation 2): %s (width %d, d_in %d, d_out %d, k %d, gradient %d); engine AUTO or GENERIC "
+                "runs this request on the generic engine", why, n.W, n.d_in, n.d_out, n.k, (int)want_grad);
+      *rc = PINN_ERR_UNSUPPORTED;
+    } else if (!ok) {
       set_error("%s engine does not support this request (width %d, d_in %d, d_out %d, k %d, act %d, gradient %d)",
                 asked == PINN_ENGINE_FUSED ? "fused" : "wide", n.W, n.d_in, n.d_out, n.k, n.act, (int)want_grad);
       *rc = PINN_ERR_UNSUPPORTED;
@@ -156,7 +171,8 @@ static int pick_jet_backward_engine(const pinn_desc* d, const Net& n, int* rc) {
   }
   const bool ok = fused_jet_backward_supports(n);
   if (asked == PINN_ENGINE_FUSED && !ok) {
-    const char* why = n.drop_p > 0.f ? "dropout_p > 0 has no external-adjoint kernel"
+    const char* why = n.act == PINN_ACT_SIN_TANH ? "the sine first layer (activation 2) has no external-adjoint kernel"
+                    : n.drop_p > 0.f ? "dropout_p > 0 has no external-adjoint kernel"
                     : n.prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only"
                     : n.K1 == 2 ? "k = 1 (one differentiated input) with gdY has no gradient kernel"
                     : n.W > 64 ? "hidden width above 64"
@@ -186,6 +202,9 @@ static int corrected_engine(const pinn_desc* desc, const Net& n, const LossReq& 
     return PINN_ERR_UNSUPPORTED;
   }
   if (*e == PINN_ENGINE_FUSED && n.drop_p > 0.f && asked_engine(desc) == PINN_ENGINE_AUTO) *e = PINN_ENGINE_GENERIC;
+  // ... and with the sine first layer: the fused engine has no EPI_PEC sine instance, AUTO runs the generic engine, which the
+  // query of a sine descriptor under AUTO covers (pinn_query_workspace)
+  if (*e == PINN_ENGINE_FUSED && n.act == PINN_ACT_SIN_TANH && asked_engine(desc) == PINN_ENGINE_AUTO) *e = PINN_ENGINE_GENERIC;
   if (*e == PINN_ENGINE_FUSED) {
     if (const char* why = fused_corrected_refusal(n)) {
       set_error("the corrected radiation stress (spec.flags bit 0) %s (activation %d, k %d, dropout_p %g)", why, n.act, n.k,
@@ -335,6 +354,11 @@ int32_t pinn_query_workspace(const pinn_desc* desc, int64_t N, int64_t* bytes) {
     if (rc1 && rc2) { *err = rc1; return -1; }      // neither kind of call is served on the engine asked for
     int64_t b = rc1 ? -1 : ws_of(e);
     if (rc2 == PINN_OK && (rc1 || eg != e)) { const int64_t bg = ws_of(eg); if (bg > b) b = bg; }
+    if (b >= 0 && nn.act == PINN_ACT_SIN_TANH && asked_engine(desc) == PINN_ENGINE_AUTO) {
+      // the sine first layer under AUTO: a corrected-radiation-stress loss request runs on the generic engine (corrected_engine)
+      const int64_t bg = generic_workspace_bytes(nn, N);
+      if (bg > b) b = bg;
+    }
     if (b >= 0) {   // pinn_jet_backward picks its engine by its own rule (a request refused there fails by itself)
       int rcj = PINN_OK;
       const int ej = pick_jet_backward_engine(desc, nn, &rcj);
@@ -814,7 +838,8 @@ static int fields_plan(const pinn_desc* desc, const pinn_residual_spec* spec, in
   }
   const bool fused_ok = fused_fields_supports(*n) && !(corrected && fused_corrected_refusal(*n));
   if (asked == PINN_ENGINE_FUSED && !fused_ok) {
-    const char* why = n->drop_p > 0.f ? "dropout_p > 0 has no field kernel"
+    const char* why = n->act == PINN_ACT_SIN_TANH ? "the sine first layer (activation 2) has no field kernel"
+                    : n->drop_p > 0.f ? "dropout_p > 0 has no field kernel"
                     : n->prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only"
                     : n->W > 64 ? "hidden width above 64"
                     : (n->d_in > 16 || n->d_out > 16) ? "d_in or d_out above 16" : "network too deep for the tile kernel";
@@ -878,6 +903,11 @@ int32_t pinn_residual_fields(const pinn_desc* desc, const pinn_residual_spec* sp
 static int jet2_net(const pinn_desc* desc, Net* n, bool* mfma) {
   int rc = make_net(desc, n); if (rc) return rc;
   if (n->k < 1) { set_error("jet2 needs k >= 1 differentiated inputs (k = %d)", n->k); return PINN_ERR_INVALID; }
+  if (n->act == PINN_ACT_SIN_TANH) {
+    set_error("the second-order entries (jet2, residual2) serve activation 0 (tanh) and 1 (LeakyReLU) only: the sine first "
+              "layer (activation 2) has no second-order kernel on any engine");
+    return PINN_ERR_UNSUPPORTED;
+  }
   if (n->prec != PINN_PREC_F32) { set_error("jet2 is implemented in fp32 only (precision bf16 refused)"); return PINN_ERR_UNSUPPORTED; }
   const int asked = asked_engine(desc);
   if (asked == PINN_ENGINE_WIDE) { set_error("jet2 does not run on the wide engine: use engine AUTO, FUSED or GENERIC"); return PINN_ERR_UNSUPPORTED; }

@@ -69,6 +69,7 @@ int64_t coop_lds_bytes(const Net& n, const Geo& g, bool grad) {
 bool use_coop(const Net& n, const Geo& g, bool grad, int64_t N) {
   const int forced = n.fused_kernel == FUSED_KERNEL_COOP ? 1 : (n.fused_kernel == FUSED_KERNEL_TILE ? 0 : -1);
   if (forced == 0 || g.WP != 64 || n.drop_p > 0.f) return false;
+  if (n.act == PINN_ACT_SIN_TANH) return false;   // the sine first layer: tile-kernel instances only
   if (coop_lds_bytes(n, g, grad) > LDS_LIMIT) return false;
   if (forced == 1) return true;
   return (N + 15) / 16 <= (int64_t)cu_count();
@@ -558,6 +559,9 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   // (the field epilogue exists in the tile kernel only: every kernel choice of desc.engine lands there; the external-adjoint
   // one in the tile and in the batch kernel)
   const bool pec = is_pec(rq), fpec = fld && fld->spec.residual_id == RES_PE_CORRECTED;
+  if (n.act == PINN_ACT_SIN_TANH && (adj || fld || n.drop_p > 0.f)) {   // (refused upstream: never a tanh kernel on a sine network)
+    set_error("fused engine: no kernel for the sine first layer (activation 2) on this request"); return PINN_ERR_UNSUPPORTED;
+  }
   if ((pec || fpec) && fused_corrected_refusal(n)) {
     set_error("fused engine: the corrected radiation stress %s", fused_corrected_refusal(n)); return PINN_ERR_UNSUPPORTED;
   }
@@ -667,6 +671,14 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     // kernel, one weight fetch per 64 points (pinn_fused_plain.hip)
     rc = launch_fused_plain(g.WP, P, cu_count(), s);
   }
+  else if (n.act == PINN_ACT_SIN_TANH) {   // the sine first layer: instances of its own (pinn_fused_sin_wXX.hip), generic epilogue only
+    if (wtq || coefq || pec || batch || coop) { set_error("fused engine: no kernel for the sine first layer (activation 2) on this request"); return PINN_ERR_UNSUPPORTED; }
+    switch (g.WP) {
+      case 16: rc = launch_fused_sin<16>(n.K1, grad, P, grid, lds, s); break;
+      case 32: rc = launch_fused_sin<32>(n.K1, grad, P, grid, lds, s); break;
+      default: rc = launch_fused_sin<64>(n.K1, grad, P, grid, lds, s); break;
+    }
+  }
   else if (wtq) switch (g.WP) {   // EPI_WEIGHTED instances: pinn_fused_wt_wXX.hip
     case 16: rc = launch_fused_wt<16>(n.K1, grad, P, grid, lds, s); break;
     case 32: rc = launch_fused_wt<32>(n.K1, grad, P, grid, lds, s); break;
@@ -757,6 +769,12 @@ bool fused_batch_has_kernel(int WP, int W, int d_in, int K1, int act) {
 
 bool fused_supports(const Net& n, bool want_grad) {
   if (n.L + 1 > MAX_LOCKS) return false;
+  // the sine first layer: exactly where a k_fused<.., PINN_ACT_SIN_TANH, EPI_GENERIC> instance exists (pinn_fused_sin.inc) —
+  // K1 in {1, 3, 4}, no dropout, the tile kernel (never the cooperative or the batch kernel: use_coop, fused_batch_has_kernel)
+  if (n.act == PINN_ACT_SIN_TANH &&
+      (n.drop_p > 0.f || n.prec != PINN_PREC_F32 || n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH ||
+       !(n.K1 == 1 || n.K1 == 3 || n.K1 == 4)))
+    return false;
   if (n.drop_p > 0.f) {   // dropout: gradient passes of tanh networks of padded width 64 whose gradient copy fits LDS
     if (!(want_grad && padded_width(n.W) == 64 && n.act == PINN_ACT_TANH && fits_lds(geo_of(n)) && n.fused_kernel != FUSED_KERNEL_COOP &&
           (n.K1 == 1 || n.K1 == 3 || n.K1 == 4)))
@@ -772,7 +790,7 @@ bool fused_supports(const Net& n, bool want_grad) {
 // the batch kernel has no instance for runs on the tile kernel), only for which of the two kernels serves it:
 bool fused_jet_backward_supports(const Net& n) {
   Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
-  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && fused_supports(t, true);
+  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && n.act != PINN_ACT_SIN_TANH && fused_supports(t, true);   // (no EPI_ADJ sine instance)
 }
 int fused_jet_backward_kernel(const Net& n, int64_t N) {
   return use_batch_adj(n, geo_of(n), N) ? PINN_ENGINE_FUSED_BATCH : PINN_ENGINE_FUSED_TILE;
@@ -783,11 +801,12 @@ int fused_jet_backward_kernel(const Net& n, int64_t N) {
 // does not matter here (run() always takes the tile kernel).
 bool fused_fields_supports(const Net& n) {
   Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
-  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && (n.K1 == 3 || n.K1 == 4) && fused_supports(t, false);
+  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && n.act != PINN_ACT_SIN_TANH && (n.K1 == 3 || n.K1 == 4) && fused_supports(t, false);   // (no EPI_FIELD sine instance)
 }
 
 // The corrected radiation stress (EPI_PEC / EPI_FIELD_PEC instances): tanh, k = 2, no dropout.  nullptr = served.
 const char* fused_corrected_refusal(const Net& n) {
+  if (n.act == PINN_ACT_SIN_TANH) return "has no instance for the sine first layer (activation 2) on the fused engine: use engine AUTO or GENERIC";
   if (n.act != PINN_ACT_TANH) return "has no LeakyReLU instance on the fused engine: use engine GENERIC";
   if (n.K1 != 3) return "has fused instances for k = 2 networks only: use engine GENERIC";
   if (n.drop_p > 0.f) return "has no dropout instance on the fused engine: use engine AUTO or GENERIC";
@@ -800,6 +819,7 @@ const char* fused_coef_refusal(const Net& n) {
     return "the coefficient instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
   if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no coefficient kernel";
   if (n.W > 64) return "hidden width above 64 has no coefficient kernel on the fused engine";
+  if (n.act == PINN_ACT_SIN_TANH) return "the sine first layer (activation 2) has no coefficient kernel on the fused engine";
   if (n.act != PINN_ACT_TANH) return "LeakyReLU has no coefficient kernel on the fused engine";
   if (n.drop_p > 0.f) return "dropout_p > 0 has no coefficient kernel on the fused engine";
   if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
@@ -824,6 +844,7 @@ const char* fused_weighted_refusal(const Net& n) {
     return "the weighted instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
   if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no weighted kernel";
   if (n.W > 64) return "hidden width above 64 has no weighted kernel on the fused engine";
+  if (n.act == PINN_ACT_SIN_TANH) return "the sine first layer (activation 2) has no weighted kernel on the fused engine";
   if (n.act != PINN_ACT_TANH) return "LeakyReLU has no weighted kernel on the fused engine";
   if (n.drop_p > 0.f) return "dropout_p > 0 has no weighted kernel on the fused engine";
   if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
@@ -1027,6 +1048,7 @@ const char* fused_ensemble_refusal(const Net& n, const LossReq& rq) {
     return "the ensemble instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
   if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no ensemble kernel";
   if (n.W > 64) return "hidden width above 64 has no ensemble kernel";
+  if (n.act == PINN_ACT_SIN_TANH) return "the sine first layer (activation 2) has no ensemble kernel";
   if (n.act != PINN_ACT_TANH) return "LeakyReLU has no ensemble kernel";
   if (n.drop_p > 0.f) return "dropout_p > 0 has no ensemble kernel";
   if (rq.kind != 1 && rq.spec.residual_id == RES_PE_CORRECTED) return "the corrected radiation stress (spec.flags bit 0) has no ensemble kernel";

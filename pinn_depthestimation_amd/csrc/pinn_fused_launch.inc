@@ -44,6 +44,8 @@ static int launch_one(const FusedParams& P, int grid, size_t lds, hipStream_t s)
       }
     }
   }
+  // (never a tanh or LeakyReLU kernel on anything else: the sine first layer has launchers of its own, pinn_fused_sin.inc)
+  if (P.act != PINN_ACT_TANH && P.act != PINN_ACT_LEAKY_RELU) { set_error("fused engine: no kernel for activation %d here", P.act); return PINN_ERR_UNSUPPORTED; }
   return P.act == PINN_ACT_TANH ? launch_one_act<K1, GRAD, LDSACC, PINN_ACT_TANH>(P, grid, lds, s)
                                 : launch_one_act<K1, GRAD, LDSACC, PINN_ACT_LEAKY_RELU>(P, grid, lds, s);
 }

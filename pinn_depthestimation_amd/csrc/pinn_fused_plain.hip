@@ -54,7 +54,13 @@ __global__ __launch_bounds__(FUSED_THREADS, plain4_occ(WP)) void k_fused_plain4(
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float z = acc0[c][MT][r] + bias[MT][r];
-            a[c][MT][r] = ACT == PINN_ACT_TANH ? tanh_f32(z) : (z > 0.f ? z : 0.01f * z);
+            if constexpr (ACT == PINN_ACT_SIN_TANH) {   // the sine first layer: z_0 in double, as the tile kernel forms it (activate_sin_to)
+              const int64_t pc = pt[c] < P.N ? pt[c] : P.N - 1;
+              float sn, cs;
+              sincos_f64arg(sin_layer_z(Wp_ + (16 * MT + 4 * q + r) * 16, bias[MT][r], P.X + pc * P.d_in, P.d_in), sn, cs);
+              a[c][MT][r] = sn;
+            }
+            else a[c][MT][r] = ACT == PINN_ACT_TANH ? tanh_f32(z) : (z > 0.f ? z : 0.01f * z);
           }
     }
     for (int l = 1; l < L; ++l) {
@@ -70,7 +76,7 @@ __global__ __launch_bounds__(FUSED_THREADS, plain4_occ(WP)) void k_fused_plain4(
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float z = nx[c][MT][r] + bias[MT][r];
-            a[c][MT][r] = ACT == PINN_ACT_TANH ? tanh_f32(z) : (z > 0.f ? z : 0.01f * z);
+            a[c][MT][r] = (ACT == PINN_ACT_TANH || ACT == PINN_ACT_SIN_TANH) ? tanh_f32(z) : (z > 0.f ? z : 0.01f * z);
           }
     }
     f4 out[C][1];
@@ -101,6 +107,8 @@ static int launch_plain(const FusedParams& P, int64_t n_tiles, int cus, hipStrea
   const int64_t want = ((n_tiles + 3) / 4 + FUSED_WAVES - 1) / FUSED_WAVES, cap = (int64_t)plain4_occ(WP) * cus;
   const int grid = (int)(want < cap ? want : cap);
   if (P.act == PINN_ACT_TANH) hipLaunchKernelGGL((k_fused_plain4<WP, PINN_ACT_TANH>), dim3(grid), dim3(FUSED_THREADS), 0, s, P);
+  else if (P.act == PINN_ACT_SIN_TANH) hipLaunchKernelGGL((k_fused_plain4<WP, PINN_ACT_SIN_TANH>), dim3(grid), dim3(FUSED_THREADS), 0, s, P);
+  else if (P.act != PINN_ACT_LEAKY_RELU) { set_error("fused plain-forward kernel: no instance for activation %d", P.act); return PINN_ERR_UNSUPPORTED; }
   else hipLaunchKernelGGL((k_fused_plain4<WP, PINN_ACT_LEAKY_RELU>), dim3(grid), dim3(FUSED_THREADS), 0, s, P);
   return check_launch("fused plain-forward kernel (four tiles per wave)");
 }

@@ -33,6 +33,11 @@ __device__ inline float act_slope(int act, float a) {  // act'(z) expressed thro
   if (act == PINN_ACT_TANH) return 1.f - a * a;
   return a > 0.f ? 1.f : 0.01f;
 }
+// The activation of hidden layer l as the layer kernels take it.  PINN_ACT_SIN_TANH: the sine on layer 0 — handed on as
+// PINN_ACT_SIN_TANH, which in a layer kernel means "this layer is a sine" — and tanh on every other hidden layer.
+inline int layer_act(const Net& n, int l) {
+  return n.act == PINN_ACT_SIN_TANH ? (l == 0 ? PINN_ACT_SIN_TANH : PINN_ACT_TANH) : n.act;
+}
 
 // a0[c][i][n]: c = 0 -> X[n][i]; c = 1+j -> unit tangent e_{dir_col[j]}
 template <int K1>
@@ -58,10 +63,11 @@ struct Drop {
 
 // mode: 0 = linear output layer, 1 = hidden layer (activation applied, then dropout: a <- m a / (1-p), the
 // tangents likewise — the same mask multiplies value and derivatives, as autograd through nn.Dropout does)
+// (X: the row-major inputs, read by the sine layer only — its z_0 is formed in double, residuals.h sincos_f64arg)
 template <int K1>
 __global__ void k_fwd_layer(const float* __restrict__ Wt, const float* __restrict__ b, int in_dim, int out_dim,
                             const float* __restrict__ a_in, float* __restrict__ a_out, int64_t N, int hidden,
-                            int act, Drop dr) {
+                            int act, Drop dr, const float* __restrict__ X) {
   int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   for (int o0 = 0; o0 < out_dim; o0 += OB) {
@@ -88,7 +94,9 @@ __global__ void k_fwd_layer(const float* __restrict__ Wt, const float* __restric
       if (o0 + j >= out_dim) break;
       float a = acc[0][j], s = 1.f;
       if (hidden) {
-        a = act_fwd(act, a); s = act_slope(act, a);
+        if (act == PINN_ACT_SIN_TANH)   // the sine layer: a = sin z, s = cos z
+          sincos_f64arg(sin_layer_z(Wt + (int64_t)(o0 + j) * in_dim, b[o0 + j], X + n * in_dim, in_dim), a, s);
+        else { a = act_fwd(act, a); s = act_slope(act, a); }
         if (dr.thresh) {
           const float m = dropout_bits(dr.seed, dr.layer, o0 + j, n) >= dr.thresh ? dr.scale : 0.f;
           a *= m; s *= m;
@@ -159,6 +167,37 @@ __global__ void k_bwd_layer(const float* __restrict__ Wt, int in_dim, int out_di
 #pragma unroll
       for (int c = 0; c < K1; ++c) g_in[((int64_t)c * in_dim + i0 + j) * N + n] = acc[c][j];
     }
+  }
+}
+
+// k_bwd_layer's hidden part for the sine layer (layer 0 of a PINN_ACT_SIN_TANH network; it has no input adjoint to form).
+// cos z cannot be had from the stored a = sin z, so z_0 = W_0 x + b_0 is formed again from the inputs X — the forward
+// kernel's own double sum, hence its z bit for bit — and the tangents zdot_j are the columns dir_col[j] of W_0:
+//   zbardot_j = cos z * abardot_j ;  zbar = cos z * abar - sin z * sum_j abardot_j * zdot_j
+// (with dropout both factors carry the unit's m / (1 - p), as in k_bwd_layer).  The workspace is the one it was.
+template <int K1>
+__global__ void k_bwd_sin0(const float* __restrict__ Wt, const float* __restrict__ b, int in_dim, int out_dim,
+                           float* __restrict__ g, const float* __restrict__ X, int64_t N, int dir0, int dir1, int dir2,
+                           Drop dr) {
+  int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const int dirs[3] = {dir0, dir1, dir2};
+  for (int o = 0; o < out_dim; ++o) {
+    float sn, cs;
+    sincos_f64arg(sin_layer_z(Wt + (int64_t)o * in_dim, b[o], X + n * in_dim, in_dim), sn, cs);
+    if (dr.thresh) {
+      const float m = dropout_bits(dr.seed, dr.layer, o, n) >= dr.thresh ? dr.scale : 0.f;
+      sn *= m; cs *= m;
+    }
+    float cross = 0.f;
+#pragma unroll
+    for (int c = 1; c < K1; ++c) {
+      const int64_t idx = ((int64_t)c * out_dim + o) * N + n;
+      const float gd = g[idx];
+      cross = fmaf(gd, Wt[(int64_t)o * in_dim + dirs[c - 1]], cross);
+      g[idx] = cs * gd;
+    }
+    g[(int64_t)o * N + n] = fmaf(-sn, cross, cs * g[(int64_t)o * N + n]);
   }
 }
 
@@ -453,13 +492,13 @@ int run_forward(const Net& n, const float* params, const float* X, int64_t N, ch
     const Drop dr{n.drop_p > 0.f ? n.drop_thresh : 0u, n.drop_seed, l, 1.f / (1.f - n.drop_p), 1.f - n.drop_p};
     hipLaunchKernelGGL(k_fwd_layer<K1>, dim3(grid), dim3(TPB), 0, s, params + n.w_off(l), params + n.b_off(l),
                        n.in_dim(l), n.out_dim(l), (const float*)(ws + lo.act_off[l]),
-                       (float*)(ws + lo.act_off[l + 1]), N, l < n.L ? 1 : 0, n.act, dr);
+                       (float*)(ws + lo.act_off[l + 1]), N, l < n.L ? 1 : 0, layer_act(n, l), dr, X);
   }
   return check_launch("generic forward");
 }
 
 template <int K1>
-int run_backward(const Net& n, const float* params, int64_t N, char* ws, const Layout& lo, float* grad,
+int run_backward(const Net& n, const float* params, const float* X, int64_t N, char* ws, const Layout& lo, float* grad,
                  hipStream_t s) {
   const unsigned grid = (unsigned)lo.nblocks;
   float* gcur = (float*)(ws + lo.g0);
@@ -468,8 +507,12 @@ int run_backward(const Net& n, const float* params, int64_t N, char* ws, const L
   for (int l = n.L; l >= 0; --l) {
     const int in_dim = n.in_dim(l), out_dim = n.out_dim(l);
     const Drop dr{n.drop_p > 0.f ? n.drop_thresh : 0u, n.drop_seed, l, 1.f / (1.f - n.drop_p), 1.f - n.drop_p};
-    hipLaunchKernelGGL(k_bwd_layer<K1>, dim3(grid), dim3(TPB), 0, s, params + n.w_off(l), in_dim, out_dim, gcur,
-                       (const float*)(ws + lo.act_off[l + 1]), gnext, N, l < n.L ? 1 : 0, n.act, l > 0 ? 1 : 0, dr);
+    if (l == 0 && n.act == PINN_ACT_SIN_TANH)
+      hipLaunchKernelGGL(k_bwd_sin0<K1>, dim3(grid), dim3(TPB), 0, s, params + n.w_off(0), params + n.b_off(0), in_dim, out_dim,
+                         gcur, X, N, n.dir_col[0], n.dir_col[1], n.dir_col[2], dr);
+    else
+      hipLaunchKernelGGL(k_bwd_layer<K1>, dim3(grid), dim3(TPB), 0, s, params + n.w_off(l), in_dim, out_dim, gcur,
+                         (const float*)(ws + lo.act_off[l + 1]), gnext, N, l < n.L ? 1 : 0, layer_act(n, l), l > 0 ? 1 : 0, dr);
     dim3 wg((in_dim + 15) / 16, (out_dim + 15) / 16, (unsigned)((N + chunk - 1) / chunk));
     hipLaunchKernelGGL(k_wgrad<K1>, wg, dim3(256), 0, s, (const float*)gcur, (const float*)(ws + lo.act_off[l]),
                        in_dim, out_dim, N, chunk, grad + n.w_off(l), grad + n.b_off(l));
@@ -573,7 +616,7 @@ int run_loss(const Net& n, const LossReq& rq, const float* params, const float* 
   }
   rc = check_launch("generic loss");
   if (rc || !want_grad) return rc;
-  return run_backward<K1>(n, params, N, ws, lo, rq.grad, s);
+  return run_backward<K1>(n, params, X, N, ws, lo, rq.grad, s);
 }
 
 }  // namespace
@@ -628,7 +671,7 @@ int generic_jet_backward(const Net& n, const float* params, const float* X, int6
     if (rc) return rc;
     hipLaunchKernelGGL(k_seed_adjoint<K1>, dim3(grid), dim3(TPB), 0, s, gY, gdY, n.d_out, N,
                        (float*)((char*)ws + lo.g0));
-    rc = run_backward<K1>(n, params, N, (char*)ws, lo, grad, s);
+    rc = run_backward<K1>(n, params, X, N, (char*)ws, lo, grad, s);
   });
   return rc;
 }

@@ -597,6 +597,38 @@ __device__ inline f2 tanh_f32x2(f2 x) {
             fabsf(x[1]) < 0.625f ? small[1] : copysignf(big[1], x[1])};
 }
 
+// sin z and cos z together for the sine first layer (PINN_ACT_SIN_TANH), from z in DOUBLE.  A Fourier layer's arguments reach
+// tens to a few hundred, where (a) the hardware sine (v_sin_f32 / __sinf, input in revolutions) has lost most of its bits and
+// (b) an fp32 z itself is the largest error there is: one rounding of z = 8 is 5e-7 of sin z, of z = 256 it is 1.5e-5, whatever
+// evaluates the sine afterwards (measured on a one-point Navier_Stokes sum of a 3 -> 10 -> 4 network: 3.3e-6 relative with z_0
+// formed by the fp32 fmaf chain, 2.9e-7 with z_0 exact).  So the callers form z_0 = W_0 x + b_0 in double — the products of
+// fp32 numbers are exact there — and the reduction r = z - k pi/2 is one double fused multiply-add; then the Cephes
+// single-precision minimax polynomials on |r| <= pi/4 in fp32 and the quadrant swap.  Absolute error <= 7e-8 for both against
+// fp64.  No table, no branch, no scratch.
+__device__ inline void sincos_f64arg(double z, float& sn, float& cs) {
+  const double k = rint(z * 0.63661977236758134308);
+  const float r = (float)fma(-k, 1.57079632679489661923, z);
+  const float r2 = r * r;
+  float ps = -1.9515295891e-4f;
+  ps = fmaf(ps, r2, 8.3321608736e-3f);
+  ps = fmaf(ps, r2, -1.6666654611e-1f);
+  const float s = fmaf(ps * r2, r, r);
+  float pc = 2.443315711809948e-5f;
+  pc = fmaf(pc, r2, -1.388731625493765e-3f);
+  pc = fmaf(pc, r2, 4.166664568298827e-2f);
+  const float c = fmaf(pc * r2, r2, fmaf(-0.5f, r2, 1.f));
+  const int n = (int)k;
+  const float s1 = (n & 1) ? c : s, c1 = (n & 1) ? s : c;
+  sn = (n & 2) ? -s1 : s1;
+  cs = ((n + 1) & 2) ? -c1 : c1;
+}
+// z_0 of one unit in double: b + sum_i w[i] x[i], d_in terms (w: the unit's row of W_0, x: the point's row of X)
+__device__ inline double sin_layer_z(const float* __restrict__ w, float b, const float* __restrict__ x, int d_in) {
+  double z = (double)b;
+  for (int i = 0; i < d_in; ++i) z = fma((double)w[i], (double)x[i], z);
+  return z;
+}
+
 // ---- point weights (pinn_residual_weighted_loss_grad) ---------------------------------------------------------------------
 // The value of x behind a barrier the optimiser cannot see through.  The weighted kernels form the fields that go into the
 // sums (and into the optional field store) from opaque copies of the jet and take them out through it again: that piece of

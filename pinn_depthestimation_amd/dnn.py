@@ -8,6 +8,9 @@ initialisation (dnn.py:42-52), nn.Module semantics.  Differences, all deliberate
   * Dropout(p>0) in training mode (dnn.py:38, train.py:186) uses the engine's counter-based mask (one fresh
     seed per forward call, drawn from torch's CPU generator; include/pinn_hip.h pinn_desc.dropout_p): same
     distribution as nn.Dropout, not torch's random stream.
+One addition the reference does not have: first_activation="sin" makes the FIRST hidden layer a Fourier-feature layer,
+a_1 = sin(W_0 x + b_0) with W_0 ~ N(0, fourier_sigma^2) and b_0 ~ U[0, 2 pi) (include/pinn_hip.h, PINN_ACT_SIN_TANH); W_0 and
+b_0 stay ordinary trained parameters under the same state_dict keys.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ from typing import List, Optional, Sequence
 import torch
 import torch.nn as nn
 
-from ._lib import PinnError
+from ._lib import ACT_SIN_TANH, PinnError
 from .engine import ACTIVATION_OF_INIT
 
 
@@ -28,14 +31,45 @@ def _check_init_type(init_type: str):
         raise ValueError(f"Invalid init_type: {init_type}. Use 'kaiming' or 'xavier'.")
 
 
-def init_flat_params(layers: Sequence[int], init_type: str = "xavier", generator=None) -> torch.Tensor:
+def _check_first_activation(first_activation, init_type: str, fourier_sigma):
+    if first_activation is None:
+        return
+    if first_activation != "sin":
+        raise ValueError(f"Invalid first_activation: {first_activation!r}. Use None or 'sin'.")
+    if init_type != "xavier":
+        raise ValueError("first_activation='sin' needs init_type='xavier' (the other hidden layers are tanh layers), "
+                         f"got init_type={init_type!r}")
+    if not (float(fourier_sigma) > 0.0 and math.isfinite(float(fourier_sigma))):
+        raise ValueError(f"fourier_sigma must be a positive finite number, got {fourier_sigma!r}")
+
+
+class Sin(nn.Module):
+    """sin(x): the activation of a Fourier-feature first layer (no parameters)."""
+
+    def forward(self, x):
+        return torch.sin(x)
+
+
+def activation_id_of(init_type: str, first_activation=None) -> int:
+    """The ACT_* value of the engine (include/pinn_hip.h) for a network built with these constructor arguments."""
+    return ACT_SIN_TANH if first_activation == "sin" else ACTIVATION_OF_INIT[init_type]
+
+
+def init_flat_params(layers: Sequence[int], init_type: str = "xavier", generator=None, first_activation=None,
+                     fourier_sigma: float = 1.0) -> torch.Tensor:
     """Flat [W0,b0,...] fp32 vector drawn from the distributions of dnn.py:42-52
-    (Xavier/Kaiming-uniform weights; zero bias except the last layer's nn.Linear default)."""
+    (Xavier/Kaiming-uniform weights; zero bias except the last layer's nn.Linear default).
+    first_activation="sin": layer 0 is W_0 ~ N(0, fourier_sigma^2), b_0 ~ U[0, 2 pi) from the same generator."""
     _check_init_type(init_type)
+    _check_first_activation(first_activation, init_type, fourier_sigma)
     parts = []
     n_lin = len(layers) - 1
     for i in range(n_lin):
         fan_in, fan_out = layers[i], layers[i + 1]
+        if i == 0 and first_activation == "sin":
+            parts.append(torch.empty(fan_out * fan_in).normal_(0.0, float(fourier_sigma), generator=generator))
+            parts.append(torch.empty(fan_out).uniform_(0.0, 2.0 * math.pi, generator=generator))
+            continue
         if init_type == "xavier":
             bound = math.sqrt(6.0 / (fan_in + fan_out))
         else:
@@ -54,9 +88,14 @@ def init_flat_params(layers: Sequence[int], init_type: str = "xavier", generator
 class DNN(nn.Module):
     """The deep neural network (reference dnn.py:5-55)."""
 
-    def __init__(self, layers, dropout_rate, init_type):
+    def __init__(self, layers, dropout_rate, init_type, first_activation=None, fourier_sigma=1.0):
         super().__init__()
         _check_init_type(init_type)
+        _check_first_activation(first_activation, init_type, fourier_sigma)
+        self.first_activation = first_activation
+        self.fourier_sigma = float(fourier_sigma)
+        if first_activation == "sin" and len(layers) < 3:
+            raise ValueError("first_activation='sin' needs at least one hidden layer")
         self.activation = nn.Tanh() if init_type == "xavier" else nn.LeakyReLU(negative_slope=0.01)
         self.layer_sizes: List[int] = [int(v) for v in layers]
         self.dropout_rate = float(dropout_rate)
@@ -71,9 +110,12 @@ class DNN(nn.Module):
                 nn.init.xavier_uniform_(lin.weight)
             if i < n - 2:
                 nn.init.zeros_(lin.bias)
+            if i == 0 and first_activation == "sin":        # Fourier features: B ~ N(0, sigma^2), a random phase
+                nn.init.normal_(lin.weight, 0.0, self.fourier_sigma)
+                nn.init.uniform_(lin.bias, 0.0, 2.0 * math.pi)
             mods.append((f"layer_{i}", lin))
             if i < n - 2:
-                mods.append((f"activation_{i}", self.activation))
+                mods.append((f"activation_{i}", Sin() if i == 0 and first_activation == "sin" else self.activation))
                 mods.append((f"dropout_{i}", nn.Dropout(self.dropout_rate)))
         self.layers = nn.Sequential(OrderedDict(mods))
         self._flat: Optional[torch.Tensor] = None
@@ -143,7 +185,15 @@ class DNN(nn.Module):
             drops = [m for m in self.layers if isinstance(m, nn.Dropout)]
             self.dropout_rate = float(drops[0].p) if drops else 0.0
             self._grad_cols_override = None
+        if "first_activation" not in self.__dict__:     # the reference's class, or this one before it had the attribute
+            self.first_activation = None
+            self.fourier_sigma = 1.0
         self._flat = None
+
+    @property
+    def activation_id(self) -> int:
+        """The engine's ACT_* value for this network (include/pinn_hip.h)."""
+        return activation_id_of(self.init_type, self.__dict__.get("first_activation"))
 
     def set_grad_columns(self, cols: Optional[Sequence[int]]):
         """Name the differentiated input columns explicitly instead of reading them off the

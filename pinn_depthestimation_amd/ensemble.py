@@ -17,8 +17,8 @@ import torch
 
 from ._lib import PinnError
 from .config import PinnConfig, load_config
-from .dnn import DNN, init_flat_params
-from .engine import ACTIVATION_OF_INIT, Engine, NetDesc, ResidualSpec
+from .dnn import DNN, activation_id_of, init_flat_params
+from .engine import Engine, NetDesc, ResidualSpec
 from .parallel import Reducer
 from .trainer import _as_f32
 
@@ -95,7 +95,8 @@ class EnsemblePINN:
             self._N, self._n_res = nr + nfp, nr
         else:
             self._N, self._n_res = nr, nr
-        act = ACTIVATION_OF_INIT[cfg.init_type]
+        # (a sine first layer has no ensemble kernel: the engine's refusal below says so in its own words)
+        act = activation_id_of(cfg.init_type, cfg.first_activation)
         self.eng = Engine(NetDesc.from_layers(cfg.layers, cfg.grad_cols, act, engine, 0, cfg.dropout_rate), self.device)
         why = self.eng.ensemble_refusal(self.spec, M, self._N, self._n_res, len(self.fid_cols))
         if why:

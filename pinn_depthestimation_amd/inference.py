@@ -22,7 +22,7 @@ from . import physics
 from .config import PinnConfig, load_config
 from ._lib import PinnError
 from .dnn import DNN
-from .engine import ACTIVATION_OF_INIT, RESIDUAL_ROLES, Engine, NetDesc, ResidualSpec
+from .engine import RESIDUAL_ROLES, Engine, NetDesc, ResidualSpec
 
 
 FIELD_NAMES = {"Navier_Stokes": ("fc", "fm_x", "fm_y"), "physics_equation": ("fc", "fx", "fy"),
@@ -70,7 +70,8 @@ class Tester:
             if isinstance(obj, DNN):
                 m = obj
             else:
-                m = DNN(self.config.layers, self.config.dropout_rate, self.config.init_type)
+                m = DNN(self.config.layers, self.config.dropout_rate, self.config.init_type,
+                        first_activation=self.config.first_activation, fourier_sigma=self.config.fourier_sigma)
                 m.load_state_dict(obj)
         m.to(self.device)
         m.eval()
@@ -135,10 +136,10 @@ class Tester:
         grad_cols = tuple(i for i, k in enumerate(names) if "true" in self.test_input_vars[k].get("requires_grad", []))
         spec = ResidualSpec.from_names(self.residual, names, grad_cols, self.test_output_vars, corrected=self.corrected,
                                        nu=self.eddy_viscosity)
-        key = (tuple(self.model.layer_sizes), grad_cols)
+        key = (tuple(self.model.layer_sizes), grad_cols, self.model.activation_id)
         if getattr(self, "_fields_engine_key", None) != key:
             self._fields_engine = Engine(NetDesc.from_layers(self.model.layer_sizes, grad_cols,
-                                                             ACTIVATION_OF_INIT[self.model.init_type]), self.device)
+                                                             self.model.activation_id), self.device)
             self._fields_engine_key = key
         if spec.nu != 0:
             F = self._fields_engine.residual2_loss_grad(spec, None, self.model.flat_params(), data, grad=None, fields=True)[1]

@@ -197,8 +197,9 @@ class HipEvaluator:
     """Local-shard loss sums and gradient through libpinn_hip.so."""
 
     def __init__(self, cfg_layers, init_type, grad_cols, spec: ResidualSpec, fid_cols: Sequence[int], device,
-                 engine: int = 0, precision: int = 0, dropout_rate: float = 0.0):
-        act = ACTIVATION_OF_INIT[init_type]
+                 engine: int = 0, precision: int = 0, dropout_rate: float = 0.0, activation: Optional[int] = None):
+        # (activation: DNN.activation_id — the sine first layer is no function of init_type)
+        act = ACTIVATION_OF_INIT[init_type] if activation is None else int(activation)
         self.dropout_rate = float(dropout_rate)
         self.eng = Engine(NetDesc.from_layers(cfg_layers, grad_cols, act, engine, precision), device)
         # training-mode dropout (dnn.py:38 with train.py:186): its own engine (generic kernels carry the mask)
@@ -488,7 +489,8 @@ class PINN:
         self._run_coef_log = None
         self._fold_refused = None   # key of the (evaluator, point sets) whose folded request the engine has refused
         self.layers = cfg.layers                                           # train.py:52-56
-        self.dnn = dnn if dnn is not None else DNN(cfg.layers, cfg.dropout_rate, cfg.init_type)
+        self.dnn = dnn if dnn is not None else DNN(cfg.layers, cfg.dropout_rate, cfg.init_type,
+                                                   first_activation=cfg.first_activation, fourier_sigma=cfg.fourier_sigma)
         self.dnn.to(self.device)
         self.theta = self.dnn.flat_params()
         self.reducer.broadcast_(self.theta)                                # replicas start identical
@@ -534,7 +536,8 @@ class PINN:
         self.grad = self.buf[:P]
         self._fid_sums, self._res_sums = self.buf[P:P + nf], self.buf[P + nf:]
         self.evaluator = evaluator or HipEvaluator(cfg.layers, cfg.init_type, cfg.grad_cols, self.spec,
-                                                   self.fid_cols, dev, engine, precision, cfg.dropout_rate)
+                                                   self.fid_cols, dev, engine, precision, cfg.dropout_rate,
+                                                   activation=self.dnn.activation_id)
         # the coefficients: every one of the residual's, given or default, in ResidualSpec.coef_names order
         self.coef_names: Tuple[str, ...] = self.spec.coef_names if (coef_in or coef_tr) else ()
         self.trainable_coefficients = tuple(n for n in self.coef_names if n in coef_tr)
