@@ -10,10 +10,9 @@ struct AdamExtReq {
                         // grad = grad_flat (OVERWRITTEN by the finishing kernel), adam null
   LossReq fid;          // the fidelity pass: kind 1; read only when N_fid > 0
   const float* Xf; int64_t N_fid;
-  float* params; float* m; float* v;
+  AdamReq adam;         // params, m, v, packed_valid and the loss rows (c is not read: each iteration forms its own scalars)
   double beta1, beta2, eps; int64_t step;   // iteration i runs step + i
-  bool packed_valid;
-  int n_loss_rows; const float* loss_rows; float* losses; int row_cols;   // row_cols: the caller's n_cols (loss_rows' stride)
+  int row_cols;         // the caller's n_cols (loss_rows' stride)
   float* col_sums;      // the caller's (row_cols): zeroed once when there is no fidelity pass
   // coefficients (res.coef set): updated in place unless coef_grad is null
   float* coef; float* coef_m; float* coef_v; float* coef_grad; const float* coef_mask; float* coef_log; int n_coef;
@@ -22,9 +21,9 @@ struct AdamExtReq {
   int n_iters; const double* lr; const double* lr_coef; const double* lr_w;   // HOST arrays (n_iters)
 };
 
-// why the fused engine does not run the request as a device-enqueued run, or nullptr (pure host logic): the coefficient /
-// weighted instances' own rules (fused_coef_refusal / fused_weighted_refusal) and a K1 = 1 gradient pass for the fidelity points
-const char* fused_adam_ext_refusal(const Net& n, bool coefficients);
+// why the fused engine does not run the request as a device-enqueued run, or nullptr (pure host logic): the rule of the
+// family's instances (fused_tile_refusal of TILE_COEF / TILE_WEIGHTED) and a K1 = 1 gradient pass for the fidelity points
+const char* fused_adam_ext_refusal(const Net& n, int family);
 int64_t fused_adam_ext_workspace_bytes(const Net& n, int64_t N_res, int64_t N_fid);
 int fused_adam_ext(const Net& n, const AdamExtReq& q, const float* X, int64_t N_res, void* ws, int64_t ws_bytes, hipStream_t s);
 

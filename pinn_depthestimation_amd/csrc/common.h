@@ -134,24 +134,29 @@ int fused_loss(const Net& n, const LossReq& rq, const float* params, const float
 // Ensembles (pinn_ensemble_*): M networks of one shape through the tile kernel's ensemble instances (fused_kernel.h,
 // k_fused_ens), one launch for all members.  rq (and rq.adam) hold the BASE pointers of the (M, .) arrays: params, grad, m, v
 // (M, P); sums (M, n_terms); mse_sums (M, n_cols); losses (M, n_loss_rows).  flags: PINN_ENSEMBLE_OWN_X / _OWN_T.
-// fused_ensemble_refusal: why the request has no ensemble kernel, or nullptr (pure host logic).
+// fused_ensemble_refusal: why the request has no ensemble kernel, or nullptr (pure host logic): the descriptor's part is
+// fused_tile_refusal(TILE_ENSEMBLE, n), the request's the corrected radiation stress and the split request at width 33..64.
 const char* fused_ensemble_refusal(const Net& n, const LossReq& rq);
 // the per-member grid gx, whether a workgroup's gradient copy lives in LDS, and the workspace of M members on N points
 void fused_ensemble_plan(const Net& n, int M, int64_t N, int* gx, int* copy_in_lds, int64_t* ws_bytes);
 int fused_ensemble_loss(const Net& n, const LossReq& rq, int M, int flags, const float* params, const float* X, int64_t N,
                         void* ws, int64_t ws_bytes, hipStream_t s);
-// pinn_jet_backward on the tile kernel (fused_kernel.h, EPI_ADJ): grad += d/dtheta [sum(gY * Y) + sum(gdY * dY)]
-bool fused_jet_backward_supports(const Net& n);
+// The tile kernel's families of instances beside the plain forward / loss ones: external adjoint (pinn_jet_backward, EPI_ADJ),
+// per-point fields (EPI_FIELD), runtime coefficients (EPI_COEF), point weights (EPI_WEIGHTED), ensembles (k_fused_ens).
+// fused_tile_refusal: why the descriptor has no instance in the family, or nullptr = served (pure host logic; the text
+// lives in a per-thread buffer until the next call).  One rule, pinn_fused.hip; "supports" is !refusal.
+enum { TILE_ADJ, TILE_FIELD, TILE_COEF, TILE_WEIGHTED, TILE_ENSEMBLE };
+const char* fused_tile_refusal(int family, const Net& n);
 // which fused kernel a served pinn_jet_backward request runs: PINN_ENGINE_FUSED_TILE or PINN_ENGINE_FUSED_BATCH (pure host
 // logic: the decision run() itself takes)
 int fused_jet_backward_kernel(const Net& n, int64_t N);
+// pinn_jet_backward on the tile kernel (fused_kernel.h, EPI_ADJ): grad += d/dtheta [sum(gY * Y) + sum(gdY * dY)]
 int fused_jet_backward(const Net& n, const float* params, const float* X, int64_t N, const float* gY,
                        const float* gdY, float* grad, void* ws, int64_t ws_bytes, hipStream_t s);
 
-// pinn_residual_fields on the tile kernel (fused_kernel.h, EPI_FIELD): fields (NF, N) of the residual in `spec`
-bool fused_fields_supports(const Net& n);
-// ... and whether the fused engine serves a corrected-radiation-stress loss request (RES_PE_CORRECTED); if not, why not
+// whether the fused engine serves a corrected-radiation-stress loss or field request (RES_PE_CORRECTED); if not, why not
 const char* fused_corrected_refusal(const Net& n);
+// pinn_residual_fields on the tile kernel (fused_kernel.h, EPI_FIELD): fields (NF, N) of the residual in `spec`
 int64_t fused_fields_workspace_bytes(const Net& n);
 int fused_residual_fields(const Net& n, const pinn_residual_spec& spec, const float* params, const float* X, int64_t N,
                           float* fields, void* ws, int64_t ws_bytes, hipStream_t s);
@@ -159,19 +164,11 @@ int fused_residual_fields(const Net& n, const pinn_residual_spec& spec, const fl
 int fields_from_jet(const Net& net, const pinn_residual_spec& spec, const float* X, const float* Y, const float* dY,
                     int64_t n, int64_t n0, int64_t N, float* fields, hipStream_t s);
 
-// pinn_residual_coef_loss_grad on the tile kernel's coefficient instances (fused_kernel.h, EPI_COEF): why the fused engine
-// does not serve the descriptor, or nullptr (pure host logic); the workspace of a served call; the call itself (rq.coef set)
-const char* fused_coef_refusal(const Net& n);
-int64_t fused_coef_workspace_bytes(const Net& n, int64_t N);
-int fused_coef_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
+// pinn_residual_coef_loss_grad / pinn_residual_weighted_loss_grad on the tile kernel's coefficient / weighted instances
+// (family TILE_COEF: rq.coef set; TILE_WEIGHTED: rq.point_w set): the workspace of a served call (-1: not served), the call
+int64_t fused_tile_workspace_bytes(int family, const Net& n, int64_t N);
+int fused_tile_loss(int family, const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
                     int64_t ws_bytes, hipStream_t s);
-
-// pinn_residual_weighted_loss_grad on the tile kernel's weighted instances (fused_kernel.h, EPI_WEIGHTED): the same three
-// (rq.point_w set)
-const char* fused_weighted_refusal(const Net& n);
-int64_t fused_weighted_workspace_bytes(const Net& n, int64_t N);
-int fused_weighted_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
-                        int64_t ws_bytes, hipStream_t s);
 
 // wide MFMA engine, 64 < W <= 256 (pinn_wide.hip)
 bool wide_supports(const Net& n);
@@ -185,6 +182,13 @@ int wide_loss(const Net& n, const LossReq& rq, const float* params, const float*
 int device_cu_count();
 // raise a kernel's dynamic-LDS limit above 64 KB, once per (kernel, device) instead of on every launch
 int ensure_dynamic_lds(const void* kernel, size_t lds_bytes);
+
+// the caller's workspace must hold `need` bytes: every engine's check before its first launch, and the message's one place
+inline int check_workspace(const void* ws, int64_t ws_bytes, int64_t need) {
+  if (ws && ws_bytes >= need) return PINN_OK;
+  set_error("workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+  return PINN_ERR_WORKSPACE;
+}
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();

@@ -169,24 +169,23 @@ static int pick_jet_backward_engine(const pinn_desc* d, const Net& n, int* rc) {
     *rc = PINN_ERR_UNSUPPORTED;
     return PINN_ENGINE_GENERIC;
   }
-  const bool ok = fused_jet_backward_supports(n);
-  if (asked == PINN_ENGINE_FUSED && !ok) {
-    const char* why = n.act == PINN_ACT_SIN_TANH ? "the sine first layer (activation 2) has no external-adjoint kernel"
-                    : n.drop_p > 0.f ? "dropout_p > 0 has no external-adjoint kernel"
-                    : n.prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only"
-                    : n.K1 == 2 ? "k = 1 (one differentiated input) with gdY has no gradient kernel"
-                    : n.W > 64 ? "hidden width above 64"
-                    : (n.d_in > 16 || n.d_out > 16) ? "d_in or d_out above 16" : "network too deep for the per-layer locks";
+  const char* why = fused_tile_refusal(TILE_ADJ, n);
+  if (asked == PINN_ENGINE_FUSED && why) {
     set_error("pinn_jet_backward on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, hidden layers %d); "
               "engine AUTO or GENERIC runs this request on the generic engine", why, n.W, n.d_in, n.d_out, n.k, n.L);
     *rc = PINN_ERR_UNSUPPORTED;
   }
-  return ok ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
+  return why ? PINN_ENGINE_GENERIC : PINN_ENGINE_FUSED;
+}
+
+// engine e's member of a trio of functions with one signature (fused_X, wide_X, generic_X of common.h)
+template <class F>
+static F* on_engine(int e, F* fused, F* wide, F* generic) {
+  return e == PINN_ENGINE_FUSED ? fused : e == PINN_ENGINE_WIDE ? wide : generic;
 }
 
 static int64_t engine_workspace_bytes(int engine, const Net& n, int64_t N) {
-  return engine == PINN_ENGINE_FUSED ? fused_workspace_bytes(n, N)
-       : engine == PINN_ENGINE_WIDE ? wide_workspace_bytes(n, N) : generic_workspace_bytes(n, N);
+  return on_engine(engine, fused_workspace_bytes, wide_workspace_bytes, generic_workspace_bytes)(n, N);
 }
 
 // A request with the corrected radiation stress (spec.flags bit 0 -> RES_PE_CORRECTED, check_spec) is served on the engine
@@ -221,10 +220,7 @@ static int run_loss(const pinn_desc* desc, const Net& n, bool want_grad, const L
   int rc; int e = pick_engine(desc, n, want_grad, &rc);
   if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
   if (rc) return rc;
-  const hipStream_t s = (hipStream_t)stream;
-  return e == PINN_ENGINE_FUSED ? fused_loss(n, rq, params, X, N, ws, ws_bytes, s)
-       : e == PINN_ENGINE_WIDE ? wide_loss(n, rq, params, X, N, ws, ws_bytes, s)
-                               : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
+  return on_engine(e, fused_loss, wide_loss, generic_loss)(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // the fidelity columns: each must name an output of the network; copied into rq->out_col
@@ -251,7 +247,18 @@ static const ResidualInfo* residual_info(int id) {
 // (-1 for an id that names no residual)
 static int residual_terms(int id) { const ResidualInfo* r = residual_info(id); return r ? r->terms : -1; }
 static int residual_dirs(int id) { const ResidualInfo* r = residual_info(id); return r ? r->dirs : -1; }
-static int residual_n_fields(int id) { const ResidualInfo* r = residual_info(id); return r ? r->fields : -1; }
+// (the terms a point weight applies to: the residual's terms that are sums of a squared field, pinn_hip.h's n_w)
+static int residual_n_weighted(int id) { const ResidualInfo* r = residual_info(id); return !r ? -1 : r->terms < r->fields ? r->terms : r->fields; }
+
+// the entries that evaluate the residual on the network's own jet: k must be its number of directions (note: "" or what
+// the message adds after the residual's id)
+static int check_k(const char* who, const Net& n, const pinn_residual_spec* spec, const char* note) {
+  const int dirs = residual_dirs(spec->residual_id);
+  if (n.k == dirs) return PINN_OK;
+  set_error("%s: the network carries k = %d tangent directions, residual %d%s has %d (k must equal the residual's number of "
+            "directions)", who, n.k, spec->residual_id, note, dirs);
+  return PINN_ERR_UNSUPPORTED;
+}
 
 // Checks the roles the residual USES (its first nr output roles, nd direction roles) and returns in *norm a copy whose
 // unused entries are inert: out_col = -1 (matches no output column), dir_of = -1 (quantity 0 is never a direction).
@@ -281,6 +288,50 @@ static int check_spec(const Net& n, const pinn_residual_spec* sp, pinn_residual_
   // flags bit 0 on physics_equation: the corrected radiation stress, carried as an id of its own from here on
   if (sp->residual_id == PINN_RES_PHYSICS_EQUATION && (sp->flags & 1)) norm->residual_id = RES_PE_CORRECTED;
   return PINN_OK;
+}
+
+// The part of a loss request that every entry with a residual builds alike, into a zeroed *rq: the normalised spec and its
+// number of terms; the residual on points [0, n_res) and the n_cols fidelity columns on the rest (n_res < 0: both on every
+// point), with the range rules of n_res and n_cols (min_cols: 1 where the entry has no meaning for none); the columns
+// (out_col == NULL is left to the entry's own NULL checks, which follow); kind and n_split.  A residual-only entry
+// passes n_res = N and no columns.  The entry adds its pointers.
+static int build_request(const Net& n, const pinn_residual_spec* spec, int64_t N, int64_t n_res, int min_cols, int32_t n_cols,
+                         const int32_t* out_col, LossReq* rq) {
+  memset(rq, 0, sizeof(*rq));
+  if (int rc = check_spec(n, spec, &rq->spec)) return rc;
+  rq->n_terms = residual_terms(spec->residual_id);
+  if (n_res > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_res, (long long)N); return PINN_ERR_INVALID; }
+  if (n_cols < min_cols || n_cols > PINN_MAX_ROLES) {
+    set_error("n_cols=%d outside %d..%d", n_cols, min_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID;
+  }
+  if (n_cols == 0 && n_res != N) { set_error("no fidelity columns: n_res must equal N"); return PINN_ERR_INVALID; }
+  rq->n_cols = n_cols;
+  if (out_col) { if (int rc = set_out_cols(n, n_cols, out_col, rq)) return rc; }
+  if (n_res == N) { rq->kind = 0; rq->n_split = -1; }      // residual term only
+  else { rq->kind = 2; rq->n_split = n_res < 0 ? -1 : n_res; }
+  return PINN_OK;
+}
+
+// the folded update of a loss + gradient pass from the caller's state (its moments and step were checked by the entry)
+static int adam_req(const pinn_adam_state* adam, float* params, AdamReq* a) {
+  if (adam->n_loss_rows < 0 || adam->n_loss_rows > 8 || (adam->n_loss_rows > 0 && (!adam->loss_rows || !adam->losses))) {
+    set_error("bad loss_rows arguments"); return PINN_ERR_INVALID;
+  }
+  a->params = params; a->m = adam->m; a->v = adam->v;
+  a->c = adam_scalars(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step);
+  a->packed_valid = adam->packed_valid != 0;
+  a->n_loss_rows = adam->n_loss_rows; a->loss_rows = adam->loss_rows; a->losses = adam->losses;
+  return PINN_OK;
+}
+
+// the state of iteration i of a host-side loop over the folded update: its step and learning rate, the packed weights left
+// by the iteration before, and its `stride` floats of the losses array
+static pinn_adam_state adam_state_at(const pinn_adam_state* adam, int32_t i, const double* lr, int64_t stride) {
+  pinn_adam_state st = *adam;
+  st.step = adam->step + i; st.lr = lr[i];
+  st.packed_valid = (i > 0 || adam->packed_valid) ? 1 : 0;
+  if (adam->n_loss_rows > 0 && adam->losses) st.losses = adam->losses + (int64_t)i * stride;
+  return st;
 }
 
 // The one column-sum kernel of the library: the fused, wide and generic hosts launch it through reduce_sums (reduce_adam.h).
@@ -391,9 +442,7 @@ static int32_t forward_impl(const pinn_desc* desc, const float* params, const fl
   if (!jet) { n.k = 0; n.K1 = 1; dY = nullptr; }
   if (jet && n.k == 0) { set_error("forward_jet needs k >= 1"); return PINN_ERR_INVALID; }
   const int e = pick_engine(desc, n, false, &rc); if (rc) return rc;
-  return e == PINN_ENGINE_FUSED ? fused_forward(n, params, X, N, Y, dY, ws, ws_bytes, (hipStream_t)stream)
-       : e == PINN_ENGINE_WIDE ? wide_forward(n, params, X, N, Y, dY, ws, ws_bytes, (hipStream_t)stream)
-                               : generic_forward(n, params, X, N, Y, dY, ws, ws_bytes, (hipStream_t)stream);
+  return on_engine(e, fused_forward, wide_forward, generic_forward)(n, params, X, N, Y, dY, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int32_t pinn_forward(const pinn_desc* desc, const float* params, const float* X, int64_t N, float* Y, void* ws,
@@ -430,13 +479,11 @@ static int32_t residual_impl(const pinn_desc* desc, const pinn_residual_spec* sp
                              const float* params, const float* X, int64_t N, float* term_sums, float* grad_flat,
                              void* ws, int64_t ws_bytes, void* stream, bool want_grad) {
   Net n; int rc = make_net(desc, &n); if (rc) return rc;
-  pinn_residual_spec nspec; rc = check_spec(n, spec, &nspec); if (rc) return rc;
+  LossReq rq; rc = build_request(n, spec, N, N, 0, 0, nullptr, &rq); if (rc) return rc;
   if (!params || (!X && N > 0) || N < 0 || !term_sums || (want_grad && (!grad_flat || !term_scale))) {
     set_error("NULL pointer argument"); return PINN_ERR_INVALID;
   }
-  LossReq rq; memset(&rq, 0, sizeof(rq));
-  rq.kind = 0; rq.n_split = -1; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums;
-  rq.grad = want_grad ? grad_flat : nullptr; rq.n_terms = residual_terms(spec->residual_id);
+  rq.scale = term_scale; rq.sums = term_sums; rq.grad = want_grad ? grad_flat : nullptr;
   if (N == 0) { (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), (hipStream_t)stream); return PINN_OK; }
   return run_loss(desc, n, want_grad, rq, params, X, N, ws, ws_bytes, stream);
 }
@@ -473,26 +520,20 @@ static int32_t residual_mse_impl(int64_t n_split, const pinn_desc* desc, const p
                                     const float* params, const float* X, int64_t N, float* term_sums,
                                     float* col_sums, float* grad_flat, void* ws, int64_t ws_bytes, void* stream) {
   Net n; int rc = make_net(desc, &n); if (rc) return rc;
-  pinn_residual_spec nspec; rc = check_spec(n, spec, &nspec); if (rc) return rc;
-  if (n_split > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_split, (long long)N); return PINN_ERR_INVALID; }
+  LossReq rq; rc = build_request(n, spec, N, n_split, 1, n_cols, out_col, &rq); if (rc) return rc;
   if (!params || ((!X || (!T && n_split != N)) && N > 0) || N < 0 || !term_sums || !col_sums || !out_col || !grad_flat || !term_scale ||
       !col_scale) {
     set_error("NULL pointer argument"); return PINN_ERR_INVALID;
   }
-  if (n_cols < 1 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 1..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
-  LossReq rq; memset(&rq, 0, sizeof(rq));
-  rq.kind = 2; rq.n_split = n_split; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums; rq.n_terms = residual_terms(spec->residual_id);
-  rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
-  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
+  rq.scale = term_scale; rq.sums = term_sums;
+  rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
   if (N == 0) {
     (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), (hipStream_t)stream);
     (void)hipMemsetAsync(col_sums, 0, n_cols * sizeof(float), (hipStream_t)stream);
     return PINN_OK;
   }
-  if (n_split == N) {   // no fidelity points: the residual-only pass (T may be NULL)
-    rq.kind = 0; rq.n_split = -1;
-    (void)hipMemsetAsync(col_sums, 0, n_cols * sizeof(float), (hipStream_t)stream);
-  }
+  // no fidelity points: the residual-only pass (T may be NULL)
+  if (rq.kind == 0) (void)hipMemsetAsync(col_sums, 0, n_cols * sizeof(float), (hipStream_t)stream);
   return run_loss(desc, n, true, rq, params, X, N, ws, ws_bytes, stream);
 }
 
@@ -530,20 +571,13 @@ int32_t pinn_loss_grad_adam_step(const pinn_desc* desc, const pinn_residual_spec
                                  int64_t ws_bytes, void* stream) {
   Net n; int rc = make_net(desc, &n); if (rc) return rc;
   if (!spec || !adam) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
-  pinn_residual_spec nspec; rc = check_spec(n, spec, &nspec); if (rc) return rc;
+  LossReq rq; rc = build_request(n, spec, N, n_res, 0, n_cols, out_col, &rq); if (rc) return rc;
   if (!params || !X || N < 1 || !term_sums || !term_scale || !grad_flat || !adam->m || !adam->v || adam->step < 1) {
     set_error("bad arguments"); return PINN_ERR_INVALID;
   }
-  if (n_res > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_res, (long long)N); return PINN_ERR_INVALID; }
-  if (n_cols < 0 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 0..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
-  if (n_cols == 0 && n_res != N) { set_error("no fidelity columns: n_res must equal N"); return PINN_ERR_INVALID; }
   if (n_cols > 0 && (!out_col || !col_scale || !col_sums || (!T && n_res != N))) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
-  LossReq rq; memset(&rq, 0, sizeof(rq));
-  rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums; rq.n_terms = residual_terms(spec->residual_id);
-  rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
-  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
-  if (n_res == N) { rq.kind = 0; rq.n_split = -1; }      // residual term only
-  else { rq.kind = 2; rq.n_split = n_res < 0 ? -1 : n_res; }
+  rq.scale = term_scale; rq.sums = term_sums;
+  rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
   int e = pick_engine(desc, n, true, &rc);
   if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
   if (rc) return rc;
@@ -551,14 +585,7 @@ int32_t pinn_loss_grad_adam_step(const pinn_desc* desc, const pinn_residual_spec
     set_error("pinn_loss_grad_adam_step: needs a one-pass request on the fused engine (use the loss call + pinn_adam_step)");
     return PINN_ERR_UNSUPPORTED;
   }
-  AdamReq a;
-  a.params = params; a.m = adam->m; a.v = adam->v;
-  a.c = adam_scalars(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step);
-  a.packed_valid = adam->packed_valid != 0;
-  if (adam->n_loss_rows < 0 || adam->n_loss_rows > 8 || (adam->n_loss_rows > 0 && (!adam->loss_rows || !adam->losses))) {
-    set_error("bad loss_rows arguments"); return PINN_ERR_INVALID;
-  }
-  a.n_loss_rows = adam->n_loss_rows; a.loss_rows = adam->loss_rows; a.losses = adam->losses;
+  AdamReq a; rc = adam_req(adam, params, &a); if (rc) return rc;
   rq.adam = &a;
   if (rq.kind == 0 && n_cols > 0) (void)hipMemsetAsync(col_sums, 0, n_cols * sizeof(float), (hipStream_t)stream);
   return fused_loss(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
@@ -571,10 +598,7 @@ int32_t pinn_adam_loop(const pinn_desc* desc, const pinn_residual_spec* spec, co
                        void* stream) {
   if (!adam || !lr || n_iters < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
   for (int32_t i = 0; i < n_iters; ++i) {
-    pinn_adam_state st = *adam;
-    st.step = adam->step + i; st.lr = lr[i];
-    st.packed_valid = (i > 0 || adam->packed_valid) ? 1 : 0;
-    if (adam->n_loss_rows > 0 && adam->losses) st.losses = adam->losses + (int64_t)i * adam->n_loss_rows;
+    const pinn_adam_state st = adam_state_at(adam, i, lr, adam->n_loss_rows);
     const int32_t rc = pinn_loss_grad_adam_step(desc, spec, term_scale, T, n_cols, out_col, col_scale, params, X, N, n_res,
                                                 term_sums, col_sums, grad_flat, &st, ws, ws_bytes, stream);
     if (rc) return rc;      // (unsupported requests are refused by the first iteration, before anything is launched)
@@ -625,17 +649,12 @@ static int32_t ensemble_impl(const char* who, const pinn_desc* desc, const pinn_
                              const pinn_adam_state* adam, void* ws, int64_t ws_bytes, void* stream) {
   Net n; int rc = ensemble_net(who, desc, M, &n); if (rc) return rc;
   if (!spec) { set_error("%s: spec is NULL", who); return PINN_ERR_INVALID; }
-  pinn_residual_spec nspec; rc = check_spec(n, spec, &nspec); if (rc) return rc;
+  // (without out_col: no array is looked at before the refusals below; the columns follow the NULL checks)
+  LossReq rq; rc = build_request(n, spec, N, n_res, 0, n_cols, nullptr, &rq); if (rc) return rc;
   if (N < 1) { set_error("%s: N = %lld, need at least one point", who, (long long)N); return PINN_ERR_INVALID; }
-  if (n_res > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_res, (long long)N); return PINN_ERR_INVALID; }
-  if (n_cols < 0 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 0..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
-  if (n_cols == 0 && n_res != N) { set_error("no fidelity columns: n_res must equal N"); return PINN_ERR_INVALID; }
   if (flags & ~(PINN_ENSEMBLE_OWN_X | PINN_ENSEMBLE_OWN_T)) { set_error("%s: unknown flags 0x%x", who, flags); return PINN_ERR_INVALID; }
-  LossReq rq; memset(&rq, 0, sizeof(rq));
-  rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums; rq.n_terms = residual_terms(spec->residual_id);
-  rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
-  if (n_res == N) { rq.kind = 0; rq.n_split = -1; }      // residual term only
-  else { rq.kind = 2; rq.n_split = n_res < 0 ? -1 : n_res; }
+  rq.scale = term_scale; rq.sums = term_sums;
+  rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
   // the request's refusals (corrected radiation stress, the split request at width 64), before the pointers are looked at
   if (const char* why = fused_ensemble_refusal(n, rq)) { set_error("%s: %s", who, why); return PINN_ERR_UNSUPPORTED; }
   if (!params || !X || !term_sums || !term_scale || !grad_flat) { set_error("%s: NULL pointer argument", who); return PINN_ERR_INVALID; }
@@ -644,21 +663,12 @@ static int32_t ensemble_impl(const char* who, const pinn_desc* desc, const pinn_
   AdamReq a;
   if (adam) {
     if (!adam->m || !adam->v || adam->step < 1) { set_error("%s: bad adam state", who); return PINN_ERR_INVALID; }
-    if (adam->n_loss_rows < 0 || adam->n_loss_rows > 8 || (adam->n_loss_rows > 0 && (!adam->loss_rows || !adam->losses))) {
-      set_error("bad loss_rows arguments"); return PINN_ERR_INVALID;
-    }
-    a.params = params_rw; a.m = adam->m; a.v = adam->v;
-    a.c = adam_scalars(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step);
-    a.packed_valid = adam->packed_valid != 0;
-    a.n_loss_rows = adam->n_loss_rows; a.loss_rows = adam->loss_rows; a.losses = adam->losses;
+    rc = adam_req(adam, params_rw, &a); if (rc) return rc;
     rq.adam = &a;
   }
   int64_t need = 0;
   fused_ensemble_plan(n, M, N, nullptr, nullptr, &need);
-  if (!ws || ws_bytes < need) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
+  rc = check_workspace(ws, ws_bytes, need); if (rc) return rc;
   if (rq.kind == 0 && n_cols > 0) (void)hipMemsetAsync(col_sums, 0, (size_t)M * n_cols * sizeof(float), (hipStream_t)stream);
   return fused_ensemble_loss(n, rq, M, flags, params, X, N, ws, ws_bytes, (hipStream_t)stream);
 }
@@ -687,10 +697,7 @@ int32_t pinn_ensemble_adam_loop(const pinn_desc* desc, const pinn_residual_spec*
                                 int64_t ws_bytes, void* stream) {
   if (!adam || !lr || n_iters < 0) { set_error("pinn_ensemble_adam_loop: bad arguments"); return PINN_ERR_INVALID; }
   for (int32_t i = 0; i < n_iters; ++i) {
-    pinn_adam_state st = *adam;
-    st.step = adam->step + i; st.lr = lr[i];
-    st.packed_valid = (i > 0 || adam->packed_valid) ? 1 : 0;
-    if (adam->n_loss_rows > 0 && adam->losses) st.losses = adam->losses + (int64_t)i * M * adam->n_loss_rows;
+    const pinn_adam_state st = adam_state_at(adam, i, lr, (int64_t)M * adam->n_loss_rows);
     const int32_t rc = pinn_ensemble_adam_step(desc, spec, M, term_scale, T, n_cols, out_col, col_scale, params, X, N, n_res,
                                                flags, term_sums, col_sums, grad_flat, &st, ws, ws_bytes, stream);
     if (rc) return rc;      // (refusals come from the first iteration, before anything is launched)
@@ -757,12 +764,9 @@ int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, c
                         void* ws, int64_t ws_bytes, void* stream) {
   Net n; int rc = lbfgs_loop_net("pinn_lbfgs_loop", desc, &n); if (rc) return rc;
   if (!spec) { set_error("pinn_lbfgs_loop: NULL pointer argument"); return PINN_ERR_INVALID; }
-  pinn_residual_spec nspec; rc = check_spec(n, spec, &nspec); if (rc) return rc;
+  LossReq rq; rc = build_request(n, spec, N, n_res, 0, n_cols, out_col, &rq); if (rc) return rc;
   if (!params || !X || N < 1 || !term_scale || !state || !loss_rows) { set_error("pinn_lbfgs_loop: NULL pointer argument or N < 1"); return PINN_ERR_INVALID; }
   if (n_slots < 0) { set_error("pinn_lbfgs_loop: n_slots = %d", n_slots); return PINN_ERR_INVALID; }
-  if (n_res > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_res, (long long)N); return PINN_ERR_INVALID; }
-  if (n_cols < 0 || n_cols > PINN_MAX_ROLES) { set_error("n_cols=%d outside 0..%d", n_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID; }
-  if (n_cols == 0 && n_res != N) { set_error("no fidelity columns: n_res must equal N"); return PINN_ERR_INVALID; }
   if (n_cols > 0 && (!out_col || !col_scale || (!T && n_res != N))) { set_error("pinn_lbfgs_loop: NULL pointer argument"); return PINN_ERR_INVALID; }
   if (n_loss_rows < 1 || n_loss_rows > 8 || total_row < 0 || total_row >= n_loss_rows) {
     set_error("pinn_lbfgs_loop: n_loss_rows = %d outside 1..8 or total_row = %d outside it", n_loss_rows, total_row);
@@ -775,22 +779,15 @@ int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, c
     return PINN_ERR_WORKSPACE;
   }
   const LblPtrs p = lbl_ptrs(state, params, P);
-  LossReq rq; memset(&rq, 0, sizeof(rq));
-  rq.spec = nspec; rq.scale = term_scale; rq.n_terms = residual_terms(spec->residual_id);
-  rq.T = T; rq.n_cols = n_cols; rq.mse_scale = col_scale; rq.mse_sums = p.sums; rq.sums = p.sums + n_cols; rq.grad = p.gnew;
-  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
-  if (n_res == N) { rq.kind = 0; rq.n_split = -1; }      // residual term only
-  else { rq.kind = 2; rq.n_split = n_res < 0 ? -1 : n_res; }
+  rq.scale = term_scale;
+  rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = p.sums; rq.sums = p.sums + n_cols; rq.grad = p.gnew;
   {   // the refusals of the loss request itself, before anything is launched
     int e = pick_engine(desc, n, true, &rc);
     if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
     if (rc) return rc;
     const int64_t ws_need = engine_workspace_bytes(e, n, N);
     if (ws_need < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
-    if (!ws || ws_bytes < ws_need) {
-      set_error("workspace too small: need %lld bytes, got %lld", (long long)ws_need, (long long)ws_bytes);
-      return PINN_ERR_WORKSPACE;
-    }
+    rc = check_workspace(ws, ws_bytes, ws_need); if (rc) return rc;
   }
   const hipStream_t s = (hipStream_t)stream;
   for (int32_t i = 0; i < n_slots; ++i) {
@@ -804,7 +801,7 @@ int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, c
 }
 
 // ---- per-point residual fields -------------------------------------------------------------------------------------
-// Two paths. The fused tile kernel's field instances (one launch, nothing staged) where fused_fields_supports(); for
+// Two paths. The fused tile kernel's field instances (one launch, nothing staged) where fused_tile_refusal(TILE_FIELD) has none; for
 // every other request the descriptor's own pinn_forward_jet into a staging area, FIELDS_CHUNK points at a time (fixed:
 // the staging stays bounded however large the pool), followed by the point-wise kernel of pinn_fields.hip.
 // AUTO: the first where it applies, else the second.  FUSED (and sub-values): the first or refused, as pinn_jet_backward.
@@ -822,27 +819,19 @@ static int fields_plan(const pinn_desc* desc, const pinn_residual_spec* spec, in
   int rc = make_net(desc, n); if (rc) return rc;
   rc = check_spec(*n, spec, nspec); if (rc) return rc;
   const bool corrected = nspec->residual_id == RES_PE_CORRECTED;
-  if (n->k != residual_dirs(spec->residual_id)) {
-    set_error("pinn_residual_fields: the network carries k = %d tangent directions, residual %d%s has %d (k must equal the "
-              "residual's number of directions)", n->k, spec->residual_id, corrected ? " (corrected radiation stress)" : "",
-              residual_dirs(spec->residual_id));
-    return PINN_ERR_UNSUPPORTED;
-  }
+  rc = check_k("pinn_residual_fields", *n, spec, corrected ? " (corrected radiation stress)" : ""); if (rc) return rc;
   if (N < 1) { set_error("pinn_residual_fields: N = %lld, need at least one point", (long long)N); return PINN_ERR_INVALID; }
   const int asked = asked_engine(desc);
+  const char* why = fused_tile_refusal(TILE_FIELD, *n);
   // (the corrected radiation stress: the tile kernel's EPI_FIELD_PEC instances, tanh only; everything else is staged)
-  if (corrected && asked == PINN_ENGINE_FUSED && fused_fields_supports(*n) && fused_corrected_refusal(*n)) {
+  const char* why_pec = corrected ? fused_corrected_refusal(*n) : nullptr;
+  if (asked == PINN_ENGINE_FUSED && !why && why_pec) {
     set_error("pinn_residual_fields on the fused engine: the corrected radiation stress (spec.flags bit 0) %s; engine AUTO "
-              "runs this request through the forward jet", fused_corrected_refusal(*n));
+              "runs this request through the forward jet", why_pec);
     return PINN_ERR_UNSUPPORTED;
   }
-  const bool fused_ok = fused_fields_supports(*n) && !(corrected && fused_corrected_refusal(*n));
-  if (asked == PINN_ENGINE_FUSED && !fused_ok) {
-    const char* why = n->act == PINN_ACT_SIN_TANH ? "the sine first layer (activation 2) has no field kernel"
-                    : n->drop_p > 0.f ? "dropout_p > 0 has no field kernel"
-                    : n->prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only"
-                    : n->W > 64 ? "hidden width above 64"
-                    : (n->d_in > 16 || n->d_out > 16) ? "d_in or d_out above 16" : "network too deep for the tile kernel";
+  const bool fused_ok = !why && !why_pec;
+  if (asked == PINN_ENGINE_FUSED && why) {
     set_error("pinn_residual_fields on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, hidden layers %d); "
               "engine AUTO runs this request through the forward jet", why, n->W, n->d_in, n->d_out, n->k, n->L);
     return PINN_ERR_UNSUPPORTED;
@@ -878,10 +867,7 @@ int32_t pinn_residual_fields(const pinn_desc* desc, const pinn_residual_spec* sp
   Net n; pinn_residual_spec nspec; FieldsPlan pl;
   int rc = fields_plan(desc, spec, N, &n, &nspec, &pl); if (rc) return rc;
   if (!params || !X || !fields) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
-  if (!ws || ws_bytes < pl.total) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)pl.total, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
+  rc = check_workspace(ws, ws_bytes, pl.total); if (rc) return rc;
   const hipStream_t s = (hipStream_t)stream;
   if (pl.fused) return fused_residual_fields(n, nspec, params, X, N, fields, ws, ws_bytes, s);
   char* base = (char*)ws;
@@ -1003,11 +989,7 @@ static int residual2_plan(const pinn_desc* desc, const pinn_residual_spec* spec,
     set_error("pinn_residual2_loss_grad: residual %d has no momentum equation: no second-order term", spec->residual_id);
     return PINN_ERR_UNSUPPORTED;
   }
-  if (n->k != residual_dirs(spec->residual_id)) {
-    set_error("pinn_residual2_loss_grad: the network carries k = %d tangent directions, residual %d has %d (k must equal the "
-              "residual's number of directions)", n->k, spec->residual_id, residual_dirs(spec->residual_id));
-    return PINN_ERR_UNSUPPORTED;
-  }
+  rc = check_k("pinn_residual2_loss_grad", *n, spec, ""); if (rc) return rc;
   return jet2_net(desc, n, mfma);
 }
 
@@ -1054,27 +1036,25 @@ static void residual_coef_point(const float* v, const float* coef, const float* 
 }  // extern "C++"
 
 // 0 = the residual has a coefficient form; else the refusal ("no coefficient" / "corrected" in the message) or INVALID
+static bool is_corrected(int residual_id, int flags) { return residual_id == PINN_RES_PHYSICS_EQUATION && (flags & 1); }
 static int coef_residual(const char* who, int residual_id, int flags) {
-  switch (residual_id) {
-    case PINN_RES_NAVIER_STOKES: return PINN_OK;
-    case PINN_RES_PHYSICS_EQUATION:
-      if (flags & 1) {
-        set_error("%s: the corrected radiation stress (spec.flags bit 0) has no coefficient form", who);
-        return PINN_ERR_UNSUPPORTED;
-      }
-      return PINN_OK;
-    case PINN_RES_CONTINUITY_FTEMP: case PINN_RES_CONTINUITY_ONLY:
-      set_error("%s: residual %d has no closure: no coefficient", who, residual_id);
-      return PINN_ERR_UNSUPPORTED;
-    default: set_error("unknown residual_id %d", residual_id); return PINN_ERR_INVALID;
+  if (!residual_info(residual_id)) { set_error("unknown residual_id %d", residual_id); return PINN_ERR_INVALID; }
+  if (is_corrected(residual_id, flags)) {
+    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no coefficient form", who);
+    return PINN_ERR_UNSUPPORTED;
   }
+  if (residual_id != PINN_RES_NAVIER_STOKES && residual_id != PINN_RES_PHYSICS_EQUATION) {
+    set_error("%s: residual %d has no closure: no coefficient", who, residual_id);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  return PINN_OK;
 }
 
 int32_t pinn_residual_coef_count(int32_t residual_id, int32_t flags, int32_t* n) {
   if (!n) { set_error("n is NULL"); return PINN_ERR_INVALID; }
-  if (!residual_info(residual_id)) { set_error("unknown residual_id %d", residual_id); return PINN_ERR_INVALID; }
-  const bool has = residual_id == PINN_RES_NAVIER_STOKES || (residual_id == PINN_RES_PHYSICS_EQUATION && !(flags & 1));
-  *n = has ? 1 : 0;
+  const int rc = coef_residual("pinn_residual_coef_count", residual_id, flags);
+  if (rc == PINN_ERR_INVALID) return rc;
+  *n = rc == PINN_OK ? 1 : 0;      // (a residual without a coefficient form is no error here: it has none)
   return PINN_OK;
 }
 
@@ -1095,108 +1075,96 @@ int32_t pinn_residual_coef_point(int32_t residual_id, const float* v, const floa
   return PINN_OK;
 }
 
-// validation shared by the query and the call (no HIP call before it has passed); *engine <- PINN_ENGINE_FUSED (the tile
-// kernel's coefficient instances) or PINN_ENGINE_GENERIC
-static int coef_plan(const pinn_desc* desc, const pinn_residual_spec* spec, Net* n, pinn_residual_spec* nspec, int* engine) {
-  const char* who = "pinn_residual_coef_loss_grad";
-  int rc = make_net(desc, n); if (rc) return rc;
-  rc = check_spec(*n, spec, nspec); if (rc) return rc;
-  rc = coef_residual(who, spec->residual_id, spec->flags); if (rc) return rc;
-  if (n->k != residual_dirs(spec->residual_id)) {
-    set_error("%s: the network carries k = %d tangent directions, residual %d has %d (k must equal the residual's number of "
-              "directions)", who, n->k, spec->residual_id, residual_dirs(spec->residual_id));
+// ---- the residual with coefficients or with point weights: the single entries and pinn_adam_loop_ext ----------------------
+// The rules the three share, in the order of the header's tables, after the network and the spec have passed (no HIP call
+// before a refusal).  What differs is passed in: the family (TILE_COEF refuses the residuals without a coefficient form,
+// TILE_WEIGHTED the corrected radiation stress), whether k is checked before that refusal (the weighted entry's table) or
+// after it, and whether the request may leave the tile kernel: the single entries run AUTO and GENERIC on the generic
+// engine where the tile kernel has no instance, pinn_adam_loop_ext runs there or nowhere.
+// *engine <- PINN_ENGINE_FUSED (the tile kernel's instances of the family) or PINN_ENGINE_GENERIC.
+static int extra_rules(const char* who, int family, bool k_first, bool single, const pinn_desc* desc, const Net& n,
+                       const pinn_residual_spec* spec, int* engine) {
+  int rc = PINN_OK;
+  if (k_first) { rc = check_k(who, n, spec, ""); if (rc) return rc; }
+  if (family == TILE_COEF) { rc = coef_residual(who, spec->residual_id, spec->flags); if (rc) return rc; }
+  else if (is_corrected(spec->residual_id, spec->flags)) {
+    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no point-weighted form", who);
     return PINN_ERR_UNSUPPORTED;
   }
-  if (n->prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
+  if (!k_first) { rc = check_k(who, n, spec, ""); if (rc) return rc; }
+  if (n.prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
   const int asked = asked_engine(desc);
-  if (asked == PINN_ENGINE_WIDE) { set_error("%s does not run on the wide engine: use engine AUTO, FUSED or GENERIC", who); return PINN_ERR_UNSUPPORTED; }
-  const char* why = fused_coef_refusal(*n);
-  if (asked == PINN_ENGINE_FUSED && why) {
-    set_error("%s on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); engine AUTO or "
-              "GENERIC runs this request on the generic engine", who, why, n->W, n->d_in, n->d_out, n->k, n->act, (double)n->drop_p);
+  if (single && asked == PINN_ENGINE_WIDE) { set_error("%s does not run on the wide engine: use engine AUTO, FUSED or GENERIC", who); return PINN_ERR_UNSUPPORTED; }
+  if (!single && (asked == PINN_ENGINE_GENERIC || asked == PINN_ENGINE_WIDE)) {
+    set_error("%s runs on the fused tile kernel only (engine AUTO, FUSED or FUSED_TILE), not on engine %d: use the single "
+              "entries and pinn_adam_step", who, desc->engine);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  const char* why = single ? fused_tile_refusal(family, n) : fused_adam_ext_refusal(n, family);
+  if (why && (asked == PINN_ENGINE_FUSED || !single)) {
+    set_error("%s%s: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); %s", who, single ? " on the fused engine" : "",
+              why, n.W, n.d_in, n.d_out, n.k, n.act, (double)n.drop_p,
+              single ? "engine AUTO or GENERIC runs this request on the generic engine" : "use the single entries and pinn_adam_step");
     return PINN_ERR_UNSUPPORTED;
   }
   *engine = (asked != PINN_ENGINE_GENERIC && !why) ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
   return PINN_OK;
 }
 
-int32_t pinn_query_residual_coef_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
-  Net n; pinn_residual_spec nspec; int e;
-  int rc = coef_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
+// the single entries: validation shared by the query and the call; *rq <- the residual-only request
+static int single_plan(const char* who, int family, const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, Net* n,
+                       LossReq* rq, int* engine) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  rc = build_request(*n, spec, N, N, 0, 0, nullptr, rq); if (rc) return rc;
+  return extra_rules(who, family, family == TILE_WEIGHTED, true, desc, *n, spec, engine);
+}
+static int32_t single_query(const char* who, int family, const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
+  Net n; LossReq rq; int e;
+  int rc = single_plan(who, family, desc, spec, N, &n, &rq, &e); if (rc) return rc;
   if (!bytes || N < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
-  const int64_t b = e == PINN_ENGINE_FUSED ? fused_coef_workspace_bytes(n, N) : generic_workspace_bytes(n, N);
+  const int64_t b = e == PINN_ENGINE_FUSED ? fused_tile_workspace_bytes(family, n, N) : generic_workspace_bytes(n, N);
   if (b < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
   *bytes = b;
   return PINN_OK;
+}
+static int32_t single_run(int family, int e, const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N,
+                          void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (N == 0) { (void)hipMemsetAsync(rq.sums, 0, rq.n_terms * sizeof(float), s); return PINN_OK; }
+  return e == PINN_ENGINE_FUSED ? fused_tile_loss(family, n, rq, params, X, N, ws, ws_bytes, s)
+                                : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
+}
+
+int32_t pinn_query_residual_coef_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
+  return single_query("pinn_residual_coef_loss_grad", TILE_COEF, desc, spec, N, bytes);
 }
 
 int32_t pinn_residual_coef_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, const float* coef,
                                      const float* term_scale, const float* params, const float* X, int64_t N,
                                      float* term_sums, float* grad_flat, float* coef_grad, void* ws, int64_t ws_bytes,
                                      void* stream) {
-  Net n; pinn_residual_spec nspec; int e;
-  int rc = coef_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
+  Net n; LossReq rq; int e;
+  int rc = single_plan("pinn_residual_coef_loss_grad", TILE_COEF, desc, spec, N, &n, &rq, &e); if (rc) return rc;
   if (!coef || !params || (!X && N > 0) || N < 0 || !term_sums || (grad_flat && !term_scale)) {
     set_error("NULL pointer argument"); return PINN_ERR_INVALID;
   }
   if (coef_grad && !grad_flat) { set_error("coef_grad without grad_flat: the coefficient gradient comes out of the gradient pass"); return PINN_ERR_INVALID; }
-  LossReq rq; memset(&rq, 0, sizeof(rq));
-  rq.kind = 0; rq.n_split = -1; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums;
-  rq.grad = grad_flat; rq.n_terms = residual_terms(spec->residual_id);
+  rq.scale = term_scale; rq.sums = term_sums; rq.grad = grad_flat;
   rq.coef = coef; rq.coef_grad = coef_grad; rq.n_coef = 1;
-  const hipStream_t s = (hipStream_t)stream;
-  if (N == 0) { (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), s); return PINN_OK; }
-  return e == PINN_ENGINE_FUSED ? fused_coef_loss(n, rq, params, X, N, ws, ws_bytes, s)
-                                : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
+  return single_run(TILE_COEF, e, n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- per-point weights on the residual's squares -------------------------------------------------------------------------
-// validation shared by the query and the call (no HIP call before it has passed), in the order of the header's table;
-// *engine <- PINN_ENGINE_FUSED (the tile kernel's weighted instances) or PINN_ENGINE_GENERIC
-static int weighted_plan(const pinn_desc* desc, const pinn_residual_spec* spec, Net* n, pinn_residual_spec* nspec, int* engine) {
-  const char* who = "pinn_residual_weighted_loss_grad";
-  int rc = make_net(desc, n); if (rc) return rc;
-  rc = check_spec(*n, spec, nspec); if (rc) return rc;
-  if (n->k != residual_dirs(spec->residual_id)) {
-    set_error("%s: the network carries k = %d tangent directions, residual %d has %d (k must equal the residual's number of "
-              "directions)", who, n->k, spec->residual_id, residual_dirs(spec->residual_id));
-    return PINN_ERR_UNSUPPORTED;
-  }
-  if (spec->residual_id == PINN_RES_PHYSICS_EQUATION && (spec->flags & 1)) {
-    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no point-weighted form", who);
-    return PINN_ERR_UNSUPPORTED;
-  }
-  if (n->prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
-  const int asked = asked_engine(desc);
-  if (asked == PINN_ENGINE_WIDE) { set_error("%s does not run on the wide engine: use engine AUTO, FUSED or GENERIC", who); return PINN_ERR_UNSUPPORTED; }
-  const char* why = fused_weighted_refusal(*n);
-  if (asked == PINN_ENGINE_FUSED && why) {
-    set_error("%s on the fused engine: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); engine AUTO or "
-              "GENERIC runs this request on the generic engine", who, why, n->W, n->d_in, n->d_out, n->k, n->act, (double)n->drop_p);
-    return PINN_ERR_UNSUPPORTED;
-  }
-  *engine = (asked != PINN_ENGINE_GENERIC && !why) ? PINN_ENGINE_FUSED : PINN_ENGINE_GENERIC;
-  return PINN_OK;
-}
-
 int32_t pinn_query_residual_weighted_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N, int64_t* bytes) {
-  Net n; pinn_residual_spec nspec; int e;
-  int rc = weighted_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
-  if (!bytes || N < 0) { set_error("bad arguments"); return PINN_ERR_INVALID; }
-  const int64_t b = e == PINN_ENGINE_FUSED ? fused_weighted_workspace_bytes(n, N) : generic_workspace_bytes(n, N);
-  if (b < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
-  *bytes = b;
-  return PINN_OK;
+  return single_query("pinn_residual_weighted_loss_grad", TILE_WEIGHTED, desc, spec, N, bytes);
 }
 
 int32_t pinn_residual_weighted_loss_grad(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
                                          const float* point_w, int32_t w_rows, const float* params, const float* X,
                                          int64_t N, float* term_sums, float* fields, float* grad_flat, void* ws,
                                          int64_t ws_bytes, void* stream) {
-  Net n; pinn_residual_spec nspec; int e;
-  int rc = weighted_plan(desc, spec, &n, &nspec, &e); if (rc) return rc;
-  const int n_terms = residual_terms(spec->residual_id), n_fields = residual_n_fields(spec->residual_id);
-  const int n_w = n_terms < n_fields ? n_terms : n_fields;
+  Net n; LossReq rq; int e;
+  int rc = single_plan("pinn_residual_weighted_loss_grad", TILE_WEIGHTED, desc, spec, N, &n, &rq, &e); if (rc) return rc;
+  const int n_w = residual_n_weighted(spec->residual_id);
   if (!point_w) { set_error("pinn_residual_weighted_loss_grad: point_w is NULL"); return PINN_ERR_INVALID; }
   if (w_rows != 1 && w_rows != n_w) {
     set_error("pinn_residual_weighted_loss_grad: w_rows = %d, residual %d takes 1 row or %d (one per weighted term)", w_rows,
@@ -1206,23 +1174,18 @@ int32_t pinn_residual_weighted_loss_grad(const pinn_desc* desc, const pinn_resid
   if (!params || (!X && N > 0) || N < 0 || !term_sums || (grad_flat && !term_scale)) {
     set_error("NULL pointer argument"); return PINN_ERR_INVALID;
   }
-  LossReq rq; memset(&rq, 0, sizeof(rq));
-  rq.kind = 0; rq.n_split = -1; rq.spec = nspec; rq.scale = term_scale; rq.sums = term_sums;
-  rq.grad = grad_flat; rq.n_terms = n_terms;
+  rq.scale = term_scale; rq.sums = term_sums; rq.grad = grad_flat;
   rq.point_w = point_w; rq.w_stride = w_rows == 1 ? 0 : N; rq.n_weighted = n_w; rq.fields_out = fields;
-  const hipStream_t s = (hipStream_t)stream;
-  if (N == 0) { (void)hipMemsetAsync(term_sums, 0, rq.n_terms * sizeof(float), s); return PINN_OK; }
-  return e == PINN_ENGINE_FUSED ? fused_weighted_loss(n, rq, params, X, N, ws, ws_bytes, s)
-                                : generic_loss(n, rq, params, X, N, ws, ws_bytes, s);
+  return single_run(TILE_WEIGHTED, e, n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- device-enqueued Adam runs with coefficients or point weights (pinn_hip.h; kernels: pinn_fused.hip) -------------------
 // validation shared by the query and the call, in the order of the header's table (no HIP call before it has passed);
-// *coef <- the request carries coefficients (else weights), *n_w <- the residual's weighted terms
+// *res <- the residual pass's request with the group's arrays (coef set: the request carries coefficients, else weights)
 static int adam_ext_plan(const char* who, const pinn_desc* desc, const pinn_residual_spec* spec, const pinn_adam_extras* ex,
-                         int64_t N_res, int64_t N_fid, Net* n, pinn_residual_spec* nspec, bool* coef, int* n_w) {
+                         int64_t N_res, int64_t N_fid, Net* n, LossReq* res) {
   int rc = make_net(desc, n); if (rc) return rc;
-  rc = check_spec(*n, spec, nspec); if (rc) return rc;
+  rc = build_request(*n, spec, N_res, N_res, 0, 0, nullptr, res); if (rc) return rc;
   if (!ex) { set_error("%s: extras is NULL (use pinn_adam_loop for the plain request)", who); return PINN_ERR_INVALID; }
   if (ex->coef && ex->point_w) {
     set_error("%s: coefficients and point weights together: no kernel carries both", who); return PINN_ERR_UNSUPPORTED;
@@ -1230,37 +1193,17 @@ static int adam_ext_plan(const char* who, const pinn_desc* desc, const pinn_resi
   if (!ex->coef && !ex->point_w) {
     set_error("%s: neither coef nor point_w is given (use pinn_adam_loop for the plain request)", who); return PINN_ERR_INVALID;
   }
-  *coef = ex->coef != nullptr;
-  if (*coef) { rc = coef_residual(who, spec->residual_id, spec->flags); if (rc) return rc; }
-  else if (spec->residual_id == PINN_RES_PHYSICS_EQUATION && (spec->flags & 1)) {
-    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no point-weighted form", who);
-    return PINN_ERR_UNSUPPORTED;
-  }
-  if (n->k != residual_dirs(spec->residual_id)) {
-    set_error("%s: the network carries k = %d tangent directions, residual %d has %d (k must equal the residual's number of "
-              "directions)", who, n->k, spec->residual_id, residual_dirs(spec->residual_id));
-    return PINN_ERR_UNSUPPORTED;
-  }
-  if (n->prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
-  const int asked = asked_engine(desc);
-  if (asked == PINN_ENGINE_GENERIC || asked == PINN_ENGINE_WIDE) {
-    set_error("%s runs on the fused tile kernel only (engine AUTO, FUSED or FUSED_TILE), not on engine %d: use the single "
-              "entries and pinn_adam_step", who, desc->engine);
-    return PINN_ERR_UNSUPPORTED;
-  }
-  if (const char* why = fused_adam_ext_refusal(*n, *coef)) {
-    set_error("%s: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); use the single entries and "
-              "pinn_adam_step", who, why, n->W, n->d_in, n->d_out, n->k, n->act, (double)n->drop_p);
-    return PINN_ERR_UNSUPPORTED;
-  }
-  const int n_terms = residual_terms(spec->residual_id), n_fields = residual_n_fields(spec->residual_id);
-  *n_w = n_terms < n_fields ? n_terms : n_fields;
-  if (!*coef) {
-    if (ex->w_rows != 1 && ex->w_rows != *n_w) {
-      set_error("%s: w_rows = %d, residual %d takes 1 row or %d (one per weighted term)", who, ex->w_rows, spec->residual_id, *n_w);
+  int e;
+  rc = extra_rules(who, ex->coef ? TILE_COEF : TILE_WEIGHTED, false, false, desc, *n, spec, &e); if (rc) return rc;
+  if (ex->coef) { res->coef = ex->coef; res->coef_grad = ex->coef_grad; res->n_coef = 1; }
+  else {
+    const int n_w = residual_n_weighted(spec->residual_id);
+    if (ex->w_rows != 1 && ex->w_rows != n_w) {
+      set_error("%s: w_rows = %d, residual %d takes 1 row or %d (one per weighted term)", who, ex->w_rows, spec->residual_id, n_w);
       return PINN_ERR_INVALID;
     }
     if (ex->lam && ex->sa_mask != 0 && ex->sa_mask != 1) { set_error("%s: sa_mask = %d (0: w = lam^2, 1: w = lam)", who, ex->sa_mask); return PINN_ERR_INVALID; }
+    res->point_w = ex->point_w; res->w_stride = ex->w_rows == 1 ? 0 : N_res; res->n_weighted = n_w; res->fields_out = ex->fields;
   }
   if (N_res < 1 || N_fid < 0) { set_error("%s: N_res = %lld must be >= 1, N_fid = %lld >= 0", who, (long long)N_res, (long long)N_fid); return PINN_ERR_INVALID; }
   return PINN_OK;
@@ -1268,8 +1211,8 @@ static int adam_ext_plan(const char* who, const pinn_desc* desc, const pinn_resi
 
 int32_t pinn_query_adam_ext_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, const pinn_adam_extras* extras,
                                       int64_t N_res, int64_t N_fid, int64_t* bytes) {
-  Net n; pinn_residual_spec nspec; bool coef; int n_w;
-  int rc = adam_ext_plan("pinn_query_adam_ext_workspace", desc, spec, extras, N_res, N_fid, &n, &nspec, &coef, &n_w); if (rc) return rc;
+  Net n; LossReq res;
+  int rc = adam_ext_plan("pinn_query_adam_ext_workspace", desc, spec, extras, N_res, N_fid, &n, &res); if (rc) return rc;
   if (!bytes) { set_error("bytes is NULL"); return PINN_ERR_INVALID; }
   *bytes = fused_adam_ext_workspace_bytes(n, N_res, N_fid);
   return PINN_OK;
@@ -1282,8 +1225,10 @@ int32_t pinn_adam_loop_ext(const pinn_desc* desc, const pinn_residual_spec* spec
                            const pinn_adam_extras* extras, int32_t n_iters, const double* lr, const double* lr_coef,
                            const double* lr_w, void* ws, int64_t ws_bytes, void* stream) {
   const char* who = "pinn_adam_loop_ext";
-  Net n; pinn_residual_spec nspec; bool coef; int n_w;
-  int rc = adam_ext_plan(who, desc, spec, extras, N_res, N_fid, &n, &nspec, &coef, &n_w); if (rc) return rc;
+  Net n; AdamExtReq q; memset(&q, 0, sizeof(q));
+  LossReq& r = q.res;
+  int rc = adam_ext_plan(who, desc, spec, extras, N_res, N_fid, &n, &r); if (rc) return rc;
+  const bool coef = r.coef != nullptr;
   if (!adam || n_iters < 0) { set_error("%s: bad arguments", who); return PINN_ERR_INVALID; }
   if (n_iters == 0) return PINN_OK;
   if (!params || !X || !term_sums || !term_scale || !grad_flat || !adam->m || !adam->v || adam->step < 1 || !lr) {
@@ -1293,32 +1238,22 @@ int32_t pinn_adam_loop_ext(const pinn_desc* desc, const pinn_residual_spec* spec
   if (N_fid > 0 && (n_cols < 1 || !Xf || !T || !out_col || !col_scale || !col_sums)) {
     set_error("%s: fidelity points need n_cols >= 1, Xf, T, out_col, col_scale and col_sums", who); return PINN_ERR_INVALID;
   }
-  if (adam->n_loss_rows < 0 || adam->n_loss_rows > 8 || (adam->n_loss_rows > 0 && (!adam->loss_rows || !adam->losses))) {
-    set_error("bad loss_rows arguments"); return PINN_ERR_INVALID;
-  }
+  rc = adam_req(adam, params, &q.adam); if (rc) return rc;
   if (coef && extras->coef_grad && (!extras->coef_m || !extras->coef_v || !lr_coef)) {
     set_error("%s: trainable coefficients need coef_m, coef_v and lr_coef", who); return PINN_ERR_INVALID;
   }
   if (!coef && extras->lam && (!extras->lam_m || !extras->lam_v || !extras->fields || !lr_w)) {
     set_error("%s: self-adaptive weights need lam_m, lam_v, fields and lr_w", who); return PINN_ERR_INVALID;
   }
-  AdamExtReq q; memset(&q, 0, sizeof(q));
-  LossReq& r = q.res;
-  r.kind = 0; r.n_split = -1; r.spec = nspec; r.scale = term_scale; r.sums = term_sums; r.grad = grad_flat;
-  r.n_terms = residual_terms(spec->residual_id);
-  if (coef) { r.coef = extras->coef; r.coef_grad = extras->coef_grad; r.n_coef = 1; }
-  else { r.point_w = extras->point_w; r.w_stride = extras->w_rows == 1 ? 0 : N_res; r.n_weighted = n_w; r.fields_out = extras->fields; }
+  r.scale = term_scale; r.sums = term_sums; r.grad = grad_flat;
   if (N_fid > 0) {
     LossReq& m = q.fid;
     m.kind = 1; m.n_split = -1; m.T = T; m.n_cols = n_cols; m.mse_scale = col_scale; m.mse_sums = col_sums; m.grad = grad_flat;
     rc = set_out_cols(n, n_cols, out_col, &m); if (rc) return rc;
   }
   q.Xf = Xf; q.N_fid = N_fid;
-  q.params = params; q.m = adam->m; q.v = adam->v;
   q.beta1 = adam->beta1; q.beta2 = adam->beta2; q.eps = adam->eps; q.step = adam->step;
-  q.packed_valid = adam->packed_valid != 0;
-  q.n_loss_rows = adam->n_loss_rows; q.loss_rows = adam->loss_rows; q.losses = adam->losses; q.row_cols = n_cols;
-  q.col_sums = col_sums;
+  q.row_cols = n_cols; q.col_sums = col_sums;
   if (coef) {
     q.coef = extras->coef; q.coef_m = extras->coef_m; q.coef_v = extras->coef_v; q.coef_grad = extras->coef_grad;
     q.coef_mask = extras->coef_mask; q.coef_log = extras->coef_log; q.n_coef = 1;

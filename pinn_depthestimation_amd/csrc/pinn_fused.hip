@@ -522,10 +522,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   const Geo g = geo_of(n);
   WsLayout w = ws_layout(n, g, N, fld != nullptr);
   if (po) { w.scratch = po->scratch; w.wg_sums = po->wg_sums; w.wg_grads = po->wg_grads; }
-  if (!po && (!ws || ws_bytes < w.total)) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)w.total, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
+  if (!po) { if (int rc = check_workspace(ws, ws_bytes, w.total)) return rc; }
   char* base = (char*)ws;
   FusedParams P;
   memset(&P, 0, sizeof(P));
@@ -785,23 +782,68 @@ bool fused_supports(const Net& n, bool want_grad) {
   return n.W <= 64 && n.d_in <= 16 && n.d_out <= 16 && n.L >= 1 && n.K1 >= 1 && n.K1 <= 4;
 }
 
-// pinn_jet_backward on the external-adjoint instances of the tile kernel (pinn_fused_adj_wXX.hip): every gradient shape of
-// the tile kernel without dropout.  desc.engine's kernel choice does not matter for WHETHER the call is served (a request
-// the batch kernel has no instance for runs on the tile kernel), only for which of the two kernels serves it:
-bool fused_jet_backward_supports(const Net& n) {
-  Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
-  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && n.act != PINN_ACT_SIN_TANH && fused_supports(t, true);   // (no EPI_ADJ sine instance)
+// ---- the serving rule of the tile kernel's families of instances (common.h: TILE_*) ---------------------------------------
+// Every family is the tile kernel's shape class (fp32, width <= 64, d_in and d_out <= 16, a lock per layer) without dropout
+// and without the sine first layer, narrowed by what its instances exist for.  Each condition is written once, with the
+// reason a refusal gives; a family is its name in those reasons and the conditions that apply to it, in the order in which
+// its entry's table names them (with two causes at once the first is reported, and callers match on the text).
+namespace {
+enum TileCond {
+  T_FORCED,    // desc.engine forces the cooperative or the batch kernel.  Not a condition of the external-adjoint and field
+               // families: there the kernel choice does not matter for WHETHER the call is served (a request the batch kernel
+               // has no instance for runs on the tile kernel; run() always takes the tile kernel for fields)
+  T_PREC, T_WIDTH, T_SINE,
+  T_LEAKY,     // (the external-adjoint and field instances exist for LeakyReLU)
+  T_DROPOUT,
+  T_K23,       // k is a residual's number of directions: K1 = 3 or 4
+  T_K1,        // the gradient kernels' rule: no K1 = 2 (no residual of the reference has one direction); K1 = 1 is served
+  T_IO, T_DEPTH, T_END
+};
+const TileCond ADJ_CONDS[] = {T_SINE, T_DROPOUT, T_PREC, T_K1, T_WIDTH, T_IO, T_DEPTH, T_END};
+const TileCond FIELD_CONDS[] = {T_SINE, T_DROPOUT, T_PREC, T_K23, T_WIDTH, T_IO, T_DEPTH, T_END};
+const TileCond LOSS_CONDS[] = {T_FORCED, T_PREC, T_WIDTH, T_SINE, T_LEAKY, T_DROPOUT, T_K23, T_IO, T_DEPTH, T_END};
+struct TileFamily { const char* noun; const char* kernel; const TileCond* conds; };
+const TileFamily TILE_FAMILIES[] = {   // indexed by TILE_*
+    {"external-adjoint", "external-adjoint kernel", ADJ_CONDS},
+    {"field", "field kernel", FIELD_CONDS},
+    {"coefficient", "coefficient kernel on the fused engine", LOSS_CONDS},
+    {"weighted", "weighted kernel on the fused engine", LOSS_CONDS},
+    {"ensemble", "ensemble kernel", LOSS_CONDS},
+};
+// the reason of one condition, or nullptr where the network meets it (%s: the family's noun in T_FORCED, else its kernel)
+const char* tile_cond_reason(TileCond c, const Net& n) {
+  switch (c) {
+    case T_FORCED:
+      return n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH
+                 ? "the %s instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)" : nullptr;
+    case T_PREC: return n.prec != PINN_PREC_F32 ? "bf16 precision exists on the wide engine only, which has no %s" : nullptr;
+    case T_WIDTH: return n.W > 64 ? "hidden width above 64 has no %s" : nullptr;
+    case T_SINE: return n.act == PINN_ACT_SIN_TANH ? "the sine first layer (activation 2) has no %s" : nullptr;
+    case T_LEAKY: return n.act == PINN_ACT_LEAKY_RELU ? "LeakyReLU has no %s" : nullptr;
+    case T_DROPOUT: return n.drop_p > 0.f ? "dropout_p > 0 has no %s" : nullptr;
+    case T_K23: return n.K1 != 3 && n.K1 != 4 ? "k must be 2 or 3" : nullptr;
+    case T_K1: return n.K1 == 2 ? "k = 1 (one differentiated input) with gdY has no gradient kernel" : nullptr;
+    case T_IO: return n.d_in > 16 || n.d_out > 16 ? "d_in or d_out above 16" : nullptr;
+    case T_DEPTH: return n.L + 1 > MAX_LOCKS ? "network too deep for the per-layer locks" : nullptr;
+    default: return nullptr;
+  }
 }
-int fused_jet_backward_kernel(const Net& n, int64_t N) {
-  return use_batch_adj(n, geo_of(n), N) ? PINN_ENGINE_FUSED_BATCH : PINN_ENGINE_FUSED_TILE;
+}  // namespace
+
+const char* fused_tile_refusal(int family, const Net& n) {
+  static thread_local char why[192];
+  const TileFamily& f = TILE_FAMILIES[family];
+  for (const TileCond* c = f.conds; *c != T_END; ++c)
+    if (const char* fmt = tile_cond_reason(*c, n)) {
+      snprintf(why, sizeof(why), fmt, *c == T_FORCED ? f.noun : f.kernel);
+      return why;
+    }
+  return nullptr;
 }
 
-// pinn_residual_fields on the tile kernel's field instances (pinn_fused_field_wXX.hip): every forward shape of the tile
-// kernel in fp32 without dropout whose k is the residual's number of directions (K1 = 3 or 4).  desc.engine's kernel choice
-// does not matter here (run() always takes the tile kernel).
-bool fused_fields_supports(const Net& n) {
-  Net t = n; t.fused_kernel = FUSED_KERNEL_TILE;
-  return n.drop_p == 0.f && n.prec == PINN_PREC_F32 && n.act != PINN_ACT_SIN_TANH && (n.K1 == 3 || n.K1 == 4) && fused_supports(t, false);   // (no EPI_FIELD sine instance)
+// (which of the two kernels with external-adjoint instances serves a request that fused_tile_refusal(TILE_ADJ) passes)
+int fused_jet_backward_kernel(const Net& n, int64_t N) {
+  return use_batch_adj(n, geo_of(n), N) ? PINN_ENGINE_FUSED_BATCH : PINN_ENGINE_FUSED_TILE;
 }
 
 // The corrected radiation stress (EPI_PEC / EPI_FIELD_PEC instances): tanh, k = 2, no dropout.  nullptr = served.
@@ -813,58 +855,21 @@ const char* fused_corrected_refusal(const Net& n) {
   return nullptr;
 }
 
-// Runtime coefficients (EPI_COEF instances): the tile kernel only, fp32, tanh, k = 2 or 3, no dropout.  nullptr = served.
-const char* fused_coef_refusal(const Net& n) {
-  if (n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH)
-    return "the coefficient instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
-  if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no coefficient kernel";
-  if (n.W > 64) return "hidden width above 64 has no coefficient kernel on the fused engine";
-  if (n.act == PINN_ACT_SIN_TANH) return "the sine first layer (activation 2) has no coefficient kernel on the fused engine";
-  if (n.act != PINN_ACT_TANH) return "LeakyReLU has no coefficient kernel on the fused engine";
-  if (n.drop_p > 0.f) return "dropout_p > 0 has no coefficient kernel on the fused engine";
-  if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
-  if (n.d_in > 16 || n.d_out > 16) return "d_in or d_out above 16";
-  if (n.L + 1 > MAX_LOCKS) return "network too deep for the per-layer locks";
-  return nullptr;
-}
-int64_t fused_coef_workspace_bytes(const Net& n, int64_t N) {
-  if (fused_coef_refusal(n)) return -1;
+// Runtime coefficients (EPI_COEF instances, TILE_COEF) and point weights (EPI_WEIGHTED, TILE_WEIGHTED): one rule — the tile
+// kernel only, fp32, tanh, k = 2 or 3, no dropout — one workspace, one way to the kernel.
+int64_t fused_tile_workspace_bytes(int family, const Net& n, int64_t N) {
+  if (fused_tile_refusal(family, n)) return -1;
   return ws_layout(n, geo_of(n), N > 0 ? N : 1).total;
 }
-int fused_coef_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
+int fused_tile_loss(int family, const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
                     int64_t ws_bytes, hipStream_t s) {
-  if (const char* why = fused_coef_refusal(n)) { set_error("fused engine, coefficients: %s", why); return PINN_ERR_UNSUPPORTED; }
-  return run(n, rq.grad != nullptr, &rq, params, X, N, nullptr, nullptr, ws, ws_bytes, s);
-}
-
-// Point weights (EPI_WEIGHTED instances): the coefficient instances' rules — the tile kernel only, fp32, tanh, k = 2 or 3, no
-// dropout — and their workspace.
-const char* fused_weighted_refusal(const Net& n) {
-  if (n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH)
-    return "the weighted instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
-  if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no weighted kernel";
-  if (n.W > 64) return "hidden width above 64 has no weighted kernel on the fused engine";
-  if (n.act == PINN_ACT_SIN_TANH) return "the sine first layer (activation 2) has no weighted kernel on the fused engine";
-  if (n.act != PINN_ACT_TANH) return "LeakyReLU has no weighted kernel on the fused engine";
-  if (n.drop_p > 0.f) return "dropout_p > 0 has no weighted kernel on the fused engine";
-  if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
-  if (n.d_in > 16 || n.d_out > 16) return "d_in or d_out above 16";
-  if (n.L + 1 > MAX_LOCKS) return "network too deep for the per-layer locks";
-  return nullptr;
-}
-int64_t fused_weighted_workspace_bytes(const Net& n, int64_t N) {
-  if (fused_weighted_refusal(n)) return -1;
-  return ws_layout(n, geo_of(n), N > 0 ? N : 1).total;
-}
-int fused_weighted_loss(const Net& n, const LossReq& rq, const float* params, const float* X, int64_t N, void* ws,
-                        int64_t ws_bytes, hipStream_t s) {
-  if (const char* why = fused_weighted_refusal(n)) { set_error("fused engine, point weights: %s", why); return PINN_ERR_UNSUPPORTED; }
+  if (const char* why = fused_tile_refusal(family, n)) { set_error("fused engine: %s", why); return PINN_ERR_UNSUPPORTED; }
   return run(n, rq.grad != nullptr, &rq, params, X, N, nullptr, nullptr, ws, ws_bytes, s);
 }
 
 // ---- pinn_adam_loop_ext ---------------------------------------------------------------------------------------------------
-const char* fused_adam_ext_refusal(const Net& n, bool coefficients) {
-  if (const char* why = coefficients ? fused_coef_refusal(n) : fused_weighted_refusal(n)) return why;
+const char* fused_adam_ext_refusal(const Net& n, int family) {
+  if (const char* why = fused_tile_refusal(family, n)) return why;
   Net n1 = n; n1.k = 0; n1.K1 = 1;
   if (!fused_supports(n1, true)) return "the fidelity pass has no fused gradient kernel for this network";
   return nullptr;
@@ -889,15 +894,12 @@ int64_t fused_adam_ext_workspace_bytes(const Net& n, int64_t N_res, int64_t N_fi
   return ext_layout(n, geo_of(n), N_res, N_fid).total;
 }
 int fused_adam_ext(const Net& n, const AdamExtReq& q, const float* X, int64_t N_res, void* ws, int64_t ws_bytes, hipStream_t s) {
-  if (const char* why = fused_adam_ext_refusal(n, q.res.coef != nullptr)) {
+  if (const char* why = fused_adam_ext_refusal(n, q.res.coef ? TILE_COEF : TILE_WEIGHTED)) {
     set_error("fused engine, pinn_adam_loop_ext: %s", why); return PINN_ERR_UNSUPPORTED;
   }
   const Geo g = geo_of(n);
   const ExtLayout L = ext_layout(n, g, N_res, q.N_fid);
-  if (!ws || ws_bytes < L.total) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)L.total, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace(ws, ws_bytes, L.total)) return rc;
   char* base = (char*)ws;
   Net n1 = n; n1.k = 0; n1.K1 = 1;   // the fidelity term needs no input derivatives (pinn_mse_loss_grad)
   const int64_t np = n.n_params();
@@ -911,23 +913,23 @@ int fused_adam_ext(const Net& n, const AdamExtReq& q, const float* X, int64_t N_
   f.param_blocks = (int)((np + 63) / 64);
   f.n_terms = q.res.n_terms; f.n_cols = q.N_fid > 0 ? q.fid.n_cols : 0; f.row_cols = q.row_cols;
   f.term_sums = q.res.sums; f.col_sums = q.col_sums; f.grad = q.res.grad;
-  f.params = q.params; f.m = q.m; f.v = q.v;
+  f.params = q.adam.params; f.m = q.adam.m; f.v = q.adam.v;
   f.Wp = (float*)(base + L.w.wp); f.WTp = (float*)(base + L.w.wtp); f.Bp = (float*)(base + L.w.bp);
-  f.n_loss_rows = q.n_loss_rows; f.loss_rows = q.loss_rows;
+  f.n_loss_rows = q.adam.n_loss_rows; f.loss_rows = q.adam.loss_rows;
   f.n_coef = q.res.coef ? q.n_coef : 0;
   f.coef = q.coef; f.coef_m = q.coef_m; f.coef_v = q.coef_v; f.coef_grad = q.coef_grad; f.coef_mask = q.coef_mask;
   f.rows = q.w_rows; f.n_w = q.res.n_weighted; f.sa_mask = q.sa_mask; f.N = N_res;
   f.scale = q.res.scale; f.fields = q.res.fields_out; f.lam = q.lam; f.lam_m = q.lam_m; f.lam_v = q.lam_v; f.point_w = q.point_w;
   const unsigned blocks = (unsigned)f.param_blocks + 1 + (unsigned)((n_lam + 255) / 256);
   for (int i = 0; i < q.n_iters; ++i) {
-    PassOnly pr = {L.w.scratch, L.w.wg_sums, L.w.wg_grads, i == 0 && !q.packed_valid, 0, 0};
-    int rc = run(n, true, &q.res, q.params, X, N_res, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pr);
+    PassOnly pr = {L.w.scratch, L.w.wg_sums, L.w.wg_grads, i == 0 && !q.adam.packed_valid, 0, 0};
+    int rc = run(n, true, &q.res, q.adam.params, X, N_res, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pr);
     if (rc) return rc;
     // (on whichever kernel pinn_mse_loss_grad would take for these points: the cooperative one at padded width 64 while there
     // is at most one tile per CU, else the tile kernel — both natural order, one gradient copy and one sums row per workgroup)
     PassOnly pf = {L.w.scratch, L.sums_f, L.grads_f, false, 0, 0};
     if (q.N_fid > 0) {
-      rc = run(n1, true, &q.fid, q.params, q.Xf, q.N_fid, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pf);
+      rc = run(n1, true, &q.fid, q.adam.params, q.Xf, q.N_fid, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pf);
       if (rc) return rc;
     }
     f.wg_r = (const float*)(base + L.w.wg_grads); f.copies_r = pr.n_copies; f.sums_r = (const float*)(base + L.w.wg_sums); f.grid_r = pr.grid;
@@ -935,7 +937,7 @@ int fused_adam_ext(const Net& n, const AdamExtReq& q, const float* X, int64_t N_
     f.c = adam_scalars(q.lr[i], q.beta1, q.beta2, q.eps, q.step + i);
     if (f.n_coef && q.coef_grad) f.cc = adam_scalars(q.lr_coef[i], q.beta1, q.beta2, q.eps, q.step + i);
     if (q.lam) f.cw = adam_scalars(q.lr_w[i], q.beta1, q.beta2, q.eps, q.step + i);
-    f.losses = q.n_loss_rows > 0 ? q.losses + (int64_t)i * q.n_loss_rows : nullptr;
+    f.losses = q.adam.n_loss_rows > 0 ? q.adam.losses + (int64_t)i * q.adam.n_loss_rows : nullptr;
     f.coef_log = q.coef_log ? q.coef_log + (int64_t)i * f.n_coef : nullptr;
     hipLaunchKernelGGL(k_finish_adam_ext, dim3(blocks), dim3(256), 0, s, n, g.WP, g.PP, g.PW, f);
     rc = check_launch("fused finish + adam (ext)");
@@ -945,13 +947,13 @@ int fused_adam_ext(const Net& n, const AdamExtReq& q, const float* X, int64_t N_
 }
 
 int64_t fused_fields_workspace_bytes(const Net& n) {
-  if (!fused_fields_supports(n)) return -1;
+  if (fused_tile_refusal(TILE_FIELD, n)) return -1;
   return ws_layout(n, geo_of(n), 1, true).total;
 }
 
 int fused_residual_fields(const Net& n, const pinn_residual_spec& spec, const float* params, const float* X, int64_t N,
                           float* fields, void* ws, int64_t ws_bytes, hipStream_t s) {
-  if (!fused_fields_supports(n)) { set_error("fused engine: no field kernel for this request (k = %d)", n.k); return PINN_ERR_UNSUPPORTED; }
+  if (const char* why = fused_tile_refusal(TILE_FIELD, n)) { set_error("fused engine: %s", why); return PINN_ERR_UNSUPPORTED; }
   const FieldReq fld{spec, fields};
   return run(n, false, nullptr, params, X, N, nullptr, nullptr, ws, ws_bytes, s, nullptr, &fld);
 }
@@ -978,7 +980,7 @@ int fused_forward(const Net& n, const float* params, const float* X, int64_t N, 
 
 int fused_jet_backward(const Net& n, const float* params, const float* X, int64_t N, const float* gY, const float* gdY,
                        float* grad, void* ws, int64_t ws_bytes, hipStream_t s) {
-  if (!fused_jet_backward_supports(n)) { set_error("fused engine: no external-adjoint kernel for this request (k = %d)", n.k); return PINN_ERR_UNSUPPORTED; }
+  if (const char* why = fused_tile_refusal(TILE_ADJ, n)) { set_error("fused engine: %s", why); return PINN_ERR_UNSUPPORTED; }
   const AdjReq adj{gY, gdY, grad};
   return run(n, true, nullptr, params, X, N, nullptr, nullptr, ws, ws_bytes, s, &adj);
 }
@@ -1044,17 +1046,9 @@ EnsPlan ens_plan(const Net& n, const Geo& g, int M, int64_t N) {
 }  // namespace
 
 const char* fused_ensemble_refusal(const Net& n, const LossReq& rq) {
-  if (n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH)
-    return "the ensemble instances are the tile kernel's: engine FUSED_COOP / FUSED_BATCH has none (use AUTO, FUSED or FUSED_TILE)";
-  if (n.prec != PINN_PREC_F32) return "bf16 precision exists on the wide engine only, which has no ensemble kernel";
-  if (n.W > 64) return "hidden width above 64 has no ensemble kernel";
-  if (n.act == PINN_ACT_SIN_TANH) return "the sine first layer (activation 2) has no ensemble kernel";
-  if (n.act != PINN_ACT_TANH) return "LeakyReLU has no ensemble kernel";
-  if (n.drop_p > 0.f) return "dropout_p > 0 has no ensemble kernel";
-  if (rq.kind != 1 && rq.spec.residual_id == RES_PE_CORRECTED) return "the corrected radiation stress (spec.flags bit 0) has no ensemble kernel";
-  if (n.K1 != 3 && n.K1 != 4) return "k must be 2 or 3";
-  if (n.d_in > 16 || n.d_out > 16) return "d_in or d_out above 16";
-  if (n.L + 1 > MAX_LOCKS) return "network too deep for the per-layer locks";
+  // (the descriptor's rule first: the entries decide it before they have a request, pinn_abi.hip ensemble_net)
+  if (const char* why = fused_tile_refusal(TILE_ENSEMBLE, n)) return why;
+  if (is_pec(&rq)) return "the corrected radiation stress (spec.flags bit 0) has no ensemble kernel";
   if (rq.kind == 2 && rq.n_split >= 0 && padded_width(n.W) == 64)
     return "the split request (0 <= n_res < N) at hidden width 33..64: the tile kernel carries no split code there";
   return nullptr;
@@ -1072,10 +1066,7 @@ int fused_ensemble_loss(const Net& n, const LossReq& rq, int M, int flags, const
   if (const char* why = fused_ensemble_refusal(n, rq)) { set_error("fused engine, ensemble: %s", why); return PINN_ERR_UNSUPPORTED; }
   const Geo g = geo_of(n);
   const EnsPlan e = ens_plan(n, g, M, N);
-  if (!ws || ws_bytes < e.total) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)e.total, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace(ws, ws_bytes, e.total)) return rc;
   char* base = (char*)ws;
   FusedParams P;
   memset(&P, 0, sizeof(P));

@@ -638,11 +638,7 @@ int64_t generic_workspace_bytes(const Net& n, int64_t N) {
 
 static int prep(const Net& n, int64_t N, int64_t ws_bytes, void* ws, Layout* lo) {
   if (!make_layout(n, N, lo)) { set_error("too many layers for the generic engine"); return PINN_ERR_UNSUPPORTED; }
-  if (!ws || ws_bytes < lo->total) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)lo->total, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
-  return PINN_OK;
+  return check_workspace(ws, ws_bytes, lo->total);
 }
 
 int generic_forward(const Net& n, const float* params, const float* X, int64_t N, float* Y, float* dY, void* ws,

@@ -134,7 +134,7 @@ extern "C" {
 int32_t pinn_nanminmax_f64(const double* data, int64_t n, double* out2, void* ws, int64_t ws_bytes, void* stream) {
   if (!data || n < 0 || !out2) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
   const int nb = (int)(n / IB + 1 < 1024 ? n / IB + 1 : 1024);
-  if (!ws || ws_bytes < (int64_t)nb * 16) { set_error("workspace too small: need %d bytes", nb * 16); return PINN_ERR_WORKSPACE; }
+  if (int rc = check_workspace(ws, ws_bytes, (int64_t)nb * 16)) return rc;
   hipLaunchKernelGGL(k_nanminmax_partial, dim3(nb), dim3(IB), 0, (hipStream_t)stream, data, n, (double*)ws);
   hipLaunchKernelGGL(k_nanminmax_final, dim3(1), dim3(IB), 0, (hipStream_t)stream, (const double*)ws, nb, out2);
   return check_launch("nanminmax");
@@ -154,7 +154,7 @@ int32_t pinn_stage_grid_columns(const double* const* grids, int32_t d_in, int64_
   const int64_t nys = (ny + ix - 1) / ix, nxs = (nx + iy - 1) / iy, rows = nys * nxs;
   if (rows > ((int64_t)1 << 31) - 1) { set_error("more than 2^31 staged rows"); return PINN_ERR_UNSUPPORTED; }
   const int64_t need = pinn_stage_workspace_bytes(ny, nx, ix, iy);
-  if (!ws || ws_bytes < need) { set_error("workspace too small: need %lld bytes", (long long)need); return PINN_ERR_WORKSPACE; }
+  if (int rc = check_workspace(ws, ws_bytes, need)) return rc;
   Grids g;
   for (int c = 0; c < 16; ++c) g.p[c] = c < d_in ? grids[c] : nullptr;
   for (int c = 0; c < d_in; ++c) if (!g.p[c]) { set_error("grid %d is NULL", c); return PINN_ERR_INVALID; }

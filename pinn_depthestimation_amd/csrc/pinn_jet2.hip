@@ -766,11 +766,7 @@ void run_bwd_chunk(const Net& n, const float* params, int64_t n0, char* ws, cons
 
 int prep2(const Net& n, int64_t N, int64_t ws_bytes, void* ws, Layout2* lo) {
   if (!make_layout2(n, N, lo)) { set_error("too many layers for the jet2 kernels"); return PINN_ERR_UNSUPPORTED; }
-  if (!ws || ws_bytes < lo->total) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)lo->total, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
-  return PINN_OK;
+  return check_workspace(ws, ws_bytes, lo->total);
 }
 
 }  // namespace
@@ -879,10 +875,7 @@ int residual2_loss_grad(const Net& n, bool mfma, const pinn_residual_spec& spec,
   Layout2 lo;
   if (!make_layout2(n, N, &lo)) { set_error("too many layers for the jet2 kernels"); return PINN_ERR_UNSUPPORTED; }
   const int64_t need = lo.total + align256(residual2_rows(N, lo.Nc) * RES2_NT * 4);
-  if (!ws || ws_bytes < need) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace(ws, ws_bytes, need)) return rc;
   char* w = (char*)ws;
   float* partial = (float*)(w + lo.total);
   int64_t rows = 0;

@@ -354,10 +354,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
         float* dY, void* ws, int64_t ws_bytes, hipStream_t s) {
   const WGeo g = wgeo(n);
   const WLayout w = wlayout(n, g, N);
-  if (!ws || ws_bytes < w.total) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)w.total, (long long)ws_bytes);
-    return PINN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace(ws, ws_bytes, w.total)) return rc;
   return g.NTW == 8 ? run_w<8>(n, g, grad, rq, params, X, N, Y, dY, (char*)ws, w, s)
                     : run_w<16>(n, g, grad, rq, params, X, N, Y, dY, (char*)ws, w, s);
 }
