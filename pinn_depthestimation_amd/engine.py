@@ -6,8 +6,10 @@ libpinn_hip.so.  Nothing in this file synchronises the device.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-from dataclasses import dataclass, field
+import dataclasses
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -56,11 +58,7 @@ class NetDesc:
         return sum(ls[i] * ls[i + 1] + ls[i + 1] for i in range(len(ls) - 1))
 
     def with_(self, **kw) -> "NetDesc":
-        d = dict(d_in=self.d_in, d_out=self.d_out, n_hidden=self.n_hidden, width=self.width,
-                 grad_cols=self.grad_cols, activation=self.activation, engine=self.engine,
-                 precision=self.precision, dropout_p=self.dropout_p)
-        d.update(kw)
-        return NetDesc(**d)
+        return dataclasses.replace(self, **kw)
 
     def c_struct(self) -> PinnDesc:
         if self.k > _lib.PINN_MAX_DIRS:
@@ -198,6 +196,41 @@ def _chk(t: torch.Tensor, name: str, shape=None):
         raise PinnError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
 
 
+def _out_cols(out_col: Sequence[int]):
+    """The fidelity columns as the C-ABI's int32 array (never of length zero: ctypes would have no address for it)."""
+    return (C.c_int32 * max(len(out_col), 1))(*out_col)
+
+
+def _lr_list(lr, sequence: bool = False) -> Optional[List[float]]:
+    """A list or tuple of learning rates (sequence=True: any iterable) as floats, one per enqueued iteration; None for one
+    scalar rate."""
+    return [float(x) for x in lr] if sequence or isinstance(lr, (list, tuple)) else None
+
+
+def _adam_state(m, v, step, lr, beta1, beta2, eps, packed_valid: bool, n_rows: int, loss_rows, losses) -> _lib.PinnAdamState:
+    """pinn_adam_state of a folded-Adam call; lr None: the rates travel beside it, one per iteration."""
+    return _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0 if lr is None else float(lr), float(beta1), float(beta2),
+                              float(eps), 1 if packed_valid else 0, n_rows, _ptr(loss_rows), _ptr(losses))
+
+
+# ---- the packed-weights token ------------------------------------------------------------------------------------------
+# A folded-Adam call leaves the packed copy of the weights it trained in its workspace; the next one may skip the packing
+# kernel only if that copy is still what it would pack: the same workspace tensor, the same `params` storage and torch
+# version counter, the same caller's token and the same request (which picks the kernel, and with it the packed layout).
+# A rule that forgot one of the five would train on stale weights without an error: it lives here, once.
+def _packed_token(ws: torch.Tensor, params: torch.Tensor, params_token, req: tuple) -> tuple:
+    """What a successful folded-Adam call stores: read AFTER the call, so the version is the one the call left."""
+    return (ws, params.data_ptr(), params._version, params_token, req)
+
+
+def _packed_valid(tok: Optional[tuple], ws: torch.Tensor, params: torch.Tensor, params_token, req: tuple) -> bool:
+    """Whether the packed copy described by the stored token `tok` serves this call (the workspace by identity)."""
+    return tok is not None and tok[0] is ws and tok[1:] == _packed_token(ws, params, params_token, req)[1:]
+
+
+_NO_GUARD = contextlib.nullcontext()
+
+
 class Engine:
     """One network geometry bound to one device; owns the workspace cache."""
 
@@ -205,10 +238,10 @@ class Engine:
         self.lib = _lib.load()
         self.desc = desc
         self.device = torch.device(device)
-        self._cdesc: Dict[Tuple[int, int], PinnDesc] = {}
-        self._ws: Dict[object, torch.Tensor] = {}
-        self._ws_need: Dict[tuple, int] = {}
-        self._packed_tok = None      # (workspace, params storage, params version, caller's token) after loss_grad_adam_step
+        self._cdesc: Dict[int, PinnDesc] = {}
+        self._ws: Dict[object, torch.Tensor] = {}      # buffer key -> workspace (_workspace)
+        self._ws_need: Dict[tuple, int] = {}           # need key -> bytes the query answered
+        self._packed_tok = None      # _packed_token after loss_grad_adam_step / adam_loop_ext
         self._ens_packed_tok = None  # ... after ensemble_adam_step, for the M packed copies in the ensemble workspace
         self.dropout_seed = 0        # training-mode dropout: the caller sets a fresh seed per forward pass; the
                                      # reverse sweep of that pass must run under the same one (include/pinn_hip.h)
@@ -217,8 +250,11 @@ class Engine:
         self.n_params = cnt.value
 
     # ---- plumbing -------------------------------------------------------------------
+    def _e(self, engine: Optional[int]) -> int:
+        return self.desc.engine if engine is None else engine
+
     def _d(self, engine: Optional[int] = None) -> PinnDesc:
-        e = self.desc.engine if engine is None else engine
+        e = self._e(engine)
         if e not in self._cdesc:
             self._cdesc[e] = self.desc.with_(engine=e).c_struct()
         d = self._cdesc[e]
@@ -230,61 +266,111 @@ class Engine:
         if t.device.index != self._index():
             raise PinnError(f"{name} lives on {t.device} but this engine is bound to {self.device}")
 
+    def _chk_px(self, params: torch.Tensor, X: torch.Tensor) -> int:
+        """Checks the flat parameter vector and the points; returns N."""
+        N = X.shape[0]
+        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        return N
+
+    def _sums(self, sums: Optional[torch.Tensor], name: str, shape, like: torch.Tensor) -> torch.Tensor:
+        """The caller's buffer for loss sums, checked like every other argument, or a new one on `like`'s device."""
+        if sums is None:
+            return torch.empty(shape, dtype=torch.float32, device=like.device)
+        self._chk(sums, name, shape)
+        return sums
+
+    def _chk_losses(self, loss_rows: Optional[torch.Tensor], losses, n_in: int, lead: tuple) -> int:
+        """Checks loss_rows (rows, n_in) and losses (*lead, rows); returns rows, 0 without loss_rows."""
+        if loss_rows is None:
+            return 0
+        n_rows = loss_rows.shape[0]
+        self._chk(loss_rows, "loss_rows", (n_rows, n_in)); self._chk(losses, "losses", (*lead, n_rows))
+        return n_rows
+
+    @staticmethod
+    def _unsupported(rc: int, what: str) -> bool:
+        """True where the library refused the request (the caller returns False, the reason is in last_error()); any other
+        failure is raised."""
+        if rc == _lib.ERR_UNSUPPORTED:
+            return True
+        check(rc, what)
+        return False
+
     def _index(self) -> int:
         """Ordinal of this engine's GPU ("cuda" without an index binds to the device current at first use)."""
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         return self.device.index
 
+    def _guard(self):
+        """A context in which this engine's device is current; nothing is exchanged where it already is."""
+        idx = self._index()
+        return _NO_GUARD if torch.cuda.current_device() == idx else torch.cuda.device(idx)
+
+    def _stream(self):
+        """The current stream of this engine's device, as the last argument of a C-ABI call."""
+        return C.c_void_p(torch.cuda.current_stream(self._index()).cuda_stream)
+
     def _run(self, what: str, fn, *args):
         """Call one C-ABI entry point on THIS engine's device and on that device's current stream
         (appended as the last argument), whatever device the calling thread has current: launch
         geometry (CU count) and the stream both belong to the device the tensors live on."""
-        idx = self._index()
         self._packed_tok = None      # any other call may re-pack the workspace from ITS params argument
         self._ens_packed_tok = None  # (the ensemble calls' token: the same rule)
-        if torch.cuda.current_device() != idx:
-            with torch.cuda.device(idx):
-                check(fn(*args, C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)), what)
-        else:
-            check(fn(*args, C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)), what)
+        with self._guard():
+            check(fn(*args, self._stream()), what)
+
+    # ---- the workspace cache ----------------------------------------------------------------------------------------
+    def _workspace(self, buf_key, need_key, query) -> Tuple[int, Optional[torch.Tensor]]:
+        """(0, the buffer `buf_key`, of at least the bytes the query answers for `need_key`), or (rc, None) where the
+        query fails.  query() -> (rc, bytes) runs once per need key; a failed one is not remembered and touches no buffer.
+        One uint8 buffer per buf_key on this engine's device, of at least 256 bytes: it only grows, and a request that
+        fits gets the very tensor the last one got.  Kinds never share a buffer: what one call leaves in its workspace
+        (the packed weights) survives calls of another kind."""
+        need = self._ws_need.get(need_key)
+        if need is None:
+            rc, need = query()
+            if rc != 0:
+                return rc, None
+            self._ws_need[need_key] = need
+        ws = self._ws.get(buf_key)
+        if ws is None or ws.numel() < need:
+            self._ws[buf_key] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            if buf_key == "ens":      # the members' packed copies went with the old buffer
+                self._ens_packed_tok = None
+        return 0, ws
+
+    def _query(self, symbol: str, *args) -> Tuple[int, int]:
+        """(rc, bytes) of the workspace query `symbol`, asked with this engine's device current (the answer depends on
+        that device's CU count wherever the query reads it)."""
+        need = C.c_int64()
+        with self._guard():
+            rc = getattr(self.lib, symbol)(*args, C.byref(need))
+        return rc, need.value
+
+    def _checked_workspace(self, kind, symbol: str, spec: Optional[ResidualSpec], N: int, engine, *key) -> torch.Tensor:
+        """The buffer (kind, engine) — kind None: workspace()'s own, keyed by the engine alone — sized by `symbol`
+        (desc[, spec], N), one query per (kind, engine, *key, N); a failed query is raised."""
+        e = self._e(engine)
+        buf_key, need_key = (e, (e, N)) if kind is None else ((kind, e), (kind, e, *key, N))
+
+        def query():
+            of = (C.byref(self._d(e)),) if spec is None else (C.byref(self._d(e)), C.byref(spec.c_struct()))
+            return self._query(symbol, *of, N)
+        rc, ws = self._workspace(buf_key, need_key, query)
+        check(rc, symbol)
+        return ws
 
     def workspace(self, N: int, engine: Optional[int] = None) -> torch.Tensor:
-        e = self.desc.engine if engine is None else engine
-        key = (e, N)
-        need = self._ws_need.get(key)
-        if need is None:
-            c_need = C.c_int64()
-            idx = self._index()
-            if torch.cuda.current_device() != idx:      # the answer depends on the device's CU count
-                with torch.cuda.device(idx):
-                    check(self.lib.pinn_query_workspace(C.byref(self._d(e)), N, C.byref(c_need)), "pinn_query_workspace")
-            else:
-                check(self.lib.pinn_query_workspace(C.byref(self._d(e)), N, C.byref(c_need)), "pinn_query_workspace")
-            need = self._ws_need[key] = c_need.value
-        ws = self._ws.get(e)
-        if ws is None or ws.numel() < need:
-            self._ws[e] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return ws
+        return self._checked_workspace(None, "pinn_query_workspace", None, N, engine)
 
     def jet2_workspace(self, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of the second-order calls (pinn_query_jet2_workspace), cached apart from workspace()'s."""
-        e = self.desc.engine if engine is None else engine
-        key = ("jet2", e, N)
-        need = self._ws_need.get(key)
-        if need is None:
-            c_need = C.c_int64()
-            check(self.lib.pinn_query_jet2_workspace(C.byref(self._d(e)), N, C.byref(c_need)), "pinn_query_jet2_workspace")
-            need = self._ws_need[key] = c_need.value
-        ws = self._ws.get(("jet2", e))
-        if ws is None or ws.numel() < need:
-            self._ws[("jet2", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return ws
+        return self._checked_workspace("jet2", "pinn_query_jet2_workspace", None, N, engine)
 
-    # ---- calls ------------------------------------------------------------------------
+    # ---- calls ------------------------------------------------------------------------------------
     def forward(self, params: torch.Tensor, X: torch.Tensor, engine=None) -> torch.Tensor:
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         Y = torch.empty(N, self.desc.d_out, dtype=torch.float32, device=X.device)
         ws = self.workspace(N, engine)
         self._run("pinn_forward", self.lib.pinn_forward, C.byref(self._d(engine)), _ptr(params), _ptr(X), N, _ptr(Y), _ptr(ws),
@@ -292,8 +378,7 @@ class Engine:
         return Y
 
     def forward_jet(self, params: torch.Tensor, X: torch.Tensor, engine=None):
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         Y = torch.empty(N, self.desc.d_out, dtype=torch.float32, device=X.device)
         dY = torch.empty(self.desc.k, N, self.desc.d_out, dtype=torch.float32, device=X.device)
         ws = self.workspace(N, engine)
@@ -307,8 +392,7 @@ class Engine:
         is the descriptor's engine: AUTO runs an MFMA kernel where one serves the request (width <= 64, no dropout,
         k != 1 when gdY is given; the batch kernel for narrow tanh networks from 4096 points on, else the tile kernel)
         and the generic engine otherwise; FUSED is refused where AUTO would fall back.  jet_backward_kernel() tells which."""
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         self._chk(grad, "grad", (self.n_params,))
         if gY is not None: self._chk(gY, "gY", (N, self.desc.d_out))
         if gdY is not None: self._chk(gdY, "gdY", (self.desc.k, N, self.desc.d_out))
@@ -334,8 +418,7 @@ class Engine:
     def forward_jet2(self, params: torch.Tensor, X: torch.Tensor, engine=None):
         """(Y, dY, d2Y): Y (N, d_out), dY (k, N, d_out), d2Y (P, N, d_out) with row p = pair (i, j) of the
         differentiated columns, upper triangle row-major (pinn_forward_jet2)."""
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         Y = torch.empty(N, self.desc.d_out, dtype=torch.float32, device=X.device)
         dY = torch.empty(self.desc.k, N, self.desc.d_out, dtype=torch.float32, device=X.device)
         d2Y = torch.empty(self.n_pairs, N, self.desc.d_out, dtype=torch.float32, device=X.device)
@@ -347,8 +430,7 @@ class Engine:
     def jet2_backward(self, params, X, gY: Optional[torch.Tensor], gdY: Optional[torch.Tensor],
                       gd2Y: Optional[torch.Tensor], grad: torch.Tensor, engine=None) -> torch.Tensor:
         """grad += d/d params [sum(gY*Y) + sum(gdY*dY) + sum(gd2Y*d2Y)] (pinn_jet2_backward); any adjoint may be None."""
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         self._chk(grad, "grad", (self.n_params,))
         if gY is not None: self._chk(gY, "gY", (N, self.desc.d_out))
         if gdY is not None: self._chk(gdY, "gdY", (self.desc.k, N, self.desc.d_out))
@@ -360,9 +442,8 @@ class Engine:
 
     def residual_loss(self, spec: ResidualSpec, params, X, engine=None) -> torch.Tensor:
         spec.first_order("residual_loss")
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
-        sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
+        N = self._chk_px(params, X)
+        sums = self._sums(None, "sums", (spec.n_terms,), X)
         ws = self.workspace(N, engine)
         self._run("pinn_residual_loss", self.lib.pinn_residual_loss, C.byref(self._d(engine)), C.byref(spec.c_struct()), _ptr(params),
                                           _ptr(X), N, _ptr(sums), _ptr(ws), ws.numel())
@@ -371,19 +452,7 @@ class Engine:
     def fields_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual_fields (pinn_query_fields_workspace), cached apart from workspace()'s."""
         spec.first_order("fields_workspace")
-        e = self.desc.engine if engine is None else engine
-        key = ("fields", e, spec.residual_id, spec.corrected, N)
-        need = self._ws_need.get(key)
-        if need is None:
-            c_need = C.c_int64()
-            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
-                check(self.lib.pinn_query_fields_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
-                      "pinn_query_fields_workspace")
-            need = self._ws_need[key] = c_need.value
-        ws = self._ws.get(("fields", e))
-        if ws is None or ws.numel() < need:
-            self._ws[("fields", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return ws
+        return self._checked_workspace("fields", "pinn_query_fields_workspace", spec, N, engine, spec.residual_id, spec.corrected)
 
     def residual_fields(self, spec: ResidualSpec, params, X, engine=None) -> torch.Tensor:
         """The residual's signed per-point fields, (n_fields, N): row f is field f at every row of X
@@ -391,8 +460,7 @@ class Engine:
         descriptor's engine: AUTO runs the MFMA tile kernel's field instances where they exist (width <= 64, fp32, no
         dropout) and the forward jet plus a point-wise kernel otherwise; FUSED is refused where AUTO would fall back."""
         spec.first_order("residual_fields")
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         out = torch.empty(spec.n_fields, N, dtype=torch.float32, device=X.device)
         ws = self.fields_workspace(spec, N, engine)
         self._run("pinn_residual_fields", self.lib.pinn_residual_fields, C.byref(self._d(engine)), C.byref(spec.c_struct()),
@@ -403,11 +471,9 @@ class Engine:
                            engine=None, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
         """grad += sum_t term_scale[t] * d(term_sums[t])/d(params); returns term_sums (device)."""
         spec.first_order("residual_loss_grad")
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
-        if sums is None:
-            sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
+        sums = self._sums(sums, "sums", (spec.n_terms,), X)
         ws = self.workspace(N, engine)
         self._run("pinn_residual_loss_grad", self.lib.pinn_residual_loss_grad, C.byref(self._d(engine)), C.byref(spec.c_struct()),
                                                _ptr(term_scale), _ptr(params), _ptr(X), N, _ptr(sums),
@@ -417,19 +483,7 @@ class Engine:
     def residual_coef_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual_coef_loss_grad (pinn_query_residual_coef_workspace), cached apart from the others."""
         spec.first_order("residual_coef_workspace")
-        e = self.desc.engine if engine is None else engine
-        key = ("coef", e, spec.residual_id, spec.corrected, N)
-        need = self._ws_need.get(key)
-        if need is None:
-            c_need = C.c_int64()
-            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
-                check(self.lib.pinn_query_residual_coef_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
-                      "pinn_query_residual_coef_workspace")
-            need = self._ws_need[key] = c_need.value
-        ws = self._ws.get(("coef", e))
-        if ws is None or ws.numel() < need:
-            self._ws[("coef", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return ws
+        return self._checked_workspace("coef", "pinn_query_residual_coef_workspace", spec, N, engine, spec.residual_id, spec.corrected)
 
     def residual_coef_loss_grad(self, spec: ResidualSpec, coef: torch.Tensor, term_scale: Optional[torch.Tensor], params, X,
                                 grad: Optional[torch.Tensor] = None, coef_grad: Optional[torch.Tensor] = None,
@@ -442,8 +496,7 @@ class Engine:
         engine=None is the descriptor's: AUTO runs the tile kernel's coefficient instances where they exist (fp32, tanh,
         width <= 64, no dropout) and the generic engine otherwise."""
         spec.first_order("residual_coef_loss_grad")
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         if coef is None:
             raise PinnError("residual_coef_loss_grad: coef is None (use residual_loss_grad for the compiled-in constants)")
         self._chk(coef, "coef", (max(spec.n_coefs, 1),))
@@ -453,10 +506,7 @@ class Engine:
             if grad is None:
                 raise PinnError("residual_coef_loss_grad: coef_grad without grad (the coefficient gradient comes out of the gradient pass)")
             self._chk(coef_grad, "coef_grad", (max(spec.n_coefs, 1),))
-        if sums is None:
-            sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
-        else:
-            self._chk(sums, "sums", (spec.n_terms,))
+        sums = self._sums(sums, "sums", (spec.n_terms,), X)
         ws = self.residual_coef_workspace(spec, N, engine)
         self._run("pinn_residual_coef_loss_grad", self.lib.pinn_residual_coef_loss_grad, C.byref(self._d(engine)),
                   C.byref(spec.c_struct()), _ptr(coef), _ptr(term_scale) if grad is not None else None, _ptr(params), _ptr(X), N,
@@ -466,19 +516,8 @@ class Engine:
     def residual_weighted_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual_weighted_loss_grad (pinn_query_residual_weighted_workspace), cached apart from the others."""
         spec.first_order("residual_weighted_workspace")
-        e = self.desc.engine if engine is None else engine
-        key = ("weighted", e, spec.residual_id, spec.corrected, N)
-        need = self._ws_need.get(key)
-        if need is None:
-            c_need = C.c_int64()
-            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
-                check(self.lib.pinn_query_residual_weighted_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
-                      "pinn_query_residual_weighted_workspace")
-            need = self._ws_need[key] = c_need.value
-        ws = self._ws.get(("weighted", e))
-        if ws is None or ws.numel() < need:
-            self._ws[("weighted", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return ws
+        return self._checked_workspace("weighted", "pinn_query_residual_weighted_workspace", spec, N, engine, spec.residual_id,
+                                       spec.corrected)
 
     def residual_weighted_loss_grad(self, spec: ResidualSpec, weights: torch.Tensor, scale: Optional[torch.Tensor], theta, X,
                                     grad: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None, fields=None,
@@ -490,8 +529,7 @@ class Engine:
         (scale may then be None).  fields: None, a (n_fields, N) tensor to overwrite with the unweighted signed fields, or
         True to allocate one.  Returns term_sums, or (term_sums, fields) when fields were asked for."""
         spec.first_order("residual_weighted_loss_grad")
-        N = X.shape[0]
-        self._chk(theta, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(theta, X)
         if weights is None:
             raise PinnError("residual_weighted_loss_grad: weights is None (use residual_loss_grad for the unweighted sums)")
         if weights.dim() not in (1, 2) or weights.shape[-1] != N:
@@ -500,10 +538,7 @@ class Engine:
         self._chk(weights, "weights", tuple(weights.shape))
         if grad is not None:
             self._chk(grad, "grad", (self.n_params,)); self._chk(scale, "term_scale", (spec.n_terms,))
-        if sums is None:
-            sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
-        else:
-            self._chk(sums, "sums", (spec.n_terms,))
+        sums = self._sums(sums, "sums", (spec.n_terms,), X)
         if fields is True:
             fields = torch.empty(spec.n_fields, N, dtype=torch.float32, device=X.device)
         elif fields is not None and fields is not False:
@@ -521,18 +556,7 @@ class Engine:
 
     def residual2_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual2_loss_grad (pinn_query_residual2_workspace), cached apart from the others."""
-        e = self.desc.engine if engine is None else engine
-        key = ("res2", e, spec.residual_id, N)
-        need = self._ws_need.get(key)
-        if need is None:
-            c_need = C.c_int64()
-            check(self.lib.pinn_query_residual2_workspace(C.byref(self._d(e)), C.byref(spec.c_struct()), N, C.byref(c_need)),
-                  "pinn_query_residual2_workspace")
-            need = self._ws_need[key] = c_need.value
-        ws = self._ws.get(("res2", e))
-        if ws is None or ws.numel() < need:
-            self._ws[("res2", e)] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return ws
+        return self._checked_workspace("res2", "pinn_query_residual2_workspace", spec, N, engine, spec.residual_id)
 
     def residual2_loss_grad(self, spec: ResidualSpec, term_scale: Optional[torch.Tensor], params, X,
                             grad: Optional[torch.Tensor] = None, fields: bool = False,
@@ -542,14 +566,10 @@ class Engine:
         also grad += sum_t term_scale[t] * d(term_sums[t])/d(params).  grad=None runs no backward sweep (term_scale may
         then be None).  spec.nu == 0 gives the first-order residual.  engine=None is the descriptor's: AUTO runs the MFMA
         kernels where every layer is at most 64 wide (fp32, no dropout) and the generic ones otherwise."""
-        N = X.shape[0]
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N = self._chk_px(params, X)
         if grad is not None:
             self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
-        if sums is None:
-            sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
-        else:
-            self._chk(sums, "sums", (spec.n_terms,))
+        sums = self._sums(sums, "sums", (spec.n_terms,), X)
         out = torch.empty(spec.n_fields, N, dtype=torch.float32, device=X.device) if fields else None
         ws = self.residual2_workspace(spec, N, engine)
         self._run("pinn_residual2_loss_grad", self.lib.pinn_residual2_loss_grad, C.byref(self._d(engine)),
@@ -560,34 +580,29 @@ class Engine:
     def mse_loss_grad(self, params, X, T: torch.Tensor, out_col: Sequence[int],
                       col_scale: Optional[torch.Tensor], grad: Optional[torch.Tensor], engine=None,
                       sums: Optional[torch.Tensor] = None) -> torch.Tensor:
-        N, nc = X.shape[0], len(out_col)
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in)); self._chk(T, "T", (N, nc))
+        N, nc = self._chk_px(params, X), len(out_col)
+        self._chk(T, "T", (N, nc))
         if grad is not None:
             self._chk(grad, "grad", (self.n_params,)); self._chk(col_scale, "col_scale", (nc,))
-        if sums is None:
-            sums = torch.empty(nc, dtype=torch.float32, device=X.device)
-        oc = (C.c_int32 * nc)(*out_col)
+        sums = self._sums(sums, "sums", (nc,), X)
         ws = self.workspace(N, engine)
-        self._run("pinn_mse_loss_grad", self.lib.pinn_mse_loss_grad, C.byref(self._d(engine)), _ptr(params), _ptr(X), _ptr(T), N, nc, oc,
-                                          _ptr(col_scale), _ptr(sums), _ptr(grad), _ptr(ws), ws.numel())
+        self._run("pinn_mse_loss_grad", self.lib.pinn_mse_loss_grad, C.byref(self._d(engine)), _ptr(params), _ptr(X), _ptr(T), N, nc,
+                                          _out_cols(out_col), _ptr(col_scale), _ptr(sums), _ptr(grad), _ptr(ws), ws.numel())
         return sums
 
     def residual_mse_loss_grad(self, spec: ResidualSpec, term_scale, T: torch.Tensor, out_col: Sequence[int],
                                col_scale, params, X, grad, engine=None, term_sums=None, col_sums=None):
         """One pass over one point set: PDE residual + fidelity columns (train_newmethod.py:122-159)."""
         spec.first_order("residual_mse_loss_grad")
-        N, nc = X.shape[0], len(out_col)
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in)); self._chk(T, "T", (N, nc))
+        N, nc = self._chk_px(params, X), len(out_col)
+        self._chk(T, "T", (N, nc))
         self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
         self._chk(col_scale, "col_scale", (nc,))
-        if term_sums is None:
-            term_sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
-        if col_sums is None:
-            col_sums = torch.empty(nc, dtype=torch.float32, device=X.device)
-        oc = (C.c_int32 * nc)(*out_col)
+        term_sums = self._sums(term_sums, "term_sums", (spec.n_terms,), X)
+        col_sums = self._sums(col_sums, "col_sums", (nc,), X)
         ws = self.workspace(N, engine)
         self._run("pinn_residual_mse_loss_grad", self.lib.pinn_residual_mse_loss_grad, C.byref(self._d(engine)), C.byref(spec.c_struct()), _ptr(term_scale),
-                                                   _ptr(T), nc, oc, _ptr(col_scale), _ptr(params), _ptr(X), N,
+                                                   _ptr(T), nc, _out_cols(out_col), _ptr(col_scale), _ptr(params), _ptr(X), N,
                                                    _ptr(term_sums), _ptr(col_sums), _ptr(grad), _ptr(ws), ws.numel())
         return term_sums, col_sums
 
@@ -597,18 +612,15 @@ class Engine:
         """train.py:131-157 in one launch: X = [n_res collocation points ; fidelity points], T = the
         fidelity targets (N - n_res, n_cols)."""
         spec.first_order("residual_mse_split_loss_grad")
-        N, nc = X.shape[0], len(out_col)
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in)); self._chk(T, "T", (N - n_res, nc))
+        N, nc = self._chk_px(params, X), len(out_col)
+        self._chk(T, "T", (N - n_res, nc))
         self._chk(grad, "grad", (self.n_params,)); self._chk(term_scale, "term_scale", (spec.n_terms,))
         self._chk(col_scale, "col_scale", (nc,))
-        if term_sums is None:
-            term_sums = torch.empty(spec.n_terms, dtype=torch.float32, device=X.device)
-        if col_sums is None:
-            col_sums = torch.empty(nc, dtype=torch.float32, device=X.device)
-        oc = (C.c_int32 * nc)(*out_col)
+        term_sums = self._sums(term_sums, "term_sums", (spec.n_terms,), X)
+        col_sums = self._sums(col_sums, "col_sums", (nc,), X)
         ws = self.workspace(N, engine)
-        self._run("pinn_residual_mse_split_loss_grad", self.lib.pinn_residual_mse_split_loss_grad, 
-            C.byref(self._d(engine)), C.byref(spec.c_struct()), _ptr(term_scale), _ptr(T), nc, oc, _ptr(col_scale),
+        self._run("pinn_residual_mse_split_loss_grad", self.lib.pinn_residual_mse_split_loss_grad,
+            C.byref(self._d(engine)), C.byref(spec.c_struct()), _ptr(term_scale), _ptr(T), nc, _out_cols(out_col), _ptr(col_scale),
             _ptr(params), _ptr(X), N, int(n_res), _ptr(term_sums), _ptr(col_sums), _ptr(grad), _ptr(ws), ws.numel())
         return term_sums, col_sums
 
@@ -625,14 +637,13 @@ class Engine:
         Returns False — nothing launched — when the request is not a one-pass request of the fused engine.
         The packing kernel is skipped when the previous call on this engine was this method and `params` has not
         been written since: same workspace, same storage, same torch version counter of `params` AND the same
-        `params_token`.  torch's version counter is per alias family: tensors that share `params`' storage through
-        `.data` (dnn.DNN's Linear weights, `p.data = flat[...]`) have counters of their own, so a caller whose buffer
+        `params_token` (_packed_valid).  torch's version counter is per alias family: tensors that share `params`' storage
+        through `.data` (dnn.DNN's Linear weights, `p.data = flat[...]`) have counters of their own, so a caller whose buffer
         is aliased that way passes a token that changes whenever any alias is written (DNN.write_token(): the
         Parameters' version counters); writes no counter sees (`p.data.mul_()`) need invalidate_packed()."""
         spec.first_order("loss_grad_adam_step")
-        N, nc = X.shape[0], len(out_col)
-        lrs = [float(x) for x in lr] if isinstance(lr, (list, tuple)) else None
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        lrs = _lr_list(lr)
+        N, nc = self._chk_px(params, X), len(out_col)
         for t, nme in ((grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
             self._chk(t, nme, (self.n_params,))
         self._chk(term_scale, "term_scale", (spec.n_terms,)); self._chk(term_sums, "term_sums", (spec.n_terms,))
@@ -640,32 +651,23 @@ class Engine:
             self._chk(col_scale, "col_scale", (nc,)); self._chk(col_sums, "col_sums", (nc,))
             if n_res != N:
                 self._chk(T, "T", (N - n_res if n_res >= 0 else N, nc))
-        n_rows = 0
-        if loss_rows is not None:
-            n_rows = loss_rows.shape[0]
-            self._chk(loss_rows, "loss_rows", (n_rows, nc + spec.n_terms))
-            self._chk(losses, "losses", (n_rows,) if lrs is None else (len(lrs), n_rows))
+        n_rows = self._chk_losses(loss_rows, losses, nc + spec.n_terms, () if lrs is None else (len(lrs),))
         ws = self.workspace(N)
-        tok = self._packed_tok
-        packed_valid = (tok is not None and tok[0] is ws and tok[1] == params.data_ptr() and tok[2] == params._version
-                        and tok[3] == params_token and tok[4] == (N, int(n_res), nc, spec.residual_id, spec.corrected))     # (the request picks the kernel, and with it the packed layout)
+        req = (N, int(n_res), nc, spec.residual_id, spec.corrected)
+        st = _adam_state(m, v, step, None if lrs is not None else lr, beta1, beta2, eps,
+                         _packed_valid(self._packed_tok, ws, params, params_token, req), n_rows, loss_rows, losses)
         self._packed_tok = None
-        st = _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0 if lrs is not None else float(lr), float(beta1), float(beta2),
-                                float(eps), 1 if packed_valid else 0, n_rows, _ptr(loss_rows), _ptr(losses))
-        oc = (C.c_int32 * max(nc, 1))(*out_col)
-        idx = self._index()
-        head = (C.byref(self._d()), C.byref(spec.c_struct()), _ptr(term_scale), _ptr(T), nc, oc, _ptr(col_scale),
+        head = (C.byref(self._d()), C.byref(spec.c_struct()), _ptr(term_scale), _ptr(T), nc, _out_cols(out_col), _ptr(col_scale),
                 _ptr(params), _ptr(X), N, int(n_res), _ptr(term_sums), _ptr(col_sums), _ptr(grad), C.byref(st))
-        with torch.cuda.device(idx):
-            tail = (_ptr(ws), ws.numel(), C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+        with self._guard():
+            tail = (_ptr(ws), ws.numel(), self._stream())
             if lrs is None:
                 rc = self.lib.pinn_loss_grad_adam_step(*head, *tail)
             else:
                 rc = self.lib.pinn_adam_loop(*head, len(lrs), (C.c_double * len(lrs))(*lrs), *tail)
-        if rc == _lib.ERR_UNSUPPORTED:
+        if self._unsupported(rc, "pinn_loss_grad_adam_step" if lrs is None else "pinn_adam_loop"):
             return False
-        check(rc, "pinn_loss_grad_adam_step" if lrs is None else "pinn_adam_loop")
-        self._packed_tok = (ws, params.data_ptr(), params._version, params_token, (N, int(n_res), nc, spec.residual_id, spec.corrected))
+        self._packed_tok = _packed_token(ws, params, params_token, req)
         return True
 
     def adam_loop_ext(self, spec: ResidualSpec, term_scale, params, X, grad, m, v, step: int, lr: Sequence[float],
@@ -688,10 +690,9 @@ class Engine:
         last_error() — where the request is not served (engine, precision, activation, width, dropout, corrected, the
         continuity residuals with coef, both groups).  The packing kernel is skipped under loss_grad_adam_step's rules."""
         spec.first_order("adam_loop_ext")
-        N, nc = X.shape[0], len(out_col)
-        lrs = [float(x) for x in lr]
+        lrs = _lr_list(lr, sequence=True)
         k = len(lrs)
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N, nc = self._chk_px(params, X), len(out_col)
         for t, nme in ((grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
             self._chk(t, nme, (self.n_params,))
         self._chk(term_scale, "term_scale", (spec.n_terms,)); self._chk(term_sums, "term_sums", (spec.n_terms,))
@@ -700,10 +701,7 @@ class Engine:
             self._chk(col_sums, "col_sums", (nc,))
         if n_fid:
             self._chk(Xf, "Xf", (n_fid, self.desc.d_in)); self._chk(T, "T", (n_fid, nc)); self._chk(col_scale, "col_scale", (nc,))
-        n_rows = 0
-        if loss_rows is not None:
-            n_rows = loss_rows.shape[0]
-            self._chk(loss_rows, "loss_rows", (n_rows, nc + spec.n_terms)); self._chk(losses, "losses", (k, n_rows))
+        n_rows = self._chk_losses(loss_rows, losses, nc + spec.n_terms, (k,))
         ex = _lib.PinnAdamExtras()
         kind = ("coef" if coef is not None else "") + ("w" if point_w is not None else "") + ("sa" if lam is not None else "")
         keep = []          # ctypes arrays must outlive the call
@@ -742,47 +740,32 @@ class Engine:
             a = (C.c_double * max(k, 1))(*xs); keep.append(a)
             return a
 
-        idx = self._index()
-        key = ("adamext", kind, spec.residual_id, spec.corrected, N, n_fid)
-        with torch.cuda.device(idx):
-            need = self._ws_need.get(key)
-            if need is None:
-                c_need = C.c_int64()
-                rc = self.lib.pinn_query_adam_ext_workspace(C.byref(self._d()), C.byref(spec.c_struct()), C.byref(ex), N, n_fid,
-                                                            C.byref(c_need))
-                if rc == _lib.ERR_UNSUPPORTED:
-                    return False
-                check(rc, "pinn_query_adam_ext_workspace")
-                need = self._ws_need[key] = c_need.value
-            ws = self._ws.get("adamext")
-            if ws is None or ws.numel() < need:
-                self._ws["adamext"] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-            req = ("ext", kind, N, n_fid, nc, spec.residual_id, spec.corrected)
-            tok = self._packed_tok
-            packed_valid = (tok is not None and tok[0] is ws and tok[1] == params.data_ptr() and tok[2] == params._version
-                            and tok[3] == params_token and tok[4] == req)
-            self._packed_tok = None
-            self._ens_packed_tok = None
-            st = _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0, float(beta1), float(beta2), float(eps),
-                                    1 if packed_valid else 0, n_rows, _ptr(loss_rows), _ptr(losses))
-            oc = (C.c_int32 * max(nc, 1))(*out_col)
+        rc, ws = self._workspace("adamext", ("adamext", kind, spec.residual_id, spec.corrected, N, n_fid), lambda: self._query(
+            "pinn_query_adam_ext_workspace", C.byref(self._d()), C.byref(spec.c_struct()), C.byref(ex), N, n_fid))
+        if self._unsupported(rc, "pinn_query_adam_ext_workspace"):
+            return False
+        req = ("ext", kind, N, n_fid, nc, spec.residual_id, spec.corrected)
+        st = _adam_state(m, v, step, None, beta1, beta2, eps, _packed_valid(self._packed_tok, ws, params, params_token, req),
+                         n_rows, loss_rows, losses)
+        self._packed_tok = None
+        self._ens_packed_tok = None
+        with self._guard():
             rc = self.lib.pinn_adam_loop_ext(
                 C.byref(self._d()), C.byref(spec.c_struct()), _ptr(term_scale), _ptr(Xf) if n_fid else None,
-                _ptr(T) if n_fid else None, n_fid, nc, oc, _ptr(col_scale) if n_fid else None, _ptr(params), _ptr(X), N,
+                _ptr(T) if n_fid else None, n_fid, nc, _out_cols(out_col), _ptr(col_scale) if n_fid else None, _ptr(params), _ptr(X), N,
                 _ptr(term_sums), _ptr(col_sums) if nc else None, _ptr(grad), C.byref(st), C.byref(ex), k, darr(lrs),
-                darr(lr_coef), darr(lr_w), _ptr(ws), ws.numel(), C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        if rc == _lib.ERR_UNSUPPORTED:
+                darr(lr_coef), darr(lr_w), _ptr(ws), ws.numel(), self._stream())
+        if self._unsupported(rc, "pinn_adam_loop_ext"):
             return False
-        check(rc, "pinn_adam_loop_ext")
         if k > 0:
-            self._packed_tok = (ws, params.data_ptr(), params._version, params_token, req)
+            self._packed_tok = _packed_token(ws, params, params_token, req)
         return True
 
     # ---- the device-resident L-BFGS loop (pinn_lbfgs_loop) ------------------------------------------------------------
     def lbfgs_loop_query(self, N: int, history_size: int) -> Tuple[int, int]:
         """(workspace bytes, state bytes) of lbfgs_loop on N points with this history size (pinn_query_lbfgs_loop)."""
         ws, st = C.c_int64(), C.c_int64()
-        with torch.cuda.device(self._index()):      # the pass's workspace depends on the device's CU count
+        with self._guard():      # the pass's workspace depends on the device's CU count
             check(self.lib.pinn_query_lbfgs_loop(C.byref(self._d()), int(N), int(history_size), C.byref(ws), C.byref(st)),
                   "pinn_query_lbfgs_loop")
         return ws.value, st.value
@@ -801,8 +784,7 @@ class Engine:
         loss_grad_adam_step; loss_rows (rows x (len(out_col) + n_terms)), total_row the objective's row.  `params` holds the
         accepted iterate whenever the enqueued work has run; trace (n_slots, LBFGS_TRACE_COLS) float64, optional."""
         spec.first_order("lbfgs_loop")
-        N, nc = X.shape[0], len(out_col)
-        self._chk(params, "params", (self.n_params,)); self._chk(X, "X", (N, self.desc.d_in))
+        N, nc = self._chk_px(params, X), len(out_col)
         self._chk(term_scale, "term_scale", (spec.n_terms,))
         self._chk(loss_rows, "loss_rows", (loss_rows.shape[0], nc + spec.n_terms))
         if nc:
@@ -816,41 +798,28 @@ class Engine:
             raise PinnError("state must be a contiguous uint8 tensor on the engine's device")
         if ws is None:
             ws = self.workspace(N)
-        oc = (C.c_int32 * max(nc, 1))(*out_col)
         self._run("pinn_lbfgs_loop", self.lib.pinn_lbfgs_loop, C.byref(self._d()), C.byref(spec.c_struct()), _ptr(term_scale),
-                  _ptr(T), nc, oc, _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), loss_rows.shape[0], _ptr(loss_rows),
-                  int(total_row), _ptr(state), state.numel(), int(n_slots), _ptr(trace), _ptr(ws), ws.numel())
+                  _ptr(T), nc, _out_cols(out_col), _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), loss_rows.shape[0],
+                  _ptr(loss_rows), int(total_row), _ptr(state), state.numel(), int(n_slots), _ptr(trace), _ptr(ws), ws.numel())
 
     # ---- ensembles: M networks of this geometry in one launch (pinn_ensemble_*) ---------------------------------------------
-    def _ensemble_need(self, M: int, N: int) -> Tuple[int, int]:
-        """(return code, workspace bytes) of pinn_ensemble_query_workspace, cached; host logic only."""
-        key = ("ens", int(M), int(N))
-        got = self._ws_need.get(key)
-        if got is None:
-            c_need = C.c_int64()
-            with torch.cuda.device(self._index()):      # the answer depends on the device's CU count
-                rc = self.lib.pinn_ensemble_query_workspace(C.byref(self._d()), int(M), int(N), C.byref(c_need))
-            got = (rc, c_need.value)
-            if rc == 0:
-                self._ws_need[key] = got
-        return got
+    def _ensemble_workspace(self, M: int, N: int) -> Tuple[int, Optional[torch.Tensor]]:
+        """(rc, workspace) of the ensemble calls: _workspace on pinn_ensemble_query_workspace, the one buffer "ens"."""
+        return self._workspace("ens", ("ens", int(M), int(N)), lambda: self._query(
+            "pinn_ensemble_query_workspace", C.byref(self._d()), int(M), int(N)))
 
     def ensemble_workspace(self, M: int, N: int) -> torch.Tensor:
         """Workspace of the ensemble calls for M members on N points (pinn_ensemble_query_workspace), cached apart from
         workspace()'s.  Raises PinnError with the engine's reason where the ensemble calls are refused."""
-        rc, need = self._ensemble_need(M, N)
+        rc, ws = self._ensemble_workspace(M, N)
         check(rc, "pinn_ensemble_query_workspace")
-        ws = self._ws.get("ens")
-        if ws is None or ws.numel() < need:
-            self._ws["ens"] = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-            self._ens_packed_tok = None
         return ws
 
     def ensemble_plan(self, M: int, N: int) -> Tuple[int, bool]:
         """(workgroups per member, whether a workgroup's gradient copy lives in LDS) of an ensemble pass of M members on N
         points (pinn_ensemble_plan).  Raises PinnError where the ensemble calls are refused.  Host logic only."""
         gx, lds = C.c_int32(), C.c_int32()
-        with torch.cuda.device(self._index()):
+        with self._guard():
             check(self.lib.pinn_ensemble_plan(C.byref(self._d()), int(M), int(N), C.byref(gx), C.byref(lds)), "pinn_ensemble_plan")
         return gx.value, bool(lds.value)
 
@@ -860,12 +829,12 @@ class Engine:
         hidden width 33..64) from pinn_ensemble_loss_grad called WITHOUT arrays — it decides its refusals before it
         looks at a pointer (pinn_hip.h) and then stops at the NULL arguments.  Host logic only: nothing is launched."""
         gx, lds = C.c_int32(), C.c_int32()
-        with torch.cuda.device(self._index()):
+        with self._guard():
             rc = self.lib.pinn_ensemble_plan(C.byref(self._d()), int(M), int(N), C.byref(gx), C.byref(lds))
             if rc == 0:
-                oc = (C.c_int32 * max(n_cols, 1))(*range(n_cols))
                 rc = self.lib.pinn_ensemble_loss_grad(C.byref(self._d()), C.byref(spec.c_struct()), int(M), None, None, int(n_cols),
-                                                      oc, None, None, None, int(N), int(n_res), 0, None, None, None, None, 0, None)
+                                                      _out_cols(range(n_cols)), None, None, None, int(N), int(n_res), 0, None, None,
+                                                      None, None, 0, None)
         if rc == _lib.ERR_UNSUPPORTED:
             return self.last_error()
         if rc not in (0, _lib.ERR_INVALID):
@@ -885,14 +854,10 @@ class Engine:
         self._chk(X, "X", (M, N, self.desc.d_in) if own_x else (N, self.desc.d_in))
         self._chk(term_scale, "term_scale", (spec.n_terms,))
         flags = _lib.ENSEMBLE_OWN_X if own_x else 0
-        if term_sums is None:
-            term_sums = torch.empty(M, spec.n_terms, dtype=torch.float32, device=params.device)
-        self._chk(term_sums, "term_sums", (M, spec.n_terms))
+        term_sums = self._sums(term_sums, "term_sums", (M, spec.n_terms), params)
         if nc:
             self._chk(col_scale, "col_scale", (nc,))
-            if col_sums is None:
-                col_sums = torch.empty(M, nc, dtype=torch.float32, device=params.device)
-            self._chk(col_sums, "col_sums", (M, nc))
+            col_sums = self._sums(col_sums, "col_sums", (M, nc), params)
             if n_res != N:
                 rows = N - n_res if n_res >= 0 else N
                 if T is not None and T.dim() == 3:
@@ -913,9 +878,8 @@ class Engine:
         M, N, nc, flags, term_sums, col_sums = self._ensemble_args(spec, term_scale, params, X, n_res, grad, T, out_col, col_scale,
                                                                    term_sums, col_sums)
         ws = self.ensemble_workspace(M, N)
-        oc = (C.c_int32 * max(nc, 1))(*out_col)
         self._run("pinn_ensemble_loss_grad", self.lib.pinn_ensemble_loss_grad, C.byref(self._d()), C.byref(spec.c_struct()), M,
-                  _ptr(term_scale), _ptr(T), nc, oc, _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), flags,
+                  _ptr(term_scale), _ptr(T), nc, _out_cols(out_col), _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), flags,
                   _ptr(term_sums), _ptr(col_sums), _ptr(grad), _ptr(ws), ws.numel())
         return term_sums, col_sums
 
@@ -930,41 +894,30 @@ class Engine:
         learning-rate schedule for all members.  Returns False — nothing launched, the reason in last_error() — where the
         request has no ensemble kernel.  The packed-weights token is this method's own, under loss_grad_adam_step's rules."""
         spec.first_order("ensemble_adam_step")
-        lrs = [float(x) for x in lr] if isinstance(lr, (list, tuple)) else None
+        lrs = _lr_list(lr)
         M, N, nc, flags, term_sums, col_sums = self._ensemble_args(spec, term_scale, params, X, n_res, grad, T, out_col, col_scale,
                                                                    term_sums, col_sums)
         for t, nme in ((m, "exp_avg"), (v, "exp_avg_sq")):
             self._chk(t, nme, (M, self.n_params))
-        n_rows = 0
-        if loss_rows is not None:
-            n_rows = loss_rows.shape[0]
-            self._chk(loss_rows, "loss_rows", (n_rows, nc + spec.n_terms))
-            self._chk(losses, "losses", (M, n_rows) if lrs is None else (len(lrs), M, n_rows))
-        rc, _ = self._ensemble_need(M, N)
-        if rc == _lib.ERR_UNSUPPORTED:
+        n_rows = self._chk_losses(loss_rows, losses, nc + spec.n_terms, (M,) if lrs is None else (len(lrs), M))
+        rc, ws = self._ensemble_workspace(M, N)
+        if self._unsupported(rc, "pinn_ensemble_query_workspace"):
             return False
-        ws = self.ensemble_workspace(M, N)
         req = (M, N, int(n_res), nc, flags, spec.residual_id, spec.corrected)
-        tok = self._ens_packed_tok
-        packed_valid = (tok is not None and tok[0] is ws and tok[1] == params.data_ptr() and tok[2] == params._version
-                        and tok[3] == params_token and tok[4] == req)
+        st = _adam_state(m, v, step, None if lrs is not None else lr, beta1, beta2, eps,
+                         _packed_valid(self._ens_packed_tok, ws, params, params_token, req), n_rows, loss_rows, losses)
         self._ens_packed_tok = None
-        st = _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0 if lrs is not None else float(lr), float(beta1), float(beta2),
-                                float(eps), 1 if packed_valid else 0, n_rows, _ptr(loss_rows), _ptr(losses))
-        oc = (C.c_int32 * max(nc, 1))(*out_col)
-        idx = self._index()
-        head = (C.byref(self._d()), C.byref(spec.c_struct()), M, _ptr(term_scale), _ptr(T), nc, oc, _ptr(col_scale),
+        head = (C.byref(self._d()), C.byref(spec.c_struct()), M, _ptr(term_scale), _ptr(T), nc, _out_cols(out_col), _ptr(col_scale),
                 _ptr(params), _ptr(X), N, int(n_res), flags, _ptr(term_sums), _ptr(col_sums), _ptr(grad), C.byref(st))
-        with torch.cuda.device(idx):
-            tail = (_ptr(ws), ws.numel(), C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+        with self._guard():
+            tail = (_ptr(ws), ws.numel(), self._stream())
             if lrs is None:
                 rc = self.lib.pinn_ensemble_adam_step(*head, *tail)
             else:
                 rc = self.lib.pinn_ensemble_adam_loop(*head, len(lrs), (C.c_double * len(lrs))(*lrs), *tail)
-        if rc == _lib.ERR_UNSUPPORTED:
+        if self._unsupported(rc, "pinn_ensemble_adam_step" if lrs is None else "pinn_ensemble_adam_loop"):
             return False
-        check(rc, "pinn_ensemble_adam_step" if lrs is None else "pinn_ensemble_adam_loop")
-        self._ens_packed_tok = (ws, params.data_ptr(), params._version, params_token, req)
+        self._ens_packed_tok = _packed_token(ws, params, params_token, req)
         return True
 
     def last_error(self) -> str:
@@ -984,6 +937,6 @@ class Engine:
         n = self.n_params if count is None else int(count)
         for t, nme in ((params, "params"), (grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
             self._chk(t, nme, (n,))
-        self._packed_tok = None
         self._run("pinn_adam_step", self.lib.pinn_adam_step, _ptr(params), _ptr(grad), _ptr(m), _ptr(v), n, step, lr, beta1,
                                       beta2, eps)
+

@@ -20,7 +20,7 @@ from .config import PinnConfig, load_config
 from .dnn import DNN, activation_id_of, init_flat_params
 from .engine import Engine, NetDesc, ResidualSpec
 from .parallel import Reducer
-from .trainer import _as_f32
+from .trainer import _as_f32, steplr_factors
 
 DEFAULT_SEED = 1234      # trainer.PINN's default seed: member i starts from DEFAULT_SEED + i
 
@@ -190,7 +190,7 @@ class EnsemblePINN:
         n = int(n)
         while n > 0:
             k = min(n, self.MAX_RUN)
-            lrs = [a["learning_rate"] * a["scheduler_gamma"] ** ((self._sched_steps + i) // a["scheduler_step_size"]) for i in range(k)]
+            lrs = [a["learning_rate"] * f for f in steplr_factors(a, self._sched_steps, k)]
             out = self._run_losses[:k]
             nf = len(self.fid_cols)
             ok = self.eng.ensemble_adam_step(self.spec, self._res_scale, self.theta, self.X, self._n_res, self.grad, self._adam_m,

@@ -193,6 +193,17 @@ def _as_f32(a, device) -> Optional[torch.Tensor]:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _dropout_seed() -> int:
+    """A fresh seed for one forward pass's dropout masks, from torch's global CPU generator."""
+    return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+
+
+def steplr_factors(adam: dict, sched_steps: int, k: int = 1) -> List[float]:
+    """StepLR(step_size, gamma) stepped once per Adam iteration (train.py:109-113,193): the factor on the base learning
+    rate at schedule steps sched_steps .. sched_steps + k - 1.  `adam`: the configuration's adam_optimizer section."""
+    return [adam["scheduler_gamma"] ** ((sched_steps + i) // adam["scheduler_step_size"]) for i in range(k)]
+
+
 class HipEvaluator:
     """Local-shard loss sums and gradient through libpinn_hip.so."""
 
@@ -222,110 +233,63 @@ class HipEvaluator:
     point_w = None
     fields_out = None
 
-    def _call_weighted(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
-        """The residual with point weights (self.point_w): Engine.residual_weighted_loss_grad on the collocation points, the
-        fidelity term a separate mse_loss_grad, as _call_coef.  With dropout the engine is eng_drop's (AUTO: generic)."""
+    def _split_pass(self, theta, Xf, Tf, fid_scale, Xr, grad, fid_sums, res_sums, residual):
+        """The two loss terms as a pass each: the fidelity term through mse_loss_grad, then residual(engine) on the
+        collocation points; a term without points launches nothing and zeroes its sums.  In training mode with dropout the
+        engine is eng_drop's, and every pass that IS launched first draws a fresh seed (the reference runs the network twice
+        per loss_func call, train.py:133,148: two forward passes, two masks)."""
         drop = self.eng_drop is not None and self.training
         e = self.eng_drop if drop else self.eng
         if Xf is not None and Xf.shape[0] > 0:
             if drop:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+                e.dropout_seed = _dropout_seed()
             e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
         else:
             fid_sums.zero_()
         if Xr is not None and Xr.shape[0] > 0:
             if drop:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            e.residual_weighted_loss_grad(self.spec, self.point_w, res_scale, theta, Xr, grad, sums=res_sums,
-                                          fields=self.fields_out)
-        else:
-            res_sums.zero_()
-
-    def _call_nu(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
-        """The residual with the lateral-mixing term (spec.nu != 0): Engine.residual2_loss_grad on the collocation points,
-        the fidelity term a separate mse_loss_grad (also where both terms share one point set)."""
-        drop = self.eng_drop is not None and self.training
-        e = self.eng_drop if drop else self.eng
-        if Xf is not None and Xf.shape[0] > 0:
-            if drop:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
-        else:
-            fid_sums.zero_()
-        if Xr is not None and Xr.shape[0] > 0:
-            if drop:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            e.residual2_loss_grad(self.spec, res_scale, theta, Xr, grad, sums=res_sums)
-        else:
-            res_sums.zero_()
-
-    def _call_coef(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
-        """The residual with runtime closure coefficients (self.coef): Engine.residual_coef_loss_grad on the collocation
-        points, the fidelity term a separate mse_loss_grad, as _call_nu.  self.coef_grad, when set, is overwritten with
-        d loss / d coef of this evaluation."""
-        drop = self.eng_drop is not None and self.training
-        e = self.eng_drop if drop else self.eng
-        if self.coef_grad is not None:
-            self.coef_grad.zero_()
-        if Xf is not None and Xf.shape[0] > 0:
-            if drop:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
-        else:
-            fid_sums.zero_()
-        if Xr is not None and Xr.shape[0] > 0:
-            if drop:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            e.residual_coef_loss_grad(self.spec, self.coef, res_scale, theta, Xr, grad, self.coef_grad, sums=res_sums)
+                e.dropout_seed = _dropout_seed()
+            residual(e)
         else:
             res_sums.zero_()
 
     def __call__(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums):
         if self.point_w is not None:
-            return self._call_weighted(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
-        if self.coef is not None:
-            return self._call_coef(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
-        if self.spec.nu != 0:
-            return self._call_nu(theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums)
-        if self.eng_drop is not None and self.training:
-            # the reference runs the network twice per loss_func call (train.py:133,148): two forward passes, two
-            # masks — one fresh seed per pass, from torch's CPU generator
-            e = self.eng_drop
-            if Xf is not None and Xf.shape[0] > 0:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-                if Xf is Xr:
-                    e.residual_mse_loss_grad(self.spec, res_scale, Tf, self.fid_cols, fid_scale, theta, Xr, grad,
-                                             term_sums=res_sums, col_sums=fid_sums)
-                    return
-                e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
-            else:
-                fid_sums.zero_()
-            if Xr is not None and Xr.shape[0] > 0:
-                e.dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            # point weights (self.point_w) on the residual; the pass's unweighted signed fields go to self.fields_out
+            def residual(e):
+                e.residual_weighted_loss_grad(self.spec, self.point_w, res_scale, theta, Xr, grad, sums=res_sums, fields=self.fields_out)
+        elif self.coef is not None:
+            # runtime closure coefficients (self.coef); self.coef_grad, when set, is overwritten with d loss / d coef
+            if self.coef_grad is not None:
+                self.coef_grad.zero_()
+
+            def residual(e):
+                e.residual_coef_loss_grad(self.spec, self.coef, res_scale, theta, Xr, grad, self.coef_grad, sums=res_sums)
+        elif self.spec.nu != 0:
+            # the lateral-mixing term: the second-order entry (also where both terms share one point set)
+            def residual(e):
+                e.residual2_loss_grad(self.spec, res_scale, theta, Xr, grad, sums=res_sums)
+        else:
+            drop = self.eng_drop is not None and self.training
+            if Xf is not None and Xf is Xr and Xr.shape[0] > 0:
+                # one point set for both terms (train_newmethod.py:122-159): one pass, one forward, one dropout mask
+                e = self.eng_drop if drop else self.eng
+                if drop:
+                    e.dropout_seed = _dropout_seed()
+                e.residual_mse_loss_grad(self.spec, res_scale, Tf, self.fid_cols, fid_scale, theta, Xr, grad,
+                                         term_sums=res_sums, col_sums=fid_sums)
+                return
+            if (not drop and self.merge_sets and Xf is not None and Xr is not None
+                    and 0 < Xf.shape[0] <= self.MERGE_MAX_FID and Xr.shape[0] > 0):
+                # train.py:131-157 in ONE launch: collocation points first, fidelity points after them
+                cat = self._merged(Xr, Xf)
+                self.eng.residual_mse_split_loss_grad(self.spec, res_scale, Tf, self.fid_cols, fid_scale, theta, cat,
+                                                      Xr.shape[0], grad, term_sums=res_sums, col_sums=fid_sums)
+                return
+
+            def residual(e):
                 e.residual_loss_grad(self.spec, res_scale, theta, Xr, grad, sums=res_sums)
-            else:
-                res_sums.zero_()
-            return
-        if (self.merge_sets and Xf is not None and Xr is not None and Xf is not Xr
-                and 0 < Xf.shape[0] <= self.MERGE_MAX_FID and Xr.shape[0] > 0):
-            # train.py:131-157 in ONE launch: collocation points first, fidelity points after them
-            cat = self._merged(Xr, Xf)
-            self.eng.residual_mse_split_loss_grad(self.spec, res_scale, Tf, self.fid_cols, fid_scale, theta, cat,
-                                                  Xr.shape[0], grad, term_sums=res_sums, col_sums=fid_sums)
-            return
-        if Xf is not None and Xf is Xr and Xr.shape[0] > 0:
-            # one point set for both terms (train_newmethod.py:122-159): one pass, one forward
-            self.eng.residual_mse_loss_grad(self.spec, res_scale, Tf, self.fid_cols, fid_scale, theta, Xr, grad,
-                                            term_sums=res_sums, col_sums=fid_sums)
-            return
-        if Xf is not None and Xf.shape[0] > 0:
-            self.eng.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
-        else:
-            fid_sums.zero_()
-        if Xr is not None and Xr.shape[0] > 0:
-            self.eng.residual_loss_grad(self.spec, res_scale, theta, Xr, grad, sums=res_sums)
-        else:
-            res_sums.zero_()
+        self._split_pass(theta, Xf, Tf, fid_scale, Xr, grad, fid_sums, res_sums, residual)
 
     def adam_step(self, theta, grad, m, v, step, lr):
         self.eng.adam_step(theta, grad, m, v, step, lr)
@@ -632,17 +596,17 @@ class PINN:
     def current_lr(self) -> float:
         """StepLR(step_size, gamma) stepped once per Adam iteration (train.py:109-113,193)."""
         a = self.config.adam
-        return a["learning_rate"] * a["scheduler_gamma"] ** (self._sched_steps // a["scheduler_step_size"])
+        return a["learning_rate"] * steplr_factors(a, self._sched_steps)[0]
 
     def current_coefficient_lr(self) -> float:
         """The coefficients' learning rate: adam_optimizer.coefficient_learning_rate (default: the network's) on the same StepLR."""
         a = self.config.adam
-        return float(a.get("coefficient_learning_rate", a["learning_rate"])) * a["scheduler_gamma"] ** (self._sched_steps // a["scheduler_step_size"])
+        return float(a.get("coefficient_learning_rate", a["learning_rate"])) * steplr_factors(a, self._sched_steps)[0]
 
     def current_weight_lr(self) -> float:
         """The self-adaptive weights' learning rate: adam_optimizer.weight_learning_rate (default: the network's) on the same StepLR."""
         a = self.config.adam
-        return self.config.weight_learning_rate * a["scheduler_gamma"] ** (self._sched_steps // a["scheduler_step_size"])
+        return self.config.weight_learning_rate * steplr_factors(a, self._sched_steps)[0]
 
     def set_residual_weights(self, weights):
         """Fixed weights on the collocation points: (N_res,) or (n_w, N_res) (None: back to the unweighted loss).  Not with
@@ -885,7 +849,7 @@ class PINN:
         or the multipliers' Adam state and their learning rates on the StepLR schedule (current_coefficient_lr /
         current_weight_lr at each iteration); coef_log: where the coefficients each iteration ran with go."""
         a = self.config.adam
-        sched = [a["scheduler_gamma"] ** ((self._sched_steps + i) // a["scheduler_step_size"]) for i in range(k)]
+        sched = steplr_factors(a, self._sched_steps, k)
         if self._coef is not None:
             kw = {"coef_log": coef_log}
             if self._coef_grad is not None:
@@ -941,7 +905,7 @@ class PINN:
         if hasattr(self.evaluator, "training"):
             self.evaluator.training = self.dnn.training
         a = self.config.adam
-        lrs = [a["learning_rate"] * a["scheduler_gamma"] ** ((self._sched_steps + i) // a["scheduler_step_size"]) for i in range(k)]
+        lrs = [a["learning_rate"] * f for f in steplr_factors(a, self._sched_steps, k)]
         if self._run_losses is None or self._run_losses.shape[0] < k:
             self._run_losses = torch.zeros(max(k, self.MAX_RUN), 3, dtype=torch.float32, device=self.device)
         out = self._run_losses[:k]
