@@ -96,12 +96,22 @@ extern "C" {
 #define PINN_MAX_DIRS 3   /* tangent directions (inputs with requires_grad) */
 #define PINN_MAX_ROLES 8
 
+/* Non-finite inputs.  A NaN anywhere in X, the parameters or the targets propagates as IEEE arithmetic propagates it: the
+   point's row of every per-point output is NaN, and so are every sum that includes the point and the gradient.  An
+   INFINITE entry of X is read as +-FLT_MAX by the fused MFMA kernels (tile, cooperative, batch, plain forward: their hidden
+   layers are padded with zero-weight units, where 0 * inf would be NaN): the row is what the saturated network gives, a weight
+   that is exactly 0 times that input gives 0, and the gradient stays finite.  GENERIC, WIDE and bf16 mode take the infinity
+   as it is: w * inf saturates tanh, 0 * inf is NaN (the layer-0 weight gradient of that input column; the whole row where
+   a real weight is 0).  The sine first layer reads X as it is on every engine: sin(inf) is NaN. */
+
 /* activation (dnn.py:18-21) */
 #define PINN_ACT_TANH 0        /* init_type == 'xavier'  */
 #define PINN_ACT_LEAKY_RELU 1  /* init_type == 'kaiming', negative_slope 0.01 */
 /* Fourier-feature first layer: a_1 = sin(W_0 x + b_0) on the FIRST hidden layer, tanh on every other hidden layer, the
    last layer bare (n_hidden == 1: the only hidden layer is the sine).  W_0 and b_0 are the ordinary first-layer
-   parameters of the flat buffer: no struct gains a field.  Served by the generic engine for every first-order request
+   parameters of the flat buffer: no struct gains a field.  The argument W_0 x + b_0 is formed in double; sine and cosine
+   are within 7e-8 of fp64 for |W_0 x + b_0| <= 2^16 (tested), degrade slowly beyond 2^26 and mean nothing from 2^31 on.
+   Served by the generic engine for every first-order request
    and by the fused tile kernel (AUTO, FUSED, FUSED_TILE) for the plain requests: forward, forward jet with k in {0, 2, 3},
    the residual / mse / merged / split loss calls and the folded Adam and L-BFGS loops on them.  Requests whose fused
    kernel has no sine instance (coefficients, point weights, corrected radiation stress, residual fields, pinn_jet_backward,

@@ -449,7 +449,7 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
       int64_t pc = (tile0 + t) * 16 + p;
       pc = pc < P.N ? pc : P.N - 1;
 #pragma unroll
-      for (int s = 0; s < KS0; ++s) xin[t][s] = (4 * s + q < P.d_in) ? P.X[pc * P.d_in + 4 * s + q] : 0.f;
+      for (int s = 0; s < KS0; ++s) xin[t][s] = (4 * s + q < P.d_in) ? finite_input(P.X[pc * P.d_in + 4 * s + q]) : 0.f;
     });
     // EPI_ADJ: the caller's output adjoints of tile t sit in gadj[t & 1] (two register sets: tile t + 1 is requested
     // while tile t is worked on, output-layer step below).  The one-tile instances have nothing to overlap there, so

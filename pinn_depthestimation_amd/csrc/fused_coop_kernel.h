@@ -113,7 +113,7 @@ __global__ __launch_bounds__(COOP_THREADS, 1) void k_fused_coop(const FusedParam
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int f = 4 * q + r;
-        b[0][0][r] = (f < P.d_in) ? P.X[ptc * P.d_in + f] : 0.f;
+        b[0][0][r] = (f < P.d_in) ? finite_input(P.X[ptc * P.d_in + f]) : 0.f;
 #pragma unroll
         for (int c = 1; c < K1; ++c) b[c][0][r] = (f == P.dir_col[c - 1]) ? 1.f : 0.f;
       }

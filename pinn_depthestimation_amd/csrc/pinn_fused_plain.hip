@@ -33,7 +33,7 @@ __global__ __launch_bounds__(FUSED_THREADS, plain4_occ(WP)) void k_fused_plain4(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int f = 4 * q + r;
-        b0[c][0][r] = f < P.d_in ? P.X[pc * P.d_in + f] : 0.f;
+        b0[c][0][r] = f < P.d_in ? finite_input(P.X[pc * P.d_in + f]) : 0.f;
       }
     }
     f4 a[C][NTH];

@@ -75,7 +75,10 @@ struct ResNavierStokes {
 // roles: outputs h=0 U=1 V=2 eta_mean=3 Hrms=4 k=5; directions x=0 y=1.
 // Bug-compatible with physics.py:106: E = 1/8**rho*g*Hrms**2 == 0.0, so the
 // radiation-stress terms Sxx_x, Syy_y contribute exactly 0 to loss and gradient
-// and Hrms, k receive zero adjoints.
+// and Hrms, k receive zero adjoints.  The zero is written 0 * |rx + ry|: +0 at every finite point, NaN
+// where the point's momentum fields are not finite, so that the gradient of the two output biases is NaN at a NaN point as
+// the reference's is (0.0 * nan; tests/test_nonfinite_gpu.py).  It is a NaN carrier only, not physics.py's expression: there
+// E = 0.0 * Hrms**2 also makes fx and fy NaN when Hrms or k ALONE is not finite, which these kernels' forward does not.
 struct ResPhysicsEquation {
   static constexpr int NR = 6, ND = 2, NT = 3;
   template <bool GRAD>
@@ -102,6 +105,7 @@ struct ResPhysicsEquation {
       const float dD = -RHO * D * D;             // d D / d(eta+h)
       const float gS = dD * (rx * tbx + ry * tby);
       g[0][0] = gS; g[0][3] = gS;
+      g[0][4] = g[0][5] = 0.f * fabsf(rx + ry);
       g[0][1] = rx * (U_x + D * RC * 2.f * fabsf(U)) + ry * V_x;
       g[0][2] = rx * U_y + ry * (V_y + D * RC * 2.f * fabsf(V));
       g[1][1] = rc + rx * U;   // d/dU_x
@@ -556,9 +560,27 @@ struct Residual2 {
   }
 };
 
+// ---- inputs ---------------------------------------------------------------------------------------------------------------
+// An input of +-inf as +-FLT_MAX, everything else (NaN included) unchanged: what the MFMA kernels hand X to layer 0 through.
+// Their hidden layers are padded to a multiple of 16 units with zero weights, and 0 * inf = NaN in a padded unit of layer 0
+// would spread to every real unit of layer 1 (0 * NaN), although the network itself saturates: tanh(w * inf) = +-1 and the
+// row is finite (oracle, generic and wide engine; tests/test_nonfinite_gpu.py).  w * FLT_MAX saturates tanh_f32 the same way
+// for every normal w; a NaN must NOT be caught here (fmin / fmax / med3 would drop it).  In integers, without a compare (the
+// width-64 kernels spill scalar registers already, and a compare's mask is one more): t = 0 for an infinity and 1 otherwise,
+// and bits + t - 1 steps an infinity down to the largest finite pattern of its sign and leaves everything else alone.
+__device__ __forceinline__ float finite_input(float x) {
+  const unsigned b = __float_as_uint(x);
+  const unsigned t = min((b & 0x7fffffffu) ^ 0x7f800000u, 1u);
+  return __uint_as_float(b + t - 1u);
+}
+
 // ---- activations (dnn.py:18-21) ------------------------------------------------
-// tanh: odd minimax polynomial below 0.625 (relative error ~1e-7), the
-// exponential form above; abs error <= ~1.5e-7 everywhere in fp32.
+// tanh: odd minimax polynomial below 0.625, the exponential form above.  Measured over all 2^32 inputs against fp64
+// (tests/test_devmath_gpu.py): relative error <= 7.61e-8 below 0.625 (subnormals included), absolute error
+// <= 9.70e-8 everywhere (asserted: 1.0e-7 and 1.5e-7); monotonic from one bit pattern to the next; |tanh_f32| <= 1, so that
+// s = 1 - a^2 >= 0 in every caller; +-inf -> +-1, NaN -> NaN.  The sign goes on LAST, on whichever branch was taken: both
+// branches are sign-symmetric in magnitude, so tanh_f32(-x) = -tanh_f32(x) bit for bit, -0 included (the polynomial alone
+// gives fma(-0, -0, -0) = +0 there).
 __device__ inline float tanh_f32(float x) {
   const float ax = fabsf(x);
   const float x2 = x * x;
@@ -570,15 +592,16 @@ __device__ inline float tanh_f32(float x) {
   const float small = fmaf(p * x2, x, x);
   // 1 - 2/(exp(2|x|)+1); exp2 argument clamps naturally (inf -> 1)
   const float e = __expf(2.f * ax);
-  const float big = copysignf(fmaf(-2.f, __builtin_amdgcn_rcpf(e + 1.f), 1.f), x);   // v_rcp_f32: 1 ulp
-  return ax < 0.625f ? small : big;
+  const float big = fmaf(-2.f, __builtin_amdgcn_rcpf(e + 1.f), 1.f);   // v_rcp_f32: 1 ulp
+  return copysignf(ax < 0.625f ? small : big, x);
 }
 
 // Two tanh_f32 evaluations on one register pair, every fp32 operation written on the pair (v_pk_mul_f32 / v_pk_fma_f32 /
 // v_pk_add_f32): per element the same operations in the same order as tanh_f32, so each half is bitwise tanh_f32 of its
-// input.  The one liberty: |x| is taken BEHIND the doubling and the multiply by log2(e) instead of in front of them — both
-// are sign-symmetric, the magnitudes are the same bits — so that these two run packed (packed fp32 has no |.| modifier;
-// v_exp_f32 has).  __expf(y) is v_exp_f32(y * log2(e)) with exactly this constant (0x3fb8aa3b).
+// input (all 2^32 patterns through either half: tests/test_devmath_gpu.py).  The one liberty: |x| is taken BEHIND the
+// doubling and the multiply by log2(e) instead of in front of them — both are sign-symmetric, the magnitudes are the same
+// bits — so that these two run packed (packed fp32 has no |.| modifier; v_exp_f32 has).  __expf(y) is
+// v_exp_f32(y * log2(e)) with exactly this constant (0x3fb8aa3b).
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ inline f2 tanh_f32x2(f2 x) {
   const f2 x2 = x * x;
@@ -593,8 +616,8 @@ __device__ inline f2 tanh_f32x2(f2 x) {
   const f2 d = e + f2{1.f, 1.f};
   const f2 r = f2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
   const f2 big = __builtin_elementwise_fma(f2{-2.f, -2.f}, r, f2{1.f, 1.f});
-  return f2{fabsf(x[0]) < 0.625f ? small[0] : copysignf(big[0], x[0]),
-            fabsf(x[1]) < 0.625f ? small[1] : copysignf(big[1], x[1])};
+  return f2{copysignf(fabsf(x[0]) < 0.625f ? small[0] : big[0], x[0]),
+            copysignf(fabsf(x[1]) < 0.625f ? small[1] : big[1], x[1])};
 }
 
 // sin z and cos z together for the sine first layer (PINN_ACT_SIN_TANH), from z in DOUBLE.  A Fourier layer's arguments reach
@@ -603,20 +626,31 @@ __device__ inline f2 tanh_f32x2(f2 x) {
 // evaluates the sine afterwards (measured on a one-point Navier_Stokes sum of a 3 -> 10 -> 4 network: 3.3e-6 relative with z_0
 // formed by the fp32 fmaf chain, 2.9e-7 with z_0 exact).  So the callers form z_0 = W_0 x + b_0 in double — the products of
 // fp32 numbers are exact there — and the reduction r = z - k pi/2 is one double fused multiply-add; then the Cephes
-// single-precision minimax polynomials on |r| <= pi/4 in fp32 and the quadrant swap.  Absolute error <= 7e-8 for both against
-// fp64.  No table, no branch, no scratch.
+// single-precision minimax polynomials on |r| <= pi/4 in fp32 and the quadrant swap.  No table, no branch, no scratch.
+// Two roundings are carried along exactly, rl = the double r minus its fp32 rounding and res = (1 - w) - h for
+// w = fl(1 - h), h = r^2 / 2, and
+//   sin(r + rl) = r + [r^3 ps + rl],   cos(r + rl) = w + [res + r^4 pc - rl r]
+// add the small bracket to the large term in one final rounding (with r, 1 - h and the result each rounded the figure is
+// 9.25e-8).  Every product is an operand of an explicit fmaf or stands alone, so no contraction can change a rounding: the
+// numpy restatement in tests/devmath_util.py is this function bit for bit.  Absolute error <= 7e-8 for both against fp64,
+// measured 5.5e-8, on every fp32 z with |z| <= 1024, on doubles up to 2^16 and beside every quadrant
+// boundary k pi/2 up to k = 2^20.  Beyond 2^26 the double pi/2's own error (6.1e-17 k) grows into it; from |z| = 2^31 on the
+// quadrant count leaves int and the result is meaningless (|sn|, |cs| <= 1 holds up to 2^30).  NaN and +-inf give NaN.
 __device__ inline void sincos_f64arg(double z, float& sn, float& cs) {
   const double k = rint(z * 0.63661977236758134308);
-  const float r = (float)fma(-k, 1.57079632679489661923, z);
+  const double rd = fma(-k, 1.57079632679489661923, z);
+  const float r = (float)rd;
+  const float rl = (float)(rd - (double)r);
   const float r2 = r * r;
   float ps = -1.9515295891e-4f;
   ps = fmaf(ps, r2, 8.3321608736e-3f);
   ps = fmaf(ps, r2, -1.6666654611e-1f);
-  const float s = fmaf(ps * r2, r, r);
+  const float s = r + fmaf(ps * r2, r, rl);
   float pc = 2.443315711809948e-5f;
   pc = fmaf(pc, r2, -1.388731625493765e-3f);
   pc = fmaf(pc, r2, 4.166664568298827e-2f);
-  const float c = fmaf(pc * r2, r2, fmaf(-0.5f, r2, 1.f));
+  const float h = 0.5f * r2, w = 1.f - h, res = (1.f - w) - h;
+  const float c = w + fmaf(-rl, r, fmaf(pc * r2, r2, res));
   const int n = (int)k;
   const float s1 = (n & 1) ? c : s, c1 = (n & 1) ? s : c;
   sn = (n & 2) ? -s1 : s1;

@@ -61,7 +61,7 @@ struct WideLayer {
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bf16x4 to_bf16x4(f4 v) {
   typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-  bf4 b = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};   // v_cvt_pk_bf16_f32 (RNE, NaN-safe)
+  bf4 b = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};   // v_cvt_pk_bf16_f32 (RNE, NaN-safe: all 2^32 patterns, test_devmath_gpu.py)
   return __builtin_bit_cast(bf16x4, b);
 }
 __device__ __forceinline__ f4 mfma_bf16(bf16x4 a, bf16x4 b, f4 c) {
