@@ -38,6 +38,9 @@
  *   pinn_adam_loop          train.py:188-193, n iterations of the above enqueued by one call
  *   pinn_adam_loop_ext      the same for the residual with runtime coefficients or point weights (fixed or self-adaptive):
  *                           three launches per iteration, the coefficients' / multipliers' Adam step on the device
+ *   pinn_balance_update     the weights of the loss terms, which the reference sets by hand (train.py:94-95,157: weight_fid,
+ *                           weight_res), set from the terms' own gradients instead: statistics, update, weighted combination
+ *   pinn_adam_loop_balanced train.py:188-193 with the residual and the fidelity gradient balanced that way on the device
  *
  * Conventions
  *   - plain C, no exceptions; every function returns 0 on success, <0 on error;
@@ -73,7 +76,9 @@
  *     pinn_residual_coef_loss_grad (whose coef_grad is += too; its coef is read-only), pinn_residual_weighted_loss_grad
  *     (whose point_w is read-only and whose fields, if given, are overwritten at (n_fields, N)), pinn_mse_loss_grad,
  *     pinn_residual_mse_loss_grad and pinn_residual_mse_split_loss_grad (the caller zeroes it, or accumulates several
- *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step, pinn_adam_loop and pinn_adam_loop_ext.  Y, dY, d2Y, fields,
+ *     terms into it); it is OVERWRITTEN by pinn_loss_grad_adam_step, pinn_adam_loop, pinn_adam_loop_ext and
+ *     pinn_adam_loop_balanced (whose lam is in/out and whose lam_log, stats_log rows and group_grads are overwritten).
+ *     pinn_balance_update reads grads, updates lam in place and overwrites stats (G, 3) and grad_out (P).  Y, dY, d2Y, fields,
  *     term_sums, col_sums, losses, X_out, n_rows_out, out2 and d are overwritten, whatever they held.
  *   - pinn_lbfgs_loop: writes params (P), trace (n_slots x PINN_LBFGS_TRACE_COLS) and state (the bytes pinn_query_lbfgs_loop
  *     states) at those extents only; `state` is the one buffer whose content a call relies on (pinn_lbfgs_loop_init arms it).
@@ -630,6 +635,96 @@ int32_t pinn_adam_loop_ext(const pinn_desc* desc, const pinn_residual_spec* spec
                            float* term_sums, float* col_sums, float* grad_flat, const pinn_adam_state* adam,
                            const pinn_adam_extras* extras, int32_t n_iters, const double* lr, const double* lr_coef,
                            const double* lr_w, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- gradient-statistics loss balancing -----------------------------------------------------------------------------------
+ * (added under ABI version 4, as the entries above were: no existing entry, struct or constant changed)
+ * The weights of a weighted sum of loss groups, set from the groups' own gradients (Wang, Teng & Perdikaris 2021, "learning-
+ * rate annealing": MAX_MEAN; Wang et al. 2023, gradient-norm balancing: NORM).  Group j = 0 .. G-1 has a flat fp32 gradient
+ * g_j of P entries, a weight lam[j] and three statistics, as doubles: A = max|g_j|, S = sum|g_j|, Q = sum g_j^2.
+ *   MAX_MEAN   lam_hat[j] = A[ref] / (S[j] / P) for j != ref; lam[ref] is left alone
+ *   NORM       lam_hat[j] = (sum_i sqrt(Q[i])) / sqrt(Q[j]) for every j, the sum in group order; ref is ignored
+ *   then       lam[j] <- (float)((1 - alpha) * (double)lam[j] + alpha * lam_hat[j]): formed in double, no fused multiply-add,
+ *              rounded to fp32 once
+ * A group whose lam_hat is not a finite positive number keeps its lam bit for bit: a zero denominator, A[ref] = 0, a NaN or
+ * infinite statistic (under NORM a NaN or infinite Q makes the SUM non-finite, so every group keeps its weight).
+ * pinn_balance_weights_host: the rule alone, on HOST arrays, no device touched — the very function the kernels call.
+ * NONE copies lam_in to lam_out.  PINN_ERR_INVALID: alpha outside (0, 1], G outside 1..PINN_BALANCE_MAX_GROUPS, ref outside
+ * 0..G-1, P < 1, an unknown mode, NULL pointers (stats may be NULL under NONE). */
+#define PINN_BALANCE_NONE      0   /* combine only */
+#define PINN_BALANCE_MAX_MEAN  1
+#define PINN_BALANCE_NORM      2
+#define PINN_BALANCE_MAX_GROUPS 8
+#define PINN_BALANCE_STATS 3       /* per group: A = max|g|, S = sum|g|, Q = sum g^2, as doubles */
+int32_t pinn_balance_weights_host(int32_t mode, int32_t G, int32_t ref, double alpha, int64_t P,
+                                  const double* stats /* (G,3) */, const float* lam_in, float* lam_out);
+/* The same on the device, for G flat gradients (row j of grads, row stride ld >= P), independent of engine and descriptor —
+ * the loss calls of any engine can fill the rows.  In stream order, at most three small launches:
+ *   statistics   one pass over (G, P): per-block partials of A, S, Q in double (g^2 is exact there), then one block folds them
+ *                in an order fixed by (P, G) alone: bit-reproducible.  A NaN entry makes all three statistics of its group NaN
+ *                (the max keeps it, unlike fmaxf).  stats, if given, is OVERWRITTEN at (G, 3).
+ *   update       the rule above on lam, in place
+ *   combination  with grad_out: grad_out[i] = ((lam[0] g_0[i]) + (lam[1] g_1[i])) + ..., group order, the NEW weights, no
+ *                fused multiply-add; OVERWRITTEN at (P).  grad_out may alias none of the inputs.
+ * Mode NONE skips statistics and update and only combines: lam is read only, stats, if given, is left alone.
+ * Refusals, before any device work: the arguments pinn_balance_weights_host refuses; ld < P, NULL grads or lam:
+ * PINN_ERR_INVALID; a workspace below pinn_query_balance_workspace's answer: PINN_ERR_WORKSPACE (the workspace may hold
+ * anything on entry). */
+int32_t pinn_query_balance_workspace(int64_t P, int32_t G, int64_t* bytes);
+int32_t pinn_balance_update(int32_t mode, int32_t G, int32_t ref, double alpha,
+                            const float* grads /* (G, ld) device, row j = g_j */, int64_t P, int64_t ld,
+                            float* lam        /* (G) device, in/out */,
+                            double* stats     /* NULL or (G,3) device, overwritten */,
+                            float* grad_out   /* NULL or (P) device, overwritten */,
+                            void* ws, int64_t ws_bytes, void* stream);
+
+/* Device-enqueued Adam runs with two balanced groups: the PDE residual on the collocation points (group 0) and the fidelity
+ * MSE on its own points (group 1).  pinn_adam_loop_ext's arguments with `balance` in place of `extras` and lr only.  One call
+ * enqueues n_iters iterations; iteration i uses step adam->step + i and the HOST array lr[i] and is, in stream order:
+ *   1. the plain residual pass on (X, N_res), weighted by the caller's term_scale;
+ *   2. the fidelity pass (no input derivatives) on (Xf, T, N_fid), weighted by the caller's col_scale; Xf may alias X;
+ *   3. on update iterations only — (adam->step + i - 1) % every == 0 — two launches: the statistics of the two per-group
+ *      gradients, each summed over its pass's gradient copies in pinn_loss_grad_adam_step's order, and the rule on balance->lam;
+ *   4. ONE finishing kernel: g = (lam[0] g_res) + (lam[1] g_fid), no fused multiply-add, on the same sums of the copies;
+ *      grad_flat OVERWRITTEN with g; Adam on params / m / v (pinn_adam_step's arithmetic, bit for bit); packed weights
+ *      refreshed; term_sums, col_sums and the optional weighted losses as in pinn_adam_loop_ext.
+ * Three launches on ordinary iterations, five on update iterations; a zero-fill per pass where the gradient copies do not fit
+ * in LDS; one packing kernel per call unless adam->packed_valid.  adam->lr is ignored.
+ * term_sums, col_sums and adam->losses are weighted by the caller's scales and loss_rows, NOT by lam: lam_log gives the caller
+ * what it needs to form the balanced total.
+ * One packed copy of the weights serves both passes and the finishing kernel, so both passes run in natural unit order: the
+ * residual pass takes the cooperative kernel where pinn_residual_loss_grad would, else the tile kernel's natural-order
+ * instance — never the batch kernel and never the width-64 instances with permuted inputs / outputs, which the single entry
+ * may choose.  Its term_sums therefore equal the single entry's bit for bit only where that entry takes the same kernel.
+ * Rules, all decided before any device work (nothing is launched on a refusal); the query follows the same rules:
+ *   fp32, tanh, width <= 64, d_in and d_out <= 16, dropout_p == 0, k = the residual's directions; engine AUTO, FUSED,
+ *   FUSED_TILE, FUSED_COOP (padded width 64 only, as in the single entries)     served
+ *   FUSED_BATCH, GENERIC, WIDE, bf16, LeakyReLU, the sine first layer, width > 64, dropout, k mismatch
+ *                                               PINN_ERR_UNSUPPORTED with the reason (AUTO is NOT moved to another engine:
+ *                                               use the loss calls, pinn_balance_update and pinn_adam_step)
+ *   spec.flags bit 0 (corrected stress)         PINN_ERR_UNSUPPORTED, "corrected" in the message
+ *   N_res < 1, N_fid < 1, every < 1, mode other than MAX_MEAN / NORM, ref other than 0 / 1, alpha outside (0, 1],
+ *   NULL balance or lam, NULL pointers          PINN_ERR_INVALID
+ *   n_iters == 0                                PINN_OK, nothing launched
+ * The workspace is the entry's own (pinn_query_adam_balanced_workspace): pinn_adam_loop_ext's layout and the statistics'
+ * partials; never smaller than pinn_query_adam_ext_workspace's answer for the same (N_res, N_fid). */
+typedef struct pinn_balance {
+  int32_t mode;        /* MAX_MEAN or NORM */
+  int32_t every;       /* >= 1: iteration i updates iff (adam->step + i - 1) % every == 0 */
+  int32_t ref;         /* 0 = residual group, 1 = fidelity group */
+  double  alpha;
+  float*  lam;         /* (2) device in/out: [residual, fidelity] */
+  float*  lam_log;     /* NULL or (n_iters, 2): the weights iteration i STEPPED with (after its update, if any) */
+  double* stats_log;   /* NULL or (n_iters, 2, 3): rows of update iterations overwritten, others untouched */
+  float*  group_grads; /* NULL or (2, P): iteration i's g_res, g_fid as summed from the copies, overwritten */
+} pinn_balance;
+int32_t pinn_query_adam_balanced_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N_res, int64_t N_fid,
+                                           int64_t* bytes);
+int32_t pinn_adam_loop_balanced(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
+                                const float* Xf, const float* T, int64_t N_fid, int32_t n_cols, const int32_t* out_col,
+                                const float* col_scale, float* params, const float* X, int64_t N_res,
+                                float* term_sums, float* col_sums, float* grad_flat, const pinn_adam_state* adam,
+                                const pinn_balance* balance, int32_t n_iters, const double* lr,
+                                void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- ensembles: M networks of one shape in one launch --------------------------------------------------------------
  * (added under ABI version 4, as the fields entries were: no existing entry, struct or constant changed)

@@ -61,6 +61,19 @@ class PinnAdamExtras(C.Structure):
     ]
 
 
+class PinnBalance(C.Structure):
+    """pinn_balance (pinn_adam_loop_balanced): the rule, the two device weights [residual, fidelity] and the optional logs."""
+    _fields_ = [
+        ("mode", C.c_int32), ("every", C.c_int32), ("ref", C.c_int32), ("alpha", C.c_double),
+        ("lam", C.c_void_p), ("lam_log", C.c_void_p), ("stats_log", C.c_void_p), ("group_grads", C.c_void_p),
+    ]
+
+
+BALANCE_NONE, BALANCE_MAX_MEAN, BALANCE_NORM = 0, 1, 2      # pinn_hip.h: PINN_BALANCE_*
+BALANCE_MODES = {None: BALANCE_NONE, "none": BALANCE_NONE, "max_mean": BALANCE_MAX_MEAN, "norm": BALANCE_NORM}
+BALANCE_MAX_GROUPS, BALANCE_STATS = 8, 3
+
+
 class PinnLsState(C.Structure):
     """pinn_ls_state: torch's _strong_wolfe as a resumable state machine (csrc/lbfgs_line_search.h)."""
     _fields_ = [
@@ -179,6 +192,16 @@ _SIGNATURES = {
                                        C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(PinnAdamState),
                                        C.POINTER(PinnAdamExtras), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), _P, C.c_int64, _P]),
+    "pinn_balance_weights_host": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pinn_query_balance_workspace": (C.c_int32, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "pinn_balance_update": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _P, C.c_int64, C.c_int64, _P, _P, _P,
+                                        _P, C.c_int64, _P]),
+    "pinn_query_adam_balanced_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int64, C.c_int64,
+                                                       C.POINTER(C.c_int64)]),
+    "pinn_adam_loop_balanced": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, _P, C.c_int64, C.c_int32,
+                                            C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(PinnAdamState),
+                                            C.POINTER(PinnBalance), C.c_int32, C.POINTER(C.c_double), _P, C.c_int64, _P]),
     "pinn_ensemble_query_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_ensemble_plan": (C.c_int32, [C.POINTER(PinnDesc), C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pinn_ensemble_loss_grad": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int32, _P, _P, C.c_int32,

@@ -87,6 +87,33 @@ class PinnConfig:
         runs (trainer.PINN(fold_extras=True)); off unless asked for."""
         return bool(self.adam.get("fold_extras", False))
 
+    # gradient-statistics loss balancing (trainer.PINN(loss_balancing=...)): the weights of the loss groups set from the run
+    @property
+    def loss_balancing(self) -> Optional[str]:
+        """loss.balancing: None (absent, null or "none"), "max_mean" or "norm"."""
+        v = self.raw.get("loss", {}).get("balancing")
+        return None if v in (None, False, "none") else str(v)
+
+    @property
+    def balance_every(self) -> int:
+        """loss.balance_every: the weights are updated on every balance_every-th Adam iteration, from the first."""
+        return int(self.raw.get("loss", {}).get("balance_every", 10))
+
+    @property
+    def balance_alpha(self) -> float:
+        """loss.balance_alpha: the moving average's rate, in (0, 1]."""
+        return float(self.raw.get("loss", {}).get("balance_alpha", 0.1))
+
+    @property
+    def balance_ref(self) -> str:
+        """loss.balance_ref: the max/mean rule's reference group, "residual" or "fidelity"."""
+        return str(self.raw.get("loss", {}).get("balance_ref", "residual"))
+
+    @property
+    def balance_groups(self) -> str:
+        """loss.balance_groups: "sets" (residual, fidelity) or "terms" (a group per weighted residual term, and fidelity)."""
+        return str(self.raw.get("loss", {}).get("balance_groups", "sets"))
+
     def default_residual(self) -> str:
         """The reference hard-codes the residual by import (train.py:17, train_newmethod.py:18);
         pick the one whose argument names the config's variables satisfy."""

@@ -145,7 +145,8 @@ int fused_ensemble_loss(const Net& n, const LossReq& rq, int M, int flags, const
 // per-point fields (EPI_FIELD), runtime coefficients (EPI_COEF), point weights (EPI_WEIGHTED), ensembles (k_fused_ens).
 // fused_tile_refusal: why the descriptor has no instance in the family, or nullptr = served (pure host logic; the text
 // lives in a per-thread buffer until the next call).  One rule, pinn_fused.hip; "supports" is !refusal.
-enum { TILE_ADJ, TILE_FIELD, TILE_COEF, TILE_WEIGHTED, TILE_ENSEMBLE };
+// (TILE_BALANCE: no instances of its own — the plain gradient instances, as pinn_adam_loop_balanced serves them)
+enum { TILE_ADJ, TILE_FIELD, TILE_COEF, TILE_WEIGHTED, TILE_ENSEMBLE, TILE_BALANCE };
 const char* fused_tile_refusal(int family, const Net& n);
 // which fused kernel a served pinn_jet_backward request runs: PINN_ENGINE_FUSED_TILE or PINN_ENGINE_FUSED_BATCH (pure host
 // logic: the decision run() itself takes)

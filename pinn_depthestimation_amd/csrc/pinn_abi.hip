@@ -7,6 +7,7 @@
 #include "common.h"
 #include "reduce_adam.h"
 #include "adam_ext.h"
+#include "balance.h"
 #include "residuals.h"
 #include "lbfgs_loop.h"
 #include "lbfgs_line_search.h"
@@ -1263,6 +1264,119 @@ int32_t pinn_adam_loop_ext(const pinn_desc* desc, const pinn_residual_spec* spec
   }
   q.n_iters = n_iters; q.lr = lr; q.lr_coef = lr_coef; q.lr_w = lr_w;
   return fused_adam_ext(n, q, X, N_res, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- gradient-statistics loss balancing (pinn_hip.h; the rule and the reductions: balance.h) -------------------------------
+// the rule's arguments, checked once for the host entry, the flat-gradient entry and the balanced loop
+static int balance_args(const char* who, int mode, bool allow_none, int G, int ref, double alpha, int64_t P) {
+  if (mode != PINN_BALANCE_MAX_MEAN && mode != PINN_BALANCE_NORM && !(allow_none && mode == PINN_BALANCE_NONE)) {
+    set_error("%s: unknown mode %d (%s1 = max/mean, 2 = gradient norm)", who, mode, allow_none ? "0 = combine only, " : ""); return PINN_ERR_INVALID;
+  }
+  if (G < 1 || G > PINN_BALANCE_MAX_GROUPS) { set_error("%s: G = %d outside 1..%d", who, G, PINN_BALANCE_MAX_GROUPS); return PINN_ERR_INVALID; }
+  if (ref < 0 || ref >= G) { set_error("%s: ref = %d outside 0..%d", who, ref, G - 1); return PINN_ERR_INVALID; }
+  if (!(alpha > 0.0 && alpha <= 1.0)) { set_error("%s: alpha = %g outside (0, 1]", who, alpha); return PINN_ERR_INVALID; }
+  if (P < 1) { set_error("%s: P = %lld must be >= 1", who, (long long)P); return PINN_ERR_INVALID; }
+  return PINN_OK;
+}
+
+int32_t pinn_balance_weights_host(int32_t mode, int32_t G, int32_t ref, double alpha, int64_t P, const double* stats,
+                                  const float* lam_in, float* lam_out) {
+  const char* who = "pinn_balance_weights_host";
+  int rc = balance_args(who, mode, true, G, ref, alpha, P); if (rc) return rc;
+  if (!lam_in || !lam_out || (!stats && mode != PINN_BALANCE_NONE)) { set_error("%s: NULL pointer argument", who); return PINN_ERR_INVALID; }
+  float in[PINN_BALANCE_MAX_GROUPS];
+  for (int j = 0; j < G; ++j) in[j] = lam_in[j];   // (lam_out may be lam_in)
+  balance_weights(mode, G, ref, alpha, P, stats, in, lam_out);
+  return PINN_OK;
+}
+
+int32_t pinn_query_balance_workspace(int64_t P, int32_t G, int64_t* bytes) {
+  const char* who = "pinn_query_balance_workspace";
+  int rc = balance_args(who, PINN_BALANCE_NONE, true, G, 0, 1.0, P); if (rc) return rc;
+  if (!bytes) { set_error("%s: bytes is NULL", who); return PINN_ERR_INVALID; }
+  *bytes = balance_workspace_bytes(P, G);
+  return PINN_OK;
+}
+
+int32_t pinn_balance_update(int32_t mode, int32_t G, int32_t ref, double alpha, const float* grads, int64_t P, int64_t ld,
+                            float* lam, double* stats, float* grad_out, void* ws, int64_t ws_bytes, void* stream) {
+  const char* who = "pinn_balance_update";
+  int rc = balance_args(who, mode, true, G, ref, alpha, P); if (rc) return rc;
+  if (ld < P) { set_error("%s: ld = %lld is below P = %lld", who, (long long)ld, (long long)P); return PINN_ERR_INVALID; }
+  if (!grads || !lam) { set_error("%s: grads or lam is NULL", who); return PINN_ERR_INVALID; }
+  if (mode != PINN_BALANCE_NONE) { rc = check_workspace(ws, ws_bytes, balance_workspace_bytes(P, G)); if (rc) return rc; }
+  return balance_update(mode, G, ref, alpha, grads, P, ld, lam, stats, grad_out, ws, (hipStream_t)stream);
+}
+
+// validation shared by the balanced loop's query and call, next to adam_ext_plan and in the order of the header's table (no
+// HIP call before it has passed); bal may be null in the query only; *res <- the plain residual pass's request
+static int adam_bal_plan(const char* who, bool query, const pinn_desc* desc, const pinn_residual_spec* spec, const pinn_balance* bal,
+                         int64_t N_res, int64_t N_fid, Net* n, LossReq* res) {
+  int rc = make_net(desc, n); if (rc) return rc;
+  rc = build_request(*n, spec, N_res, N_res, 0, 0, nullptr, res); if (rc) return rc;
+  if (is_corrected(spec->residual_id, spec->flags)) {
+    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no natural-order pass in the balanced loop", who);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  rc = check_k(who, *n, spec, ""); if (rc) return rc;
+  if (n->prec != PINN_PREC_F32) { set_error("%s is implemented in fp32 only (precision bf16 refused)", who); return PINN_ERR_UNSUPPORTED; }
+  const int asked = asked_engine(desc);
+  if (asked == PINN_ENGINE_GENERIC || asked == PINN_ENGINE_WIDE) {
+    set_error("%s runs on the fused engine only (engine AUTO, FUSED, FUSED_TILE or FUSED_COOP), not on engine %d: use the loss "
+              "calls, pinn_balance_update and pinn_adam_step", who, desc->engine);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (const char* why = fused_adam_bal_refusal(*n)) {
+    set_error("%s: %s (width %d, d_in %d, d_out %d, k %d, activation %d, dropout_p %g); use the loss calls, pinn_balance_update "
+              "and pinn_adam_step", who, why, n->W, n->d_in, n->d_out, n->k, n->act, (double)n->drop_p);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (N_res < 1 || N_fid < 1) { set_error("%s: N_res = %lld and N_fid = %lld must be >= 1", who, (long long)N_res, (long long)N_fid); return PINN_ERR_INVALID; }
+  if (query && !bal) return PINN_OK;
+  if (!bal || !bal->lam) { set_error("%s: balance or balance->lam is NULL", who); return PINN_ERR_INVALID; }
+  if (bal->every < 1) { set_error("%s: every = %d must be >= 1", who, bal->every); return PINN_ERR_INVALID; }
+  return balance_args(who, bal->mode, false, 2, bal->ref, bal->alpha, 1);
+}
+
+int32_t pinn_query_adam_balanced_workspace(const pinn_desc* desc, const pinn_residual_spec* spec, int64_t N_res, int64_t N_fid,
+                                           int64_t* bytes) {
+  Net n; LossReq res;
+  int rc = adam_bal_plan("pinn_query_adam_balanced_workspace", true, desc, spec, nullptr, N_res, N_fid, &n, &res); if (rc) return rc;
+  if (!bytes) { set_error("bytes is NULL"); return PINN_ERR_INVALID; }
+  *bytes = fused_adam_bal_workspace_bytes(n, N_res, N_fid);
+  return PINN_OK;
+}
+
+int32_t pinn_adam_loop_balanced(const pinn_desc* desc, const pinn_residual_spec* spec, const float* term_scale,
+                                const float* Xf, const float* T, int64_t N_fid, int32_t n_cols, const int32_t* out_col,
+                                const float* col_scale, float* params, const float* X, int64_t N_res,
+                                float* term_sums, float* col_sums, float* grad_flat, const pinn_adam_state* adam,
+                                const pinn_balance* balance, int32_t n_iters, const double* lr,
+                                void* ws, int64_t ws_bytes, void* stream) {
+  const char* who = "pinn_adam_loop_balanced";
+  Net n; AdamBalReq q; memset(&q, 0, sizeof(q));
+  LossReq& r = q.res;
+  int rc = adam_bal_plan(who, false, desc, spec, balance, N_res, N_fid, &n, &r); if (rc) return rc;
+  if (!adam || n_iters < 0) { set_error("%s: bad arguments", who); return PINN_ERR_INVALID; }
+  if (n_iters == 0) return PINN_OK;
+  if (!params || !X || !term_sums || !term_scale || !grad_flat || !adam->m || !adam->v || adam->step < 1 || !lr) {
+    set_error("%s: bad arguments", who); return PINN_ERR_INVALID;
+  }
+  if (n_cols < 1 || n_cols > PINN_MAX_ROLES || !Xf || !T || !out_col || !col_scale || !col_sums) {
+    set_error("%s: the fidelity group needs n_cols in 1..%d, Xf, T, out_col, col_scale and col_sums", who, PINN_MAX_ROLES); return PINN_ERR_INVALID;
+  }
+  rc = adam_req(adam, params, &q.adam); if (rc) return rc;
+  r.scale = term_scale; r.sums = term_sums; r.grad = grad_flat;
+  LossReq& m = q.fid;
+  m.kind = 1; m.n_split = -1; m.T = T; m.n_cols = n_cols; m.mse_scale = col_scale; m.mse_sums = col_sums; m.grad = grad_flat;
+  rc = set_out_cols(n, n_cols, out_col, &m); if (rc) return rc;
+  q.Xf = Xf; q.N_fid = N_fid;
+  q.beta1 = adam->beta1; q.beta2 = adam->beta2; q.eps = adam->eps; q.step = adam->step;
+  q.row_cols = n_cols; q.col_sums = col_sums;
+  q.mode = balance->mode; q.every = balance->every; q.ref = balance->ref; q.alpha = balance->alpha;
+  q.lam = balance->lam; q.lam_log = balance->lam_log; q.stats_log = balance->stats_log; q.group_grads = balance->group_grads;
+  q.n_iters = n_iters; q.lr = lr;
+  return fused_adam_bal(n, q, X, N_res, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "fused_batch_kernel.h"
 #include "reduce_adam.h"
 #include "adam_ext.h"
+#include "balance.h"
 
 namespace pinn {
 
@@ -455,6 +456,64 @@ __global__ void k_sa_weights(const float* __restrict__ lam, float* __restrict__ 
   if (e < count) w[e] = sa_weight_of(lam[e], sa_mask);
 }
 
+// ---- pinn_adam_loop_balanced: the plain residual pass and the fidelity pass, their gradients combined with device weights -----
+// Both kernels sum a group's gradient over its pass's copies with grad_of_param, residual first, so the statistics are
+// taken on the very floats the finishing kernel combines.
+struct BalFinish {
+  const float* wg_r; int copies_r; const float* sums_r; int grid_r;   // the residual pass
+  const float* wg_f; int copies_f; const float* sums_f; int grid_f;   // the fidelity pass
+  int param_blocks;
+  int n_terms, n_cols, row_cols;
+  float* term_sums; float* col_sums; float* grad;
+  float* params; float* m; float* v; float* Wp; float* WTp; float* Bp;
+  AdamScalars c;
+  int n_loss_rows; const float* loss_rows; float* losses;
+  const float* lam; float* lam_log; float* group_grads;   // (2) [residual, fidelity]; null or this iteration's row (2); null or (2, P)
+};
+// update iterations only, one block per 64 parameters: partials[b] = the block's (max|g|, sum|g|, sum g^2) of the residual
+// gradient, then of the fidelity gradient
+__global__ void k_bal_stats(Net n, int WP, int PP, int PW, const float* __restrict__ wg_r, int copies_r,
+                            const float* __restrict__ wg_f, int copies_f, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+  const ParamGrad r = grad_of_param(n, WP, wg_r, copies_r, PP, PW, 0);
+  __syncthreads();                 // (grad_of_param's partial sums are read before they are written again)
+  const ParamGrad q = grad_of_param(n, WP, wg_f, copies_f, PP, PW, 0);
+  for (int j = 0; j < 2; ++j) {
+    const double gv = r.owner ? (double)(j == 0 ? r.g : q.g) : 0.0;
+    double a = fabs(gv), s = a, sq = gv * gv;
+    if (j) __syncthreads();
+    balance_block_reduce(a, s, sq);
+    if (threadIdx.x == 0) {
+      double* out = partials + ((int64_t)blockIdx.x * 2 + j) * PINN_BALANCE_STATS;
+      out[BAL_A] = a; out[BAL_S] = s; out[BAL_Q] = sq;
+    }
+  }
+}
+// ... one block of 256 threads: the partials folded in a fixed order, the rule on lam, the statistics' log row
+__global__ void k_bal_weights(int mode, int ref, double alpha, int64_t P, const double* __restrict__ partials, int nb,
+                              float* __restrict__ lam, double* __restrict__ stats_row) {
+  balance_finish(mode, 2, ref, alpha, P, partials, nb, lam, stats_row);
+}
+__global__ void k_finish_adam_bal(Net n, int WP, int PP, int PW, BalFinish f) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x;
+  if (b < f.param_blocks) {        // g = (lam[0] g_res) + (lam[1] g_fid), Adam, packed entries (natural unit order)
+    ParamGrad r = grad_of_param(n, WP, f.wg_r, f.copies_r, PP, PW, 0);
+    __syncthreads();
+    const ParamGrad q = grad_of_param(n, WP, f.wg_f, f.copies_f, PP, PW, 0);
+    if (r.owner) {
+      if (f.group_grads) { f.group_grads[r.at.i] = r.g; f.group_grads[n.n_params() + r.at.i] = q.g; }
+      const float wr = f.lam[0] * r.g, wf = f.lam[1] * q.g;
+      r.g = wr + wf;
+    }
+    finish_adam_apply(n, WP, r, f.grad, f.params, f.m, f.v, f.Wp, f.WTp, f.Bp, f.c);
+    return;
+  }
+  finish_sums2(f.sums_r, f.grid_r, f.sums_f, f.grid_f, f.n_terms, f.term_sums, f.n_cols, f.col_sums, f.n_loss_rows,
+               f.loss_rows, f.losses, f.row_cols);
+  if (f.lam_log && threadIdx.x < 2) f.lam_log[threadIdx.x] = f.lam[threadIdx.x];   // the weights this iteration stepped with
+}
+
 // The ensemble's finishing kernels, grid (parameter blocks + 1, M): member blockIdx.y's share of every array, then the
 // single-network functions.  gx is the per-member grid of the pass (a gradient copy and a row of partial sums per workgroup); terms_stride / row_cols are
 // the caller's n_terms / n_cols: the row lengths of term_sums / col_sums, also when this pass carried no fidelity columns.
@@ -514,6 +573,9 @@ struct PassOnly {
   int64_t scratch, wg_sums, wg_grads;   // in
   bool pack;                            // in: the packed weights are not valid yet
   int grid, n_copies;                   // out: rows of partial sums, gradient copies
+  bool natural = false;                 // in: keep the pass in natural unit order — neither the batch kernel (PACK_PERM) nor the
+                                        // width-64 KRO > 0 instances (PACK_IN | PACK_OUT), which a PLAIN residual request may
+                                        // otherwise choose (pinn_adam_loop_balanced); the tile kernel with io1 = 0 serves instead
 };
 
 int run(const Net& n, bool grad, const LossReq* rq, const float* params, const float* X, int64_t N, float* Y,
@@ -562,7 +624,8 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   if ((pec || fpec) && fused_corrected_refusal(n)) {
     set_error("fused engine: the corrected radiation stress %s", fused_corrected_refusal(n)); return PINN_ERR_UNSUPPORTED;
   }
-  const bool batch = !fld && !coefq && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
+  const bool natural = po && po->natural;
+  const bool batch = !natural && !fld && !coefq && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
   const bool coop = !adj && !fld && !batch && !pec && !coefq && use_coop(n, g, grad, N);   // (FUSED_COOP with it: the tile kernel)
   if (coop) {
     P.acc_lds = grad ? 1 : 0;
@@ -594,7 +657,7 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     P.scratch_per_wave = (int64_t)T * (n.L > 1 ? n.L - 1 : 1) * n.K1 * batch_ks(n) * 64;
   }
   // k_fused<64, ..., KRO > 0>: the specialised-epilogue kernels take inputs / outputs in k-step-major order
-  if (!batch && !coop && !coefq && n.drop_p == 0.f && g.WP == 64 && grad && P.acc_lds && n.act == PINN_ACT_TANH && P.loss_kind == 1 && !Y && P.n_split < 0 &&
+  if (!natural && !batch && !coop && !coefq && n.drop_p == 0.f && g.WP == 64 && grad && P.acc_lds && n.act == PINN_ACT_TANH && P.loss_kind == 1 && !Y && P.n_split < 0 &&
       n.d_in <= 4) {
     const int rid = P.residual_id;
     P.io1 = (n.K1 == 4 && rid == PINN_RES_NAVIER_STOKES && n.d_out <= 4) ||
@@ -609,12 +672,12 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
 
   const AdamReq* adam = rq ? rq->adam : nullptr;
   const int packN = g.PW > g.PB ? g.PW : g.PB;
-  // pinn_adam_loop_ext: one packed copy serves its two passes and its finishing kernel, so both must take natural unit order.
+  // pinn_adam_loop_ext / pinn_adam_loop_balanced: one packed copy serves its two passes and its finishing kernel, so both must take natural unit order.
   // An INTERNAL INVARIANT, not a refusal a caller can meet: a coefficient / weighted request never takes the batch kernel or
   // the KRO > 0 order (coefq above), and a K1 = 1 pass has neither (fused_batch_has_kernel wants K1 = 3 or 4, io1 a residual),
   // so perm is 0 for both passes by construction.  Should a later kernel choice break that, the call stops here with what it
   // has enqueued so far instead of finishing an iteration on weights packed in the wrong order.
-  if (po && perm) { set_error("fused engine: a pass of pinn_adam_loop_ext would run in permuted unit order"); return PINN_ERR_UNSUPPORTED; }
+  if (po && perm) { set_error("fused engine: a pass of a device-enqueued Adam run would run in permuted unit order"); return PINN_ERR_UNSUPPORTED; }
   if (po ? po->pack : !(adam && adam->packed_valid))
     hipLaunchKernelGGL(k_pack, dim3((packN + 255) / 256), dim3(256), 0, s, n, g.WP, params, (float*)(base + w.wp),
                        (float*)(base + w.wtp), (float*)(base + w.bp), g.PW, g.PB, perm);
@@ -809,6 +872,7 @@ const TileFamily TILE_FAMILIES[] = {   // indexed by TILE_*
     {"coefficient", "coefficient kernel on the fused engine", LOSS_CONDS},
     {"weighted", "weighted kernel on the fused engine", LOSS_CONDS},
     {"ensemble", "ensemble kernel", LOSS_CONDS},
+    {"balanced", "balanced loop on the fused engine", LOSS_CONDS},
 };
 // the reason of one condition, or nullptr where the network meets it (%s: the family's noun in T_FORCED, else its kernel)
 const char* tile_cond_reason(TileCond c, const Net& n) {
@@ -941,6 +1005,79 @@ int fused_adam_ext(const Net& n, const AdamExtReq& q, const float* X, int64_t N_
     f.coef_log = q.coef_log ? q.coef_log + (int64_t)i * f.n_coef : nullptr;
     hipLaunchKernelGGL(k_finish_adam_ext, dim3(blocks), dim3(256), 0, s, n, g.WP, g.PP, g.PW, f);
     rc = check_launch("fused finish + adam (ext)");
+    if (rc) return rc;
+  }
+  return PINN_OK;
+}
+
+// ---- pinn_adam_loop_balanced ----------------------------------------------------------------------------------------------
+// The residual pass is the PLAIN gradient request held to natural unit order (PassOnly::natural): the cooperative kernel
+// where run() would take it anyway, else the tile kernel with io1 = 0 — never the batch kernel, never a KRO > 0 instance.
+const char* fused_adam_bal_refusal(const Net& n) {
+  if (n.fused_kernel == FUSED_KERNEL_BATCH)
+    return "engine FUSED_BATCH: the batch kernel runs in permuted unit order, the balanced loop needs natural order (use AUTO, "
+           "FUSED, FUSED_TILE or FUSED_COOP)";
+  Net t = n; t.fused_kernel = FUSED_KERNEL_AUTO;   // (the forced-kernel condition of the family: handled above and below)
+  if (const char* why = fused_tile_refusal(TILE_BALANCE, t)) return why;
+  if (!fused_supports(n, true)) return "engine FUSED_COOP serves padded hidden width 64 (width 33..64) only";
+  Net n1 = n; n1.k = 0; n1.K1 = 1;
+  if (!fused_supports(n1, true)) return "the fidelity pass has no fused gradient kernel for this network";
+  return nullptr;
+}
+namespace {
+struct BalLayout { ExtLayout e; int64_t partials, total; };
+BalLayout bal_layout(const Net& n, const Geo& g, int64_t N_res, int64_t N_fid) {
+  BalLayout b;
+  b.e = ext_layout(n, g, N_res, N_fid);
+  b.partials = b.e.total;
+  b.total = b.partials + align256(((n.n_params() + 63) / 64) * 2 * PINN_BALANCE_STATS * (int64_t)sizeof(double));
+  return b;
+}
+}  // namespace
+int64_t fused_adam_bal_workspace_bytes(const Net& n, int64_t N_res, int64_t N_fid) {
+  return bal_layout(n, geo_of(n), N_res, N_fid).total;
+}
+int fused_adam_bal(const Net& n, const AdamBalReq& q, const float* X, int64_t N_res, void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (const char* why = fused_adam_bal_refusal(n)) {
+    set_error("fused engine, pinn_adam_loop_balanced: %s", why); return PINN_ERR_UNSUPPORTED;
+  }
+  const Geo g = geo_of(n);
+  const BalLayout B = bal_layout(n, g, N_res, q.N_fid);
+  const ExtLayout& L = B.e;
+  if (int rc = check_workspace(ws, ws_bytes, B.total)) return rc;
+  char* base = (char*)ws;
+  Net n1 = n; n1.k = 0; n1.K1 = 1;
+  const int64_t np = n.n_params();
+  BalFinish f;
+  memset(&f, 0, sizeof(f));
+  f.param_blocks = (int)((np + 63) / 64);
+  f.n_terms = q.res.n_terms; f.n_cols = q.fid.n_cols; f.row_cols = q.row_cols;
+  f.term_sums = q.res.sums; f.col_sums = q.col_sums; f.grad = q.res.grad;
+  f.params = q.adam.params; f.m = q.adam.m; f.v = q.adam.v;
+  f.Wp = (float*)(base + L.w.wp); f.WTp = (float*)(base + L.w.wtp); f.Bp = (float*)(base + L.w.bp);
+  f.n_loss_rows = q.adam.n_loss_rows; f.loss_rows = q.adam.loss_rows;
+  f.lam = q.lam; f.group_grads = q.group_grads;
+  double* partials = (double*)(base + B.partials);
+  for (int i = 0; i < q.n_iters; ++i) {
+    PassOnly pr = {L.w.scratch, L.w.wg_sums, L.w.wg_grads, i == 0 && !q.adam.packed_valid, 0, 0, true};
+    int rc = run(n, true, &q.res, q.adam.params, X, N_res, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pr);
+    if (rc) return rc;
+    PassOnly pf = {L.w.scratch, L.sums_f, L.grads_f, false, 0, 0, true};
+    rc = run(n1, true, &q.fid, q.adam.params, q.Xf, q.N_fid, nullptr, nullptr, ws, ws_bytes, s, nullptr, nullptr, &pf);
+    if (rc) return rc;
+    f.wg_r = (const float*)(base + L.w.wg_grads); f.copies_r = pr.n_copies; f.sums_r = (const float*)(base + L.w.wg_sums); f.grid_r = pr.grid;
+    f.wg_f = (const float*)(base + L.grads_f); f.copies_f = pf.n_copies; f.sums_f = (const float*)(base + L.sums_f); f.grid_f = pf.grid;
+    if ((q.step + i - 1) % q.every == 0) {   // statistics of the two gradients, the rule on lam
+      hipLaunchKernelGGL(k_bal_stats, dim3((unsigned)f.param_blocks), dim3(256), 0, s, n, g.WP, g.PP, g.PW, f.wg_r, f.copies_r,
+                         f.wg_f, f.copies_f, partials);
+      hipLaunchKernelGGL(k_bal_weights, dim3(1), dim3(256), 0, s, q.mode, q.ref, q.alpha, np, (const double*)partials,
+                         f.param_blocks, q.lam, q.stats_log ? q.stats_log + (int64_t)i * 2 * PINN_BALANCE_STATS : nullptr);
+    }
+    f.c = adam_scalars(q.lr[i], q.beta1, q.beta2, q.eps, q.step + i);
+    f.losses = q.adam.n_loss_rows > 0 ? q.adam.losses + (int64_t)i * q.adam.n_loss_rows : nullptr;
+    f.lam_log = q.lam_log ? q.lam_log + (int64_t)i * 2 : nullptr;
+    hipLaunchKernelGGL(k_finish_adam_bal, dim3((unsigned)f.param_blocks + 1), dim3(256), 0, s, n, g.WP, g.PP, g.PW, f);
+    rc = check_launch("fused finish + adam (balanced)");
     if (rc) return rc;
   }
   return PINN_OK;

@@ -207,6 +207,15 @@ def _lr_list(lr, sequence: bool = False) -> Optional[List[float]]:
     return [float(x) for x in lr] if sequence or isinstance(lr, (list, tuple)) else None
 
 
+def _balance_mode(mode) -> int:
+    """A balancing mode by name (None / "none", "max_mean", "norm") or by its PINN_BALANCE_* number."""
+    if isinstance(mode, int) and not isinstance(mode, bool):
+        return mode
+    if mode not in _lib.BALANCE_MODES:
+        raise PinnError(f"loss balancing mode {mode!r}: use None, 'max_mean' or 'norm'")
+    return _lib.BALANCE_MODES[mode]
+
+
 def _adam_state(m, v, step, lr, beta1, beta2, eps, packed_valid: bool, n_rows: int, loss_rows, losses) -> _lib.PinnAdamState:
     """pinn_adam_state of a folded-Adam call; lr None: the rates travel beside it, one per iteration."""
     return _lib.PinnAdamState(_ptr(m), _ptr(v), int(step), 0.0 if lr is None else float(lr), float(beta1), float(beta2),
@@ -756,6 +765,103 @@ class Engine:
                 _ptr(term_sums), _ptr(col_sums) if nc else None, _ptr(grad), C.byref(st), C.byref(ex), k, darr(lrs),
                 darr(lr_coef), darr(lr_w), _ptr(ws), ws.numel(), self._stream())
         if self._unsupported(rc, "pinn_adam_loop_ext"):
+            return False
+        if k > 0:
+            self._packed_tok = _packed_token(ws, params, params_token, req)
+        return True
+
+    # ---- gradient-statistics loss balancing (pinn_balance_*) ------------------------------------------------------------
+    def balance_weights_host(self, stats, lam, mode, ref: int = 0, alpha: float = 0.1, P: int = 1):
+        """The update rule alone, on host arrays (pinn_balance_weights_host; no device): stats (G, 3) float64 rows
+        [max|g|, sum|g|, sum g^2], lam (G,) float32 -> the new weights, a float32 numpy array."""
+        import numpy as np
+        st = np.ascontiguousarray(stats, dtype=np.float64)
+        lam_in = np.ascontiguousarray(lam, dtype=np.float32)
+        G = lam_in.shape[0]
+        if st.shape != (G, _lib.BALANCE_STATS):
+            raise PinnError(f"balance_weights_host: stats has shape {st.shape}, expected {(G, _lib.BALANCE_STATS)}")
+        out = np.empty_like(lam_in)
+        check(self.lib.pinn_balance_weights_host(
+            _balance_mode(mode), G, int(ref), float(alpha), int(P), st.ctypes.data_as(C.POINTER(C.c_double)),
+            lam_in.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float))), "pinn_balance_weights_host")
+        return out
+
+    def balance_update(self, grads: torch.Tensor, lam: torch.Tensor, mode, ref: int = 0, alpha: float = 0.1,
+                       stats: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, P: Optional[int] = None):
+        """pinn_balance_update on G flat gradients, the rows of grads (G, ld): the statistics of the first P (default ld)
+        entries of every row into stats (G, 3) float64 if given, the rule on lam (G,) in place, and with `out` (P,) the
+        combination out = sum_j lam[j] grads[j] with the new weights.  mode None / "none": combination only."""
+        if grads.dim() != 2:
+            raise PinnError(f"balance_update: grads must be (G, ld), got {tuple(grads.shape)}")
+        G, ld = int(grads.shape[0]), int(grads.shape[1])
+        P = ld if P is None else int(P)
+        self._chk(grads, "grads", (G, ld)); self._chk(lam, "lam", (G,))
+        if out is not None:
+            self._chk(out, "out", (P,))
+        if stats is not None:
+            if stats.dtype != torch.float64 or not stats.is_contiguous() or tuple(stats.shape) != (G, _lib.BALANCE_STATS) or stats.device != grads.device:
+                raise PinnError(f"balance_update: stats must be a contiguous float64 ({G}, {_lib.BALANCE_STATS}) tensor on {grads.device}")
+        rc, ws = self._workspace("balance", ("balance", P, G), lambda: self._query("pinn_query_balance_workspace", P, G))
+        check(rc, "pinn_query_balance_workspace")
+        tok = self._packed_tok, self._ens_packed_tok      # (this call touches no packed weights: the tokens survive it)
+        self._run("pinn_balance_update", self.lib.pinn_balance_update, _balance_mode(mode), G, int(ref), float(alpha), _ptr(grads),
+                  P, ld, _ptr(lam), _ptr(stats), _ptr(out), _ptr(ws), ws.numel())
+        self._packed_tok, self._ens_packed_tok = tok
+        return out
+
+    def adam_loop_balanced(self, spec: ResidualSpec, term_scale, params, X, grad, m, v, step: int, lr: Sequence[float],
+                           Xf: torch.Tensor, T: torch.Tensor, out_col: Sequence[int], col_scale, lam: torch.Tensor, mode,
+                           every: int = 10, ref: int = 0, alpha: float = 0.1, term_sums=None, col_sums=None,
+                           lam_log=None, stats_log=None, group_grads=None, beta1=0.9, beta2=0.999, eps=1e-8,
+                           loss_rows: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None,
+                           params_token=None) -> bool:
+        """len(lr) Adam iterations with two balanced loss groups enqueued by ONE call (pinn_adam_loop_balanced): per iteration
+        the plain residual pass on X, the fidelity pass on (Xf, T), on iterations with (step + i - 1) % every == 0 the
+        statistics of the two gradients and the rule on lam (2,) = [residual, fidelity], and one finishing kernel:
+        grad = lam[0] g_res + lam[1] g_fid, Adam on params / m / v, the sums, the weighted losses (by the caller's scales,
+        not by lam).  lam_log (k, 2): the weights each iteration stepped with; stats_log (k, 2, 3) float64: the statistics of
+        the update iterations; group_grads (2, P): the last iteration's two gradients.  Returns False — nothing launched,
+        the reason in last_error() — where the request is not served.  The packing kernel is skipped under
+        loss_grad_adam_step's rules."""
+        spec.first_order("adam_loop_balanced")
+        lrs = _lr_list(lr, sequence=True)
+        k = len(lrs)
+        N, nc = self._chk_px(params, X), len(out_col)
+        for t, nme in ((grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
+            self._chk(t, nme, (self.n_params,))
+        self._chk(term_scale, "term_scale", (spec.n_terms,)); self._chk(term_sums, "term_sums", (spec.n_terms,))
+        n_fid = Xf.shape[0]
+        self._chk(col_sums, "col_sums", (nc,)); self._chk(col_scale, "col_scale", (nc,))
+        self._chk(Xf, "Xf", (n_fid, self.desc.d_in)); self._chk(T, "T", (n_fid, nc))
+        self._chk(lam, "lam", (2,))
+        if lam_log is not None:
+            self._chk(lam_log, "lam_log", (k, 2))
+        if group_grads is not None:
+            self._chk(group_grads, "group_grads", (2, self.n_params))
+        if stats_log is not None and (stats_log.dtype != torch.float64 or not stats_log.is_contiguous() or
+                                      tuple(stats_log.shape) != (k, 2, _lib.BALANCE_STATS) or stats_log.device != params.device):
+            raise PinnError(f"adam_loop_balanced: stats_log must be a contiguous float64 ({k}, 2, {_lib.BALANCE_STATS}) tensor on {params.device}")
+        n_rows = self._chk_losses(loss_rows, losses, nc + spec.n_terms, (k,))
+        bal = _lib.PinnBalance(_balance_mode(mode), int(every), int(ref), float(alpha), lam.data_ptr(),
+                               None if lam_log is None else lam_log.data_ptr(), None if stats_log is None else stats_log.data_ptr(),
+                               None if group_grads is None else group_grads.data_ptr())
+        # (the extended loop's buffer: the same layout with the statistics' partials behind it, one packed copy for both)
+        rc, ws = self._workspace("adamext", ("adambal", spec.residual_id, spec.corrected, N, n_fid), lambda: self._query(
+            "pinn_query_adam_balanced_workspace", C.byref(self._d()), C.byref(spec.c_struct()), N, n_fid))
+        if self._unsupported(rc, "pinn_query_adam_balanced_workspace"):
+            return False
+        req = ("bal", N, n_fid, nc, spec.residual_id, spec.corrected)
+        st = _adam_state(m, v, step, None, beta1, beta2, eps, _packed_valid(self._packed_tok, ws, params, params_token, req),
+                         n_rows, loss_rows, losses)
+        self._packed_tok = None
+        self._ens_packed_tok = None
+        lr_arr = (C.c_double * max(k, 1))(*lrs)
+        with self._guard():
+            rc = self.lib.pinn_adam_loop_balanced(
+                C.byref(self._d()), C.byref(spec.c_struct()), _ptr(term_scale), _ptr(Xf), _ptr(T), n_fid, nc, _out_cols(out_col),
+                _ptr(col_scale), _ptr(params), _ptr(X), N, _ptr(term_sums), _ptr(col_sums), _ptr(grad), C.byref(st),
+                C.byref(bal), k, lr_arr, _ptr(ws), ws.numel(), self._stream())
+        if self._unsupported(rc, "pinn_adam_loop_balanced"):
             return False
         if k > 0:
             self._packed_tok = _packed_token(ws, params, params_token, req)

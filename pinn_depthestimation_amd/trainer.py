@@ -186,6 +186,53 @@ def fold_extras_refusal(fold_extras=False, coefficients=False, weighted=False, r
     return None
 
 
+def balance_refusal(loss_balancing=None, groups="sets", every=10, alpha=0.1, ref="residual", fold_extras=False, coefficients=False,
+                    weighted=False, rad_importance=False, eddy_viscosity=0.0, reducer_active=False, custom_evaluator=False):
+    """Why trainer.PINN cannot run this configuration with gradient-statistics loss balancing (None: it can, or none is asked
+    for).  Pure host logic, evaluated before anything touches a device."""
+    if loss_balancing is None:
+        return None
+    if loss_balancing not in ("max_mean", "norm"):
+        return f"loss_balancing={loss_balancing!r}: use None, 'max_mean' or 'norm'"
+    if groups not in ("sets", "terms"):
+        return f"balance_groups={groups!r}: use 'sets' (residual, fidelity) or 'terms' (a group per weighted residual term, and fidelity)"
+    if int(every) < 1:
+        return f"balance_every={every} must be >= 1"
+    if not (0.0 < float(alpha) <= 1.0):
+        return f"balance_alpha={alpha} must lie in (0, 1]"
+    if ref not in ("residual", "fidelity"):
+        return f"balance_ref={ref!r}: use 'residual' or 'fidelity'"
+    if coefficients:
+        return "loss balancing does not run with runtime closure coefficients (their gradient belongs to no group)"
+    if weighted or rad_importance:
+        return ("loss balancing does not run with point weights on the residual (residual_weights, self_adaptive, rad_importance): "
+                "two schemes would set the same weights")
+    if eddy_viscosity:
+        return "loss balancing does not run with eddy_viscosity != 0"
+    if reducer_active:
+        return "loss balancing does not run under data parallelism (the statistics are taken on one rank's gradients)"
+    if custom_evaluator:
+        return "loss balancing needs the library's own evaluator, not a custom one"
+    if groups == "terms" and fold_extras:
+        return "balance_groups='terms' does not run with fold_extras (the device-enqueued runs balance the two point sets; a group per term needs one-hot passes)"
+    return None
+
+
+def balance_fold_refusal(residual_batch=None, resample="uniform", dropout_rate=0.0, fold_adam=True):
+    """Why balanced Adam iterations stay on the classic path although fold_extras is on (None: they run as device-enqueued
+    runs, Engine.adam_loop_balanced, where the engine serves them).  Nothing is refused: the classic path computes the same
+    iteration.  Pure host logic."""
+    if not fold_adam:
+        return "fold_adam is off: every Adam iteration takes the classic path"
+    if resample == "rad":
+        return "resample='rad': the host draws a mini-batch for every iteration"
+    if residual_batch is not None:
+        return "residual_batch: the host draws a mini-batch for every iteration"
+    if dropout_rate and dropout_rate > 0:
+        return "dropout: a fresh seed per forward pass has no place in an enqueued run"
+    return None
+
+
 def _as_f32(a, device) -> Optional[torch.Tensor]:
     if a is None:
         return None
@@ -291,11 +338,26 @@ class HipEvaluator:
                 e.residual_loss_grad(self.spec, res_scale, theta, Xr, grad, sums=res_sums)
         self._split_pass(theta, Xf, Tf, fid_scale, Xr, grad, fid_sums, res_sums, residual)
 
+    def group_passes(self, theta, Xf, Tf, fid_scale, Xr, res_scale, g_res, g_fid, fid_sums, res_sums):
+        """Loss balancing's classic path: the residual's gradient ADDED to g_res and the fidelity term's to g_fid, a pass each
+        (either may be None: that pass is not run and its sums are left alone) — the plain entries of whatever engine serves
+        the network, with a fresh dropout seed per pass in training mode as in _split_pass."""
+        drop = self.eng_drop is not None and self.training
+        e = self.eng_drop if drop else self.eng
+        if g_fid is not None:
+            if drop:
+                e.dropout_seed = _dropout_seed()
+            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, g_fid, sums=fid_sums)
+        if g_res is not None:
+            if drop:
+                e.dropout_seed = _dropout_seed()
+            e.residual_loss_grad(self.spec, res_scale, theta, Xr, g_res, sums=res_sums)
+
     def adam_step(self, theta, grad, m, v, step, lr):
         self.eng.adam_step(theta, grad, m, v, step, lr)
 
     def adam_iteration(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums, m, v, step, lr,
-                       loss_rows=None, losses=None, params_token=None, extras=None) -> bool:
+                       loss_rows=None, losses=None, params_token=None, extras=None, balance=None) -> bool:
         """loss_func + backward + Adam.step (train.py:189-193) in two launches where the engine can
         (Engine.loss_grad_adam_step); False — nothing done — otherwise: the caller then runs __call__ + adam_step.
         extras (trainer.PINN(fold_extras=True)): with runtime coefficients or point weights set, the keyword arguments of
@@ -305,6 +367,16 @@ class HipEvaluator:
             return False
         if self.spec.nu != 0:     # the second-order residual is layer kernels per chunk, not one pass: the classic path
             return False
+        if balance is not None:
+            # gradient-statistics loss balancing (trainer.PINN(loss_balancing=..., fold_extras=True)): the keyword arguments of
+            # Engine.adam_loop_balanced — the two point sets as a pass each, the weights updated on the device
+            if self.coef is not None or self.point_w is not None or Xf is None or Xf.shape[0] == 0:
+                return False
+            single = not isinstance(lr, (list, tuple))
+            return self.eng.adam_loop_balanced(self.spec, res_scale, theta, Xr, grad, m, v, step, [lr] if single else lr, Xf, Tf,
+                                               self.fid_cols, fid_scale, term_sums=res_sums, col_sums=fid_sums, loss_rows=loss_rows,
+                                               losses=losses.reshape(1, -1) if single and losses is not None else losses,
+                                               params_token=params_token, **balance)
         if self.coef is not None or self.point_w is not None:
             # the folded iteration runs the entries that carry the constants and no weights: these requests have a loop entry
             # of their own, taken only when the trainer asks for it
@@ -379,8 +451,25 @@ class PINN:
                  resample: str = "uniform", rad_every: int = 100, rad_k: float = 1.0, rad_c: float = 1.0,
                  corrected: bool = False, eddy_viscosity: float = 0.0, coefficients: Optional[dict] = None,
                  trainable_coefficients: Sequence[str] = (), residual_weights=None, self_adaptive=None,
-                 rad_importance: Optional[bool] = None, fold_extras: bool = False):
-        """fold_extras (or the config key adam_optimizer.fold_extras; off unless asked for): Adam iterations with runtime
+                 rad_importance: Optional[bool] = None, fold_extras: bool = False, loss_balancing: Optional[str] = None,
+                 balance_every: Optional[int] = None, balance_alpha: Optional[float] = None, balance_ref: Optional[str] = None,
+                 balance_groups: Optional[str] = None):
+        """loss_balancing (or the config key loss.balancing): "max_mean" (Wang, Teng & Perdikaris 2021) or "norm" (Wang et al.
+        2023) — the weights of the loss groups are set from the groups' own gradients during the Adam stage
+        (include/pinn_hip.h: pinn_balance_update): on every balance_every-th iteration, from the first, the statistics of the
+        per-group gradients move the weights by a moving average of rate balance_alpha; every iteration steps along
+        sum_j lam_j g_j.  balance_groups "sets": residual and fidelity (balance_ref, the max/mean rule's reference group:
+        "residual" or "fidelity"); "terms": a group per weighted residual term (ResidualSpec.n_weighted_terms; "residual"
+        then names the first term) and fidelity — on update iterations the residual runs once per term with a one-hot scale.
+        The weights multiply the hand-set ones (weight_fid / weight_res and the per-output weights stay in the scales); the
+        logged losses stay weighted by the hand-set ones alone, loss_weights() and the log's extra columns give the rest.
+        The classic path — two loss calls into two rows of a (G, P) buffer, Engine.balance_update, pinn_adam_step, no host
+        synchronisation — runs on every engine and with residual_batch and resample="rad"; with fold_extras and "sets" the
+        iterations run as device-enqueued runs (Engine.adam_loop_balanced) where that entry serves the network
+        (self.balance_why says why not).  The L-BFGS stage holds the weights frozen at their Adam-final values: they are
+        folded into the scales once when it starts.  Refused (balance_refusal): runtime coefficients, point weights of any
+        kind, eddy_viscosity, data parallelism, a custom evaluator, "terms" with fold_extras.
+        fold_extras (or the config key adam_optimizer.fold_extras; off unless asked for): Adam iterations with runtime
         coefficients, fixed residual_weights or self_adaptive weights run as device-enqueued runs (Engine.adam_loop_ext: three
         launches per iteration, no Python in between; the coefficients, the multipliers and their Adam moments are updated on
         the device) instead of the classic path.  Checkpoint iterations, mat_dump_iter, residual_batch, resample="rad",
@@ -439,6 +528,20 @@ class PINN:
                                lbfgs_impl, evaluator is not None, residual_batch, resample)
         if why:
             raise PinnError(why)
+        # gradient-statistics loss balancing: parsed and refused before anything touches a device
+        self.loss_balancing = cfg.loss_balancing if loss_balancing is None else (None if loss_balancing == "none" else loss_balancing)
+        self.balance_every = cfg.balance_every if balance_every is None else balance_every
+        self.balance_alpha = cfg.balance_alpha if balance_alpha is None else balance_alpha
+        self.balance_ref = cfg.balance_ref if balance_ref is None else balance_ref
+        self.balance_groups = cfg.balance_groups if balance_groups is None else balance_groups
+        why = balance_refusal(self.loss_balancing, self.balance_groups, self.balance_every, self.balance_alpha, self.balance_ref,
+                              bool(fold_extras) or cfg.fold_extras, bool(coef_in or coef_tr),
+                              residual_weights is not None or sa_opt is not None, rad_imp, nu0, self.reducer.active, evaluator is not None)
+        if why:
+            raise PinnError(why)
+        if self.loss_balancing is not None and (fidelity_input is None or residual_input is None or
+                                                len(fidelity_input) == 0 or len(residual_input) == 0):
+            raise PinnError("loss balancing weighs the fidelity set against the collocation set: it needs points in both")
         if lbfgs_impl == "device":       # decided before anything touches a device
             nu = float(eddy_viscosity) if eddy_viscosity else float(cfg.raw.get("loss", {}).get("eddy_viscosity", 0.0))
             why = device_lbfgs_refusal(self.reducer.active, residual_batch, nu, evaluator is not None,
@@ -450,6 +553,12 @@ class PINN:
         self.fold_extras_why = fold_extras_refusal(self.fold_extras, bool(coef_in or coef_tr), residual_weights is not None or sa_opt is not None,
                                                    rad_imp, residual_batch, resample, cfg.dropout_rate, self.reducer.active, nu0,
                                                    evaluator is not None, bool(fold_adam))
+        # (balanced iterations: where fold_extras is on, why they keep the classic path all the same — None: they run as
+        # device-enqueued runs wherever the engine serves the request)
+        self.balance_why = None
+        if self.loss_balancing is not None:
+            self.balance_why = ("fold_extras is off" if not self.fold_extras else
+                                balance_fold_refusal(residual_batch, resample, cfg.dropout_rate, bool(fold_adam)))
         self._run_coef_log = None
         self._fold_refused = None   # key of the (evaluator, point sets) whose folded request the engine has refused
         self.layers = cfg.layers                                           # train.py:52-56
@@ -565,7 +674,25 @@ class PINN:
         self.log_dir, self.log_every, self.checkpoint_every = log_dir, max(int(log_every), 1), checkpoint_every
         self._log_fh = None
         self._history: List[tuple] = []
-        self._ring = torch.zeros(max(int(log_flush_every), 1), 3 + len(self.coef_names), dtype=torch.float32, device=dev)
+        # loss balancing: the group weights, the (G, P) buffer of the per-group gradients and the run's log of the weights
+        self._bal_lam = self._bal_buf = self._bal_pair = self._run_lam_log = None
+        self._bal_frozen = False
+        self.balance_names: Tuple[str, ...] = ()
+        self._weight_history: List[tuple] = []
+        if self.loss_balancing is not None:
+            nw = self.spec.n_weighted_terms
+            self.balance_names = ("residual", "fidelity") if self.balance_groups == "sets" else \
+                tuple(f"residual_term_{t}" for t in range(nw)) + ("fidelity",)
+            G = len(self.balance_names)
+            self._bal_ref = 0 if self.balance_ref == "residual" else G - 1
+            self._bal_lam = torch.ones(G, dtype=torch.float32, device=dev)
+            self._bal_buf = torch.zeros(G, P, dtype=torch.float32, device=dev)
+            if self.balance_groups == "terms":
+                self._bal_pair = torch.ones(2, dtype=torch.float32, device=dev)      # [1, lam_fidelity] between updates
+                self._bal_onehot = torch.eye(nt, dtype=torch.float32, device=dev)[:nw].contiguous()
+                self._bal_term_scale = torch.zeros(nt, dtype=torch.float32, device=dev)
+        self._ring = torch.zeros(max(int(log_flush_every), 1), 3 + len(self.coef_names) + len(self.balance_names),
+                                 dtype=torch.float32, device=dev)
         self._ring_iters: List[int] = []
         self.last = None
         self.init_optimizers()
@@ -673,6 +800,10 @@ class PINN:
         self._ensure_loss_mat()
         nxt = self.iter + 1
         logged = nxt % self.log_every == 0 or nxt % 1000 == 0
+        # loss balancing is the Adam stage's: the L-BFGS stage (closure) has folded the weights into the scales
+        balancing = self.loss_balancing is not None and not self._bal_frozen
+        if logged and self._bal_lam is not None and not balancing:
+            self._ring[len(self._ring_iters)][3:].copy_(self._bal_lam)
         # the three losses of a logged iteration are computed straight into the device-side ring
         vec = self._ring[len(self._ring_iters)][:3] if logged else self._loss_vec
         if logged and self._coef is not None:      # the coefficients this evaluation ran with, beside its losses
@@ -680,11 +811,19 @@ class PINN:
         self._adam_folded = _adam is not None and self.evaluator.adam_iteration(
             self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad, self._fid_sums, self._res_sums,
             *_adam, loss_rows=self._loss_mat, losses=vec, params_token=self.dnn.write_token(self.theta),
-            **({"extras": self._fold_extras_kw(1)} if self._has_extras() else {}))
+            **({"extras": self._fold_extras_kw(1)} if self._has_extras() else {}),
+            **({"balance": self._balance_kw(1)} if balancing else {}))
+        if balancing and self._adam_folded and logged:      # the weights this iteration stepped with, beside its losses
+            self._ring[len(self._ring_iters)][3:].copy_(self._run_lam_log[0])
         if not self._adam_folded:
             self.buf.zero_()
-            self.evaluator(self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad,
-                           self._fid_sums, self._res_sums)
+            if balancing:
+                self._balanced_pass(Xr)
+                if logged:
+                    self._ring[len(self._ring_iters)][3:].copy_(self._bal_lam)
+            else:
+                self.evaluator(self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad,
+                               self._fid_sums, self._res_sums)
             self.reducer.allreduce_sum_(self.buf)
             torch.mv(self._loss_mat, self.buf[self.theta.numel():], out=vec)                  # one small mat-vec: the three losses
         self.iter += 1                                                                        # train.py:160
@@ -697,6 +836,77 @@ class PINN:
         if self._checkpoint_due(self.iter):
             self.save_checkpoint(f"model_{self.iter}.pth")                                    # train.py:175-179
         return loss
+
+    def _balanced_pass(self, Xr):
+        """One balanced evaluation on the classic path: the groups' gradients into the rows of the (G, P) buffer,
+        Engine.balance_update — statistics and the rule on update iterations ((step - 1) % balance_every == 0), the
+        combination sum_j lam_j g_j into self.grad on every one — and the sums of both terms.  No host synchronisation."""
+        update = self._adam_step % self.balance_every == 0          # (this iteration is Adam step _adam_step + 1)
+        ev, eng, buf, G = self.evaluator, self.evaluator.eng, self._bal_buf, self._bal_lam.numel()
+        if self.balance_groups == "sets":
+            buf.zero_()
+            ev.group_passes(self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, buf[0], buf[1],
+                            self._fid_sums, self._res_sums)
+            eng.balance_update(buf, self._bal_lam, self.loss_balancing if update else None, ref=self._bal_ref,
+                               alpha=self.balance_alpha, out=self.grad)
+            return
+        nw = G - 1
+        if update:       # the residual once per weighted term, its scale one-hot: row t = term t's gradient
+            buf.zero_()
+            for t in range(nw):
+                torch.mul(self._res_scale, self._bal_onehot[t], out=self._bal_term_scale)
+                ev.group_passes(self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._bal_term_scale, buf[t],
+                                buf[nw] if t == 0 else None, self._fid_sums, self._res_sums)
+            eng.balance_update(buf, self._bal_lam, self.loss_balancing, ref=self._bal_ref, alpha=self.balance_alpha, out=self.grad)
+            return
+        # between updates: ONE residual call with the scales lam_t * base, the fidelity term beside it, combined as [1, lam_fid]
+        pair = buf[:2]
+        pair.zero_()
+        self._bal_term_scale.copy_(self._res_scale)
+        self._bal_term_scale[:nw].mul_(self._bal_lam[:nw])
+        self._bal_pair[1:].copy_(self._bal_lam[nw:])
+        ev.group_passes(self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._bal_term_scale, pair[0], pair[1],
+                        self._fid_sums, self._res_sums)
+        eng.balance_update(pair, self._bal_pair, None, out=self.grad)
+
+    def _balance_kw(self, k: int) -> dict:
+        """What Engine.adam_loop_balanced needs beside the evaluator's own tensors for the next k iterations."""
+        if self._run_lam_log is None or self._run_lam_log.shape[0] < k:
+            self._run_lam_log = torch.zeros(max(k, self.MAX_RUN), 2, dtype=torch.float32, device=self.device)
+        return {"lam": self._bal_lam, "mode": self.loss_balancing, "every": self.balance_every, "ref": self._bal_ref,
+                "alpha": self.balance_alpha, "lam_log": self._run_lam_log[:k]}
+
+    def loss_weights(self) -> Dict[str, float]:
+        """The balanced groups' weights by name (one synchronisation): "residual" and "fidelity", or "residual_term_<t>" and
+        "fidelity"; {} without loss_balancing.  They multiply the hand-set weights."""
+        if self._bal_lam is None:
+            return {}
+        return dict(zip(self.balance_names, (float(x) for x in self._bal_lam.cpu().tolist())))
+
+    @property
+    def weight_history(self) -> List[tuple]:
+        """(iteration, weight of every group in balance_names order) of every logged iteration so far: the weights the
+        iteration stepped with."""
+        self.flush_log()
+        return self._weight_history
+
+    def freeze_loss_weights(self):
+        """The L-BFGS stage holds the balanced weights at their Adam-final values: they are folded into the scales (and into
+        the total's row of the loss matrix) once, on the device; from then on every evaluation is the plain weighted loss."""
+        if self.loss_balancing is None or self._bal_frozen:
+            return
+        self._ensure_loss_mat()
+        nw, nf = self._bal_lam.numel() - 1, self._fid_sums.numel()
+        self._fid_scale = (self._fid_scale * self._bal_lam[nw]).contiguous()
+        res = self._res_scale.clone()
+        if self.balance_groups == "sets":
+            res.mul_(self._bal_lam[0])
+        else:
+            res[:nw].mul_(self._bal_lam[:nw])
+        self._res_scale = res.contiguous()
+        self._loss_mat[2, :nf] = self._fid_scale          # (train.py:157: the total is [fid scale | res scale] . sums)
+        self._loss_mat[2, nf:] = self._res_scale
+        self._bal_frozen = True
 
     def _ensure_loss_mat(self):
         if self._loss_mat is None:
@@ -740,7 +950,9 @@ class PINN:
 
     def _log(self, it: int, fid: float, res: float, tot: float, coefs: Sequence[float] = ()):
         self._history.append((it, fid, res, tot))
-        if coefs:
+        if coefs and self.balance_names:      # (never both: balancing refuses coefficients) the groups' weights
+            self._weight_history.append((it,) + tuple(coefs))
+        elif coefs:
             self._coef_history.append((it,) + tuple(coefs))
         tail = "".join(f", {c:.6e}" for c in coefs)      # the coefficients' values, appended to the log line
         if it % 1000 == 0 and self.reducer.rank == 0:
@@ -753,7 +965,8 @@ class PINN:
             new = not os.path.exists(path) or os.stat(path).st_size == 0
             self._log_fh = open(path, "a")
             if new:
-                self._log_fh.write("Epoch, Fidelity Loss, Residual Loss, Total Loss" + "".join(f", {n}" for n in self.coef_names) + "\n")   # train.py:167
+                self._log_fh.write("Epoch, Fidelity Loss, Residual Loss, Total Loss" + "".join(f", {n}" for n in self.coef_names) +
+                                   "".join(f", weight_{n}" for n in self.balance_names) + "\n")   # train.py:167
         self._log_fh.write(f"{it}, {fid:.5e}, {res:.5e}, {tot:.5e}{tail}\n")                  # train.py:170
 
     def dump_predictions(self, path: str):
@@ -803,6 +1016,8 @@ class PINN:
         if self._coef is not None:
             self.evaluator.coef_grad = self._coef_grad      # (None when nothing is trainable: values only)
         self._sa_frozen = False
+        if self._bal_frozen:
+            raise PinnError("loss balancing: the weights were frozen for the L-BFGS stage; Adam iterations after it are not balanced")
         loss = self.loss_func((self._adam_m, self._adam_v, self._adam_step + 1, self.current_lr()) if fold else None)
         self._adam_step += 1
         if fold and not self._adam_folded:
@@ -835,6 +1050,8 @@ class PINN:
         per evaluator and point sets instead of being re-discovered by two refused C calls every iteration)."""
         if self._has_extras() and not (self.fold_extras and self.fold_extras_why is None and self.residual_batch is None):
             return False      # coefficients / point weights: the classic path unless fold_extras is on and applies
+        if self.loss_balancing is not None and not (self.balance_why is None and self.balance_groups == "sets"):
+            return False      # balanced iterations: the classic path unless fold_extras is on and applies
         return (self.fold_adam and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
                 and self._fold_refused != self._fold_key())
 
@@ -920,6 +1137,9 @@ class PINN:
                 self._sa_frozen = False
                 self.evaluator.fields_out = self._sa_fields
             ext = {"extras": self._fold_extras_kw(k, clog)}
+        if self.loss_balancing is not None:      # (_may_fold has said so) the run of Engine.adam_loop_balanced
+            ext = {"balance": self._balance_kw(k)}
+            clog = self._run_lam_log[:k]         # the weights each iteration stepped with ride in the ring's extra columns
         if not self.evaluator.adam_iteration(self.theta, self.Xf, self.Tf, self._fid_scale, self.Xr, self._res_scale, self.grad,
                                              self._fid_sums, self._res_sums, self._adam_m, self._adam_v, self._adam_step + 1,
                                              lrs, loss_rows=self._loss_mat, losses=out, params_token=self.dnn.write_token(self.theta), **ext):
@@ -958,6 +1178,7 @@ class PINN:
         if self._coef is not None:      # the L-BFGS stage holds the coefficients frozen: values only, no coefficient gradient
             self.evaluator.coef_grad = None
         self._sa_frozen = True          # ... and the self-adaptive weights at their Adam-final values
+        self.freeze_loss_weights()      # ... and the balanced group weights, folded into the scales once
         loss = self.loss_func()
         self.theta_param.grad = self.grad.clone()
         return loss
@@ -966,6 +1187,7 @@ class PINN:
         self.dnn.train()
         self.train_adam(self.adam_maxit)
         if self.config.lbfgs["max_it"] > 0:
+            self.freeze_loss_weights()
             if self.lbfgs_impl == "device":
                 self.train_lbfgs_device()
             else:
@@ -1011,7 +1233,9 @@ class PINN:
             for i in range(k):
                 it = self.iter + 1 + i
                 if it % self.log_every == 0 or it % 1000 == 0:
-                    self._ring[len(self._ring_iters)].copy_(rows[i])
+                    self._ring[len(self._ring_iters)][:3].copy_(rows[i])
+                    if self._bal_lam is not None:      # the frozen group weights, in their columns
+                        self._ring[len(self._ring_iters)][3:].copy_(self._bal_lam)
                     self._ring_iters.append(it)
                     if len(self._ring_iters) == self._ring.shape[0]:
                         self.flush_log()
