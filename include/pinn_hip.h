@@ -925,6 +925,47 @@ int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, c
                         void* state, int64_t state_bytes, int32_t n_slots, double* trace,
                         void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- the device-resident L-BFGS loop of an ensemble ---------------------------------------------------------------------
+ * pinn_lbfgs_loop for the M networks of pinn_ensemble_loss_grad: every member runs its own strong-Wolfe search, its own
+ * ring and its own stopping tests, and ONE schedule of launches per slot advances them all (kernels on a grid whose second
+ * axis is the member, the pass is pinn_ensemble_loss_grad's).  Member j gets the arithmetic pinn_lbfgs_loop applies to
+ * row j of params; where the ensemble pass gives the bits of the single-network pass (one working wave per member), the
+ * whole loop does.  One pinn_lbfgs_opts for all members.  A member that has stopped is inert in every later slot: zero
+ * trace rows, its row of params untouched, its control block unchanged but for `action`; its pass still runs.
+ *
+ * The state, every region on a 256-byte boundary, a(x) = x rounded up to a multiple of 256:
+ *   M control blocks (pinn_lbfgs_ctrl) at a stride of a(sizeof(pinn_lbfgs_ctrl)) bytes: member j's at j * stride, so the
+ *     host fetches all of them in one copy of M * stride bytes;
+ *   d (M, P) floats at M * stride; x_trial (M, P) floats — the weights of the last evaluation — a(4 M P) bytes further;
+ *   then g_new (M, P), the column sums and the term sums (M x PINN_MAX_ROLES floats reserved each), and M member blocks
+ *   (gradient pool, prev_g, s, y, q, partials, losses, recursion scratch, S, Y, M).
+ *   state_bytes = M a(sizeof(pinn_lbfgs_ctrl)) + 3 a(4 M P) + 2 a(4 M PINN_MAX_ROLES) + M member_bytes,
+ *   member_bytes = a(4 PINN_LS_POOL_ROWS P) + 4 a(4 P) + a(8 * 256 * 8) + a(32) + a(8 * 4 * 256) + a(4 * 2 * 256)
+ *                  + 2 a(4 history_size P) + a(8 history_size^2).
+ *
+ * pinn_ensemble_query_lbfgs_loop: ws_bytes is pinn_ensemble_query_workspace's answer, state_bytes the formula above.  Host
+ *   logic only, like pinn_ensemble_plan.
+ * pinn_ensemble_lbfgs_loop_init: zeroes the state and arms the M control blocks; P is the descriptor's parameter count.
+ * pinn_ensemble_lbfgs_loop: n_slots slots.  params (M, P): row j holds member j's ACCEPTED iterate whenever a call returns.
+ *   X, T, flags (PINN_ENSEMBLE_OWN_X / _OWN_T), n_res, n_cols, out_col and the scales as pinn_ensemble_loss_grad; loss_rows,
+ *   total_row as pinn_lbfgs_loop, shared by the members; history_size the one the state was initialised with (it sizes the
+ *   recursion kernels' grids: a member whose control block holds another is not advanced).  trace: (n_slots, M,
+ *   PINN_LBFGS_TRACE_COLS) doubles, the rows of pinn_lbfgs_loop's trace, one per member, or NULL.  Two calls of n slots are
+ *   one call of 2n.  Writes params, trace and state at those extents only; after the init `state` is the one buffer whose
+ *   content a call relies on.
+ * Refused before any device work, the reason in pinn_last_error(): everything pinn_ensemble_loss_grad refuses, in its own
+ *   words; M outside 1..PINN_ENSEMBLE_MAX_MEMBERS; history_size outside 1..256; n_slots < 0; n_loss_rows / total_row as
+ *   pinn_lbfgs_loop; null pointers; a state or workspace smaller than the query's answer (PINN_ERR_WORKSPACE). */
+int32_t pinn_ensemble_query_lbfgs_loop(const pinn_desc* desc, int32_t M, int64_t N, int32_t history_size, int64_t* ws_bytes,
+                                       int64_t* state_bytes);
+int32_t pinn_ensemble_lbfgs_loop_init(void* state, int64_t state_bytes, int32_t M, int64_t P, const pinn_lbfgs_opts* opts,
+                                      void* stream);
+int32_t pinn_ensemble_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M, const float* term_scale,
+                                 const float* T, int32_t n_cols, const int32_t* out_col, const float* col_scale, float* params,
+                                 const float* X, int64_t N, int64_t n_res, int32_t flags, int32_t n_loss_rows,
+                                 const float* loss_rows, int32_t total_row, int32_t history_size, void* state,
+                                 int64_t state_bytes, int32_t n_slots, double* trace, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- staging of the collocation points on the device (train.py:246-277, operations.py:4-30) --------------------
  * The reference loads each input variable as a (ny, nx) float64 grid (scipy.io.loadmat), subsamples it with
  * [::interval_x, ::interval_y] (train.py:260), maps it onto [-1, 1] with the variable's (min, max) (operations.py:4-8;

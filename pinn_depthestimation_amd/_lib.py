@@ -112,6 +112,23 @@ LBFGS_ACT_INERT, LBFGS_ACT_CONTINUE, LBFGS_ACT_ACCEPT, LBFGS_ACT_INITIAL = 0, 1,
 LBFGS_STOP_REASONS = {0: None, 1: "gradient", 2: "step", 3: "loss change", 4: "max_iter", 5: "max_eval", 6: "direction"}
 LBFGS_TRACE_COLS = 18
 
+
+def _a256(v: int) -> int:
+    return (int(v) + 255) // 256 * 256
+
+
+def ensemble_lbfgs_ctrl_stride() -> int:
+    """Bytes from one member's control block to the next in the ensemble L-BFGS state (pinn_hip.h)."""
+    return _a256(C.sizeof(PinnLbfgsCtrl))
+
+
+def ensemble_lbfgs_state_bytes(M: int, P: int, history_size: int) -> int:
+    """pinn_ensemble_query_lbfgs_loop's state_bytes by the formula pinn_hip.h documents."""
+    a, m = _a256, int(history_size)
+    member = a(4 * LS_POOL_ROWS * P) + 4 * a(4 * P) + a(8 * 256 * 8) + a(32) + a(8 * 4 * 256) + a(4 * 2 * 256) \
+        + 2 * a(4 * m * P) + a(8 * m * m)
+    return M * ensemble_lbfgs_ctrl_stride() + 3 * a(4 * M * P) + 2 * a(4 * M * PINN_MAX_ROLES) + M * member
+
 ERR_INVALID, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -2, -3
 
 
@@ -174,6 +191,12 @@ _SIGNATURES = {
     "pinn_lbfgs_loop": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), _P, _P, C.c_int32, C.POINTER(C.c_int32),
                                     _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int32,
                                     _P, _P, C.c_int64, _P]),
+    "pinn_ensemble_query_lbfgs_loop": (C.c_int32, [C.POINTER(PinnDesc), C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64),
+                                                   C.POINTER(C.c_int64)]),
+    "pinn_ensemble_lbfgs_loop_init": (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int64, C.POINTER(PinnLbfgsOpts), _P]),
+    "pinn_ensemble_lbfgs_loop": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(PinnResidualSpec), C.c_int32, _P, _P, C.c_int32,
+                                             C.POINTER(C.c_int32), _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
+                                             C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "pinn_nanminmax_f64": (C.c_int32, [_P, C.c_int64, _P, _P, C.c_int64, _P]),
     "pinn_stage_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "pinn_stage_grid_columns": (C.c_int32, [C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P,

@@ -779,9 +779,9 @@ int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, c
     set_error("pinn_lbfgs_loop: state too small: need at least %lld bytes, got %lld", (long long)need, (long long)state_bytes);
     return PINN_ERR_WORKSPACE;
   }
-  const LblPtrs p = lbl_ptrs(state, params, P);
+  const LblPtrs p = lbl_ptrs(state, params, P, n_cols);
   rq.scale = term_scale;
-  rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = p.sums; rq.sums = p.sums + n_cols; rq.grad = p.gnew;
+  rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = p.csums; rq.sums = p.tsums; rq.grad = p.gnew;
   {   // the refusals of the loss request itself, before anything is launched
     int e = pick_engine(desc, n, true, &rc);
     if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
@@ -792,10 +792,85 @@ int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, c
   }
   const hipStream_t s = (hipStream_t)stream;
   for (int32_t i = 0; i < n_slots; ++i) {
-    rc = lbl_before_pass(p, n_cols + rq.n_terms, s); if (rc) return rc;
+    rc = lbl_before_pass(p, n_cols, rq.n_terms, s); if (rc) return rc;
     rc = run_loss(desc, n, true, rq, p.xt, X, N, ws, ws_bytes, stream); if (rc) return rc;
     rc = lbl_after_pass(p, n_cols, rq.n_terms, n_loss_rows, loss_rows, total_row,
                         trace ? trace + (int64_t)i * PINN_LBFGS_TRACE_COLS : nullptr, s);
+    if (rc) return rc;
+  }
+  return PINN_OK;
+}
+
+// ---- the ensemble's device-resident L-BFGS (pinn_hip.h; kernels: pinn_lbfgs_ens.hip, the pass: fused_ensemble_loss) ----------
+int32_t pinn_ensemble_query_lbfgs_loop(const pinn_desc* desc, int32_t M, int64_t N, int32_t history_size, int64_t* ws_bytes,
+                                       int64_t* state_bytes) {
+  const char* who = "pinn_ensemble_query_lbfgs_loop";
+  Net n; int rc = ensemble_net(who, desc, M, &n); if (rc) return rc;
+  rc = lbfgs_history_ok(who, history_size); if (rc) return rc;
+  if (!ws_bytes || !state_bytes || N < 1) { set_error("%s: bad arguments", who); return PINN_ERR_INVALID; }
+  fused_ensemble_plan(n, M, N, nullptr, nullptr, ws_bytes);
+  *state_bytes = lbe_layout(M, n.n_params(), history_size).total;
+  return PINN_OK;
+}
+
+int32_t pinn_ensemble_lbfgs_loop_init(void* state, int64_t state_bytes, int32_t M, int64_t P, const pinn_lbfgs_opts* opts,
+                                      void* stream) {
+  const char* who = "pinn_ensemble_lbfgs_loop_init";
+  if (!state || !opts || P < 1) { set_error("%s: NULL pointer argument or P < 1", who); return PINN_ERR_INVALID; }
+  if (M < 1 || M > PINN_ENSEMBLE_MAX_MEMBERS) { set_error("%s: M = %d outside 1..%d", who, M, PINN_ENSEMBLE_MAX_MEMBERS); return PINN_ERR_INVALID; }
+  int rc = lbfgs_history_ok(who, opts->history_size); if (rc) return rc;
+  if (opts->max_iter < 0 || opts->max_eval < 1 || !(opts->lr > 0.0)) {
+    set_error("%s: max_iter = %d, max_eval = %d, lr = %g", who, opts->max_iter, opts->max_eval, opts->lr);
+    return PINN_ERR_INVALID;
+  }
+  const int64_t need = lbe_layout(M, P, opts->history_size).total;
+  if (state_bytes < need) {
+    set_error("%s: state too small: need %lld bytes, got %lld", who, (long long)need, (long long)state_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  return lbe_init(state, M, P, *opts, (hipStream_t)stream);
+}
+
+int32_t pinn_ensemble_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, int32_t M, const float* term_scale,
+                                 const float* T, int32_t n_cols, const int32_t* out_col, const float* col_scale, float* params,
+                                 const float* X, int64_t N, int64_t n_res, int32_t flags, int32_t n_loss_rows,
+                                 const float* loss_rows, int32_t total_row, int32_t history_size, void* state,
+                                 int64_t state_bytes, int32_t n_slots, double* trace, void* ws, int64_t ws_bytes, void* stream) {
+  const char* who = "pinn_ensemble_lbfgs_loop";
+  Net n; int rc = ensemble_net(who, desc, M, &n); if (rc) return rc;
+  rc = lbfgs_history_ok(who, history_size); if (rc) return rc;
+  if (n_slots < 0) { set_error("%s: n_slots = %d", who, n_slots); return PINN_ERR_INVALID; }
+  if (!spec) { set_error("%s: spec is NULL", who); return PINN_ERR_INVALID; }
+  // (without out_col: no array is looked at before the refusals below; the columns follow the NULL checks)
+  LossReq rq; rc = build_request(n, spec, N, n_res, 0, n_cols, nullptr, &rq); if (rc) return rc;
+  if (N < 1) { set_error("%s: N = %lld, need at least one point", who, (long long)N); return PINN_ERR_INVALID; }
+  if (flags & ~(PINN_ENSEMBLE_OWN_X | PINN_ENSEMBLE_OWN_T)) { set_error("%s: unknown flags 0x%x", who, flags); return PINN_ERR_INVALID; }
+  if (const char* why = fused_ensemble_refusal(n, rq)) { set_error("%s: %s", who, why); return PINN_ERR_UNSUPPORTED; }
+  if (n_loss_rows < 1 || n_loss_rows > 8 || total_row < 0 || total_row >= n_loss_rows) {
+    set_error("%s: n_loss_rows = %d outside 1..8 or total_row = %d outside it", who, n_loss_rows, total_row);
+    return PINN_ERR_INVALID;
+  }
+  if (!params || !X || !term_scale || !state || !loss_rows) { set_error("%s: NULL pointer argument", who); return PINN_ERR_INVALID; }
+  if (n_cols > 0 && (!out_col || !col_scale || (!T && n_res != N))) { set_error("%s: NULL pointer argument", who); return PINN_ERR_INVALID; }
+  rc = set_out_cols(n, n_cols, out_col, &rq); if (rc) return rc;
+  const int64_t P = n.n_params();
+  const int64_t need = lbe_layout(M, P, history_size).total;
+  if (state_bytes < need) {
+    set_error("%s: state too small: need %lld bytes, got %lld", who, (long long)need, (long long)state_bytes);
+    return PINN_ERR_WORKSPACE;
+  }
+  int64_t ws_need = 0;
+  fused_ensemble_plan(n, M, N, nullptr, nullptr, &ws_need);
+  rc = check_workspace(ws, ws_bytes, ws_need); if (rc) return rc;
+  const LbePtrs e = lbe_ptrs(state, params, M, P, history_size, n_cols, rq.n_terms);
+  rq.scale = term_scale;
+  rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = lbe_csums(e); rq.sums = lbe_tsums(e); rq.grad = lbe_gnew(e);
+  const hipStream_t s = (hipStream_t)stream;
+  for (int32_t i = 0; i < n_slots; ++i) {
+    rc = lbe_before_pass(e, s); if (rc) return rc;
+    rc = fused_ensemble_loss(n, rq, M, flags, lbe_xt(e), X, N, ws, ws_bytes, s); if (rc) return rc;
+    rc = lbe_after_pass(e, n_loss_rows, loss_rows, total_row,
+                        trace ? trace + (int64_t)i * M * PINN_LBFGS_TRACE_COLS : nullptr, s);
     if (rc) return rc;
   }
   return PINN_OK;

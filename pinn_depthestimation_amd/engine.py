@@ -1026,6 +1026,67 @@ class Engine:
         self._ens_packed_tok = _packed_token(ws, params, params_token, req)
         return True
 
+    # ---- the ensemble's device-resident L-BFGS loop (pinn_ensemble_lbfgs_loop) ------------------------------------------
+    def ensemble_lbfgs_loop_query(self, M: int, N: int, history_size: int) -> Tuple[int, int]:
+        """(workspace bytes, state bytes) of ensemble_lbfgs_loop for M members on N points with this history size
+        (pinn_ensemble_query_lbfgs_loop).  Raises PinnError with the engine's reason where the ensemble calls are refused."""
+        ws, st = C.c_int64(), C.c_int64()
+        with self._guard():
+            check(self.lib.pinn_ensemble_query_lbfgs_loop(C.byref(self._d()), int(M), int(N), int(history_size), C.byref(ws),
+                                                          C.byref(st)), "pinn_ensemble_query_lbfgs_loop")
+        return ws.value, st.value
+
+    def ensemble_lbfgs_loop_init(self, state: torch.Tensor, M: int, lr, max_iter, max_eval, history_size, tolerance_grad,
+                                 tolerance_change):
+        """Zeroes `state` (uint8, at least the query's state bytes) and arms its M control blocks, one set of options
+        for all members (pinn_ensemble_lbfgs_loop_init)."""
+        o = _lib.PinnLbfgsOpts(float(lr), float(tolerance_grad), float(tolerance_change), int(max_iter), int(max_eval),
+                               int(history_size))
+        self._run("pinn_ensemble_lbfgs_loop_init", self.lib.pinn_ensemble_lbfgs_loop_init, _ptr(state), state.numel(), int(M),
+                  self.n_params, C.byref(o))
+
+    def ensemble_lbfgs_loop(self, spec: ResidualSpec, term_scale, params, X, n_res: int, loss_rows: torch.Tensor, total_row: int,
+                            history_size: int, state: torch.Tensor, n_slots: int, trace: Optional[torch.Tensor] = None,
+                            T: Optional[torch.Tensor] = None, out_col: Sequence[int] = (), col_scale=None,
+                            ws: Optional[torch.Tensor] = None):
+        """n_slots slots of the device-resident L-BFGS loop of M networks (pinn_ensemble_lbfgs_loop): lbfgs_loop's slot for
+        every member — its own line search, ring and stopping tests — in one schedule of launches.  params (M, P): row j
+        holds member j's accepted iterate whenever the enqueued work has run.  X (N, d_in) or (M, N, d_in), T (rows, nc)
+        or (M, rows, nc), n_res, out_col and the scales as ensemble_loss_grad; loss_rows, total_row as lbfgs_loop, shared;
+        history_size the one `state` was initialised with; trace (n_slots, M, LBFGS_TRACE_COLS) float64, optional.  Like
+        every other call it leaves no packed weights to trust: an ensemble_adam_step after it packs again."""
+        spec.first_order("ensemble_lbfgs_loop")
+        if params.dim() != 2:
+            raise PinnError(f"params must be (M, {self.n_params}), got {tuple(params.shape)}")
+        M, nc = params.shape[0], len(out_col)
+        own_x = X.dim() == 3
+        N = X.shape[1] if own_x else X.shape[0]
+        self._chk(params, "params", (M, self.n_params))
+        self._chk(X, "X", (M, N, self.desc.d_in) if own_x else (N, self.desc.d_in))
+        self._chk(term_scale, "term_scale", (spec.n_terms,))
+        self._chk(loss_rows, "loss_rows", (loss_rows.shape[0], nc + spec.n_terms))
+        flags = _lib.ENSEMBLE_OWN_X if own_x else 0
+        if nc:
+            self._chk(col_scale, "col_scale", (nc,))
+            if n_res != N:
+                rows = N - n_res if n_res >= 0 else N
+                if T is not None and T.dim() == 3:
+                    flags |= _lib.ENSEMBLE_OWN_T
+                    self._chk(T, "T", (M, rows, nc))
+                else:
+                    self._chk(T, "T", (rows, nc))
+        if trace is not None and (trace.dtype != torch.float64 or not trace.is_contiguous()
+                                  or tuple(trace.shape) != (n_slots, M, _lib.LBFGS_TRACE_COLS) or trace.device != params.device):
+            raise PinnError(f"trace must be a contiguous float64 ({n_slots}, {M}, {_lib.LBFGS_TRACE_COLS}) tensor on {params.device}")
+        if state.dtype != torch.uint8 or not state.is_contiguous() or state.device != params.device:
+            raise PinnError("state must be a contiguous uint8 tensor on the engine's device")
+        if ws is None:
+            ws = self.ensemble_workspace(M, N)
+        self._run("pinn_ensemble_lbfgs_loop", self.lib.pinn_ensemble_lbfgs_loop, C.byref(self._d()), C.byref(spec.c_struct()), M,
+                  _ptr(term_scale), _ptr(T), nc, _out_cols(out_col), _ptr(col_scale), _ptr(params), _ptr(X), N, int(n_res), flags,
+                  loss_rows.shape[0], _ptr(loss_rows), int(total_row), int(history_size), _ptr(state), state.numel(),
+                  int(n_slots), _ptr(trace), _ptr(ws), ws.numel())
+
     def last_error(self) -> str:
         """The library's message for the last refused or failed call of this thread (pinn_last_error)."""
         msg = self.lib.pinn_last_error()

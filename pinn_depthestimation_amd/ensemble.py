@@ -6,8 +6,15 @@ The reference's problems fill a few workgroups of the chip (config_CMB.json: 243
 EnsemblePINN keeps all members' parameters in ONE (M, P) buffer and runs an Adam iteration of all of them in two launches
 (Engine.ensemble_adam_step -> pinn_ensemble_adam_loop): member i gets the arithmetic trainer.PINN applies to its own
 network.  Same config schema, loss weights and StepLR schedule as trainer.PINN; one learning-rate schedule and one set of
-loss weights for all members.  An L-BFGS stage runs per member through the single-network trainer: member(i) is a DNN whose
-parameters are views of row i, ready for trainer.PINN(dnn=...) or inference.Tester.
+loss weights for all members.
+
+The L-BFGS stage (the reference's one LBFGS.step after Adam) runs for all members at once too: train_lbfgs() ->
+lbfgs.EnsembleDeviceLBFGS -> pinn_ensemble_lbfgs_loop, the device-resident loop of trainer.PINN(lbfgs_impl="device") with
+a member axis.  Every member runs its own strong-Wolfe line search, its own history ring and its own stopping tests; one
+schedule of launches per evaluation advances them all, and a member that has stopped is inert while the others go on.
+One set of L-BFGS options (config.lbfgs) for all members.  EnsemblePINN(lbfgs_stage=True).train() is the Adam stage
+followed by train_lbfgs().  member(i) is a DNN whose parameters are views of row i — the row both stages write — ready
+for inference.Tester, or for trainer.PINN(dnn=...) where one member is to be trained on its own.
 """
 from __future__ import annotations
 
@@ -19,6 +26,7 @@ from ._lib import PinnError
 from .config import PinnConfig, load_config
 from .dnn import DNN, activation_id_of, init_flat_params
 from .engine import Engine, NetDesc, ResidualSpec
+from .lbfgs import DeviceLBFGS, EnsembleDeviceLBFGS
 from .parallel import Reducer
 from .trainer import _as_f32, steplr_factors
 
@@ -54,9 +62,12 @@ class EnsemblePINN:
 
     def __init__(self, fidelity_input, fidelity_true, residual_input, config, members: int,
                  seeds: Optional[Sequence[int]] = None, residual: Optional[str] = None, device="cuda", engine: int = 0,
-                 log_every: int = 1, coefficients=None, trainable_coefficients=()):
+                 log_every: int = 1, coefficients=None, trainable_coefficients=(), lbfgs_stage: bool = False):
         cfg = config if isinstance(config, PinnConfig) else load_config(config)
         self.config, self.device = cfg, torch.device(device)
+        self.lbfgs_stage = bool(lbfgs_stage)
+        if self.lbfgs_stage:      # the options the device loop does not serve, in its own words, before the device is touched
+            self._lbfgs_options()
         if coefficients or trainable_coefficients or cfg.raw.get("loss", {}).get("coefficients") \
                 or cfg.raw.get("loss", {}).get("trainable_coefficients"):
             raise PinnError("EnsemblePINN has no runtime closure coefficients (loss.coefficients / loss.trainable_coefficients): "
@@ -157,11 +168,14 @@ class EnsemblePINN:
         self.log_every = max(int(log_every), 1)
         self._history: List[tuple] = []
         self._pending: List[Tuple[List[int], torch.Tensor]] = []      # (iterations, their (n, M, 3) rows on the device)
+        self.device_lbfgs: Optional[EnsembleDeviceLBFGS] = None       # built by train_lbfgs(): it binds the point sets
+        self._lbfgs_traces: List[torch.Tensor] = []                   # one (slots, M, LBFGS_TRACE_COLS) CPU tensor per run
 
     # ---- members ---------------------------------------------------------------------------------------------------
     def member(self, i: int) -> DNN:
-        """Member i as a dnn.DNN whose Linear parameters are views of row i of `theta`: what it is told to do (trainer.PINN
-        (dnn=...) for an L-BFGS stage, inference.Tester, load_state_dict) happens to the ensemble's own buffer."""
+        """Member i as a dnn.DNN whose Linear parameters are views of row i of `theta` — the row train_adam and train_lbfgs
+        write: what it is told to do (inference.Tester, load_state_dict, trainer.PINN(dnn=...)) happens to the ensemble's
+        own buffer."""
         i = int(i)
         if not 0 <= i < self.members:
             raise PinnError(f"member {i} of an ensemble of {self.members}")
@@ -209,10 +223,42 @@ class EnsemblePINN:
             self._sched_steps += k
             n -= k
 
+    def _lbfgs_options(self):
+        """config.lbfgs as lbfgs.DeviceLBFGS.check_options takes it (PinnError in its words for what the loop does not do)."""
+        lb = self.config.lbfgs
+        return DeviceLBFGS.check_options(lb["learning_rate"], lb["max_it"], lb.get("max_evaluation"), lb["history_size"],
+                                         lb["tolerance_grad"], lb["tolerance_change"], lb["line_search_fn"])
+
+    def train_lbfgs(self):
+        """The L-BFGS stage of every member (train.py:200, one LBFGS.step each) through lbfgs.EnsembleDeviceLBFGS, with
+        the options of config.lbfgs as trainer.PINN.train_lbfgs_device takes them: runs of up to RUN evaluations enqueued
+        by one call each, until every member has stopped.  self.iter advances by the evaluations of the member that took
+        the most; every evaluation's three losses are kept per member (lbfgs_history)."""
+        o = self._lbfgs_options()
+        nf = len(self.fid_cols)
+        opt = self.device_lbfgs = EnsembleDeviceLBFGS(
+            self.eng, self.spec, self.theta, self.X, self._n_res, self._res_scale, self._loss_mat, 2,
+            T=self.T if nf else None, out_col=self.fid_cols, col_scale=self._fid_scale if nf else None,
+            lr=o.lr, max_iter=o.max_iter, max_eval=o.max_eval, history_size=o.history_size,
+            tolerance_grad=o.tolerance_grad, tolerance_change=o.tolerance_change)
+        opt.step(after_run=self._lbfgs_traces.append)
+        self.iter += max(opt.func_evals)
+        return opt
+
     def train(self):
-        """The Adam stage of the configuration (adam_optimizer.max_it iterations).  The L-BFGS stage is per member:
-        trainer.PINN(..., dnn=self.member(i)).optimizer_LBFGS / train_lbfgs_device."""
+        """The Adam stage of the configuration (adam_optimizer.max_it iterations); with lbfgs_stage=True followed by the
+        L-BFGS stage of all members (train_lbfgs) where lbfgs_optimizer.max_it > 0, as trainer.PINN.train does."""
         self.train_adam(self.adam_maxit)
+        if self.lbfgs_stage and self.config.lbfgs["max_it"] > 0:
+            self.train_lbfgs()
+
+    @property
+    def lbfgs_history(self) -> List[torch.Tensor]:
+        """Per member, an (evaluations, 3) float32 CPU tensor: [fidelity, residual, total] of every evaluation of its
+        L-BFGS stage, in order, from the loop's trace (inert slots — after the member's stop — left out)."""
+        from ._lib import LBFGS_TRACE_COLS
+        tr = torch.cat(self._lbfgs_traces) if self._lbfgs_traces else torch.zeros(0, self.members, LBFGS_TRACE_COLS, dtype=torch.float64)
+        return [tr[tr[:, j, 2] != 0, j, 10:13].to(torch.float32) for j in range(self.members)]
 
     @property
     def history(self) -> List[tuple]:

@@ -346,3 +346,108 @@ class DeviceLBFGS:
     def trace(self) -> torch.Tensor:
         """Every slot run so far, (slots, LBFGS_TRACE_COLS) float64 on the CPU."""
         return torch.cat(self.traces) if self.traces else torch.zeros(0, self._lib.LBFGS_TRACE_COLS, dtype=torch.float64)
+
+
+class EnsembleDeviceLBFGS:
+    """DeviceLBFGS for the M networks of an ensemble (Engine.ensemble_lbfgs_loop, pinn_ensemble_lbfgs_loop): every member
+    its own strong-Wolfe search, ring and stopping tests, all advanced by one schedule of launches per slot.  `params`
+    (M, P): row j holds member j's accepted iterate after every run.  One set of options for all members.  The host reads
+    the M control blocks once per run (one copy) and stops when every done flag is up; a member that has stopped is inert
+    in the slots the others still need."""
+
+    RUN = DeviceLBFGS.RUN
+
+    def __init__(self, engine, spec, params, X, n_res, term_scale, loss_rows, total_row, T=None, out_col=(), col_scale=None,
+                 lr=1.0, max_iter=20, max_eval=None, history_size=100, tolerance_grad=1e-7, tolerance_change=1e-9,
+                 line_search_fn="strong_wolfe"):
+        from . import _lib
+        self._lib = _lib
+        self.opts = DeviceLBFGS.check_options(lr, max_iter, max_eval, history_size, tolerance_grad, tolerance_change, line_search_fn)
+        self.engine, self.spec, self.params, self.X, self.n_res = engine, spec, params, X, int(n_res)
+        self.term_scale, self.loss_rows, self.total_row = term_scale, loss_rows, int(total_row)
+        self.T, self.out_col, self.col_scale = T, tuple(out_col), col_scale
+        self.members = int(params.shape[0])
+        N = X.shape[1] if X.dim() == 3 else X.shape[0]
+        ws_bytes, state_bytes = engine.ensemble_lbfgs_loop_query(self.members, N, self.opts.history_size)
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=params.device)
+        self.state = torch.empty(state_bytes, dtype=torch.uint8, device=params.device)
+        self.traces = []             # one (slots, M, LBFGS_TRACE_COLS) float64 CPU tensor per run
+        self.reset()
+
+    def reset(self):
+        o = self.opts
+        self.engine.ensemble_lbfgs_loop_init(self.state, self.members, o.lr, o.max_iter, o.max_eval, o.history_size,
+                                             o.tolerance_grad, o.tolerance_change)
+        self.traces = []
+        self._ctrls = None
+
+    def enqueue(self, n_slots: int) -> torch.Tensor:
+        """n_slots more slots; returns their trace (device tensor; nothing is synchronised)."""
+        trace = torch.empty(n_slots, self.members, self._lib.LBFGS_TRACE_COLS, dtype=torch.float64, device=self.params.device)
+        self.engine.ensemble_lbfgs_loop(self.spec, self.term_scale, self.params, self.X, self.n_res, self.loss_rows,
+                                        self.total_row, self.opts.history_size, self.state, n_slots, trace, T=self.T,
+                                        out_col=self.out_col, col_scale=self.col_scale, ws=self.ws)
+        self._ctrls = None
+        return trace
+
+    def run(self, n_slots: int) -> torch.Tensor:
+        """enqueue(n_slots), then the trace on the host (one synchronisation) with the control blocks re-read."""
+        tr = self.enqueue(n_slots).cpu()
+        self.traces.append(tr)
+        self.ctrls()
+        return tr
+
+    def ctrls(self):
+        """The M control blocks (pinn_lbfgs_ctrl) as the device holds them now: one copy, one synchronisation."""
+        if self._ctrls is None:
+            stride = self._lib.ensemble_lbfgs_ctrl_stride()
+            raw = self.state[:self.members * stride].cpu().numpy().tobytes()
+            self._ctrls = [self._lib.PinnLbfgsCtrl.from_buffer_copy(raw, j * stride) for j in range(self.members)]
+        return self._ctrls
+
+    @property
+    def x_trial(self) -> torch.Tensor:
+        """(M, P): the members' weights of the last evaluation (x + t d), a view into the state: the control blocks, d
+        (M, P) and x_trial (M, P), each region on a 256-byte boundary (include/pinn_hip.h)."""
+        a = lambda v: (v + 255) // 256 * 256
+        M, P = self.params.shape
+        off = M * self._lib.ensemble_lbfgs_ctrl_stride() + a(4 * M * P)
+        return self.state[off:off + 4 * M * P].view(torch.float32).view(M, P)
+
+    def step(self, before_run=None, after_run=None):
+        """Runs until every member's done flag is up.  Each run is sized by the member that still needs the most slots,
+        under DeviceLBFGS.step's rule; before_run(most evaluations of a member so far) -> an upper limit for the slots of
+        the next run; after_run(trace of the run, CPU) is called after each."""
+        while not self.done:
+            o = self.opts
+            need = max(min(o.max_iter - c.n_iter + 1, o.max_eval + 1 - c.n_evals) for c in self.ctrls() if not c.done)
+            n = max(1, min(self.RUN, need))
+            if before_run is not None:
+                n = max(1, min(n, int(before_run(max(self.func_evals)))))
+            tr = self.run(n)
+            if after_run is not None:
+                after_run(tr)
+        return self
+
+    @property
+    def done(self) -> bool:
+        return all(c.done for c in self.ctrls())
+
+    @property
+    def n_iter(self):
+        return [c.n_iter for c in self.ctrls()]
+
+    @property
+    def func_evals(self):
+        return [c.n_evals for c in self.ctrls()]
+
+    @property
+    def stop_reason(self):
+        return [self._lib.LBFGS_STOP_REASONS[c.reason] for c in self.ctrls()]
+
+    @property
+    def trace(self) -> torch.Tensor:
+        """Every slot run so far, (slots, M, LBFGS_TRACE_COLS) float64 on the CPU."""
+        if not self.traces:
+            return torch.zeros(0, self.members, self._lib.LBFGS_TRACE_COLS, dtype=torch.float64)
+        return torch.cat(self.traces)
