@@ -28,7 +28,7 @@ from .dnn import DNN, activation_id_of, init_flat_params
 from .engine import Engine, NetDesc, ResidualSpec
 from .lbfgs import DeviceLBFGS, EnsembleDeviceLBFGS
 from .parallel import Reducer
-from .trainer import _as_f32, steplr_factors
+from .trainer import _as_f32, anchor_count, loss_arithmetic, steplr_factors
 
 DEFAULT_SEED = 1234      # trainer.PINN's default seed: member i starts from DEFAULT_SEED + i
 
@@ -133,26 +133,11 @@ class EnsemblePINN:
             self.X = Xr
         self.T = Tf
         self.n_res, self.n_fid = nr, nfp
-        if cfg.variant == "newmethod":
-            fid_w = [1.0] * len(self.fid_cols)
-        else:
-            fid_w = [cfg.output_weight(k) for k in cfg.fidelity_outputs][:len(self.fid_cols)]
         self.weight_fidelity, self.weight_residual = cfg.weight_fid, cfg.weight_res
         nf, nt = len(self.fid_cols), self.spec.n_terms
-        self._fid_unit = torch.tensor(fid_w, dtype=torch.float32, device=dev) / max(nfp, 1)
-        if residual == "continuity_only":
-            xcol = cfg.grad_cols[self.spec.dir_of[0]]
-            cnt = (Xr[:, xcol] < self.spec.threshold).sum().to(torch.float32).reshape(1)
-            self._res_unit = torch.cat([torch.tensor([1.0 / nr], device=dev), 1.0 / cnt, torch.zeros(1, device=dev)])
-        else:
-            self._res_unit = torch.full((nt,), 1.0 / nr, dtype=torch.float32, device=dev)
-        self._fid_scale = (self.weight_fidelity * self._fid_unit).contiguous()
-        self._res_scale = (self.weight_residual * self._res_unit).contiguous()
-        m = torch.zeros(3, nf + nt, dtype=torch.float32, device=dev)      # [fidelity, residual, total] = m @ [fid sums | res sums]
-        m[0, :nf] = self._fid_unit
-        m[1, nf:] = self._res_unit
-        m[2] = self.weight_fidelity * m[0] + self.weight_residual * m[1]
-        self._loss_mat = m.contiguous()
+        # the trainer's loss arithmetic, one set of scales for all members
+        self._fid_unit, self._res_unit, self._fid_scale, self._res_scale, self._loss_mat = loss_arithmetic(
+            cfg, self.spec, nf, nfp, nr, dev, anchor_count(cfg, self.spec, Xr) if residual == "continuity_only" else None)
 
         # ---- parameters and optimiser state ----
         self.theta = init_ensemble_params(cfg.layers, cfg.init_type, self.seeds).to(dev).contiguous()

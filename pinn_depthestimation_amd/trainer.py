@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import json
 import os
+from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -142,9 +143,9 @@ def coefficient_refusal(residual, coefficients, trainable, corrected=False, eddy
         return None
     if residual not in RESIDUAL_ROLES:
         return f"unknown residual {residual!r}"
-    have = () if corrected else _lib.RES_COEFS[RESIDUAL_ROLES[residual][0]]
     if corrected:
         return "the corrected radiation stress has no coefficient form (the corrected kernels carry the constant Cd)"
+    have = _lib.RES_COEFS[RESIDUAL_ROLES[residual][0]]
     for name in list(coefficients) + list(trainable):
         if name not in have:
             return (f"residual {residual!r} has no coefficient {name!r}: " +
@@ -251,6 +252,34 @@ def steplr_factors(adam: dict, sched_steps: int, k: int = 1) -> List[float]:
     return [adam["scheduler_gamma"] ** ((sched_steps + i) // adam["scheduler_step_size"]) for i in range(k)]
 
 
+def anchor_count(cfg: PinnConfig, spec: ResidualSpec, Xr: torch.Tensor) -> torch.Tensor:
+    """continuity_only's data-dependent normaliser: how many of the points Xr have x < threshold, a (1,) float32 tensor."""
+    xcol = cfg.grad_cols[spec.dir_of[0]]
+    return (Xr[:, xcol] < spec.threshold).sum().to(torch.float32).reshape(1)
+
+
+def loss_arithmetic(cfg: PinnConfig, spec: ResidualSpec, nf: int, n_fid: int, n_res: int, device, anchor=None):
+    """The loss arithmetic of train.py:131-157 as (fid_unit, res_unit, fid_scale, res_scale, loss_mat): the sums of squares
+    the kernels return become means with the units, weighted terms of the total with the scales (= hand-set weight x unit),
+    and [fidelity, residual, total] = loss_mat @ [fid sums | res sums].  nf fidelity outputs on n_fid points; n_res: the
+    residual's normaliser (the point count; a mini-batch's size x the world size); anchor: continuity_only's anchor_count,
+    summed over the ranks — its second term's normaliser."""
+    if cfg.variant == "newmethod":
+        fid_w = [1.0] * nf                                                 # F.mse_loss, unweighted sum
+    else:
+        fid_w = [cfg.output_weight(k) for k in cfg.fidelity_outputs][:nf]  # train.py:94-95,140
+    fid_unit = torch.tensor(fid_w, dtype=torch.float32, device=device) / max(n_fid, 1)
+    if anchor is not None:
+        res_unit = torch.cat([torch.tensor([1.0 / n_res], device=device), 1.0 / anchor, torch.zeros(1, device=device)])
+    else:
+        res_unit = torch.full((spec.n_terms,), 1.0 / max(n_res, 1), dtype=torch.float32, device=device)
+    m = torch.zeros(3, nf + spec.n_terms, dtype=torch.float32, device=device)
+    m[0, :nf] = fid_unit
+    m[1, nf:] = res_unit
+    m[2] = cfg.weight_fid * m[0] + cfg.weight_res * m[1]                   # train.py:157
+    return fid_unit, res_unit, (cfg.weight_fid * fid_unit).contiguous(), (cfg.weight_res * res_unit).contiguous(), m.contiguous()
+
+
 class HipEvaluator:
     """Local-shard loss sums and gradient through libpinn_hip.so."""
 
@@ -269,34 +298,38 @@ class HipEvaluator:
         self._cat = None            # [collocation points ; fidelity points], allocated once
         self._cat_src = (None, None)   # the very tensor OBJECTS whose rows _cat currently holds
 
-    MERGE_MAX_FID = 2048
+    MERGE_MAX_FID = 2048   # fidelity points ride through the jet kernel (4x their own work): only when few
     # runtime closure coefficients (PINN(coefficients=..., trainable_coefficients=...)): the device tensor the residual reads
     # them from, and where their gradient goes (None: values only — frozen, or nothing trainable); set by the trainer
     coef = None
-    coef_grad = None   # fidelity points ride through the jet kernel (4x their own work): only when few
+    coef_grad = None
     # point weights on the residual (PINN(residual_weights=..., self_adaptive=..., rad_importance=...)): the device tensor
     # (w_rows, N) matching the collocation points of the call, and where the pass's unweighted signed fields go (None: not
     # wanted); set by the trainer
     point_w = None
     fields_out = None
 
+    def _dropping(self) -> bool:
+        return self.eng_drop is not None and self.training
+
+    def _engine(self):
+        """The engine of the next pass.  In training mode with dropout it is eng_drop, and a fresh seed is drawn for the
+        pass's masks first: one draw immediately before every pass that IS launched (the reference runs the network twice
+        per loss_func call, train.py:133,148: two forward passes, two masks)."""
+        if not self._dropping():
+            return self.eng
+        self.eng_drop.dropout_seed = _dropout_seed()
+        return self.eng_drop
+
     def _split_pass(self, theta, Xf, Tf, fid_scale, Xr, grad, fid_sums, res_sums, residual):
         """The two loss terms as a pass each: the fidelity term through mse_loss_grad, then residual(engine) on the
-        collocation points; a term without points launches nothing and zeroes its sums.  In training mode with dropout the
-        engine is eng_drop's, and every pass that IS launched first draws a fresh seed (the reference runs the network twice
-        per loss_func call, train.py:133,148: two forward passes, two masks)."""
-        drop = self.eng_drop is not None and self.training
-        e = self.eng_drop if drop else self.eng
+        collocation points; a term without points launches nothing and zeroes its sums."""
         if Xf is not None and Xf.shape[0] > 0:
-            if drop:
-                e.dropout_seed = _dropout_seed()
-            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
+            self._engine().mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, grad, sums=fid_sums)
         else:
             fid_sums.zero_()
         if Xr is not None and Xr.shape[0] > 0:
-            if drop:
-                e.dropout_seed = _dropout_seed()
-            residual(e)
+            residual(self._engine())
         else:
             res_sums.zero_()
 
@@ -317,16 +350,12 @@ class HipEvaluator:
             def residual(e):
                 e.residual2_loss_grad(self.spec, res_scale, theta, Xr, grad, sums=res_sums)
         else:
-            drop = self.eng_drop is not None and self.training
             if Xf is not None and Xf is Xr and Xr.shape[0] > 0:
                 # one point set for both terms (train_newmethod.py:122-159): one pass, one forward, one dropout mask
-                e = self.eng_drop if drop else self.eng
-                if drop:
-                    e.dropout_seed = _dropout_seed()
-                e.residual_mse_loss_grad(self.spec, res_scale, Tf, self.fid_cols, fid_scale, theta, Xr, grad,
-                                         term_sums=res_sums, col_sums=fid_sums)
+                self._engine().residual_mse_loss_grad(self.spec, res_scale, Tf, self.fid_cols, fid_scale, theta, Xr, grad,
+                                                      term_sums=res_sums, col_sums=fid_sums)
                 return
-            if (not drop and self.merge_sets and Xf is not None and Xr is not None
+            if (not self._dropping() and self.merge_sets and Xf is not None and Xr is not None
                     and 0 < Xf.shape[0] <= self.MERGE_MAX_FID and Xr.shape[0] > 0):
                 # train.py:131-157 in ONE launch: collocation points first, fidelity points after them
                 cat = self._merged(Xr, Xf)
@@ -341,75 +370,71 @@ class HipEvaluator:
     def group_passes(self, theta, Xf, Tf, fid_scale, Xr, res_scale, g_res, g_fid, fid_sums, res_sums):
         """Loss balancing's classic path: the residual's gradient ADDED to g_res and the fidelity term's to g_fid, a pass each
         (either may be None: that pass is not run and its sums are left alone) — the plain entries of whatever engine serves
-        the network, with a fresh dropout seed per pass in training mode as in _split_pass."""
-        drop = self.eng_drop is not None and self.training
-        e = self.eng_drop if drop else self.eng
+        the network, with a fresh dropout seed per pass in training mode as _engine draws it."""
         if g_fid is not None:
-            if drop:
-                e.dropout_seed = _dropout_seed()
-            e.mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, g_fid, sums=fid_sums)
+            self._engine().mse_loss_grad(theta, Xf, Tf, self.fid_cols, fid_scale, g_fid, sums=fid_sums)
         if g_res is not None:
-            if drop:
-                e.dropout_seed = _dropout_seed()
-            e.residual_loss_grad(self.spec, res_scale, theta, Xr, g_res, sums=res_sums)
+            self._engine().residual_loss_grad(self.spec, res_scale, theta, Xr, g_res, sums=res_sums)
 
     def adam_step(self, theta, grad, m, v, step, lr):
         self.eng.adam_step(theta, grad, m, v, step, lr)
+
+    def request_points(self, Xf, Xr, force_merge: bool = False):
+        """(X, n_res) of the request that runs both loss terms in ONE pass, as the engine's loop entries take them: the
+        collocation points alone (n_res = their count) without fidelity points, the shared point set (n_res = -1,
+        train_newmethod.py:122-159), else [collocation points ; fidelity points] (n_res = the collocation count).  None: not
+        servable in one pass — merge_sets is off or the fidelity set is larger than MERGE_MAX_FID (force_merge: the
+        caller has no second pass to fall back to, and merges all the same)."""
+        if Xf is None or Xf.shape[0] == 0:
+            return Xr, Xr.shape[0]
+        if Xf is Xr:
+            return Xr, -1
+        if not force_merge and not (self.merge_sets and Xf.shape[0] <= self.MERGE_MAX_FID):
+            return None
+        return self._merged(Xr, Xf), Xr.shape[0]
 
     def adam_iteration(self, theta, Xf, Tf, fid_scale, Xr, res_scale, grad, fid_sums, res_sums, m, v, step, lr,
                        loss_rows=None, losses=None, params_token=None, extras=None, balance=None) -> bool:
         """loss_func + backward + Adam.step (train.py:189-193) in two launches where the engine can
         (Engine.loss_grad_adam_step); False — nothing done — otherwise: the caller then runs __call__ + adam_step.
+        lr: a float, with losses (3,) — one iteration — or a list, with losses (k, 3): a device-enqueued run.
         extras (trainer.PINN(fold_extras=True)): with runtime coefficients or point weights set, the keyword arguments of
         Engine.adam_loop_ext that belong to them (moments, learning rates, coef_log / the multipliers) — the request then
-        runs as a device-enqueued run of that entry; without it such requests take the classic path."""
-        if (self.eng_drop is not None and self.training) or Xr is None or Xr.shape[0] == 0:
+        runs as a device-enqueued run of that entry; without it such requests take the classic path.
+        balance (trainer.PINN(loss_balancing=..., fold_extras=True)): the keyword arguments of Engine.adam_loop_balanced that
+        belong to gradient-statistics loss balancing — the two point sets as a pass each, the weights updated on the device."""
+        if self._dropping() or Xr is None or Xr.shape[0] == 0:
             return False
         if self.spec.nu != 0:     # the second-order residual is layer kernels per chunk, not one pass: the classic path
             return False
-        if balance is not None:
-            # gradient-statistics loss balancing (trainer.PINN(loss_balancing=..., fold_extras=True)): the keyword arguments of
-            # Engine.adam_loop_balanced — the two point sets as a pass each, the weights updated on the device
-            if self.coef is not None or self.point_w is not None or Xf is None or Xf.shape[0] == 0:
-                return False
-            single = not isinstance(lr, (list, tuple))
-            return self.eng.adam_loop_balanced(self.spec, res_scale, theta, Xr, grad, m, v, step, [lr] if single else lr, Xf, Tf,
-                                               self.fid_cols, fid_scale, term_sums=res_sums, col_sums=fid_sums, loss_rows=loss_rows,
-                                               losses=losses.reshape(1, -1) if single and losses is not None else losses,
-                                               params_token=params_token, **balance)
-        if self.coef is not None or self.point_w is not None:
-            # the folded iteration runs the entries that carry the constants and no weights: these requests have a loop entry
-            # of their own, taken only when the trainer asks for it
-            if extras is None:
-                return False
-            single = not isinstance(lr, (list, tuple))
-            has_fid = Xf is not None and Xf.shape[0] > 0
-            kw = dict(extras)
-            if self.coef is not None:
-                kw.update(coef=self.coef, coef_grad=self.coef_grad)
-            else:
-                kw.update(point_w=self.point_w, fields=self.fields_out)
-            return self.eng.adam_loop_ext(self.spec, res_scale, theta, Xr, grad, m, v, step, [lr] if single else lr,
-                                          Xf=Xf if has_fid else None, T=Tf if has_fid else None, out_col=self.fid_cols,
-                                          col_scale=fid_scale, term_sums=res_sums, col_sums=fid_sums, loss_rows=loss_rows,
-                                          losses=losses.reshape(1, -1) if single and losses is not None else losses,
-                                          params_token=params_token, **kw)
         has_fid = Xf is not None and Xf.shape[0] > 0
-        if not has_fid:
-            if fid_sums.numel():       # (a configuration with fidelity outputs but no fidelity points: classic path)
+        has_extras = self.coef is not None or self.point_w is not None
+        if balance is None and not has_extras:     # the plain request (first: the path every small problem's iteration takes)
+            request = None if not has_fid and fid_sums.numel() else self.request_points(Xf, Xr)
+            if request is None:                    # (fidelity outputs but no fidelity points, or two passes: classic path)
                 return False
-            return self.eng.loss_grad_adam_step(self.spec, res_scale, theta, Xr, Xr.shape[0], grad, m, v, step, lr,
-                                                term_sums=res_sums, loss_rows=loss_rows, losses=losses, params_token=params_token)
-        if Xf is Xr:                                       # train_newmethod.py:122-159: one point set for both terms
-            return self.eng.loss_grad_adam_step(self.spec, res_scale, theta, Xr, -1, grad, m, v, step, lr, T=Tf,
-                                                out_col=self.fid_cols, col_scale=fid_scale, term_sums=res_sums,
-                                                col_sums=fid_sums, loss_rows=loss_rows, losses=losses, params_token=params_token)
-        if not (self.merge_sets and Xf.shape[0] <= self.MERGE_MAX_FID):
+            fid = dict(T=Tf, out_col=self.fid_cols, col_scale=fid_scale, col_sums=fid_sums) if has_fid else {}
+            return self.eng.loss_grad_adam_step(self.spec, res_scale, theta, *request, grad, m, v, step, lr, term_sums=res_sums,
+                                                loss_rows=loss_rows, losses=losses, params_token=params_token, **fid)
+        # the other loop entries take runs only: one iteration is a run of one
+        single = not isinstance(lr, (list, tuple))
+        lrs = [lr] if single else lr
+        out = dict(term_sums=res_sums, col_sums=fid_sums, loss_rows=loss_rows, params_token=params_token,
+                   losses=losses.reshape(1, -1) if single and losses is not None else losses)
+        if balance is not None:
+            if has_extras or not has_fid:
+                return False
+            return self.eng.adam_loop_balanced(self.spec, res_scale, theta, Xr, grad, m, v, step, lrs, Xf, Tf, self.fid_cols,
+                                               fid_scale, **out, **balance)
+        # coefficients or point weights: the folded iteration above runs the entries that carry the constants and no weights,
+        # so these requests have a loop entry of their own, taken only when the trainer asks for it
+        if extras is None:
             return False
-        cat = self._merged(Xr, Xf)
-        return self.eng.loss_grad_adam_step(self.spec, res_scale, theta, cat, Xr.shape[0], grad, m, v, step, lr, T=Tf,
-                                            out_col=self.fid_cols, col_scale=fid_scale, term_sums=res_sums,
-                                            col_sums=fid_sums, loss_rows=loss_rows, losses=losses, params_token=params_token)
+        own = dict(coef=self.coef, coef_grad=self.coef_grad) if self.coef is not None else \
+            dict(point_w=self.point_w, fields=self.fields_out)
+        return self.eng.adam_loop_ext(self.spec, res_scale, theta, Xr, grad, m, v, step, lrs, Xf=Xf if has_fid else None,
+                                      T=Tf if has_fid else None, out_col=self.fid_cols, col_scale=fid_scale,
+                                      **out, **extras, **own)
 
     def _merged(self, Xr, Xf):
         """[collocation points ; fidelity points] in one matrix, refreshed whenever either source is a different
@@ -437,6 +462,44 @@ class HipEvaluator:
         if self.spec.nu != 0:     # the shifted fields, from the entry the loss runs on (no backward sweep)
             return self.eng.residual2_loss_grad(self.spec, None, theta, X, grad=None, fields=True)[1]
         return self.eng.residual_fields(self.spec, theta, X)
+
+
+@dataclass(frozen=True)
+class Options:
+    """What PINN.__init__ makes of its arguments and the configuration, resolved ONCE (an argument wins over its config key):
+    every refusal and every later use reads this record."""
+    residual: str
+    corrected: bool
+    nu: float                        # eddy_viscosity
+    coef_in: dict                    # coefficient values given, by name
+    coef_tr: tuple                   # names of the trainable coefficients
+    fixed_weights: bool              # residual_weights were given
+    sa_opt: Optional[dict]           # self_adaptive's options (None: off)
+    rad_imp: bool
+    fold_adam: bool
+    fold_extras: bool
+    balancing: Optional[str]
+    balance_every: int
+    balance_alpha: float
+    balance_ref: str
+    balance_groups: str
+    residual_batch: Optional[int]
+    resample: str
+    lbfgs_impl: str
+    custom_evaluator: bool
+    reducer_active: bool
+
+    @property
+    def has_coef(self) -> bool:
+        return bool(self.coef_in or self.coef_tr)
+
+    @property
+    def weighted(self) -> bool:
+        """Fixed or self-adaptive weights on the collocation points (rad_imp: the mini-batch's importance weights beside them)."""
+        return self.fixed_weights or self.sa_opt is not None
+
+
+ADAM, LBFGS = "adam", "lbfgs"      # PINN._stage: which stage the next loss evaluation belongs to
 
 
 class PINN:
@@ -467,14 +530,12 @@ class PINN:
         synchronisation — runs on every engine and with residual_batch and resample="rad"; with fold_extras and "sets" the
         iterations run as device-enqueued runs (Engine.adam_loop_balanced) where that entry serves the network
         (self.balance_why says why not).  The L-BFGS stage holds the weights frozen at their Adam-final values: they are
-        folded into the scales once when it starts.  Refused (balance_refusal): runtime coefficients, point weights of any
-        kind, eddy_viscosity, data parallelism, a custom evaluator, "terms" with fold_extras.
+        folded into the scales once when it starts.  What is refused: balance_refusal decides.
         fold_extras (or the config key adam_optimizer.fold_extras; off unless asked for): Adam iterations with runtime
         coefficients, fixed residual_weights or self_adaptive weights run as device-enqueued runs (Engine.adam_loop_ext: three
         launches per iteration, no Python in between; the coefficients, the multipliers and their Adam moments are updated on
-        the device) instead of the classic path.  Checkpoint iterations, mat_dump_iter, residual_batch, resample="rad",
-        dropout, data parallelism and eddy_viscosity keep the classic path (fold_extras_refusal says why;
-        self.fold_extras_why holds the answer); the L-BFGS stage is unchanged.
+        the device) instead of the classic path.  Checkpoint iterations and mat_dump_iter keep the classic path, and so does
+        whatever fold_extras_refusal names (self.fold_extras_why holds its answer); the L-BFGS stage is unchanged.
         residual_weights: fixed weights on the collocation points' squared residuals, (N_res,) or (n_w, N_res) with
         n_w = ResidualSpec.n_weighted_terms — a mask, a confidence map; set_residual_weights changes them later.  The
         normaliser stays the point count (res_scale = weight / N), not the sum of the weights.
@@ -485,81 +546,76 @@ class PINN:
         weights frozen.  rad_importance (or loss.rad_importance) with resample="rad": the mini-batch gets the importance weights
         mean(score) / score[idx], which makes its loss an unbiased estimate of the pool mean.  With any of the three the residual
         runs on Engine.residual_weighted_loss_grad, the fidelity term as a separate call, and Adam iterations take the classic
-        path.  Refused (weighted_refusal): data parallelism, eddy_viscosity, runtime coefficients, corrected, lbfgs_impl=
-        "device", a custom evaluator; self_adaptive with residual_batch or resample="rad".
+        path.  What is refused: weighted_refusal decides.
         coefficients (or the config key loss.coefficients), e.g. {"Cd": 0.01}: values of the residual's closure coefficients
         (ResidualSpec.coef_names: gamma_b of Navier_Stokes, Cd of physics_equation) in place of the compiled-in constants.
         trainable_coefficients (or loss.trainable_coefficients), e.g. ("Cd",): those are unknowns learned with the network —
         a small device tensor with Adam state of its own, updated with the same step count and schedule (learning rate:
         adam_optimizer.coefficient_learning_rate, default the network's).  With either set the residual runs on
         Engine.residual_coef_loss_grad, the fidelity term as a separate call, Adam iterations take the classic path, and the
-        L-BFGS stage holds the coefficients frozen at their Adam-final values.  Refused (coefficient_refusal): lbfgs_impl=
-        "device", data parallelism, eddy_viscosity, corrected, resample="rad", residual_fields(), unknown names.
+        L-BFGS stage holds the coefficients frozen at their Adam-final values.  What is refused: coefficient_refusal decides
+        (and device_lbfgs_refusal for lbfgs_impl="device", weighted_refusal and balance_refusal for their options).
         corrected (or the config key loss.corrected_radiation_stress; physics_equation only): train on the corrected
         radiation stress, E = rho g Hrms^2 / 8, hard-wired in the kernels (ResidualSpec.corrected) — every path that takes
         the spec follows: the merged launch, the folded Adam runs, residual_fields and resample="rad".
         eddy_viscosity (or the config key loss.eddy_viscosity; Navier_Stokes and physics_equation): nu of the lateral-mixing
         term -nu lap(U) in the momentum equations (ResidualSpec.nu), in the units of the network's inputs — normalised to
         [-1, 1] in the reference's pipeline.  The residual then runs on Engine.residual2_loss_grad, the fidelity term
-        as a separate call; Adam iterations take the classic path; residual_fields and resample="rad" see the shifted fields."""
+        as a separate call; Adam iterations take the classic path; residual_fields and resample="rad" see the shifted fields.
+        lbfgs_impl "device": what is refused, device_lbfgs_refusal decides."""
         cfg = config if isinstance(config, PinnConfig) else load_config(config)
         self.config, self.device = cfg, torch.device(device)
         self.reducer = reducer or Reducer()
         if lbfgs_impl not in ("flat", "torch", "device"):
             raise PinnError(f"lbfgs_impl={lbfgs_impl!r}: use 'flat', 'torch' or 'device'")
-        # runtime closure coefficients: parsed and refused before anything touches a device
         loss_cfg = cfg.raw.get("loss", {})
-        coef_in = dict(coefficients) if coefficients else dict(loss_cfg.get("coefficients") or {})
-        coef_tr = tuple(trainable_coefficients) if trainable_coefficients else tuple(loss_cfg.get("trainable_coefficients") or ())
-        nu0 = float(eddy_viscosity) if eddy_viscosity else float(loss_cfg.get("eddy_viscosity", 0.0))
-        why = coefficient_refusal(residual or cfg.default_residual(), coef_in, coef_tr,
-                                  bool(corrected) or bool(loss_cfg.get("corrected_radiation_stress", False)), nu0,
-                                  self.reducer.active, resample, evaluator is not None)
-        if why:
-            raise PinnError(why)
-        # point weights on the residual: parsed and refused before anything touches a device
-        if self_adaptive is None or self_adaptive is False:
-            sa_opt = None if self_adaptive is False else cfg.self_adaptive
-        else:
-            sa_opt = self_adaptive_options(self_adaptive)
-        rad_imp = cfg.rad_importance if rad_importance is None else bool(rad_importance)
-        why = weighted_refusal(residual_weights is not None, sa_opt is not None, rad_imp, self.reducer.active, nu0,
-                               bool(coef_in or coef_tr), bool(corrected) or bool(loss_cfg.get("corrected_radiation_stress", False)),
-                               lbfgs_impl, evaluator is not None, residual_batch, resample)
-        if why:
-            raise PinnError(why)
-        # gradient-statistics loss balancing: parsed and refused before anything touches a device
-        self.loss_balancing = cfg.loss_balancing if loss_balancing is None else (None if loss_balancing == "none" else loss_balancing)
-        self.balance_every = cfg.balance_every if balance_every is None else balance_every
-        self.balance_alpha = cfg.balance_alpha if balance_alpha is None else balance_alpha
-        self.balance_ref = cfg.balance_ref if balance_ref is None else balance_ref
-        self.balance_groups = cfg.balance_groups if balance_groups is None else balance_groups
-        why = balance_refusal(self.loss_balancing, self.balance_groups, self.balance_every, self.balance_alpha, self.balance_ref,
-                              bool(fold_extras) or cfg.fold_extras, bool(coef_in or coef_tr),
-                              residual_weights is not None or sa_opt is not None, rad_imp, nu0, self.reducer.active, evaluator is not None)
-        if why:
-            raise PinnError(why)
-        if self.loss_balancing is not None and (fidelity_input is None or residual_input is None or
-                                                len(fidelity_input) == 0 or len(residual_input) == 0):
-            raise PinnError("loss balancing weighs the fidelity set against the collocation set: it needs points in both")
-        if lbfgs_impl == "device":       # decided before anything touches a device
-            nu = float(eddy_viscosity) if eddy_viscosity else float(cfg.raw.get("loss", {}).get("eddy_viscosity", 0.0))
-            why = device_lbfgs_refusal(self.reducer.active, residual_batch, nu, evaluator is not None,
-                                       cfg.lbfgs["line_search_fn"], cfg.dropout_rate, bool(coef_in or coef_tr))
+
+        def given(arg, from_cfg):
+            return from_cfg if arg is None else arg
+        o = self.options = Options(
+            residual=residual or cfg.default_residual(),
+            corrected=bool(corrected) or bool(loss_cfg.get("corrected_radiation_stress", False)),
+            nu=float(eddy_viscosity) if eddy_viscosity else float(loss_cfg.get("eddy_viscosity", 0.0)),
+            coef_in=dict(coefficients) if coefficients else dict(loss_cfg.get("coefficients") or {}),
+            coef_tr=tuple(trainable_coefficients) if trainable_coefficients else tuple(loss_cfg.get("trainable_coefficients") or ()),
+            fixed_weights=residual_weights is not None,
+            sa_opt=cfg.self_adaptive if self_adaptive is None else None if self_adaptive is False else self_adaptive_options(self_adaptive),
+            rad_imp=bool(given(rad_importance, cfg.rad_importance)), fold_adam=bool(fold_adam),
+            fold_extras=bool(fold_extras) or cfg.fold_extras,
+            balancing=cfg.loss_balancing if loss_balancing is None else (None if loss_balancing == "none" else loss_balancing),
+            balance_every=given(balance_every, cfg.balance_every), balance_alpha=given(balance_alpha, cfg.balance_alpha),
+            balance_ref=given(balance_ref, cfg.balance_ref), balance_groups=given(balance_groups, cfg.balance_groups),
+            residual_batch=residual_batch, resample=resample, lbfgs_impl=lbfgs_impl, custom_evaluator=evaluator is not None,
+            reducer_active=self.reducer.active)
+
+        def refuse(why):
             if why:
                 raise PinnError(why)
-        self.fold_adam, self._adam_folded, self._folded_iters, self._run_losses = bool(fold_adam), False, 0, None
-        self.fold_extras = bool(fold_extras) or cfg.fold_extras
-        self.fold_extras_why = fold_extras_refusal(self.fold_extras, bool(coef_in or coef_tr), residual_weights is not None or sa_opt is not None,
-                                                   rad_imp, residual_batch, resample, cfg.dropout_rate, self.reducer.active, nu0,
-                                                   evaluator is not None, bool(fold_adam))
+        # every refusal is pure host logic on the record, decided before anything touches a device
+        refuse(coefficient_refusal(o.residual, o.coef_in, o.coef_tr, o.corrected, o.nu, o.reducer_active, o.resample,
+                                   o.custom_evaluator))
+        refuse(weighted_refusal(o.fixed_weights, o.sa_opt is not None, o.rad_imp, o.reducer_active, o.nu, o.has_coef, o.corrected,
+                                o.lbfgs_impl, o.custom_evaluator, o.residual_batch, o.resample))
+        refuse(balance_refusal(o.balancing, o.balance_groups, o.balance_every, o.balance_alpha, o.balance_ref, o.fold_extras,
+                               o.has_coef, o.weighted, o.rad_imp, o.nu, o.reducer_active, o.custom_evaluator))
+        if o.balancing is not None and (fidelity_input is None or residual_input is None or
+                                        len(fidelity_input) == 0 or len(residual_input) == 0):
+            raise PinnError("loss balancing weighs the fidelity set against the collocation set: it needs points in both")
+        if o.lbfgs_impl == "device":
+            refuse(device_lbfgs_refusal(o.reducer_active, o.residual_batch, o.nu, o.custom_evaluator, cfg.lbfgs["line_search_fn"],
+                                        cfg.dropout_rate, o.has_coef))
+        self.loss_balancing, self.balance_every, self.balance_alpha = o.balancing, o.balance_every, o.balance_alpha
+        self.balance_ref, self.balance_groups = o.balance_ref, o.balance_groups
+        self.fold_adam, self._adam_folded, self._folded_iters, self._run_losses = o.fold_adam, False, 0, None
+        self.fold_extras = o.fold_extras
+        self.fold_extras_why = fold_extras_refusal(o.fold_extras, o.has_coef, o.weighted, o.rad_imp, o.residual_batch, o.resample,
+                                                   cfg.dropout_rate, o.reducer_active, o.nu, o.custom_evaluator, o.fold_adam)
         # (balanced iterations: where fold_extras is on, why they keep the classic path all the same — None: they run as
         # device-enqueued runs wherever the engine serves the request)
         self.balance_why = None
-        if self.loss_balancing is not None:
-            self.balance_why = ("fold_extras is off" if not self.fold_extras else
-                                balance_fold_refusal(residual_batch, resample, cfg.dropout_rate, bool(fold_adam)))
-        self._run_coef_log = None
+        if o.balancing is not None:
+            self.balance_why = ("fold_extras is off" if not o.fold_extras else
+                                balance_fold_refusal(o.residual_batch, o.resample, cfg.dropout_rate, o.fold_adam))
         self._fold_refused = None   # key of the (evaluator, point sets) whose folded request the engine has refused
         self.layers = cfg.layers                                           # train.py:52-56
         self.dnn = dnn if dnn is not None else DNN(cfg.layers, cfg.dropout_rate, cfg.init_type,
@@ -569,17 +625,11 @@ class PINN:
         self.reducer.broadcast_(self.theta)                                # replicas start identical
         P = self.theta.numel()
 
-        residual = residual or cfg.default_residual()
-        self.corrected = bool(corrected) or bool(cfg.raw.get("loss", {}).get("corrected_radiation_stress", False))
-        self.eddy_viscosity = float(eddy_viscosity) if eddy_viscosity else float(cfg.raw.get("loss", {}).get("eddy_viscosity", 0.0))
-        self.spec = ResidualSpec.from_names(residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs,
-                                            corrected=self.corrected, nu=self.eddy_viscosity)   # (PinnError on any other residual)
+        self.corrected, self.eddy_viscosity = o.corrected, o.nu
+        self.spec = ResidualSpec.from_names(o.residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs,
+                                            corrected=o.corrected, nu=o.nu)   # (PinnError on any other residual)
         # i-th fidelity output is compared with output column i (train.py:137-138, train_newmethod.py:129-131)
         self.fid_cols = list(range(len(cfg.fidelity_outputs)))
-        if cfg.variant == "newmethod":
-            fid_w = [1.0] * len(self.fid_cols)                             # F.mse_loss, unweighted sum
-        else:
-            fid_w = [cfg.output_weight(k) for k in cfg.fidelity_outputs]   # train.py:94-95,140
         self.weight_fidelity, self.weight_residual = cfg.weight_fid, cfg.weight_res
 
         Xf, Tf, Xr = (_as_f32(a, self.device) for a in (fidelity_input, fidelity_true, residual_input))
@@ -593,50 +643,36 @@ class PINN:
         self.Tf = self.reducer.shard(Tf)
         nf, nt = len(self.fid_cols), self.spec.n_terms
         dev = self.device
-        self._fid_unit = torch.tensor(fid_w, dtype=torch.float32, device=dev) / max(self.n_fid, 1)
-        if residual == "continuity_only":
-            xcol = cfg.grad_cols[self.spec.dir_of[0]]
-            cnt = (self.Xr[:, xcol] < self.spec.threshold).sum().to(torch.float32).reshape(1)
-            self.reducer.allreduce_sum_(cnt)                               # global count of x < 25.5
-            self._res_unit = torch.cat([torch.tensor([1.0 / self.n_res], device=dev), 1.0 / cnt,
-                                        torch.zeros(1, device=dev)])
-        else:
-            self._res_unit = torch.full((nt,), 1.0 / max(self.n_res, 1), dtype=torch.float32, device=dev)
-        self._fid_scale = (self.weight_fidelity * self._fid_unit).contiguous()
-        self._res_scale = (self.weight_residual * self._res_unit).contiguous()
         self.buf = torch.zeros(P + nf + nt, dtype=torch.float32, device=dev)   # ONE all-reduce per closure
-        self._loss_mat = None      # (3, nf + nt): [fidelity, residual, total] = _loss_mat @ [fid sums | res sums]
         self.grad = self.buf[:P]
         self._fid_sums, self._res_sums = self.buf[P:P + nf], self.buf[P + nf:]
         self.evaluator = evaluator or HipEvaluator(cfg.layers, cfg.init_type, cfg.grad_cols, self.spec,
                                                    self.fid_cols, dev, engine, precision, cfg.dropout_rate,
                                                    activation=self.dnn.activation_id)
         # the coefficients: every one of the residual's, given or default, in ResidualSpec.coef_names order
-        self.coef_names: Tuple[str, ...] = self.spec.coef_names if (coef_in or coef_tr) else ()
-        self.trainable_coefficients = tuple(n for n in self.coef_names if n in coef_tr)
+        self.coef_names: Tuple[str, ...] = self.spec.coef_names if o.has_coef else ()
+        self.trainable_coefficients = tuple(n for n in self.coef_names if n in o.coef_tr)
         self._coef = self._coef_grad = self._coef_m = self._coef_v = self._coef_mask = None
         self._coef_history: List[tuple] = []
         if self.coef_names:
-            vals = [float(coef_in.get(n, d)) for n, d in zip(self.coef_names, self.spec.coef_defaults)]
+            vals = [float(o.coef_in.get(n, d)) for n, d in zip(self.coef_names, self.spec.coef_defaults)]
             self._coef = torch.tensor(vals, dtype=torch.float32, device=dev)
             self.evaluator.coef = self._coef
             if self.trainable_coefficients:
                 self._coef_grad = torch.zeros_like(self._coef)
-                self._coef_mask = torch.tensor([1.0 if n in coef_tr else 0.0 for n in self.coef_names], dtype=torch.float32, device=dev)
-                self.evaluator.coef_grad = self._coef_grad
+                self._coef_mask = torch.tensor([1.0 if n in o.coef_tr else 0.0 for n in self.coef_names], dtype=torch.float32, device=dev)
 
         # point weights on the residual: fixed (_w_fixed), self-adaptive (_lam -> _w_fixed = m(lambda) every pass) and / or the
-        # RAD mini-batch's importance weights (formed per draw in loss_func)
-        self.self_adaptive, self.rad_importance = sa_opt, rad_imp
+        # RAD mini-batch's importance weights (formed per draw)
+        self.self_adaptive, self.rad_importance = o.sa_opt, o.rad_imp
         self._w_fixed = self._lam = self._lam_m = self._lam_v = self._sa_fields = None
-        self._sa_frozen = False
         self._last_idx = None
         if residual_weights is not None:
             self.set_residual_weights(residual_weights)
-        if sa_opt is not None:
-            rows = self.spec.n_weighted_terms if sa_opt["per_term"] else 1
-            self._lam = torch.full((rows, self.n_res), sa_opt["init"], dtype=torch.float32, device=dev)
-            self._w_fixed = sa_weights(self._lam, sa_opt["mask"]).contiguous()
+        if o.sa_opt is not None:
+            rows = self.spec.n_weighted_terms if o.sa_opt["per_term"] else 1
+            self._lam = torch.full((rows, self.n_res), o.sa_opt["init"], dtype=torch.float32, device=dev)
+            self._w_fixed = sa_weights(self._lam, o.sa_opt["mask"]).contiguous()
             self._sa_fields = torch.zeros(self.spec.n_fields, self.n_res, dtype=torch.float32, device=dev)
             self.evaluator.point_w = self._w_fixed
 
@@ -645,11 +681,9 @@ class PINN:
         self.residual_batch = residual_batch
         self._gen = None
         if residual_batch is not None:
-            if residual == "continuity_only":
+            if o.residual == "continuity_only":
                 raise PinnError("residual_batch is not supported with continuity_only's data-dependent mean")
             self._gen = torch.Generator(device=dev).manual_seed(seed + self.reducer.rank)
-            self._res_unit = torch.full((nt,), 1.0 / (residual_batch * self.reducer.world), dtype=torch.float32, device=dev)
-            self._res_scale = (self.weight_residual * self._res_unit).contiguous()
         # resample = "rad": residual-based adaptive distribution (Wu et al. 2023) — the mini-batch is drawn with
         # probability proportional to eps^k / mean(eps^k) + c over this rank's pool, eps the per-point residual
         # magnitude (Engine.residual_fields), re-scored every rad_every iterations.  A biased sampler by design: no
@@ -657,7 +691,7 @@ class PINN:
         if resample not in ("uniform", "rad"):
             raise PinnError(f"resample={resample!r}: use 'uniform' or 'rad'")
         if resample == "rad":
-            if residual == "continuity_only":
+            if o.residual == "continuity_only":
                 raise PinnError("resample='rad' is not supported with continuity_only's data-dependent mean")
             if residual_batch is None:
                 raise PinnError("resample='rad' draws a mini-batch of the collocation pool: it needs residual_batch")
@@ -665,6 +699,14 @@ class PINN:
                 raise PinnError(f"rad_every={rad_every} must be >= 1, rad_k={rad_k} and rad_c={rad_c} must be >= 0")
         self.resample, self.rad_every, self.rad_k, self.rad_c = resample, int(rad_every), float(rad_k), float(rad_c)
         self._rad_score, self._rad_cdf, self._rad_at = None, None, None
+        # the loss arithmetic: the residual's normaliser is the global point count, or the mini-batches' size over all ranks
+        anchor = None
+        if o.residual == "continuity_only":
+            anchor = anchor_count(cfg, self.spec, self.Xr)
+            self.reducer.allreduce_sum_(anchor)                            # global count of x < 25.5
+        self._fid_unit, self._res_unit, self._fid_scale, self._res_scale, self._loss_mat = loss_arithmetic(
+            cfg, self.spec, nf, self.n_fid, self.n_res if residual_batch is None else residual_batch * self.reducer.world, dev, anchor)
+        self._loss_vec = torch.zeros(3, dtype=torch.float32, device=dev)       # the three losses of an iteration that is not logged
         self.mat_dump_iter, self.mat_dump_path = mat_dump_iter, mat_dump_path
         self.lbfgs_impl = lbfgs_impl     # "flat": lbfgs.FlatLBFGS (batched recursion); "torch": torch.optim.LBFGS;
                                          # "device": lbfgs.DeviceLBFGS (whole runs of evaluations decided on the device)
@@ -674,28 +716,36 @@ class PINN:
         self.log_dir, self.log_every, self.checkpoint_every = log_dir, max(int(log_every), 1), checkpoint_every
         self._log_fh = None
         self._history: List[tuple] = []
-        # loss balancing: the group weights, the (G, P) buffer of the per-group gradients and the run's log of the weights
-        self._bal_lam = self._bal_buf = self._bal_pair = self._run_lam_log = None
+        # loss balancing: the group weights and the (G, P) buffer of the per-group gradients
+        self._bal_lam = self._bal_buf = self._bal_pair = None
         self._bal_frozen = False
         self.balance_names: Tuple[str, ...] = ()
         self._weight_history: List[tuple] = []
-        if self.loss_balancing is not None:
+        if o.balancing is not None:
             nw = self.spec.n_weighted_terms
-            self.balance_names = ("residual", "fidelity") if self.balance_groups == "sets" else \
+            self.balance_names = ("residual", "fidelity") if o.balance_groups == "sets" else \
                 tuple(f"residual_term_{t}" for t in range(nw)) + ("fidelity",)
             G = len(self.balance_names)
-            self._bal_ref = 0 if self.balance_ref == "residual" else G - 1
+            self._bal_ref = 0 if o.balance_ref == "residual" else G - 1
             self._bal_lam = torch.ones(G, dtype=torch.float32, device=dev)
             self._bal_buf = torch.zeros(G, P, dtype=torch.float32, device=dev)
-            if self.balance_groups == "terms":
+            if o.balance_groups == "terms":
                 self._bal_pair = torch.ones(2, dtype=torch.float32, device=dev)      # [1, lam_fidelity] between updates
                 self._bal_onehot = torch.eye(nt, dtype=torch.float32, device=dev)[:nw].contiguous()
                 self._bal_term_scale = torch.zeros(nt, dtype=torch.float32, device=dev)
-        self._ring = torch.zeros(max(int(log_flush_every), 1), 3 + len(self.coef_names) + len(self.balance_names),
-                                 dtype=torch.float32, device=dev)
+        # the log's extra columns, beside the three losses: the coefficients or the balanced groups' weights (never both:
+        # balance_refusal) — their names in log.txt's header, the device tensor that holds their current values, the history
+        # their logged values go to, and (allocated at the first run) the rows a device-enqueued run logs them in
+        self._extra_names = self.coef_names or tuple(f"weight_{n}" for n in self.balance_names)
+        self._extra_vals = self._coef if self.coef_names else self._bal_lam
+        self._extra_history = self._coef_history if self.coef_names else self._weight_history
+        self._run_extras = None
+        self._ring = torch.zeros(max(int(log_flush_every), 1), 3 + len(self._extra_names), dtype=torch.float32, device=dev)
         self._ring_iters: List[int] = []
         self.last = None
+        self._stage = ADAM          # set by adam_step / _adam_run and closure / train_lbfgs_device; a bare loss_func() keeps the last
         self.init_optimizers()
+        self._bind()
 
     # ---- optimisers (train.py:100-125) ----------------------------------------------------------
     def init_optimizers(self):
@@ -740,16 +790,14 @@ class PINN:
         self_adaptive, whose weights are m(lambda)."""
         if self._lam is not None:
             raise PinnError("set_residual_weights: the weights are the self-adaptive ones, m(lambda)")
-        if weights is None:
-            self._w_fixed = None
-            self.evaluator.point_w = None
-            return
-        w = _as_f32(weights, self.device)
-        w = w.reshape(1, -1) if w.dim() == 1 else w
-        if w.dim() != 2 or w.shape[1] != self.n_res or w.shape[0] not in (1, self.spec.n_weighted_terms):
-            raise PinnError(f"residual_weights must be ({self.n_res},) or ({self.spec.n_weighted_terms}, {self.n_res}), got {tuple(w.shape)}")
-        self._w_fixed = w.contiguous()
-        self.evaluator.point_w = self._w_fixed
+        w = None
+        if weights is not None:
+            w = _as_f32(weights, self.device)
+            w = w.reshape(1, -1) if w.dim() == 1 else w
+            if w.dim() != 2 or w.shape[1] != self.n_res or w.shape[0] not in (1, self.spec.n_weighted_terms):
+                raise PinnError(f"residual_weights must be ({self.n_res},) or ({self.spec.n_weighted_terms}, {self.n_res}), got {tuple(w.shape)}")
+            w = w.contiguous()
+        self._w_fixed = self.evaluator.point_w = w
 
     def residual_weights(self) -> Optional[torch.Tensor]:
         """The weights on the collocation points in use, (w_rows, N_res): the fixed ones, or m(lambda) of the self-adaptive
@@ -765,77 +813,78 @@ class PINN:
         return dict(zip(self.coef_names, (float(x) for x in self._coef.cpu().tolist())))
 
     # ---- loss (train.py:128-181) ----------------------------------------------------------------------
-    def loss_func(self, _adam=None) -> torch.Tensor:
-        """Total loss (0-dim device tensor); self.grad holds d loss / d theta afterwards.  `_adam` (adam_step only):
-        (exp_avg, exp_avg_sq, step, lr) — the evaluator may then fold the Adam update into the pass's last kernel
-        (`self._adam_folded` says whether it did)."""
+    def _bind(self, idx: Optional[torch.Tensor] = None):
+        """Tell the evaluator what the next pass carries — after construction and set_residual_weights the ONE place that
+        writes evaluator.coef_grad, point_w and fields_out.  By the stage (self._stage): the Adam stage asks for the
+        coefficients' gradient and the self-adaptive pass's fields, the L-BFGS stage holds coefficients and multipliers frozen
+        at their Adam-final values and asks for neither.  idx: the mini-batch's indices into the collocation pool, where
+        there is one — its weights are the importance weights x the fixed ones at those points."""
+        ev = self.evaluator
+        if hasattr(ev, "training"):
+            ev.training = self.dnn.training          # dropout follows the module's mode (train.py:186)
+        if self._coef is not None:
+            ev.coef_grad = self._coef_grad if self._stage == ADAM else None      # (None too when nothing is trainable)
+        if self._lam is not None:
+            ev.fields_out = self._sa_fields if self._stage == ADAM else None
+        if idx is not None and (self.rad_importance or self._w_fixed is not None):
+            w = rad_importance_weights(self._rad_score, idx) if self.rad_importance else None
+            if self._w_fixed is not None:
+                wf = self._w_fixed.index_select(1, idx)
+                w = wf if w is None else wf * w
+            ev.point_w = w.contiguous()
+
+    def _draw_batch(self) -> torch.Tensor:
+        """The next mini-batch's indices into this rank's collocation pool: uniform, or by the RAD score (re-scored every
+        rad_every iterations)."""
+        if self.resample == "rad":
+            if self._rad_score is None or self.iter - self._rad_at >= self.rad_every:
+                self._rad_score = rad_score(self.evaluator.residual_fields(self.theta, self.Xr), self.rad_k, self.rad_c)
+                self._rad_cdf = rad_cdf(self._rad_score)
+                self._rad_at = self.iter
+            u = torch.rand(self.residual_batch, device=self.device, generator=self._gen, dtype=torch.float64)
+            self._last_idx = rad_indices(self._rad_score, u, self._rad_cdf)
+        else:
+            self._last_idx = torch.randint(0, self.Xr.shape[0], (self.residual_batch,), device=self.device, generator=self._gen)
+        return self._last_idx
+
+    def loss_func(self, _fold: bool = False) -> torch.Tensor:
+        """Total loss (0-dim device tensor); self.grad holds d loss / d theta afterwards.  `_fold` (adam_step only): the
+        evaluator may fold the Adam update into the pass's last kernel (`self._adam_folded` says whether it did)."""
         self.theta = self.dnn.flat_params()
         if self.mat_dump_iter is not None and self.iter == self.mat_dump_iter:
             self.dump_predictions(self.mat_dump_path)                      # train_newmethod.py:141-153
-        if hasattr(self.evaluator, "training"):
-            self.evaluator.training = self.dnn.training          # dropout follows the module's mode (train.py:186)
-        Xr = self.Xr
+        Xr, idx = self.Xr, None
         if self.residual_batch is not None:
-            if self.resample == "rad":
-                if self._rad_score is None or self.iter - self._rad_at >= self.rad_every:
-                    self._rad_score = rad_score(self.evaluator.residual_fields(self.theta, self.Xr), self.rad_k, self.rad_c)
-                    self._rad_cdf = rad_cdf(self._rad_score)
-                    self._rad_at = self.iter
-                u = torch.rand(self.residual_batch, device=self.device, generator=self._gen, dtype=torch.float64)
-                idx = rad_indices(self._rad_score, u, self._rad_cdf)
-            else:
-                idx = torch.randint(0, self.Xr.shape[0], (self.residual_batch,), device=self.device, generator=self._gen)
+            idx = self._draw_batch()
             Xr = self.Xr.index_select(0, idx)
-            self._last_idx = idx
-            if self.rad_importance or self._w_fixed is not None:      # the mini-batch's weights: importance x the fixed ones
-                w = rad_importance_weights(self._rad_score, idx) if self.rad_importance else None
-                if self._w_fixed is not None:
-                    wf = self._w_fixed.index_select(1, idx)
-                    w = wf if w is None else wf * w
-                self.evaluator.point_w = w.contiguous()
-        elif self._lam is not None:
-            # w = m(lambda) of this pass; the L-BFGS stage (closure) holds it and asks for no fields
+        elif self._lam is not None:      # w = m(lambda) of this pass (a device-enqueued run rewrites it itself: Engine.adam_loop_ext)
             self._w_fixed.copy_(sa_weights(self._lam, self.self_adaptive["mask"]))
-            self.evaluator.fields_out = None if self._sa_frozen else self._sa_fields
-        self._ensure_loss_mat()
-        nxt = self.iter + 1
-        logged = nxt % self.log_every == 0 or nxt % 1000 == 0
+        self._bind(idx)
+        logged = self._logged(self.iter + 1)
         # loss balancing is the Adam stage's: the L-BFGS stage (closure) has folded the weights into the scales
         balancing = self.loss_balancing is not None and not self._bal_frozen
-        if logged and self._bal_lam is not None and not balancing:
-            self._ring[len(self._ring_iters)][3:].copy_(self._bal_lam)
         # the three losses of a logged iteration are computed straight into the device-side ring
-        vec = self._ring[len(self._ring_iters)][:3] if logged else self._loss_vec
-        if logged and self._coef is not None:      # the coefficients this evaluation ran with, beside its losses
-            self._ring[len(self._ring_iters)][3:].copy_(self._coef)
-        self._adam_folded = _adam is not None and self.evaluator.adam_iteration(
-            self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad, self._fid_sums, self._res_sums,
-            *_adam, loss_rows=self._loss_mat, losses=vec, params_token=self.dnn.write_token(self.theta),
-            **({"extras": self._fold_extras_kw(1)} if self._has_extras() else {}),
-            **({"balance": self._balance_kw(1)} if balancing else {}))
-        if balancing and self._adam_folded and logged:      # the weights this iteration stepped with, beside its losses
-            self._ring[len(self._ring_iters)][3:].copy_(self._run_lam_log[0])
+        row = self._ring[len(self._ring_iters)] if logged else None
+        vec = row[:3] if logged else self._loss_vec
+        if logged and self._extra_vals is not None and not balancing:
+            row[3:].copy_(self._extra_vals)      # the values this evaluation RUNS with: a folded iteration moves the coefficients
+        self._adam_folded = _fold and self._folded_request(Xr, vec)
         if not self._adam_folded:
             self.buf.zero_()
             if balancing:
                 self._balanced_pass(Xr)
-                if logged:
-                    self._ring[len(self._ring_iters)][3:].copy_(self._bal_lam)
             else:
                 self.evaluator(self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad,
                                self._fid_sums, self._res_sums)
             self.reducer.allreduce_sum_(self.buf)
             torch.mv(self._loss_mat, self.buf[self.theta.numel():], out=vec)                  # one small mat-vec: the three losses
         self.iter += 1                                                                        # train.py:160
-        fidelity_loss, residual_loss, loss = vec[0], vec[1], vec[2]
-        self.last = (fidelity_loss, residual_loss, loss)
-        if logged:
-            self._ring_iters.append(self.iter)
-            if len(self._ring_iters) == self._ring.shape[0]:
-                self.flush_log()
+        self.last = (vec[0], vec[1], vec[2])
+        if logged:      # (balancing: the weights this iteration stepped with — they are updated before they are used)
+            self._to_ring(self.iter, None, (self._run_extras[0] if self._adam_folded else self._bal_lam) if balancing else None)
         if self._checkpoint_due(self.iter):
             self.save_checkpoint(f"model_{self.iter}.pth")                                    # train.py:175-179
-        return loss
+        return self.last[2]
 
     def _balanced_pass(self, Xr):
         """One balanced evaluation on the classic path: the groups' gradients into the rows of the (G, P) buffer,
@@ -869,13 +918,6 @@ class PINN:
                         self._fid_sums, self._res_sums)
         eng.balance_update(pair, self._bal_pair, None, out=self.grad)
 
-    def _balance_kw(self, k: int) -> dict:
-        """What Engine.adam_loop_balanced needs beside the evaluator's own tensors for the next k iterations."""
-        if self._run_lam_log is None or self._run_lam_log.shape[0] < k:
-            self._run_lam_log = torch.zeros(max(k, self.MAX_RUN), 2, dtype=torch.float32, device=self.device)
-        return {"lam": self._bal_lam, "mode": self.loss_balancing, "every": self.balance_every, "ref": self._bal_ref,
-                "alpha": self.balance_alpha, "lam_log": self._run_lam_log[:k]}
-
     def loss_weights(self) -> Dict[str, float]:
         """The balanced groups' weights by name (one synchronisation): "residual" and "fidelity", or "residual_term_<t>" and
         "fidelity"; {} without loss_balancing.  They multiply the hand-set weights."""
@@ -895,7 +937,6 @@ class PINN:
         the total's row of the loss matrix) once, on the device; from then on every evaluation is the plain weighted loss."""
         if self.loss_balancing is None or self._bal_frozen:
             return
-        self._ensure_loss_mat()
         nw, nf = self._bal_lam.numel() - 1, self._fid_sums.numel()
         self._fid_scale = (self._fid_scale * self._bal_lam[nw]).contiguous()
         res = self._res_scale.clone()
@@ -908,16 +949,6 @@ class PINN:
         self._loss_mat[2, nf:] = self._res_scale
         self._bal_frozen = True
 
-    def _ensure_loss_mat(self):
-        if self._loss_mat is None:
-            nf = self._fid_sums.numel()
-            m = torch.zeros(3, self.buf.numel() - self.theta.numel(), dtype=torch.float32, device=self.device)
-            m[0, :nf] = self._fid_unit
-            m[1, nf:] = self._res_unit
-            m[2] = self.weight_fidelity * m[0] + self.weight_residual * m[1]                  # train.py:157
-            self._loss_mat = m.contiguous()
-            self._loss_vec = torch.zeros(3, dtype=torch.float32, device=self.device)
-
     def _checkpoint_due(self, it: int) -> bool:
         if not self.checkpoint_every:
             return False
@@ -925,6 +956,42 @@ class PINN:
         if self.config.variant == "newmethod" and self.checkpoint_every == 1000:
             every = 10000 if it <= 45000 else 1000                                            # train_newmethod.py:181-188
         return it % every == 0
+
+    # ---- the log ring ---------------------------------------------------------------------------------
+    def _logged(self, it: int) -> bool:
+        """Iteration `it` (1-based) goes to the log."""
+        return it % self.log_every == 0 or it % 1000 == 0
+
+    def _to_ring(self, first: int, losses: Optional[torch.Tensor], extras: Optional[torch.Tensor]):
+        """The logged ones among iterations first .. first + k - 1 into the log ring, flushed whenever it is full.
+        losses: their (k, 3) loss rows; None: ONE logged iteration whose losses loss_func has computed into the next free row itself.
+        extras, the columns beside the losses: (k, E), a row per iteration (what a device-enqueued run logged); (E,), the
+        current values, the same for every row; None: there are none, or they are in the row already."""
+        iters, size = self._ring_iters, self._ring.shape[0]
+        if losses is None:       # (every logged loss_func call comes through here: kept short)
+            if extras is not None:
+                self._ring[len(iters), 3:].copy_(extras)
+            iters.append(first)
+            if len(iters) == size:
+                self.flush_log()
+            return
+        picks = [i for i in range(losses.shape[0]) if self._logged(first + i)]
+        while picks:
+            r0 = len(self._ring_iters)
+            now, picks = picks[:size - r0], picks[size - r0:]
+            one_copy = now[-1] - now[0] + 1 == len(now)
+            for cols, src in ((slice(0, 3), losses), (slice(3, None), extras)):
+                if src is None:
+                    continue
+                dst = self._ring[r0:r0 + len(now), cols]
+                if src.dim() == 1 or one_copy:       # the same values for every row / consecutive iterations: one copy
+                    dst.copy_(src if src.dim() == 1 else src[now[0]:now[-1] + 1])
+                else:
+                    for j, i in enumerate(now):
+                        dst[j].copy_(src[i])
+            self._ring_iters.extend(first + i for i in now)
+            if len(self._ring_iters) == size:
+                self.flush_log()
 
     @property
     def history(self) -> List[tuple]:
@@ -948,13 +1015,11 @@ class PINN:
         if self._log_fh is not None:
             self._log_fh.flush()
 
-    def _log(self, it: int, fid: float, res: float, tot: float, coefs: Sequence[float] = ()):
+    def _log(self, it: int, fid: float, res: float, tot: float, extras: Sequence[float] = ()):
         self._history.append((it, fid, res, tot))
-        if coefs and self.balance_names:      # (never both: balancing refuses coefficients) the groups' weights
-            self._weight_history.append((it,) + tuple(coefs))
-        elif coefs:
-            self._coef_history.append((it,) + tuple(coefs))
-        tail = "".join(f", {c:.6e}" for c in coefs)      # the coefficients' values, appended to the log line
+        if extras:
+            self._extra_history.append((it,) + tuple(extras))
+        tail = "".join(f", {c:.6e}" for c in extras)      # the extra columns' values, appended to the log line
         if it % 1000 == 0 and self.reducer.rank == 0:
             print(f"Epoch {it}, Fidelity Loss: {fid:.5e}, Residual Loss: {res:.5e}, Total Loss: {tot:.5e}")
         if self.log_dir is None or self.reducer.rank != 0:
@@ -965,8 +1030,8 @@ class PINN:
             new = not os.path.exists(path) or os.stat(path).st_size == 0
             self._log_fh = open(path, "a")
             if new:
-                self._log_fh.write("Epoch, Fidelity Loss, Residual Loss, Total Loss" + "".join(f", {n}" for n in self.coef_names) +
-                                   "".join(f", weight_{n}" for n in self.balance_names) + "\n")   # train.py:167
+                self._log_fh.write("Epoch, Fidelity Loss, Residual Loss, Total Loss" +
+                                   "".join(f", {n}" for n in self._extra_names) + "\n")           # train.py:167
         self._log_fh.write(f"{it}, {fid:.5e}, {res:.5e}, {tot:.5e}{tail}\n")                  # train.py:170
 
     def dump_predictions(self, path: str):
@@ -1013,12 +1078,10 @@ class PINN:
             # start of loss_func either way); with extras the .mat also carries the coefficients / residual_weights, and the
             # iteration that hands them over is kept the one that has always written that file.  _foldable_run cuts runs here.
             fold = False
-        if self._coef is not None:
-            self.evaluator.coef_grad = self._coef_grad      # (None when nothing is trainable: values only)
-        self._sa_frozen = False
+        self._stage = ADAM
         if self._bal_frozen:
             raise PinnError("loss balancing: the weights were frozen for the L-BFGS stage; Adam iterations after it are not balanced")
-        loss = self.loss_func((self._adam_m, self._adam_v, self._adam_step + 1, self.current_lr()) if fold else None)
+        loss = self.loss_func(fold)
         self._adam_step += 1
         if fold and not self._adam_folded:
             self._fold_refused = self._fold_key()      # remembered: no second refused C call per iteration from now on
@@ -1055,30 +1118,43 @@ class PINN:
         return (self.fold_adam and not self.reducer.active and hasattr(self.evaluator, "adam_iteration")
                 and self._fold_refused != self._fold_key())
 
-    def _weighted(self) -> bool:
-        return self._w_fixed is not None or self.rad_importance
-
     def _has_extras(self) -> bool:
-        return self._coef is not None or self._weighted()
+        """Runtime coefficients or point weights of any kind: the requests of Engine.adam_loop_ext."""
+        return self._coef is not None or self._w_fixed is not None or self.rad_importance
 
-    def _fold_extras_kw(self, k: int, coef_log: Optional[torch.Tensor] = None) -> dict:
-        """What Engine.adam_loop_ext needs beside the evaluator's own tensors for the next k iterations: the coefficients'
-        or the multipliers' Adam state and their learning rates on the StepLR schedule (current_coefficient_lr /
-        current_weight_lr at each iteration); coef_log: where the coefficients each iteration ran with go."""
+    def _folded_request(self, Xr, losses: torch.Tensor) -> bool:
+        """evaluator.adam_iteration for the next Adam iterations, with the keywords of the loop entry the configuration needs:
+        ONE iteration whose three losses go to `losses` (3,) — from loss_func — or a device-enqueued run of k with losses
+        (k, 3) — from _adam_run.  Learning rates on the StepLR schedule (current_lr / current_coefficient_lr /
+        current_weight_lr at each iteration).  The extra columns each iteration ran with go to self._run_extras[:k]; a single
+        iteration's coefficients are in its ring row already (loss_func) and are not asked for.  False: not served, nothing done."""
+        single = losses.dim() == 1
+        k = 1 if single else losses.shape[0]
         a = self.config.adam
         sched = steplr_factors(a, self._sched_steps, k)
-        if self._coef is not None:
-            kw = {"coef_log": coef_log}
+        lr = a["learning_rate"] * sched[0] if single else [a["learning_rate"] * f for f in sched]
+        if self._extra_names and (self._run_extras is None or self._run_extras.shape[0] < k):
+            self._run_extras = torch.zeros(max(k, self.MAX_RUN), len(self._extra_names), dtype=torch.float32, device=self.device)
+        kw = {}
+        if self.loss_balancing is not None:      # Engine.adam_loop_balanced
+            kw["balance"] = {"lam": self._bal_lam, "mode": self.loss_balancing, "every": self.balance_every, "ref": self._bal_ref,
+                             "alpha": self.balance_alpha, "lam_log": self._run_extras[:k]}
+        elif self._coef is not None:             # Engine.adam_loop_ext: the coefficients' Adam state and learning rates
+            ext = kw["extras"] = {"coef_log": None if single else self._run_extras[:k]}
             if self._coef_grad is not None:
                 base = float(a.get("coefficient_learning_rate", a["learning_rate"]))
-                kw.update(coef_m=self._coef_m, coef_v=self._coef_v, lr_coef=[base * f for f in sched])
+                ext.update(coef_m=self._coef_m, coef_v=self._coef_v, lr_coef=[base * f for f in sched])
                 if len(self.trainable_coefficients) < len(self.coef_names):
-                    kw["coef_mask"] = self._coef_mask
-            return kw
-        if self._lam is not None:
-            return {"lam": self._lam, "lam_m": self._lam_m, "lam_v": self._lam_v, "sa_mask": self.self_adaptive["mask"],
-                    "lr_w": [self.config.weight_learning_rate * f for f in sched]}
-        return {}
+                    ext["coef_mask"] = self._coef_mask
+        elif self._lam is not None:              # ... or the multipliers'
+            kw["extras"] = {"lam": self._lam, "lam_m": self._lam_m, "lam_v": self._lam_v, "sa_mask": self.self_adaptive["mask"],
+                            "lr_w": [self.config.weight_learning_rate * f for f in sched]}
+        elif self._w_fixed is not None or self.rad_importance:      # ... or fixed weights: nothing of their own
+            kw["extras"] = {}
+        return self.evaluator.adam_iteration(
+            self.theta, self.Xf, self.Tf, self._fid_scale, Xr, self._res_scale, self.grad, self._fid_sums, self._res_sums,
+            self._adam_m, self._adam_v, self._adam_step + 1, lr, loss_rows=self._loss_mat, losses=losses,
+            params_token=self.dnn.write_token(self.theta), **kw)
 
     def _foldable_run(self, n: int) -> int:
         """How many of the next n Adam iterations can be enqueued by ONE call: full batch, one process, nothing the
@@ -1095,8 +1171,7 @@ class PINN:
             k = self.mat_dump_iter - self.iter
         free, logged = self._ring.shape[0] - len(self._ring_iters), 0
         for i in range(1, k + 1):
-            it = self.iter + i
-            if it % self.log_every == 0 or it % 1000 == 0:
+            if self._logged(self.iter + i):
                 logged += 1
                 if logged > free:
                     k = i - 1
@@ -1118,50 +1193,15 @@ class PINN:
 
     def _adam_run(self, k: int) -> bool:
         self.theta = self.dnn.flat_params()
-        self._ensure_loss_mat()
-        if hasattr(self.evaluator, "training"):
-            self.evaluator.training = self.dnn.training
-        a = self.config.adam
-        lrs = [a["learning_rate"] * f for f in steplr_factors(a, self._sched_steps, k)]
+        self._stage = ADAM
+        self._bind()
         if self._run_losses is None or self._run_losses.shape[0] < k:
             self._run_losses = torch.zeros(max(k, self.MAX_RUN), 3, dtype=torch.float32, device=self.device)
         out = self._run_losses[:k]
-        ext, clog = {}, None
-        if self._has_extras():       # (fold_extras: _may_fold has said so) the run of Engine.adam_loop_ext
-            if self._coef is not None:
-                self.evaluator.coef_grad = self._coef_grad      # (None when nothing is trainable: values only)
-                if self._run_coef_log is None or self._run_coef_log.shape[0] < k:
-                    self._run_coef_log = torch.zeros(max(k, self.MAX_RUN), len(self.coef_names), dtype=torch.float32, device=self.device)
-                clog = self._run_coef_log[:k]
-            if self._lam is not None:
-                self._sa_frozen = False
-                self.evaluator.fields_out = self._sa_fields
-            ext = {"extras": self._fold_extras_kw(k, clog)}
-        if self.loss_balancing is not None:      # (_may_fold has said so) the run of Engine.adam_loop_balanced
-            ext = {"balance": self._balance_kw(k)}
-            clog = self._run_lam_log[:k]         # the weights each iteration stepped with ride in the ring's extra columns
-        if not self.evaluator.adam_iteration(self.theta, self.Xf, self.Tf, self._fid_scale, self.Xr, self._res_scale, self.grad,
-                                             self._fid_sums, self._res_sums, self._adam_m, self._adam_v, self._adam_step + 1,
-                                             lrs, loss_rows=self._loss_mat, losses=out, params_token=self.dnn.write_token(self.theta), **ext):
+        if not self._folded_request(self.Xr, out):
             return False
-        if self.log_every == 1:                      # every iteration logged: one copy into the ring
-            r0 = len(self._ring_iters)
-            if clog is None:
-                self._ring[r0:r0 + k].copy_(out)
-            else:                                    # ... and the coefficients each iteration ran with beside its losses
-                self._ring[r0:r0 + k, :3].copy_(out)
-                self._ring[r0:r0 + k, 3:].copy_(clog)
-            self._ring_iters.extend(range(self.iter + 1, self.iter + k + 1))
-        else:
-            for i in range(k):
-                it = self.iter + 1 + i
-                if it % self.log_every == 0 or it % 1000 == 0:
-                    if clog is None:
-                        self._ring[len(self._ring_iters)].copy_(out[i])
-                    else:
-                        self._ring[len(self._ring_iters)][:3].copy_(out[i])
-                        self._ring[len(self._ring_iters)][3:].copy_(clog[i])
-                    self._ring_iters.append(it)
+        # (the run was cut so that its logged iterations fit the ring: _foldable_run)
+        self._to_ring(self.iter + 1, out, self._run_extras[:k] if self._extra_names else None)
         self.iter += k
         self._adam_step += k
         self._sched_steps += k
@@ -1169,16 +1209,13 @@ class PINN:
         self._adam_folded = True
         last = out[k - 1].clone()
         self.last = (last[0], last[1], last[2])
-        if len(self._ring_iters) == self._ring.shape[0]:
-            self.flush_log()
         return True
 
     def closure(self):
-        """train.py:195-199"""
-        if self._coef is not None:      # the L-BFGS stage holds the coefficients frozen: values only, no coefficient gradient
-            self.evaluator.coef_grad = None
-        self._sa_frozen = True          # ... and the self-adaptive weights at their Adam-final values
-        self.freeze_loss_weights()      # ... and the balanced group weights, folded into the scales once
+        """train.py:195-199.  The L-BFGS stage holds the coefficients and the self-adaptive weights frozen at their
+        Adam-final values (_bind), and the balanced group weights, folded into the scales once."""
+        self._stage = LBFGS
+        self.freeze_loss_weights()
         loss = self.loss_func()
         self.theta_param.grad = self.grad.clone()
         return loss
@@ -1201,16 +1238,11 @@ class PINN:
         its LAST slot: x_trial then still holds that evaluation's weights and the host saves from there — the
         reference's "weights of the evaluation, saved from inside loss_func" (train.py:175-179)."""
         self.theta = self.dnn.flat_params()
-        self._ensure_loss_mat()
+        self._stage = LBFGS
         lb = self.config.lbfgs
         has_fid = self.Xf is not None and self.Xf.shape[0] > 0
         nc = self._fid_sums.numel()
-        if has_fid and self.Xf is self.Xr:
-            X, n_res = self.Xr, -1
-        elif has_fid:
-            X, n_res = self.evaluator._merged(self.Xr, self.Xf), self.Xr.shape[0]
-        else:
-            X, n_res = self.Xr, self.Xr.shape[0]
+        X, n_res = self.evaluator.request_points(self.Xf, self.Xr, force_merge=True)      # (the loop is ONE request)
         opt = self.device_lbfgs = DeviceLBFGS(
             self.evaluator.eng, self.spec, self.theta, X, n_res, self._res_scale, self._loss_mat, 2,
             T=self.Tf if has_fid else None, out_col=self.fid_cols if nc else (), col_scale=self._fid_scale if nc else None,
@@ -1230,15 +1262,7 @@ class PINN:
             acts = tr[:, 2]
             k = int((acts != 0).sum())               # evaluations of this run: inert slots follow a stop
             rows = tr[:k, 10:13].to(torch.float32)
-            for i in range(k):
-                it = self.iter + 1 + i
-                if it % self.log_every == 0 or it % 1000 == 0:
-                    self._ring[len(self._ring_iters)][:3].copy_(rows[i])
-                    if self._bal_lam is not None:      # the frozen group weights, in their columns
-                        self._ring[len(self._ring_iters)][3:].copy_(self._bal_lam)
-                    self._ring_iters.append(it)
-                    if len(self._ring_iters) == self._ring.shape[0]:
-                        self.flush_log()
+            self._to_ring(self.iter + 1, rows, self._extra_vals)      # (the frozen group weights, in their columns)
             self.iter += k
             if k:
                 self.last = tuple(rows[k - 1].to(self.device))
