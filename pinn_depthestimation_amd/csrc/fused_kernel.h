@@ -155,33 +155,103 @@ __device__ __forceinline__ void load_wblk(const float* __restrict__ Wl, int MT, 
 // holds block 0 on entry; while the last block computes, block 0 of the NEXT phase's matrix
 // (`Wnext`, same row stride) is fetched into `wa`: its latency hides behind this GEMM's tail and
 // the vector work between the two GEMMs.
-// `mid` (optional) is called once, right after block 1's prefetch has been issued (block 0 for short
-// GEMMs): the place for HBM traffic that must not sit in FRONT of a weight load in the in-order vmcnt
-// queue.  A spill store / activation reload issued before the GEMM has to complete before the first
-// streamed block (requested after it, consumed 2048 cycles later) can be used; issued here, the next
-// load behind it is consumed two blocks (4096 cycles) later and its own consumer a GEMM later.
-struct NoMid { __device__ __forceinline__ void operator()() const {} };
-template <int NT_IN, int NT_OUT, int K1, class Mid = NoMid>
+// PACING.  One wave per SIMD issues in order: while it issues a run of vector-memory instructions the matrix pipe idles, and
+// an instruction costs two to three times in a run what it costs alone between MFMAs (tools/ubench_coexec.hip).
+// A paced stream issues nothing in a run: a block's MFMAs are one flat index i, and the block's memory instructions go out one
+// by one from SLOTS in front of MFMA 0, GAP, 2 GAP, ...  A block's slots carry, in this order,
+//   the NT_IN loads of the next weight block (consumed a block later),
+//   in block 0 the `head` operations (the forward layers' bias loads: consumed after the GEMM),
+//   in block MID_BLOCK (1, or 0 for short GEMMs) the `mid` operations: HBM traffic that must not sit in FRONT of a weight
+//     load in the in-order vmcnt queue.  A spill store / activation reload issued before the GEMM has to complete before the
+//     first streamed block (requested after it, consumed 2048 cycles later) can be used; issued here, the next load behind
+//     it is consumed two blocks (4096 cycles) later and its own consumer a GEMM later.
+// `head` and `mid` are objects with a compile-time COUNT and op<J>(), which issues their J-th instruction.  Where a block has
+// fewer slots than operations they are dealt evenly over the slots, several per slot.  A GAP that leaves the block ONE slot
+// (PACE_OFF) gives the unpaced order: everything in one run at the block's head.  -enable-misched=0 alone does not keep the
+// source order (instruction selection clusters neighbouring loads and lets the MFMAs, which hang on no chain, drift past
+// them): every occupied slot is fenced with sched_barrier(0).
+struct NoMid { __device__ __forceinline__ void operator()() const {} };   // (wide_kernel.h's default hook)
+
+// compile-time loop: f(std::integral_constant<int, I>) for I = I0 .. N - 1 (the index must be a constant where it picks a
+// register, a slot or an immediate)
+template <int I, int N, class F>
+__device__ __forceinline__ void const_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    const_for<I + 1, N>(f);
+  }
+}
+struct NoOps {
+  static constexpr int COUNT = 0;
+  template <int J> __device__ __forceinline__ void op() const {}
+};
+// the K1 * NT blocks of a layer's activation jet to / from the wave's slot: block J = (c, MT) = (J / NT, J % NT), 1 KB each
+template <int NT, int K1, bool ON = true>
+struct SpillOps {
+  static constexpr int COUNT = ON ? K1 * NT : 0;
+  float* __restrict__ slot;
+  const f4 (&v)[K1][NT];
+  int lane;
+  template <int J> __device__ __forceinline__ void op() const { *reinterpret_cast<f4*>(slot + J * 256 + lane * 4) = v[J / NT][J % NT]; }
+};
+template <int NT, int K1>
+struct UnspillOps {
+  static constexpr int COUNT = K1 * NT;
+  const float* __restrict__ slot;
+  f4 (&v)[K1][NT];
+  int lane;
+  template <int J> __device__ __forceinline__ void op() const { v[J / NT][J % NT] = *reinterpret_cast<const f4*>(slot + J * 256 + lane * 4); }
+};
+// The bias is added behind the GEMM rather than used as the accumulators' initial value: as an initial value its L2
+// latency sat exposed in front of every layer's first MFMA, and every accumulator chain starts from the inline constant 0.
+template <int NT>
+struct BiasOps {
+  static constexpr int COUNT = NT;
+  const float* __restrict__ b;
+  f4 (&bias)[NT];
+  int q;
+  template <int J> __device__ __forceinline__ void op() const { bias[J] = *reinterpret_cast<const f4*>(b + 16 * J + 4 * q); }
+};
+// MFMAs per slot: 2 (against 1 and 4: DESIGN 3.3).  PACE_OFF is what the REVERSE stream passes (paced, its 4 + 16 loads lost
+// in every round of the same A/B) and the forward-only kernel of pinn_fused_plain.hip (not measured paced).
+// Widths 16 and 32 run 2-3 waves per SIMD, which hide issue time already: paced, 2 -> 100x20 -> 3 on this kernel lost 2 % and
+// 2 -> 10x10 -> 6 gained 0.1 %, so the tile kernel paces its forward stream and its weight gradient at width 64 only.
+constexpr int PACE_GAP = 2, PACE_OFF = 1 << 20, PACE_MIN_WP = 64;
+template <int NT_IN, int NT_OUT, int K1, class Mid = NoOps, class Head = NoOps, int GAP = PACE_GAP>
 __device__ __forceinline__ void gemm_stream(const float* __restrict__ Wl, const float* __restrict__ Wnext,
                                             f4 (&wa)[NT_IN], const f4 (&bin)[K1][NT_IN], f4 (&acc)[K1][NT_OUT],
-                                            int m, int kq, const Mid& mid = Mid()) {
+                                            int m, int kq, const Mid& mid = Mid(), const Head& head = Head()) {
   constexpr int MID_BLOCK = NT_OUT >= 3 ? 1 : 0;
-#pragma unroll
-  for (int MT = 0; MT < NT_OUT; ++MT) {
+  constexpr int NM = NT_IN * 4 * K1;                       // MFMAs of a block: i = (kt * 4 + r) * K1 + c
+  constexpr int NSLOT = (NM + GAP - 1) / GAP;
+  const_for<0, NT_OUT>([&](auto mt_) {
+    constexpr int MT = decltype(mt_)::value;
+    constexpr int NHEAD = MT == 0 ? Head::COUNT : 0, NMID = MT == MID_BLOCK ? Mid::COUNT : 0;
+    constexpr int NOPS = NT_IN + NHEAD + NMID;
     f4 wb[NT_IN];
-    if (MT + 1 < NT_OUT) load_wblk<NT_IN>(Wl, MT + 1, wb, m, kq);
-    else load_wblk<NT_IN>(Wnext, 0, wb, m, kq);
-    if (MT == MID_BLOCK) mid();
-#pragma unroll
-    for (int kt = 0; kt < NT_IN; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < K1; ++c) acc[c][MT] = mfma4(wa[kt][r], bin[c][kt][r], acc[c][MT]);
+    const float* __restrict__ wsrc = (MT + 1 < NT_OUT ? Wl + (16 * (MT + 1) + m) * (16 * NT_IN) : Wnext + m * (16 * NT_IN)) + 4 * kq;
+    const_for<0, NM>([&](auto i_) {
+      constexpr int i = decltype(i_)::value;
+      if constexpr (i % GAP == 0) {
+        constexpr int S = i / GAP;                           // this slot's operations: [K_LO, K_HI)
+        constexpr int K_LO = NOPS <= NSLOT ? (S < NOPS ? S : NOPS) : (S * NOPS + NSLOT - 1) / NSLOT;
+        constexpr int K_HI = NOPS <= NSLOT ? (S + 1 < NOPS ? S + 1 : NOPS) : ((S + 1) * NOPS + NSLOT - 1) / NSLOT;
+        if constexpr (K_HI > K_LO && i > 0) __builtin_amdgcn_sched_barrier(0);
+        const_for<K_LO, K_HI>([&](auto k_) {
+          constexpr int k = decltype(k_)::value;
+          if constexpr (k < NT_IN) wb[k] = *reinterpret_cast<const f4*>(wsrc + 16 * k);
+          else if constexpr (k < NT_IN + NHEAD) head.template op<k - NT_IN>();
+          else mid.template op<k - NT_IN - NHEAD>();
+        });
+        if constexpr (K_HI > K_LO && NSLOT > 1) __builtin_amdgcn_sched_barrier(0);
+      }
+      constexpr int kt = i / (4 * K1), r = (i / K1) % 4, c = i % K1;
+      acc[c][MT] = mfma4(wa[kt][r], bin[c][kt][r], acc[c][MT]);
+    });
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int kt = 0; kt < NT_IN; ++kt) wa[kt] = wb[kt];
-  }
+  });
 }
 
 template <int NT, int K1>
@@ -405,21 +475,6 @@ __device__ __forceinline__ void sin_adjoint_to(const float* __restrict__ W0, con
     for (int r = 0; r < 4; ++r) Z[0][MT][r] = fmaf(-sz[MT][r], cross[MT][r], cz[MT][r] * G[0][MT][r]);
 }
 
-template <int NT, int K1>
-__device__ __forceinline__ void spill(float* __restrict__ slot, const f4 (&v)[K1][NT], int lane) {
-#pragma unroll
-  for (int c = 0; c < K1; ++c)
-#pragma unroll
-    for (int MT = 0; MT < NT; ++MT) *reinterpret_cast<f4*>(slot + (c * NT + MT) * 256 + lane * 4) = v[c][MT];
-}
-template <int NT, int K1>
-__device__ __forceinline__ void unspill(const float* __restrict__ slot, f4 (&v)[K1][NT], int lane) {
-#pragma unroll
-  for (int c = 0; c < K1; ++c)
-#pragma unroll
-    for (int MT = 0; MT < NT; ++MT) v[c][MT] = *reinterpret_cast<const f4*>(slot + (c * NT + MT) * 256 + lane * 4);
-}
-
 // acc-layout 16x16 block (features x points) -> operand layout of the weight-gradient GEMM:
 // lane (m = lane&15 feature, kq = lane>>4), element s  <-  value(feature m, point 4s + kq).
 // Pad layout: row = point (64 B), 16-byte chunk c of a row stored at chunk c ^ (point & 3):
@@ -446,10 +501,15 @@ __device__ __forceinline__ f4 transpose_read(const float* __restrict__ tb, int p
 // <-> point 4 kq + s (the contraction order over points is free as long as both operands use the same one): ONE
 // conflict-free ds_read_b128 per block instead of two ds_read2st64_b32 behind a 2-way-conflicted ds_write_b128.
 // Measured A/B (round 3, same box): 8x64 6.295 -> 6.258 ms, 10x10 on the tile kernel 0.774 -> 0.764, 100x20 24.19 -> 24.02.
-__device__ __forceinline__ void transpose_write2(float* __restrict__ tb, f4 v, int p, int q) {
+template <int H>   // half H of a block's write: features 4q + 2H and 4q + 2H + 1, one ds_write2_b32
+__device__ __forceinline__ void transpose_write2_half(float* __restrict__ tb, f4 v, int p, int q) {
   float* d = tb + (4 * q) * 16 + 4 * (((p >> 2) + 2 * q) & 3) + (p & 3);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) d[r * 16] = v[r];
+  d[(2 * H) * 16] = v[2 * H];
+  d[(2 * H + 1) * 16] = v[2 * H + 1];
+}
+__device__ __forceinline__ void transpose_write2(float* __restrict__ tb, f4 v, int p, int q) {
+  transpose_write2_half<0>(tb, v, p, q);
+  transpose_write2_half<1>(tb, v, p, q);
 }
 __device__ __forceinline__ f4 transpose_read2(const float* __restrict__ tb, int p, int q) {   // p: feature, q: point group
   return *reinterpret_cast<const f4*>(tb + p * 16 + 4 * ((q + 2 * (p >> 2)) & 3));
@@ -514,7 +574,7 @@ struct GradSink {
 // for every point.  In operand layout (lane = feature p, element s = a point) that is a lane predicate, so those operands are
 // built in registers and only A[0] goes through the pad: per tile 6 LDS writes, 3 LDS reads and the tangent part of the input jet
 // less, the same products into the same accumulators in the same k-order.
-template <int MT_N, int NT_N, int K1, bool UNIT_A = false, class Sink>
+template <int MT_N, int NT_N, int K1, bool UNIT_A = false, bool PACED = true, class Sink>
 __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int woff, int boff, const f4 (&Z)[K1][MT_N],
                                             const f4 (&A)[K1][NT_N], float* __restrict__ tb, int lane,
                                             const int* __restrict__ dir_col = nullptr) {
@@ -538,45 +598,59 @@ __device__ __forceinline__ void weight_grad(const Sink& sink, int layer, int wof
       for (int NT = 0; NT < NT_N; ++NT)
         early[MT][NT] = *reinterpret_cast<const f4*>(sink.acc + woff + ((MT * NT_N + NT) * 64 + lane) * 4);
   }
-  // Transposes run one quantity AHEAD of the MFMAs that consume them: the LDS round trip of
-  // quantity c+1 (same pads: quantity c's reads have already landed in registers) overlaps the
-  // MT_N*NT_N*4 MFMAs of quantity c.
+  // Transposes run one quantity AHEAD of the MFMAs that consume them: the LDS round trip of quantity c+1 (same pads:
+  // quantity c's reads have already landed in registers) overlaps the MT_N*NT_N*4 MFMAs of quantity c.  The stage of a
+  // quantity is 2 (MT_N + NT_N) ds_write2_b32 and then MT_N + NT_N ds_read_b128, 24 at width 64, in this order (one wave's
+  // LDS instructions execute in program order: a pad is read after it is written and rewritten after it is read, no
+  // barrier).  In one run such a stage costs 24 issue cycles per write and 14 per read among fp32 MFMAs, and the run
+  // overflows the 4-bit lgkmcnt; dealt out one by one between the MFMAs it costs about 1 (tools/ubench_coexec.hip, DESIGN
+  // 3.1).  So stage(c + 1)'s instruction k is issued in front of MFMA floor(k * SPAN / NOPS) of quantity c, SPAN = the
+  // quantity's MFMAs less a tail of an eighth that covers the last read's latency: at width 64 one LDS instruction per
+  // 2-3 MFMAs, so 15 consecutive ones span 35 MFMAs (1.1 k cycles) and never 15 are outstanding.  stage(0) has no MFMAs
+  // to hide behind and stays in front (issued from the preceding GEMM's tail it was worth 0.0 %, round 3).
   f4 zt[2][MT_N], at[2][NT_N];
-  auto stage = [&](int c, f4 (&z)[MT_N], f4 (&a)[NT_N]) {
-#pragma unroll
-    for (int MT = 0; MT < MT_N; ++MT) transpose_write2(tb + MT * TB_FLOATS, Z[c][MT], p, q);
-    const bool unit = UNIT_A && c > 0;
-    if (!unit) {
-#pragma unroll
-      for (int NT = 0; NT < NT_N; ++NT) transpose_write2(tb + (4 + NT) * TB_FLOATS, A[c][NT], p, q);
-    }
-#pragma unroll
-    for (int MT = 0; MT < MT_N; ++MT) z[MT] = transpose_read2(tb + MT * TB_FLOATS, p, q);
-    if (!unit) {
-#pragma unroll
-      for (int NT = 0; NT < NT_N; ++NT) a[NT] = transpose_read2(tb + (4 + NT) * TB_FLOATS, p, q);
+  auto stage_op = [&](auto c_, auto k_, f4 (&z)[MT_N], f4 (&a)[NT_N]) {
+    constexpr int c = decltype(c_)::value, k = decltype(k_)::value;
+    constexpr int NB = MT_N + ((UNIT_A && c > 0) ? 0 : NT_N);      // blocks through the pads: Z's, then A's
+    if constexpr (k < 2 * NB) {
+      constexpr int B = k / 2;
+      if constexpr (B < MT_N) transpose_write2_half<k % 2>(tb + B * TB_FLOATS, Z[c][B], p, q);
+      else transpose_write2_half<k % 2>(tb + (4 + B - MT_N) * TB_FLOATS, A[c][B - MT_N], p, q);
     } else {
-      const float e = (p == dir_col[c - 1]) ? 1.f : 0.f;
-      a[0] = f4{e, e, e, e};
+      constexpr int B = k - 2 * NB;
+      if constexpr (B < MT_N) z[B] = transpose_read2(tb + B * TB_FLOATS, p, q);
+      else a[B - MT_N] = transpose_read2(tb + (4 + B - MT_N) * TB_FLOATS, p, q);
     }
   };
-  stage(0, zt[0], at[0]);
-#pragma unroll
-  for (int c = 0; c < K1; ++c) {
+  auto unit_operand = [&](int c, f4 (&a)[NT_N]) {
+    const float e = (p == dir_col[c - 1]) ? 1.f : 0.f;
+    a[0] = f4{e, e, e, e};
+  };
+  const_for<0, 3 * (MT_N + NT_N)>([&](auto k_) { stage_op(std::integral_constant<int, 0>{}, k_, zt[0], at[0]); });
+  constexpr int NM = 4 * MT_N * NT_N;                       // MFMAs of a quantity: i = (s * MT_N + MT) * NT_N + NT
+  constexpr int SPAN = PACED ? NM - (NM >= 8 ? NM / 8 : 1) : 1;   // (!PACED: the whole stage in front of the quantity's first MFMA)
+  const_for<0, K1>([&](auto c_) {
+    constexpr int c = decltype(c_)::value;
+    constexpr int NOPS = c + 1 < K1 ? 3 * (MT_N + ((UNIT_A && c + 1 > 0) ? 0 : NT_N)) : 0;
     __builtin_amdgcn_sched_barrier(0);
-    if (c + 1 < K1) stage(c + 1, zt[(c + 1) & 1], at[(c + 1) & 1]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (c == 0) {   // bias: zt[MT][s] = zbar(feature p, point 4s + q): sum the 4 regs here ...
+    if constexpr (UNIT_A && c + 1 < K1) unit_operand(c + 1, at[(c + 1) & 1]);
+    if constexpr (c == 0) {   // bias: zt[MT][s] = zbar(feature p, point 4s + q): sum the 4 regs here ...
 #pragma unroll
       for (int MT = 0; MT < MT_N; ++MT) bs[MT] = (zt[0][MT][0] + zt[0][MT][1]) + (zt[0][MT][2] + zt[0][MT][3]);
     }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int MT = 0; MT < MT_N; ++MT)
-#pragma unroll
-        for (int NT = 0; NT < NT_N; ++NT) dw[MT][NT] = mfma4(zt[c & 1][MT][s], at[c & 1][NT][s], dw[MT][NT]);
-  }
+    __builtin_amdgcn_sched_barrier(0);
+    const_for<0, NM>([&](auto i_) {
+      constexpr int i = decltype(i_)::value;
+      if constexpr (i < SPAN && NOPS > 0) {
+        constexpr int K_LO = (i * NOPS + SPAN - 1) / SPAN, K_HI = ((i + 1) * NOPS + SPAN - 1) / SPAN;
+        if constexpr (K_HI > K_LO && i > 0) __builtin_amdgcn_sched_barrier(0);
+        const_for<K_LO, K_HI>([&](auto k_) { stage_op(std::integral_constant<int, c + 1>{}, k_, zt[(c + 1) & 1], at[(c + 1) & 1]); });
+        if constexpr (K_HI > K_LO && PACED) __builtin_amdgcn_sched_barrier(0);
+      }
+      constexpr int s = i / (MT_N * NT_N), MT = (i / NT_N) % MT_N, NT = i % NT_N;
+      dw[MT][NT] = mfma4(zt[c & 1][MT][s], at[c & 1][NT][s], dw[MT][NT]);
+    });
+  });
   // ... and the 4 lane groups here, after the last MFMA block (row swaps in the vector ALU: add_xor16 / add_xor32)
 #pragma unroll
   for (int MT = 0; MT < MT_N; ++MT) {

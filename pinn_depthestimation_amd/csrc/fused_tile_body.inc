@@ -1,6 +1,8 @@
   // fused_tile_body.inc — the body of the fused tile kernel (fused_kernel.h), included into k_fused and k_fused_ens.  In scope:
   // the template parameters' names WP, K1, GRAD, LDSACC, ACT, EPI, KRO, DROP and the kernel parameters P.  Everything per
   // workgroup is addressed through blockIdx.x and gridDim.x only.
+  constexpr bool PACED = WP >= PACE_MIN_WP;              // fused_kernel.h, PACING
+  constexpr int GAP_FWD = PACED ? PACE_GAP : PACE_OFF;
   constexpr bool IO1 = KRO > 0;
   constexpr int KRI = IO1 ? 1 : 4;          // k-steps of the first layer's contraction (d_in <= 4 when IO1)
   constexpr int KRL = IO1 ? KRO : 4;        // k-steps of the output layer's reverse contraction
@@ -103,12 +105,13 @@
     PINN_STAMP(1);
     for (int l = 1; l < L; ++l) {
       f4 bias[NTH];
-      load_bias<NTH>(Bp_ + b_off_p<WP>(l), bias, q);
       f4 nx[K1][NTH];
       zero_tiles<NTH, K1>(nx);
-      // a_l (this GEMM's B operand) is spilled from INSIDE the GEMM (see gemm_stream); a_L is never spilled
-      auto sp = [&]() { if (GRAD) spill<NTH, K1>(scr + (l - 1) * SLOT, a, lane); };
-      gemm_stream<NTH, NTH, K1>(Wp_ + w_off_p<WP>(l), Wp_ + w_off_p<WP>(l + 1), ws, a, nx, p, q, sp);
+      // a_l (this GEMM's B operand) is spilled and the layer's bias requested from INSIDE the GEMM (see gemm_stream); a_L is
+      // never spilled
+      const SpillOps<NTH, K1, GRAD> sp{scr + (l - 1) * SLOT, a, lane};
+      const BiasOps<NTH> lb{Bp_ + b_off_p<WP>(l), bias, q};
+      gemm_stream<NTH, NTH, K1, SpillOps<NTH, K1, GRAD>, BiasOps<NTH>, GAP_FWD>(Wp_ + w_off_p<WP>(l), Wp_ + w_off_p<WP>(l + 1), ws, a, nx, p, q, sp, lb);
       PINN_STAMP(0);
       activate_to<ACT_H, NTH, K1, DROP>(nx, bias, a, &dl, l, q);
       PINN_STAMP(1);
@@ -123,10 +126,10 @@
       load_wblk<NTH>(WTp_ + w_off_p<WP>(L > 1 ? L - 1 : 0), 0, ws, p, q);
     } else {
       f4 bias_o[1];
-      load_bias<1>(Bp_ + b_off_p<WP>(L), bias_o, q);
       zero_tiles<1, K1>(out);
       // (the block fetched behind the output GEMM is W_{L-1}^T's first: the reverse sweep starts there)
-      gemm_stream<NTH, 1, K1>(Wp_ + w_off_p<WP>(L), WTp_ + w_off_p<WP>(L > 1 ? L - 1 : 0), ws, a, out, p, q);
+      const BiasOps<1> lb{Bp_ + b_off_p<WP>(L), bias_o, q};
+      gemm_stream<NTH, 1, K1, NoOps, BiasOps<1>, GAP_FWD>(Wp_ + w_off_p<WP>(L), WTp_ + w_off_p<WP>(L > 1 ? L - 1 : 0), ws, a, out, p, q, NoOps(), lb);
       out[0][0] += bias_o[0];
     }
     // reverse-sweep operands whose latency the residual evaluation below hides
@@ -149,7 +152,7 @@
     // ai's registers for a_{l-1}: each spilled layer is read once, into the registers it is used
     // from, and there are no loop-carried copies.
     if constexpr (GRAD) {
-      weight_grad<1, NTH, K1>(sink, L, w_off_p<WP>(L), P.PW + b_off_p<WP>(L), G, a, tb, lane);
+      weight_grad<1, NTH, K1, false, PACED>(sink, L, w_off_p<WP>(L), P.PW + b_off_p<WP>(L), G, a, tb, lane);
       f4 z[K1][NTH];
       {
         f4 g[K1][NTH];
@@ -164,11 +167,12 @@
         PINN_STAMP(3);
         f4 g2[K1][NTH];
         zero_tiles<NTH, K1>(g2);
-        // a_l is requested from inside the GEMM (see gemm_stream) and used by the weight gradient after it
-        auto ld = [&]() { unspill<NTH, K1>(scr + (l - 1) * SLOT, ai, lane); };
-        gemm_stream<NTH, NTH, K1>(WTp_ + w_off_p<WP>(l), WTp_ + w_off_p<WP>(l >= 2 ? l - 1 : 1), ws, z, g2, p, q, ld);
+        // a_l is requested from inside the GEMM (see gemm_stream: behind block 1's weight loads, in one run — PACE_OFF) and used
+        // by the weight gradient after it
+        const UnspillOps<NTH, K1> ld{scr + (l - 1) * SLOT, ai, lane};
+        gemm_stream<NTH, NTH, K1, UnspillOps<NTH, K1>, NoOps, PACE_OFF>(WTp_ + w_off_p<WP>(l), WTp_ + w_off_p<WP>(l >= 2 ? l - 1 : 1), ws, z, g2, p, q, ld);
         PINN_STAMP(6);
-        weight_grad<NTH, NTH, K1>(sink, l, w_off_p<WP>(l), P.PW + b_off_p<WP>(l), z, ai, tb, lane);
+        weight_grad<NTH, NTH, K1, false, PACED>(sink, l, w_off_p<WP>(l), P.PW + b_off_p<WP>(l), z, ai, tb, lane);
         PINN_STAMP(5);
         if constexpr (SIN0) {   // l == 1: the adjoint of layer 0, the sine, from a recomputed z_0
           if (l == 1) { f4 b1[K1][1]; input_jet(b1); sin_adjoint_to<NTH, K1, KRI>(Wp_, Bp_ + b_off_p<WP>(0), b1, g2, z, p, q, P.X + ptc * P.d_in, P.d_in); }
@@ -181,7 +185,7 @@
         input_jet(b1);   // recomputed rather than kept live across the whole tile; with UNIT_A weight_grad reads the coordinates only
         // (UNIT_A for the LDS-copy instances only: with it, clang 22 crashes in its 'Rewrite AGPR-Copy-MFMA' pass on the
         // width-64 LeakyReLU instance that keeps its gradient copy in global memory)
-        weight_grad<NTH, 1, K1, LDSACC>(sink, 0, 0, P.PW + b_off_p<WP>(0), z, b1, tb, lane, P.dir_col);
+        weight_grad<NTH, 1, K1, LDSACC, PACED>(sink, 0, 0, P.PW + b_off_p<WP>(0), z, b1, tb, lane, P.dir_col);
       }
     }
     PINN_STAMP(7);

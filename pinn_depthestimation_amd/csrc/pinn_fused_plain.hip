@@ -68,7 +68,7 @@ __global__ __launch_bounds__(FUSED_THREADS, plain4_occ(WP)) void k_fused_plain4(
       load_bias<NTH>(Bp_ + b_off_p<WP>(l), bias, q);
       f4 nx[C][NTH];
       zero_tiles<NTH, C>(nx);
-      gemm_stream<NTH, NTH, C>(Wp_ + w_off_p<WP>(l), Wp_ + w_off_p<WP>(l + 1), ws, a, nx, p, q);
+      gemm_stream<NTH, NTH, C, NoOps, NoOps, PACE_OFF>(Wp_ + w_off_p<WP>(l), Wp_ + w_off_p<WP>(l + 1), ws, a, nx, p, q);
 #pragma unroll
       for (int c = 0; c < C; ++c)
 #pragma unroll
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(FUSED_THREADS, plain4_occ(WP)) void k_fused_plain4(
       load_bias<1>(Bp_ + b_off_p<WP>(L), bias_o, q);
       zero_tiles<1, C>(out);
       // (the block fetched behind the output GEMM is the next pass's first streamed one; it is re-requested at the top)
-      gemm_stream<NTH, 1, C>(Wp_ + w_off_p<WP>(L), Wp_ + w_off_p<WP>(L > 1 ? 1 : L), ws, a, out, p, q);
+      gemm_stream<NTH, 1, C, NoOps, NoOps, PACE_OFF>(Wp_ + w_off_p<WP>(L), Wp_ + w_off_p<WP>(L > 1 ? 1 : L), ws, a, out, p, q);
 #pragma unroll
       for (int c = 0; c < C; ++c) out[c][0] += bias_o[0];
     }

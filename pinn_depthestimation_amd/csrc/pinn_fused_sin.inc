@@ -10,6 +10,11 @@ namespace pinn {
 
 constexpr int WP_ = FUSED_WP;
 
+#if FUSED_WP == 64
+// (this one instance is compiled in pinn_fused_sin_w64_g4.hip, without -amdgpu-mfma-vgpr-form: see there)
+extern template __global__ void k_fused<64, 4, true, false, PINN_ACT_SIN_TANH, EPI_GENERIC>(const FusedParams);
+#endif
+
 template <class K>
 static int sgo(K kern, const FusedParams& P, int grid, size_t lds, hipStream_t s, const char* what) {
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return rc;

@@ -9,7 +9,13 @@ the tile loop and 0 outside it.  Spin loops (the gradient lock) hold no MFMA and
 
 Classes: mfma | v_pk_* | v_accvgpr_* | v_mov | v_cndmask | transcendental (v_exp/v_rcp/v_log/v_rsq/v_sqrt/v_sin/v_cos) |
 other VALU | ds_* | vector memory (global_/buffer_/flat_/scratch_) | scalar (s_*, with s_waitcnt and s_nop broken out).
-Output: one line per (block, segment) with static counts, then the per-tile dynamic totals per class."""
+Output: one line per (block, segment) with static counts, then the per-tile dynamic totals per class.
+
+Last column, `memrun`: the longest run of LDS or vector-memory instructions that nothing but scalar and non-MFMA vector
+instructions separate — the wave issues in order, so during such a run the matrix pipe drains and idles.  A run is cut by
+an MFMA and by a label, not by a sched_barrier; it is booked to the segment that holds its last instruction.  The last line
+gives the longest run of the segments that hold MFMAs (the GEMM streams and the weight gradient's quantity loop), where a
+run that ends in a segment's last MFMA-free stretch (what follows the last MFMA: the next phase's business) is left out."""
 import argparse
 import collections
 import re
@@ -64,10 +70,12 @@ def kernel_lines(path, name):
 def parse(lines):
     """-> blocks: list of dict(label, segs: [Counter], ops: Counter of mnemonics, branches: [target labels])"""
     blocks = [dict(label="entry", segs=[collections.Counter()], ops=collections.Counter(), branches=[])]
+    run = 0          # LDS / vector-memory instructions since the last MFMA or label
     for line in lines:
         m = re.match(r"^(\.LBB\d+_\d+):", line)
         if m:
             blocks.append(dict(label=m.group(1), segs=[collections.Counter()], ops=collections.Counter(), branches=[]))
+            run = 0
             continue
         s = line.strip()
         if s.startswith("; sched_barrier"):
@@ -79,8 +87,15 @@ def parse(lines):
         c = classify(op)
         if c is None:
             continue
-        blocks[-1]["segs"][-1][c] += 1
+        seg = blocks[-1]["segs"][-1]
+        seg[c] += 1
         blocks[-1]["ops"][op] += 1
+        if c == "mfma":
+            seg["memrun_mfma"] = max(seg["memrun_mfma"], run)     # the runs that an MFMA of this segment ends
+            run = 0
+        elif c in ("ds", "vmem"):
+            run += 1
+            seg["memrun"] = max(seg["memrun"], run)
         if op.startswith(("s_cbranch", "s_branch")):
             blocks[-1]["branches"].append(s.split()[1])
     return blocks
@@ -120,13 +135,17 @@ def main():
         for (lo, hi), trips, nm in ((inner[0], a.fwd, "fwd-loop"), (inner[-1], a.rev, "rev-loop")):
             for i in range(lo, hi + 1):
                 weight[i] = trips; names[i] = nm
-    print("block weight segment " + " ".join(CLASSES))
+    print("block weight segment " + " ".join(CLASSES) + " memrun")
     total = collections.Counter()
+    longest = (0, "-")
     for i, b in enumerate(blocks):
         for j, s in enumerate(b["segs"]):
             if not s:
                 continue
-            print(f"{b['label']} {weight[i]} {names.get(i, 'tile' if weight[i] else 'outside')}#{j} " + " ".join(str(s[c]) for c in CLASSES))
+            where = f"{b['label']} {weight[i]} {names.get(i, 'tile' if weight[i] else 'outside')}#{j}"
+            print(where + " " + " ".join(str(s[c]) for c in CLASSES) + f" {s['memrun']}")
+            if weight[i] and s["mfma"] >= 2 and s["memrun_mfma"] > longest[0]:
+                longest = (s["memrun_mfma"], where)
             for c in CLASSES:
                 total[c] += weight[i] * s[c]
         if a.ops and weight[i]:
@@ -135,6 +154,7 @@ def main():
     valu = sum(total[c] for c in ("v_pk", "v_accvgpr", "v_mov", "v_cndmask", "trans", "valu_other"))
     print(f"per tile: MFMA {total['mfma']}, other VALU {valu}, LDS {total['ds']}, vector memory {total['vmem']}, "
           f"non-MFMA vector + LDS + vector memory {valu + total['ds'] + total['vmem']}")
+    print(f"longest LDS / vector-memory run in front of an MFMA, segments of the tile loop with MFMAs: {longest[0]} ({longest[1]})")
 
 
 if __name__ == "__main__":

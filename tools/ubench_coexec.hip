@@ -1,13 +1,15 @@
 // ubench_coexec.hip — does a gfx950 SIMD overlap one wave's VALU work with another wave's
 // v_mfma_f32_16x16x4_f32 stream?  (design input for fused_pair_kernel.h)
-//   build: hipcc -O3 --offload-arch=gfx950 tools/ubench_coexec.hip -o tools/ubench_coexec
-//   run:   tools/ubench_coexec
+//   build: hipcc -O3 --offload-arch=gfx950 -mllvm -enable-misched=0 tools/ubench_coexec.hip -o tools/ubench_coexec
+//   run:   tools/ubench_coexec          (everything)      tools/ubench_coexec mem   (the round-5 memory-instruction table alone)
 // Each workgroup = WPS waves per SIMD (256*WPS threads), one workgroup per CU, ITERS iterations of
 // [NM MFMAs on NACC accumulators] then [NV independent v_fma_f32], phases optionally separated by
 // a scheduling barrier.  Prints cycles per iteration per SIMD (wall time * clock / iters).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+#include <utility>
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -290,13 +292,181 @@ static void table_inter2(const char* name, int gap, float* out, double ghz) {
          time_inter2<KIND, 5, TRANS>(out, ghz), time_inter2<KIND, 6, TRANS>(out, ghz), time_inter2<KIND, 8, TRANS>(out, ghz));
 }
 
-int main() {
-  float* out;
-  (void)hipMalloc(&out, 256 * 512 * sizeof(float));
+// ---- round 5: what does ONE LDS / vector-memory instruction cost among fp32 MFMAs, and does it matter WHERE it sits?
+// One wave per SIMD (256 threads, one workgroup per CU), blocks of 64 v_mfma_f32_16x16x4_f32 on 16 accumulators (the tile
+// kernel's GEMM block).  Every block also issues N memory instructions of one kind, either all in one run at the block's
+// head (SPREAD = false: what the tile kernel does) or one in front of MFMA floor(j * 64 / N) (SPREAD = true).
+//   KIND 0: global_load_dwordx4, 1 KB per wave-instruction out of a 16 KB array (L2 / L1 resident)
+//   KIND 1: global_store_dwordx4 to a wave-private slot (N KB per wave, rewritten every block)
+//   KIND 2: ds_write2_b32 (two conflict-free dwords per lane into a wave-private 4 KB pad)
+//   KIND 3: ds_read_b128 (conflict-free, same pad)
+// The instructions are inline assembly (the form is pinned; the compiler places no s_waitcnt for them), so the waits are
+// written by hand, the same rule for both placements: before instruction j of a block is issued, instruction j of the
+// PREVIOUS block must have returned — vmcnt(N - 1) resp. lgkmcnt(min(N - 1, 15)): the 4-bit lgkmcnt of gfx9 cannot express
+// more than 15 outstanding LDS operations, which is the tile kernel's situation behind a run of 24.
+// PERIOD: only every PERIOD-th block carries the N instructions (the tile kernel's spill stores sit in one block of five),
+// so that a store stream of N KB per wave and block does not measure the L2's write bandwidth instead of the issue port.
+// Built with -mllvm -enable-misched=0 (as the tile kernel's translation units): source order is issue order.
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+template <int KIND, int N>
+__device__ __forceinline__ void mem_wait() {
+  if constexpr (N < 1) return;
+  else if constexpr (KIND < 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N - 1) : "memory");
+  else asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N - 1 < 15 ? N - 1 : 15) : "memory");
+}
+template <int KIND>
+__device__ __forceinline__ void mem_op(f4& dst, const float* gsrc, float* gdst, unsigned lds_w, unsigned lds_r, f4 data) {
+  if constexpr (KIND == 0) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(gsrc) : "memory");
+  else if constexpr (KIND == 1) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(gdst), "v"(data) : "memory");
+  else if constexpr (KIND == 2) asm volatile("ds_write2_b32 %0, %1, %2 offset1:64" ::"v"(lds_w), "v"(data[0]), "v"(data[1]) : "memory");
+  else asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_r) : "memory");
+}
+template <int KIND, int N, bool SPREAD, int PERIOD>
+__global__ __launch_bounds__(256) void ub_mem(float* out, const float* src, float* slots, int iters, float x) {
+  constexpr int NM = 64, NACC = 16;
+  __shared__ float pad[4 * 1024];
+  f4 acc[NACC];
+#pragma unroll
+  for (int i = 0; i < NACC; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float a = threadIdx.x * 1e-3f, b = x;
+  const f4 data = f4{a, b, a + 1.f, b + 1.f};
+  pad[threadIdx.x] = a;   // (the pad is referenced from C++ too, so that it is allocated)
+  const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)pad + wave * 4096u;
+  const unsigned lds_w = lds + lane * 4u, lds_r = lds + lane * 16u;
+  // loads: N consecutive 1 KB pieces of the 16 KB array, the start staggered by wave; stores: the wave's own N KB
+  const float* gsrc[N > 0 ? N : 1];
+  float* gdst[N > 0 ? N : 1];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    gsrc[j] = src + ((j + wave + blockIdx.x) & 15) * 256 + lane * 4;
+    gdst[j] = slots + ((size_t)(blockIdx.x * 4 + wave) * (N > 0 ? N : 1) + j) * 256 + lane * 4;
+  }
+  f4 ld[N > 0 ? N : 1];
+#pragma unroll
+  for (int j = 0; j < (N > 0 ? N : 1); ++j) ld[j] = f4{0.f, 0.f, 0.f, 0.f};
+  for (int it = 0; it < iters; it += PERIOD) {
+    // the carrying block ...
+    if constexpr (!SPREAD) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        mem_wait<KIND, N>();
+        mem_op<KIND>(ld[j], gsrc[j], gdst[j], lds_w, lds_r, data);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    static_for<NM>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      if constexpr (SPREAD) {   // the instructions j with floor(j * NM / N) == i
+        constexpr int J0 = (i * N + NM - 1) / NM, J1 = ((i + 1) * N + NM - 1) / NM;
+#pragma unroll
+        for (int j = J0; j < J1; ++j) {
+          mem_wait<KIND, N>();
+          mem_op<KIND>(ld[j], gsrc[j], gdst[j], lds_w, lds_r, data);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      acc[i % NACC] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[i % NACC], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    // ... and PERIOD - 1 bare ones, in the same straight line
+#pragma unroll
+    for (int i = 0; i < (PERIOD - 1) * NM; ++i) {
+      acc[i % NACC] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[i % NACC], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NACC; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+#pragma unroll
+  for (int j = 0; j < (N > 0 ? N : 1); ++j) s += ld[j][0];
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s + pad[threadIdx.x ^ 1];
+}
+struct MemBufs { float* out; float* src; float* slots; int grid; double ghz; };
+// cycles per block (nominal clock), median and spread (max - min) of REPS timed launches
+template <int KIND, int N, bool SPREAD, int PERIOD>
+static void time_mem(const MemBufs& B, double& med, double& spread) {
+  constexpr int REPS = 5;
+  const int iters = 4000;
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  hipLaunchKernelGGL((ub_mem<KIND, N, SPREAD, PERIOD>), dim3(B.grid), dim3(256), 0, 0, B.out, B.src, B.slots, 40, 1.0001f);
+  (void)hipDeviceSynchronize();
+  double c[REPS];
+  for (int r = 0; r < REPS; ++r) {
+    (void)hipEventRecord(e0);
+    hipLaunchKernelGGL((ub_mem<KIND, N, SPREAD, PERIOD>), dim3(B.grid), dim3(256), 0, 0, B.out, B.src, B.slots, iters, 1.0001f);
+    (void)hipEventRecord(e1);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    c[r] = ms * 1e-3 * B.ghz * 1e9 / iters;
+  }
+  for (int i = 0; i < REPS; ++i)
+    for (int j = i + 1; j < REPS; ++j)
+      if (c[j] < c[i]) { const double t = c[i]; c[i] = c[j]; c[j] = t; }
+  med = c[REPS / 2]; spread = c[REPS - 1] - c[0];
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+}
+template <int KIND, int N, int PERIOD>
+static void row_mem(const char* name, const MemBufs& B, double bare) {
+  double ma, sa, mb, sb;
+  time_mem<KIND, N, false, PERIOD>(B, ma, sa);
+  time_mem<KIND, N, true, PERIOD>(B, mb, sb);
+  // per carrying block: PERIOD blocks were timed, PERIOD - 1 of them bare
+  const double xa = (ma - bare) * PERIOD, xb = (mb - bare) * PERIOD;
+  printf("%-22s n=%2d every %d block(s) | (a) one run at the head: +%7.1f cycles per carrying block (%5.1f per instruction, spread %4.1f)"
+         " | (b) one per %4.1f MFMAs: +%7.1f (%5.1f per instruction, spread %4.1f) | (a) - (b) = %7.1f\n",
+         name, N, PERIOD, xa, xa / N, sa * PERIOD, 64.0 / N, xb, xb / N, sb * PERIOD, xa - xb);
+}
+template <int KIND, int PERIOD>
+static void table_mem(const char* name, const MemBufs& B, double bare) {
+  row_mem<KIND, 4, PERIOD>(name, B, bare);
+  row_mem<KIND, 16, PERIOD>(name, B, bare);
+  row_mem<KIND, 20, PERIOD>(name, B, bare);
+  row_mem<KIND, 24, PERIOD>(name, B, bare);
+}
+static void run_mem(double ghz) {
+  MemBufs B;
+  int cus = 0;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0);
+  B.grid = cus; B.ghz = ghz;
+  (void)hipMalloc(&B.out, (size_t)cus * 256 * sizeof(float));
+  (void)hipMalloc(&B.src, 16 * 1024);
+  (void)hipMemset(B.src, 0, 16 * 1024);
+  (void)hipMalloc(&B.slots, (size_t)cus * 4 * 24 * 1024);
+  printf("---- one wave per SIMD, %d workgroups of 4 waves: N LDS / vector-memory instructions per block of 64 v_mfma_f32_16x16x4_f32 on 16 accumulators"
+         " (host-timed at the nominal clock, median of 5 launches of 4000 blocks; compare rows) ----\n", cus);
+  double bare, sbare, bare2, sbare2;
+  for (int r = 0; r < 4; ++r) time_mem<0, 0, false, 1>(B, bare, sbare);   // (the first launches run at a clock that is still settling)
+  time_mem<0, 0, false, 1>(B, bare, sbare);
+  time_mem<0, 0, true, 1>(B, bare2, sbare2);
+  printf("bare 64 MFMAs: %7.1f cycles per block (spread %4.1f); again, from the other loop form: %7.1f (spread %4.1f)\n", bare, sbare, bare2, sbare2);
+  table_mem<0, 1>("global_load_dwordx4", B, bare);
+  table_mem<0, 4>("global_load_dwordx4", B, bare);
+  table_mem<1, 1>("global_store_dwordx4", B, bare);
+  table_mem<1, 4>("global_store_dwordx4", B, bare);
+  table_mem<2, 1>("ds_write2_b32", B, bare);
+  table_mem<3, 1>("ds_read_b128", B, bare);
+  (void)hipFree(B.slots); (void)hipFree(B.src); (void)hipFree(B.out);
+}
+
+int main(int argc, char** argv) {
   int khz = 0;
   (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, 0);
   const double ghz = khz * 1e-6;
   printf("clock %.3f GHz\n", ghz);
+  if (argc > 1 && !strcmp(argv[1], "mem")) {   // the round-5 table alone
+    run_mem(ghz);
+    return 0;
+  }
+  float* out;
+  (void)hipMalloc(&out, 256 * 512 * sizeof(float));
   run<128, 0, 4, true, false>("mfma only, 4 acc", 1, out, ghz);
   run<128, 0, 2, true, false>("mfma only, 2 acc", 1, out, ghz);
   run<128, 0, 1, true, false>("mfma only, 1 acc", 1, out, ghz);
@@ -336,5 +506,6 @@ int main() {
   run_roles_bf16<128, 512>(out, cyc, 7);
   (void)hipFree(cyc);
   (void)hipFree(out);
+  run_mem(ghz);
   return 0;
 }
