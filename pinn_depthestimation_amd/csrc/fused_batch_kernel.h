@@ -393,7 +393,7 @@ __device__ __forceinline__ void bload_adjoint(const FusedParams& P, f4 (&G)[K1][
 // WP: padded hidden width (16 / 32); KS = ceil(W / 4): k-steps of a hidden contraction; KS0 = ceil(d_in / 4);
 // T: tiles per wave and batch.  Gradient passes only (the forward-only calls stay on k_fused).
 // EPI: EPI_GENERIC (the loss epilogue of fused_kernel.h) or EPI_ADJ (pinn_jet_backward: the caller's output adjoints
-// instead of a loss; instances in pinn_fused_batch_adj_w*_k*.hip).  Everything from the output layer's pad writes on —
+// instead of a loss; instances: pinn_fused_batch.hip, BF_ADJ).  Everything from the output layer's pad writes on —
 // abar_L, dW_L, the reverse sweep, layer 0, both gradient sinks — is the same code for both.
 template <int WP, int KS, int KS0, int K1, int T, int SINK, int ACT, int EPI = EPI_GENERIC>
 __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batch(const FusedParams P) {
@@ -688,11 +688,7 @@ __global__ __launch_bounds__(BATCH_THREADS, batch_occ(WP, K1)) void k_fused_batc
   }
 }
 
-// launchers: one translation unit per padded width (pinn_fused_batch_w16.hip / _w32.hip)
-template <int WP>
-int launch_fused_batch(int W, int d_in, int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-template <int WP>      // the EPI_ADJ instances (pinn_fused_batch_adj_w{16,32}_k{3,4}.hip)
-int launch_fused_batch_adj(int W, int d_in, int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
+// launcher: fused_launch.h (launch_batch); the instances, one translation unit per (family, WP, K1): pinn_fused_batch.hip
 bool fused_batch_has_kernel(int WP, int W, int d_in, int K1, int act);
 
 }  // namespace pinn

@@ -811,14 +811,14 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 // (field_epilogue below) and nothing else happens: no sums, no Y / dY stores, no adjoint, no reverse sweep.
 // EPI_PEC: the loss epilogue with the residual family fixed to ResPhysicsEquationCorrected (pec_epilogue below): serves what
 // EPI_GENERIC serves (residual, residual + fidelity columns, split mode) but stores no Y / dY.  EPI_FIELD_PEC: EPI_FIELD
-// for that residual.  Both are compile-time choices with translation units of their own (pinn_fused_pec_wXX.hip,
-// pinn_fused_batch_pec_wXX_k3.hip), so the generic epilogues do not grow by a branch.
+// for that residual.  Both are compile-time choices with translation units of their own (the pec units of
+// pinn_fused_tile.hip and pinn_fused_batch.hip), so the generic epilogues do not grow by a branch.
 // EPI_COEF (pinn_residual_coef_loss_grad): the EPI_NS / EPI_PE epilogue with the residual's closure coefficient read from
 // a device array (coef_epilogue below) and its gradient summed beside the term sums; translation units of its own too
-// (pinn_fused_coef_wXX.hip).
+// (pinn_fused_tile.hip, TF_COEF).
 // EPI_WEIGHTED (pinn_residual_weighted_loss_grad): the residual epilogue of any first-order family with one weight per point
 // and weighted term (weighted_epilogue below), and an optional store of the signed fields; translation units of its own
-// (pinn_fused_wt_wXX.hip).
+// (pinn_fused_tile.hip, TF_WEIGHTED).
 constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5, EPI_PEC = 6, EPI_FIELD_PEC = 7,
               EPI_COEF = 8, EPI_WEIGHTED = 9;
 constexpr int COEF_SUM = 3;   // EPI_COEF: the term slot of [0, MSE_SUM0) that carries gc[0] (PINN_NS_TERMS = PINN_PE_TERMS = 3 leave it free)
@@ -1131,7 +1131,7 @@ __device__ __forceinline__ void loss_epilogue(const FusedParams& P, const f4 (&o
 // kernels place the weights accordingly (pinn_fused.hip, PACK_IN / PACK_OUT) and the host hands the epilogue PADDED row
 // indices in out_col / dir_col, so the epilogue code is the same.
 //
-// Ensembles (k_fused_ens below, pinn_fused_ens_wXX.hip): launched on a 2-D grid (gx, M), member = blockIdx.y.  blockIdx.x
+// Ensembles (k_fused_ens below; pinn_fused_tile.hip, TF_ENS): launched on a 2-D grid (gx, M), member = blockIdx.y.  blockIdx.x
 // and gridDim.x keep their per-member meaning, so the body is the single-network code: the ensemble kernel only shifts the
 // pointers it was given to its member's share, once (ens_member), and k_fused stays as it was.
 // Member strides: packed Wp / WTp PW floats, Bp PB floats, spill slots gridDim.x * FUSED_WAVES * scratch_per_wave, wg_sums
@@ -1165,7 +1165,7 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
 #include "fused_tile_body.inc"
 }
 
-// The ensemble instances (pinn_fused_ens_wXX.hip): gradient passes of tanh networks with the generic epilogue in natural
+// The ensemble instances (pinn_fused_tile.hip, TF_ENS): gradient passes of tanh networks with the generic epilogue in natural
 // unit order, launched on a 2-D grid (gx, M) — one row of workgroups per member.
 // Width 16 is compiled for FUSED_ENS_W16_WAVES = 2 waves per SIMD, not k_fused's three: at three (168 registers) the
 // width-16 gradient kernels keep 40 to 216 bytes per lane in scratch memory, at two they keep none.
@@ -1181,34 +1181,6 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_ENS_W16_WAVES : FUS
 #include "fused_tile_body.inc"
 }
 
-// launcher: pinn_fused_launch.inc, one translation unit per WP (pinn_fused_wXX.hip)
-template <int WP>
-int launch_fused(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-// external-adjoint instances: pinn_fused_adj.inc, one translation unit per WP (pinn_fused_adj_wXX.hip)
-template <int WP>
-int launch_fused_adj(int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-// field instances: pinn_fused_field.inc, one translation unit per WP (pinn_fused_field_wXX.hip)
-template <int WP>
-int launch_fused_field(int K1, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-// corrected-radiation-stress instances (EPI_PEC loss, EPI_FIELD_PEC fields; K1 = 3, tanh): pinn_fused_pec.inc, one
-// translation unit per WP (pinn_fused_pec_wXX.hip)
-template <int WP>
-int launch_fused_pec(bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-template <int WP>
-int launch_fused_field_pec(const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-// coefficient instances (EPI_COEF; K1 = 3 or 4, tanh): pinn_fused_coef.inc, one translation unit per WP (pinn_fused_coef_wXX.hip)
-template <int WP>
-int launch_fused_coef(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-// point-weighted instances (EPI_WEIGHTED; K1 = 3 or 4, tanh): pinn_fused_wt.inc, one translation unit per WP (pinn_fused_wt_wXX.hip)
-template <int WP>
-int launch_fused_wt(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-// sine-first-layer instances (PINN_ACT_SIN_TANH, EPI_GENERIC; K1 = 1, 3 or 4): pinn_fused_sin.inc, one translation unit per WP
-// (pinn_fused_sin_wXX.hip)
-template <int WP>
-int launch_fused_sin(int K1, bool grad, const FusedParams& P, int grid, size_t lds_bytes, hipStream_t s);
-// ensemble instances (k_fused_ens: grid (gx, M), gradient pass, tanh, K1 = 3 or 4): pinn_fused_ens.inc, one translation unit per WP
-// (pinn_fused_ens_wXX.hip)
-template <int WP>
-int launch_fused_ens(int K1, const FusedParams& P, int gx, int M, size_t lds_bytes, hipStream_t s);
+// launcher: fused_launch.h (launch_tile); the instances, one translation unit per (family, WP): pinn_fused_tile.hip
 
 }  // namespace pinn

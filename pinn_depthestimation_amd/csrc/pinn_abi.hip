@@ -108,7 +108,7 @@ static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc
   *rc = PINN_OK;
   const int asked = asked_engine(d);
   if (n.drop_p > 0.f) {     // training-mode dropout: the fused tile kernel for gradient passes at padded width 64
-                            // (pinn_fused_w64_drop.hip), the generic engine's kernels for everything else
+                            // (pinn_fused_tile.hip, TF_DROP), the generic engine's kernels for everything else
     if (n.prec != PINN_PREC_F32) { set_error("dropout_p > 0 is implemented in fp32 only"); *rc = PINN_ERR_UNSUPPORTED; return PINN_ENGINE_GENERIC; }
     const bool fused_ok = fused_supports(n, want_grad);
     if (asked == PINN_ENGINE_FUSED && !fused_ok) {
@@ -138,7 +138,7 @@ static int pick_engine(const pinn_desc* d, const Net& n, bool want_grad, int* rc
   if (asked == PINN_ENGINE_FUSED || asked == PINN_ENGINE_WIDE) {
     const bool ok = asked == PINN_ENGINE_FUSED ? fused_supports(n, want_grad) : wide_supports(n);
     if (!ok && n.act == PINN_ACT_SIN_TANH) {
-      // the sine first layer: the tile kernel's own instances only (pinn_fused_sin_wXX.hip)
+      // the sine first layer: the tile kernel's own instances only (pinn_fused_tile.hip, TF_SIN)
       const char* why = asked == PINN_ENGINE_WIDE ? "the wide engine has no kernel for it"
                       : n.fused_kernel == FUSED_KERNEL_COOP ? "engine FUSED_COOP: the cooperative kernel has no instance for it (use AUTO, FUSED or FUSED_TILE)"
                       : n.fused_kernel == FUSED_KERNEL_BATCH ? "engine FUSED_BATCH: the batch kernel has no instance for it (use AUTO, FUSED or FUSED_TILE)"

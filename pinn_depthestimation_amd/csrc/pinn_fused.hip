@@ -2,6 +2,7 @@
 // launch geometry, cross-workgroup reductions.  Kernel: fused_kernel.h.
 #include <algorithm>
 #include <type_traits>
+#include "fused_launch.h"
 #include "fused_coop_kernel.h"
 #include "fused_batch_kernel.h"
 #include "reduce_adam.h"
@@ -10,13 +11,8 @@
 
 namespace pinn {
 
-int launch_fused_drop64(int K1, const FusedParams& P, int grid, size_t lds, hipStream_t s);   // pinn_fused_w64_drop.hip
 int launch_fused_plain(int WP, const FusedParams& P, int cus, hipStream_t s);                      // pinn_fused_plain.hip
 int64_t fused_plain_min_tiles(int WP, int cus);
-
-// batch kernel instances (defined at the end of this file)
-template <int WP>
-int launch_fused_batch_pec(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s);
 
 namespace {
 
@@ -566,6 +562,19 @@ struct FieldReq {
   float* fields;
 };
 
+// The family of kernel instances a request takes (fused_launch.h, TileFamily), in the order of precedence: what the call
+// asks for (fields, an external adjoint), then what the network needs (dropout, the sine first layer), then the request's
+// epilogue.  run() refuses the combinations without instances; the batch kernel has the adjoint, corrected and loss families.
+TileFamily tile_family(const Net& n, const LossReq* rq, const AdjReq* adj, const FieldReq* fld) {
+  if (fld) return fld->spec.residual_id == RES_PE_CORRECTED ? TF_FIELD_PEC : TF_FIELD;
+  if (adj) return TF_ADJ;
+  if (n.drop_p > 0.f) return TF_DROP;
+  if (n.act == PINN_ACT_SIN_TANH) return TF_SIN;
+  if (is_weighted(rq)) return TF_WEIGHTED;
+  if (is_coef(rq)) return TF_COEF;
+  return is_pec(rq) ? TF_PEC : TF_LOSS;
+}
+
 // One pass of pinn_adam_loop_ext: run() launches the gradient pass ALONE — no reduction, no finishing kernel, the packing
 // kernel only if asked — with its scratch, partial sums and gradient copies at the byte offsets the caller names (the
 // caller has checked the workspace against its own layout, fused_adam_ext), and reports what the finishing kernel needs.
@@ -689,84 +698,39 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
       set_error("hipMemsetAsync failed"); return PINN_ERR_LAUNCH;
     }
   }
-  int rc;
-  if (fld) {   // forward-only grid (grid_for above, grad == false), natural unit order (perm == 0), no reductions;
-               // no dynamic LDS: these instances touch neither the pads nor the gradient copy
-    if (fpec) switch (g.WP) {
-      case 16: return launch_fused_field_pec<16>(P, grid, 0, s);
-      case 32: return launch_fused_field_pec<32>(P, grid, 0, s);
-      default: return launch_fused_field_pec<64>(P, grid, 0, s);
-    }
-    switch (g.WP) {
-      case 16: rc = launch_fused_field<16>(n.K1, P, grid, 0, s); break;
-      case 32: rc = launch_fused_field<32>(n.K1, P, grid, 0, s); break;
-      default: rc = launch_fused_field<64>(n.K1, P, grid, 0, s); break;
-    }
-    return rc;
+  // One launch: the family of instances the request takes (tile_family), on the kernel chosen above.  The field families:
+  // forward-only grid (grid_for above, grad == false), natural unit order (perm == 0), no reductions, and no dynamic LDS —
+  // these instances touch neither the pads nor the gradient copy.
+  const TileFamily fam = tile_family(n, rq, adj, fld);
+  const TileLaunch tile{n.K1, grad, P, dim3(grid), fld ? 0 : lds, s};
+  const BatchLaunch bat{n.W, n.d_in, P, grid, lds, s};
+  if (fam == TF_ADJ && n.drop_p > 0.f) { set_error("fused engine: no dropout instance of the external-adjoint kernel"); return PINN_ERR_UNSUPPORTED; }
+  if (fam == TF_DROP) {     // training-mode dropout: its own instances of the tile kernel
+    P.drop_seed = n.drop_seed; P.drop_thresh = n.drop_thresh; P.drop_scale = 1.f / (1.f - n.drop_p); P.drop_keep = 1.f - n.drop_p;
+    if (!(grad && g.WP == 64 && P.acc_lds && n.act == PINN_ACT_TANH)) { set_error("fused engine: no dropout kernel for this request"); return PINN_ERR_UNSUPPORTED; }
   }
+  int rc;
+  if ((fam == TF_LOSS || fam == TF_SIN) && !rq && !grad && !coop && !batch && n.K1 == 1 && Y && !dY && n.fused_kernel == FUSED_KERNEL_AUTO &&
+      P.n_tiles >= fused_plain_min_tiles(g.WP, cu_count())) {
+    // pinn_forward on enough points to give every wave the chip holds a pass of four tiles: the plain forward's own
+    // kernel, one weight fetch per 64 points (pinn_fused_plain.hip)
+    rc = launch_fused_plain(g.WP, P, cu_count(), s);
+  }
+  else if (fam == TF_SIN && (wtq || coefq || pec || batch || coop)) {   // the sine first layer: the tile kernel's generic epilogue only
+    set_error("fused engine: no kernel for the sine first layer (activation 2) on this request"); return PINN_ERR_UNSUPPORTED;
+  }
+  // (a field, dropout, coefficient or weighted request never has batch or coop set: above)
+  else if (batch) rc = launch_batch(fam == TF_ADJ ? BF_ADJ : fam == TF_PEC ? BF_PEC : BF_LOSS, g.WP, n.K1, bat);
+  else if (coop) rc = launch_fused_coop(n.K1, grad, P, grid, lds, s);
+  else rc = launch_tile(fam, g.WP, tile);
+  if (rc || fld) return rc;
   if (adj) {
-    if (n.drop_p > 0.f) { set_error("fused engine: no dropout instance of the external-adjoint kernel"); return PINN_ERR_UNSUPPORTED; }
-    if (batch) rc = g.WP == 16 ? launch_fused_batch_adj<16>(n.W, n.d_in, n.K1, P, grid, lds, s)
-                               : launch_fused_batch_adj<32>(n.W, n.d_in, n.K1, P, grid, lds, s);
-    else switch (g.WP) {
-      case 16: rc = launch_fused_adj<16>(n.K1, P, grid, lds, s); break;
-      case 32: rc = launch_fused_adj<32>(n.K1, P, grid, lds, s); break;
-      default: rc = launch_fused_adj<64>(n.K1, P, grid, lds, s); break;
-    }
-    if (rc) return rc;
     // (no loss sums after an adjoint pass: wg_sums is not read)
     const int64_t np = n.n_params();
     hipLaunchKernelGGL(k_reduce_grads, dim3((unsigned)((np + 63) / 64)), dim3(256), 0, s, n, g.WP,
                        (const float*)P.wg_grads, n_copies, g.PP, g.PW, adj->grad, perm | (rmajor ? PACK_RMAJOR : 0));
     return check_launch("fused reductions");
   }
-  if (n.drop_p > 0.f) {     // training-mode dropout: its own instances of the tile kernel (pinn_fused_w64_drop.hip)
-    P.drop_seed = n.drop_seed; P.drop_thresh = n.drop_thresh; P.drop_scale = 1.f / (1.f - n.drop_p); P.drop_keep = 1.f - n.drop_p;
-    if (!(grad && g.WP == 64 && P.acc_lds && n.act == PINN_ACT_TANH)) { set_error("fused engine: no dropout kernel for this request"); return PINN_ERR_UNSUPPORTED; }
-    rc = launch_fused_drop64(n.K1, P, grid, lds, s);
-  }
-  else if (!rq && !grad && !coop && !batch && n.K1 == 1 && Y && !dY && n.fused_kernel == FUSED_KERNEL_AUTO &&
-           P.n_tiles >= fused_plain_min_tiles(g.WP, cu_count())) {
-    // pinn_forward on enough points to give every wave the chip holds a pass of four tiles: the plain forward's own
-    // kernel, one weight fetch per 64 points (pinn_fused_plain.hip)
-    rc = launch_fused_plain(g.WP, P, cu_count(), s);
-  }
-  else if (n.act == PINN_ACT_SIN_TANH) {   // the sine first layer: instances of its own (pinn_fused_sin_wXX.hip), generic epilogue only
-    if (wtq || coefq || pec || batch || coop) { set_error("fused engine: no kernel for the sine first layer (activation 2) on this request"); return PINN_ERR_UNSUPPORTED; }
-    switch (g.WP) {
-      case 16: rc = launch_fused_sin<16>(n.K1, grad, P, grid, lds, s); break;
-      case 32: rc = launch_fused_sin<32>(n.K1, grad, P, grid, lds, s); break;
-      default: rc = launch_fused_sin<64>(n.K1, grad, P, grid, lds, s); break;
-    }
-  }
-  else if (wtq) switch (g.WP) {   // EPI_WEIGHTED instances: pinn_fused_wt_wXX.hip
-    case 16: rc = launch_fused_wt<16>(n.K1, grad, P, grid, lds, s); break;
-    case 32: rc = launch_fused_wt<32>(n.K1, grad, P, grid, lds, s); break;
-    default: rc = launch_fused_wt<64>(n.K1, grad, P, grid, lds, s); break;
-  }
-  else if (coefq) switch (g.WP) {   // EPI_COEF instances: pinn_fused_coef_wXX.hip
-    case 16: rc = launch_fused_coef<16>(n.K1, grad, P, grid, lds, s); break;
-    case 32: rc = launch_fused_coef<32>(n.K1, grad, P, grid, lds, s); break;
-    default: rc = launch_fused_coef<64>(n.K1, grad, P, grid, lds, s); break;
-  }
-  else if (pec) {           // EPI_PEC instances: pinn_fused_batch_pec_wXX_k3.hip / pinn_fused_pec_wXX.hip
-    if (batch) rc = g.WP == 16 ? launch_fused_batch_pec<16>(n.W, n.d_in, P, grid, lds, s)
-                               : launch_fused_batch_pec<32>(n.W, n.d_in, P, grid, lds, s);
-    else switch (g.WP) {
-      case 16: rc = launch_fused_pec<16>(grad, P, grid, lds, s); break;
-      case 32: rc = launch_fused_pec<32>(grad, P, grid, lds, s); break;
-      default: rc = launch_fused_pec<64>(grad, P, grid, lds, s); break;
-    }
-  }
-  else if (batch) rc = g.WP == 16 ? launch_fused_batch<16>(n.W, n.d_in, n.K1, P, grid, lds, s)
-                             : launch_fused_batch<32>(n.W, n.d_in, n.K1, P, grid, lds, s);
-  else if (coop) rc = launch_fused_coop(n.K1, grad, P, grid, lds, s);
-  else switch (g.WP) {
-    case 16: rc = launch_fused<16>(n.K1, grad, P, grid, lds, s); break;
-    case 32: rc = launch_fused<32>(n.K1, grad, P, grid, lds, s); break;
-    default: rc = launch_fused<64>(n.K1, grad, P, grid, lds, s); break;
-  }
-  if (rc) return rc;
   if (po) { po->grid = grid; po->n_copies = n_copies; return check_launch("fused pass"); }
   if (adam) {
     const int64_t np = n.n_params();
@@ -796,40 +760,29 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
 
 }  // namespace
 
-// batch kernel instances: pinn_fused_batch_w{16,32}_k{3,4}.hip
-template <int WP, int K1>
-int launch_fused_batch_k(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s);
-template <int WP>
-int launch_fused_batch(int W, int d_in, int K1, const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  return K1 == 3 ? launch_fused_batch_k<WP, 3>(W, d_in, P, grid, lds, s) : launch_fused_batch_k<WP, 4>(W, d_in, P, grid, lds, s);
+// ---- the entry points of fused_launch.h: one table of units per kernel -------------------------------------------------------
+#define TILE_ROW(F) {tile_unit<F, 16>, tile_unit<F, 32>, tile_unit<F, 64>}
+int launch_tile(TileFamily f, int WP, const TileLaunch& a) {
+  static int (*const unit[TF_COUNT][3])(const TileLaunch&) = {   // (in TileFamily's order)
+      TILE_ROW(TF_LOSS), TILE_ROW(TF_ADJ), TILE_ROW(TF_FIELD), TILE_ROW(TF_PEC), TILE_ROW(TF_FIELD_PEC), TILE_ROW(TF_COEF),
+      TILE_ROW(TF_WEIGHTED), TILE_ROW(TF_SIN), {nullptr, nullptr, tile_unit<TF_DROP, 64>}, TILE_ROW(TF_ENS)};
+  const auto fn = unit[f][WP == 16 ? 0 : WP == 32 ? 1 : 2];
+  if (!fn) { set_error("fused engine: no kernel of family %d at padded width %d", (int)f, WP); return PINN_ERR_UNSUPPORTED; }
+  return fn(a);
 }
-template int launch_fused_batch<16>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
-template int launch_fused_batch<32>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
-// ... and their external-adjoint siblings: pinn_fused_batch_adj_w{16,32}_k{3,4}.hip
-template <int WP, int K1>
-int launch_fused_batch_adj_k(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s);
-template <int WP>
-int launch_fused_batch_adj(int W, int d_in, int K1, const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  return K1 == 3 ? launch_fused_batch_adj_k<WP, 3>(W, d_in, P, grid, lds, s) : launch_fused_batch_adj_k<WP, 4>(W, d_in, P, grid, lds, s);
+// (K1 = 3, else the K1 = 4 unit; the corrected radiation stress has K1 = 3 units only)
+#define BATCH_ROW(F, K4) {{batch_unit<F, 16, 3>, batch_unit<F, 16, K4>}, {batch_unit<F, 32, 3>, batch_unit<F, 32, K4>}}
+int launch_batch(BatchFamily f, int WP, int K1, const BatchLaunch& a) {
+  static int (*const unit[BF_COUNT][2][2])(const BatchLaunch&) = {BATCH_ROW(BF_LOSS, 4), BATCH_ROW(BF_ADJ, 4), BATCH_ROW(BF_PEC, 3)};
+  return unit[f][WP == 16 ? 0 : 1][K1 == 3 ? 0 : 1](a);
 }
-template int launch_fused_batch_adj<16>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
-template int launch_fused_batch_adj<32>(int, int, int, const FusedParams&, int, size_t, hipStream_t);
-// ... and the corrected-radiation-stress loss instances (EPI_PEC, K1 = 3): pinn_fused_batch_pec_w{16,32}_k3.hip
-template <int WP, int K1>
-int launch_fused_batch_pec_k(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s);
-template <int WP>
-int launch_fused_batch_pec(int W, int d_in, const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  return launch_fused_batch_pec_k<WP, 3>(W, d_in, P, grid, lds, s);
-}
-template int launch_fused_batch_pec<16>(int, int, const FusedParams&, int, size_t, hipStream_t);
-template int launch_fused_batch_pec<32>(int, int, const FusedParams&, int, size_t, hipStream_t);
 bool fused_batch_has_kernel(int WP, int W, int d_in, int K1, int act) {
   return (WP == 16 || WP == 32) && W >= 1 && d_in <= 8 && (K1 == 3 || K1 == 4) && act == PINN_ACT_TANH;
 }
 
 bool fused_supports(const Net& n, bool want_grad) {
   if (n.L + 1 > MAX_LOCKS) return false;
-  // the sine first layer: exactly where a k_fused<.., PINN_ACT_SIN_TANH, EPI_GENERIC> instance exists (pinn_fused_sin.inc) —
+  // the sine first layer: exactly where a k_fused<.., PINN_ACT_SIN_TANH, EPI_GENERIC> instance exists (pinn_fused_tile.hip, TF_SIN) —
   // K1 in {1, 3, 4}, no dropout, the tile kernel (never the cooperative or the batch kernel: use_coop, fused_batch_has_kernel)
   if (n.act == PINN_ACT_SIN_TANH &&
       (n.drop_p > 0.f || n.prec != PINN_PREC_F32 || n.fused_kernel == FUSED_KERNEL_COOP || n.fused_kernel == FUSED_KERNEL_BATCH ||
@@ -865,8 +818,8 @@ enum TileCond {
 const TileCond ADJ_CONDS[] = {T_SINE, T_DROPOUT, T_PREC, T_K1, T_WIDTH, T_IO, T_DEPTH, T_END};
 const TileCond FIELD_CONDS[] = {T_SINE, T_DROPOUT, T_PREC, T_K23, T_WIDTH, T_IO, T_DEPTH, T_END};
 const TileCond LOSS_CONDS[] = {T_FORCED, T_PREC, T_WIDTH, T_SINE, T_LEAKY, T_DROPOUT, T_K23, T_IO, T_DEPTH, T_END};
-struct TileFamily { const char* noun; const char* kernel; const TileCond* conds; };
-const TileFamily TILE_FAMILIES[] = {   // indexed by TILE_*
+struct TileRule { const char* noun; const char* kernel; const TileCond* conds; };
+const TileRule TILE_RULES[] = {   // indexed by TILE_*
     {"external-adjoint", "external-adjoint kernel", ADJ_CONDS},
     {"field", "field kernel", FIELD_CONDS},
     {"coefficient", "coefficient kernel on the fused engine", LOSS_CONDS},
@@ -896,7 +849,7 @@ const char* tile_cond_reason(TileCond c, const Net& n) {
 
 const char* fused_tile_refusal(int family, const Net& n) {
   static thread_local char why[192];
-  const TileFamily& f = TILE_FAMILIES[family];
+  const TileRule& f = TILE_RULES[family];
   for (const TileCond* c = f.conds; *c != T_END; ++c)
     if (const char* fmt = tile_cond_reason(*c, n)) {
       snprintf(why, sizeof(why), fmt, *c == T_FORCED ? f.noun : f.kernel);
@@ -1233,13 +1186,7 @@ int fused_ensemble_loss(const Net& n, const LossReq& rq, int M, int flags, const
       set_error("hipMemsetAsync failed"); return PINN_ERR_LAUNCH;
     }
   }
-  int rc;
-  switch (g.WP) {
-    case 16: rc = launch_fused_ens<16>(n.K1, P, e.gx, M, e.lds, s); break;
-    case 32: rc = launch_fused_ens<32>(n.K1, P, e.gx, M, e.lds, s); break;
-    default: rc = launch_fused_ens<64>(n.K1, P, e.gx, M, e.lds, s); break;
-  }
-  if (rc) return rc;
+  if (int rc = launch_tile(TF_ENS, g.WP, TileLaunch{n.K1, true, P, dim3(e.gx, M), e.lds, s})) return rc;
   const int64_t np = n.n_params();
   const int n_terms = (P.loss_kind & 1) ? rq.n_terms : 0, n_cols = (P.loss_kind & 2) ? rq.n_cols : 0;
   const EnsFinish f{(const float*)P.wg_grads, (const float*)P.wg_sums, rq.sums, rq.mse_sums, rq.grad};

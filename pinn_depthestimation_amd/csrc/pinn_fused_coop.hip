@@ -1,25 +1,21 @@
 // pinn_fused_coop.hip — instantiations of the cooperative (four waves per tile) fused kernel for
 // small point sets (fused_coop_kernel.h); hidden width padded to 64
 #include <type_traits>
+#include "fused_launch.h"
 #include "fused_coop_kernel.h"
 
 namespace pinn {
 
 template <int K1, bool GRAD, int ACT>
 static int launch_coop_act(const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  auto kern = k_fused_coop<K1, GRAD, ACT>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(COOP_THREADS), lds, s, P);
-  return check_launch("fused cooperative kernel");
+  return launch_kernel(k_fused_coop<K1, GRAD, ACT>, dim3(grid), COOP_THREADS, lds, s, P, "fused cooperative kernel");
 }
 
 // residual-only gradient kernels with the epilogue specialised to one residual family (fused_kernel.h, EPI)
 template <int K1, int EPI>
 static int launch_coop_special(const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  auto kern = k_fused_coop<K1, true, PINN_ACT_TANH, EPI>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(COOP_THREADS), lds, s, P);
-  return check_launch("fused cooperative kernel (specialised epilogue)");
+  return launch_kernel(k_fused_coop<K1, true, PINN_ACT_TANH, EPI>, dim3(grid), COOP_THREADS, lds, s, P,
+                       "fused cooperative kernel (specialised epilogue)");
 }
 
 template <int K1, bool GRAD>

@@ -1,9 +1,11 @@
 """kernel_resources.py LOG [LOG2]: the register / scratch / spill / LDS lines of every kernel in a compiler log made with
-    make -C pinn_depthestimation_amd/csrc -B -j1 HIPCC="/opt/rocm/bin/hipcc -Rpass-analysis=kernel-resource-usage" \\
-         pinn_fused_w16.o pinn_fused_w32.o pinn_fused_w64.o pinn_fused_adj_w16.o pinn_fused_adj_w32.o pinn_fused_adj_w64.o 2> LOG
-(-j1: parallel compiles interleave their remarks).  With one log: one line per kernel.  With two (the same command in a
-checkout of the parent commit and in this tree): every kernel of LOG whose lines differ in LOG2, then the counts —
-the check that a change to fused_kernel.h left the existing instances as the compiler made them before."""
+    make -C pinn_depthestimation_amd/csrc -B -j16 -Otarget HIPCC="/opt/rocm/bin/hipcc -Rpass-analysis=kernel-resource-usage" \\
+         all > LOG 2>&1
+(-Otarget keeps each unit's remarks together; without it parallel compiles interleave them and -j1 is needed.  Name
+objects instead of `all`, e.g. pinn_fused_w64.o pinn_fused_adj_w64.o, for the units of interest only.)  With one log: one
+line per kernel.  With two (the same command in a checkout of the parent commit and in this tree): every kernel of LOG
+whose lines differ in LOG2, then the counts — the check that a change to fused_kernel.h, or to how its instances are
+built, left the existing instances as the compiler made them before."""
 import collections, re, sys
 
 KEYS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "SGPRs Spill", "VGPRs Spill", "Occupancy [waves/SIMD]",
