@@ -15,7 +15,10 @@
 //                  out of it with ds_read_b64_tr_b16 (the hardware transpose: contraction over points).  Eight waves.
 //
 //   k_chain_first_bwd / k_chain_last_fwd / k_chain_last_bwd: the thin first (d_in <= 3) and last (d_out <= 4) layers as
-//                  streaming kernels on the same jets (the first layer's forward is part of k_chain_fwd8).
+//                  streaming kernels on the same jets (the first layer's forward is part of k_chain_fwd8).  With more
+//                  inputs or outputs the thin layers run on wide_kernel.h's per-layer kernels, fp32 MFMAs on these
+//                  bf16 jets (pinn_wide_units.hip, the bf16 units).  The launch sequence: bf16_chunk in pinn_wide.hip;
+//                  the instances and their LDS sizes: pinn_chain_units.hip.
 //
 // HBM traffic per point and hidden layer: 2 KB (a written) + 2 + 2 (a, zbar in the reverse chain) + 4 (weight
 // gradient) = 10 KB, against 16 KB for one launch per layer; weights come from L2 once per workgroup and layer.
@@ -24,7 +27,7 @@
 // operand layout" carries over from fused_kernel.h with K = 32: lane (p = lane&15 point, q = lane>>4) holds, for
 // k-step s, the 8 values j = 4h + r  <->  unit 32s + 16h + 4q + r, i.e. register r of accumulator tiles
 // MT = 2s + h — two accumulator tiles, converted pairwise to bf16, ARE the B operand of k-step s.  The weights are
-// packed to match (k index permuted inside each k-step, pinn_chain.hip k_chain_pack).
+// packed to match (k index permuted inside each k-step, pinn_wide.hip k_chain_pack).
 //
 // Precision: bf16 operands, fp32 accumulate.  Jets (a_l, zbar_l) carry 8 significant bits.  The WEIGHTS are
 // split hi + lo (two bf16, two MFMAs): rounding the weights themselves to bf16 moves this loss by 1.1e-2 and its
@@ -1143,12 +1146,5 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void k_chain_last_fwd(const FusedP
     P.wg_sums[((int64_t)Lp.sums_slot + blockIdx.x) * MAX_SUMS + threadIdx.x] = v;
   }
 }
-
-template <int NTW> int launch_chain_fwd8(int K1, bool fold_first, const ChainParams& P, int grid, hipStream_t s);
-template <int NTW> int launch_chain_bwd(int K1, const ChainParams& P, int grid, hipStream_t s);
-template <int NTW> int launch_chain_wgrad8(int K1, const ChainParams& P, int grid, hipStream_t s);
-template <int NTW> int launch_chain_first_bwd(int K1, const ChainParams& P, int grid, hipStream_t s);
-template <int NTW> int launch_chain_last_bwd(int K1, const ChainParams& P, int grid, hipStream_t s);
-template <int NTW> int launch_chain_last_fwd(int K1, bool grad, const FusedParams& P, const WideLayer& Lp, int grid, hipStream_t s);
 
 }  // namespace pinn

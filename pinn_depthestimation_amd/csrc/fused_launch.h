@@ -1,29 +1,12 @@
-// fused_launch.h — host side of every launch of the fused engine's kernels: the one launch helper, and the one entry point
+// fused_launch.h — host side of every launch of the fused engine's kernels: the launch helper (launch.h), and the one entry point
 // per kernel through which pinn_fused.hip reaches the translation units that hold the instances (pinn_fused_tile.hip,
 // pinn_fused_batch.hip: one source each, compiled once per unit with the unit named on the command line — Makefile).
 // Host only: nothing here is seen by a kernel.
 #pragma once
-#include <type_traits>
+#include "launch.h"
 #include "fused_kernel.h"
 
 namespace pinn {
-
-// raise the kernel's dynamic-LDS limit if need be, launch, report a failed launch under `what`
-template <class K>
-int launch_kernel(K kern, dim3 grid, int threads, size_t lds_bytes, hipStream_t s, const FusedParams& P, const char* what) {
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_bytes)) return rc;
-  hipLaunchKernelGGL(kern, grid, dim3(threads), lds_bytes, s, P);
-  return check_launch(what);
-}
-
-// f(std::integral_constant<int, K>) for the K of KS that equals K1; NO_INSTANCE if none does
-constexpr int NO_INSTANCE = -(1 << 20);
-template <int... KS, class F>
-int with_k1(int K1, F f) {
-  int rc = NO_INSTANCE;
-  (void)((K1 == KS && (rc = f(std::integral_constant<int, KS>{}), true)) || ...);
-  return rc;
-}
 
 // ---- the tile kernel (fused_kernel.h: k_fused, k_fused_ens) -----------------------------------------------------------------
 // A family is a set of instances with one epilogue / activation / grid shape, in translation units of its own per padded

@@ -32,8 +32,8 @@ template <int KS, int KS0, int SINK>
 int bgo(const BatchLaunch& a) {
   constexpr int T = batch_tiles(BATCH_WP, BATCH_K1);
   return a.P.batch_T == 1
-             ? launch_kernel(k_fused_batch<BATCH_WP, KS, KS0, BATCH_K1, 1, SINK, PINN_ACT_TANH, BATCH_EPI>, dim3(a.grid), BATCH_THREADS, a.lds_bytes, a.s, a.P, BATCH_WHAT)
-             : launch_kernel(k_fused_batch<BATCH_WP, KS, KS0, BATCH_K1, T, SINK, PINN_ACT_TANH, BATCH_EPI>, dim3(a.grid), BATCH_THREADS, a.lds_bytes, a.s, a.P, BATCH_WHAT);
+             ? launch_kernel(k_fused_batch<BATCH_WP, KS, KS0, BATCH_K1, 1, SINK, PINN_ACT_TANH, BATCH_EPI>, dim3(a.grid), BATCH_THREADS, a.lds_bytes, a.s, BATCH_WHAT, a.P)
+             : launch_kernel(k_fused_batch<BATCH_WP, KS, KS0, BATCH_K1, T, SINK, PINN_ACT_TANH, BATCH_EPI>, dim3(a.grid), BATCH_THREADS, a.lds_bytes, a.s, BATCH_WHAT, a.P);
 }
 // KS0 = 1 or 2 first-layer k-steps (d_in <= 4 or not); a gradient copy per wave in LDS, or atomics into shared copies
 template <int KS>

@@ -8,14 +8,14 @@ namespace pinn {
 
 template <int K1, bool GRAD, int ACT>
 static int launch_coop_act(const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  return launch_kernel(k_fused_coop<K1, GRAD, ACT>, dim3(grid), COOP_THREADS, lds, s, P, "fused cooperative kernel");
+  return launch_kernel(k_fused_coop<K1, GRAD, ACT>, dim3(grid), COOP_THREADS, lds, s, "fused cooperative kernel", P);
 }
 
 // residual-only gradient kernels with the epilogue specialised to one residual family (fused_kernel.h, EPI)
 template <int K1, int EPI>
 static int launch_coop_special(const FusedParams& P, int grid, size_t lds, hipStream_t s) {
-  return launch_kernel(k_fused_coop<K1, true, PINN_ACT_TANH, EPI>, dim3(grid), COOP_THREADS, lds, s, P,
-                       "fused cooperative kernel (specialised epilogue)");
+  return launch_kernel(k_fused_coop<K1, true, PINN_ACT_TANH, EPI>, dim3(grid), COOP_THREADS, lds, s,
+                       "fused cooperative kernel (specialised epilogue)", P);
 }
 
 template <int K1, bool GRAD>

@@ -20,7 +20,7 @@ constexpr int WP_ = FUSED_WP;
 
 template <class K>
 int go(K kern, const TileLaunch& a, const char* what) {
-  return launch_kernel(kern, a.grid, FUSED_THREADS, a.lds_bytes, a.s, a.P, what);
+  return launch_kernel(kern, a.grid, FUSED_THREADS, a.lds_bytes, a.s, what, a.P);
 }
 // a forward-only instance
 template <int K1, int ACT, int EPI>

@@ -12,17 +12,17 @@ The rounding points, as read from pinn_depthestimation_amd/csrc (l = 1 .. L-1 nu
 jet (value a, tangents t_c) after hidden layer l; bf() rounds fp32 to bf16, round to nearest even):
 
   hidden weights       hi = bf(w), lo = bf(w - hi); both chains multiply by hi AND lo, fp32 accumulate.  The reverse chain's
-                       W^T is split element by element the same way.                    pinn_wide.hip:146-150 (k_chain_pack)
+                       W^T is split element by element the same way.                    pinn_wide.hip (k_chain_pack)
                        forward MFMAs chain_kernel.h:536-537, reverse :739-742.  Biases stay fp32 (:472, bias_lds :340).
   output layer forward W_L split hi + lo in the kernel, product on the stored bf16 a_L, bias and accumulate fp32.
                                                                                           chain_kernel.h:1088-1092, 1116-1117
-  first layer, folded  (d_in <= 3 and L >= 2, pinn_wide.hip:219): z = W_0 x + b_0 in fp32 from the unrounded X and W_0,
+  first layer, folded  (d_in <= 3 and L >= 2, bf16_chunk in pinn_wide.hip): z = W_0 x + b_0 in fp32 from the unrounded X and W_0,
                        a = tanh(z), t_c = (1 - a^2) W_0[:, dir_col[c]] with 1 - a^2 from the unrounded a; a and t_c are
                        rounded when they become the first MFMA operand, which is also what is stored as a_1.
                                                                                           chain_kernel.h:438-443 (make_a1)
-  first layer, wide    (d_in > 3, or L == 1): fp32 MFMA (BF16 = false in pinn_wide_launch.inc:35), activate() takes 1 - a^2
+  first layer, wide    (d_in > 3, or L == 1): fp32 MFMA (THIN_FIRST_FWD in pinn_wide_units.hip), activate() takes 1 - a^2
                        from the unrounded a (fused_kernel.h:207-211), the jet is rounded by the store (FMT_OUT16,
-                       wide_kernel.h:111).  Same rounding points as the folded form; another tanh (tanh_f32).
+                       wide_kernel.h jet_st).  Same rounding points as the folded form; another tanh (tanh_f32).
   hidden layer forward z + b in fp32, a = 1 - 2 / (exp2(2 log2(e) z) + 1), 1 - a^2 from the UNROUNDED a, tangents scaled by
                        it, only then a and t_c are rounded: the next operand and the stored a_l are the same registers.
                                                                                           chain_kernel.h:476-487 (act)
@@ -31,14 +31,14 @@ jet (value a, tangents t_c) after hidden layer l; bf() rounds fp32 to bf16, roun
                        that one rounded value is both stored (:730) and multiplied by W^T (:739-742).  abar stays in the fp32
                        accumulators between layers (:673); at l = L-1 it is read from the bf16 abar_L (:672).  abar_1 is
                        stored as bf16 (:767).
-  output layer reverse abar_L = bf(W_L^T G) from the fp32, unsplit W_L (chain_kernel.h:1038; d_out > 4: k_wide_bwd with
-                       BF16 = false and FMT_OUT16, pinn_wide_launch.inc:85).  dW_L = sum G (x) a_L on the bf16 a_L with fp32 G
-                       (:1043; wide: k_wide_wgrad, FMT_IN16), db_L = sum_p G_0 in fp32 (:1024; wide_kernel.h:464).
+  output layer reverse abar_L = bf(W_L^T G) from the fp32, unsplit W_L (chain_kernel.h:1038; d_out > 4: k_wide_bwd on fp32
+                       MFMAs with FMT_OUT16, THIN_LAST_BWD in pinn_wide_units.hip).  dW_L = sum G (x) a_L on the bf16 a_L with fp32 G
+                       (:1043; wide: k_wide_wgrad, FMT_IN16), db_L = sum_p G_0 in fp32 (:1024; k_wide_wgrad's bs).
   hidden gradients     k_chain_wgrad8: dW_l = sum zbar_l (x) a_l on the stored bf16 zbar_l and a_l (:831, :881); db_l is the
                        sum of the stored bf16 zbar_l's value quantity (:869-873).
   first layer reverse  folded (k_chain_first_bwd): zbar from the bf16 abar_1 and a_1 in fp32 (:959-964), NOT rounded: dW_0
                        and db_0 are fp32 sums of it (:965-976).  Wide (d_in > 3 or L == 1): k_wide_bwd writes zbar_0 as bf16
-                       (pinn_wide_launch.inc:79, FMT_OUT16) and k_wide_wgrad reads that (FMT_GIN16, :115): dW_0 and db_0
+                       (THIN_FIRST_BWD in pinn_wide_units.hip, FMT_OUT16) and k_wide_wgrad reads that (THIN_FIRST_WGRAD, FMT_GIN16): dW_0 and db_0
                        are sums of the ROUNDED zbar_0.
   residual epilogue    fp32 on the fp32 outputs (loss_epilogue, chain_kernel.h:1121): no bf16 anywhere.
 
@@ -122,7 +122,7 @@ class Case:
 
 
 def branches(c, kind, cus):
-    """Which path of run_w (pinn_wide.hip:201-283) a call takes: a restatement of its conditions."""
+    """Which path of bf16_chunk (pinn_wide.hip) a call takes: a restatement of its conditions."""
     N = c.N(cus)
     nh = c.L - 1
     n_tiles = (N + 15) // 16

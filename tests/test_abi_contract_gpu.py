@@ -19,7 +19,7 @@ entry was run on poison):
                                  written by the pass or zeroed by the launch code, and only those are reduced).  The
                                  locks of fused_kernel.h:370-382 live in LDS and the kernel zeroes them; nothing else
                                  in the layout is an integer.
-  wide_workspace_bytes           packed fp32 / bf16 weights and fragment planes (written by k_wide_pack / k_chain_pack),
+  wide_workspace_bytes           packed fp32 weights and, in bf16 mode, fragment planes (written by k_wide_pack / k_chain_pack),
                                  fp32 or bf16 jets and adjoints (written layer by layer before the next layer reads
                                  them), the partial-sum table (zeroed per chunk): floats and bf16 only.
   generic_workspace_bytes        a_0..a_L, out, two adjoint buffers, per-block partial sums: floats, each written by

@@ -21,7 +21,11 @@ CASES = {
 
 
 def make(name, N, seed=4321):
-    d_in, d_out, L, W, gc, res, inn, outn = CASES[name]
+    return make_case(CASES[name], N, seed)
+
+
+def make_case(case, N, seed=4321):
+    d_in, d_out, L, W, gc, res, inn, outn = case
     g = torch.Generator().manual_seed(seed)
     params = O.init_params(O.layer_sizes(d_in, L, W, d_out), "xavier", g)
     if res == "physics_equation":
@@ -119,3 +123,40 @@ def test_wide_bf16_mfma_mode():
     from pinn_depthestimation_amd import PinnError
     with pytest.raises(PinnError, match="bf16"):
         Engine(NetDesc(3, 4, 8, 64, (0, 1, 2), precision=PREC_BF16)).forward(torch.zeros(29636, device="cuda"), Xd)
+
+
+def test_wide_bf16_unfolded_first_layer_width_129():
+    """bf16 mode at padded width 256 with more than three inputs: the first layer is NOT folded into the forward chain kernel
+    (k_chain_fwd8<16, K1, false>), at K1 = 3 through a residual request and at K1 = 1 through the fidelity term (which takes no
+    input derivatives) — the two launcher arms no other test of the wide and chain engines reaches.  The smallest shape that
+    takes them: two hidden layers (one W x W matrix), width 129, N = 17 (a full tile and a partial one), d_in = 4; d_out = 6
+    puts the output layer's reverse pass on the per-layer kernels as well.  Tolerances: test_wide_bf16_mfma_mode's."""
+    from pinn_depthestimation_amd._lib import PREC_BF16
+    N = 17
+    case = (4, 6, 2, 129, (0, 1), "physics_equation", ("x", "y", "a", "b"), ("h", "U", "V", "eta_mean", "Hrms", "k"))
+    params, X, desc, res, inn, outn = make_case(case, N)
+    # the wide engine by name, so that no later dispatch rule can route this shape elsewhere and leave the test passing
+    eng = Engine(desc.with_(engine=ENGINE_WIDE, precision=PREC_BF16))
+    flat, Xd = O.flatten(params).cuda(), X.cuda().contiguous()
+    # K1 = 3: the residual and its gradient
+    spec = ResidualSpec.from_names(res, inn, desc.grad_cols, outn)
+    l64, g64 = oracle_loss_and_grad(params, X, res, inn, outn, desc.grad_cols, torch.float64)
+    scale = torch.full((spec.n_terms,), 1.0 / N, device="cuda")
+    grad = torch.zeros(desc.n_params, device="cuda")
+    sums = eng.residual_loss_grad(spec, scale, flat, Xd, grad)
+    el, eg = abs(float((sums * scale).sum()) - float(l64)) / float(l64), rel_l2(grad.cpu(), g64)
+    print(f"bf16 mode, unfolded first layer, K1 = 3: loss rel err {el:.2e}, grad rel-L2 err {eg:.2e}")
+    assert el < 2e-2 and eg < 5e-2
+    assert el > 1e-6            # it really is the reduced-precision path (as in test_wide_bf16_mfma_mode)
+    # K1 = 1: the fidelity term and its gradient
+    T = torch.rand(N, 2, generator=torch.Generator().manual_seed(2))
+    p = [q.double().requires_grad_(True) for q in params]
+    lo = O.fidelity_loss(p, X.double(), T.double(), [2, 0], [1.0, 3.0])
+    go = O.flat_grad(lo, p)
+    wts = torch.tensor([1.0, 3.0]) / N
+    grad.zero_()
+    sums = eng.mse_loss_grad(flat, Xd, T.cuda(), [2, 0], wts.cuda(), grad)
+    el, eg = abs(float((sums.cpu().double() * wts.double()).sum()) - float(lo)) / float(lo), rel_l2(grad.cpu(), go)
+    print(f"bf16 mode, unfolded first layer, K1 = 1: loss rel err {el:.2e}, grad rel-L2 err {eg:.2e}")
+    assert el < 2e-2 and eg < 5e-2
+    assert el > 1e-6
