@@ -188,6 +188,8 @@ typedef struct pinn_desc {
 /* number of loss terms each residual reports (sums of squares, un-normalised) */
 #define PINN_NS_TERMS 3   /* sum fc^2, sum fm_x^2, sum fm_y^2 */
 #define PINN_PE_TERMS 3   /* sum fc^2, sum fx^2,  sum fy^2  */
+#define PINN_PEW_TERMS 5  /* physics_equation with flags bits 0 and 1 (the wave closure): those three, sum f_d^2, sum f_E^2;
+                             its per-point fields are the same five, (fc, fx, fy, f_d, f_E) */
 #define PINN_CF_TERMS 1   /* sum fc^2 */
 #define PINN_CO_TERMS 3   /* sum fc^2, sum_{x<thr} (h-anchor)^2, count{x<thr} */
 
@@ -202,9 +204,22 @@ typedef struct pinn_residual_spec {
                                       E = rho g Hrms^2 / 8, Sxx = E (2n + 1/2), Syy = E n, n = kh / sinh 2kh, in place of
                                       the reference's E == 0 (physics.py:106); same roles, directions, terms and fields.
                                       Honoured by every entry that takes a spec (engine rules: pinn_residual_loss_grad
-                                      and pinn_residual_fields below).  Bit 0 on the other residuals and all other bits
-                                      are ignored. */
-  float param[4];                  /* continuity_only: param[0]=threshold (25.5), param[1]=anchor (0.75) */
+                                      and pinn_residual_fields below).
+                                      bit 1 with residual_id == PINN_RES_PHYSICS_EQUATION, on top of bit 0: the wave closure —
+                                      two more terms and fields (PINN_PEW_TERMS = 5), with s = k h, G = 9.81,
+                                      omega = param[0] (rad/s), gamma = param[1] (breaker index):
+                                        f_d = G k tanh(s) / omega^2 - 1                   (linear dispersion)
+                                        f_E = d/dx (Hrms^2 c_g) + eps,  c_g = (omega / k) (1/2 + n(s))
+                                        eps = (3 sqrt(pi) / 2) (omega / 2 pi) Hrms^5 / (gamma^2 h^3) [1 - (1 + q^2)^(-5/2)],
+                                        q = Hrms / (gamma h)      (Thornton & Guza 1983, B = 1; the energy equation divided
+                                        by rho g / 8; waves travel along +x, as Sxy = 0 has it)
+                                      k > 0 and h > 0 are the caller's to ensure (non-finite values propagate).  Bit 1
+                                      without bit 0, param[0] <= 0 or param[1] <= 0: PINN_ERR_INVALID, "wave" in the
+                                      message, before any device work.  Engine rules: pinn_residual_loss below; every entry
+                                      that takes a spec serves the request or refuses it with "wave" in the message.
+                                      Bits 0 and 1 on the other residuals and all other bits are ignored. */
+  float param[4];                  /* continuity_only: param[0]=threshold (25.5), param[1]=anchor (0.75);
+                                      physics_equation with flags bit 1: param[0]=omega, param[1]=gamma */
 } pinn_residual_spec;
 
 int32_t pinn_version(void);
@@ -220,6 +235,9 @@ const char* pinn_last_error(void);
  * fields <- (fc, fx, fy).  g[c * 6 + r] <- sum_t scale[t] * d(field_t^2) / dv; with scale or g NULL only the fields are
  * formed and g is left alone.  At kh = 0 the stress ratio takes its limit (n = 1/2, n' = 0, n'' = -2/3). */
 int32_t pinn_pe_corrected_point(const float v[18], const float scale[3], float fields[3], float g[18]);
+/* ... and with the wave closure (spec.flags bits 0 and 1), same conventions: fields <- (fc, fx, fy, f_d, f_E), five scales.
+ * omega <= 0 or gamma <= 0: PINN_ERR_INVALID.  k = 0 or h = 0 give non-finite values, as in the kernels. */
+int32_t pinn_pe_wave_point(const float v[18], float omega, float gamma, const float scale[5], float fields[5], float g[18]);
 
 /* P = sum_l (in_l*out_l + out_l), layers = [d_in] + [width]*n_hidden + [d_out] (train.py:56) */
 int32_t pinn_param_count(const pinn_desc* desc, int64_t* count);
@@ -447,7 +465,16 @@ int32_t pinn_residual_weighted_loss_grad(const pinn_desc* desc, const pinn_resid
  * the small N where the cooperative kernel would serve the plain residual: it has no such instance); the split request is
  * one pass at every width.  LeakyReLU and k = 3 on FUSED are refused (use GENERIC).  Every descriptor whose engine comes out
  * as WIDE — width 65..256 under AUTO or WIDE, bf16 — is refused (use GENERIC).  With dropout_p > 0 AUTO runs the generic
- * engine (the fused dropout instances do not carry the corrected residual) and FUSED is refused. */
+ * engine (the fused dropout instances do not carry the corrected residual) and FUSED is refused.
+ * Wave closure (spec.flags bits 0 and 1, PINN_PEW_TERMS term sums) — the same entries, the same rule with "wave" in every
+ * refusal, and its own instances of the tile kernel only.  GENERIC: any shape, tanh or LeakyReLU, dropout, k = 2 or 3 (the
+ * residual reads directions x and y).  AUTO, FUSED, FUSED_TILE: the tile kernel at every N, for tanh, k = 2, width <= 64,
+ * dropout_p == 0 (never the batch or the cooperative kernel); the split request is one pass at every width.  FUSED_BATCH,
+ * FUSED_COOP, every descriptor whose engine comes out as WIDE, the sine first layer under an explicit FUSED*, and LeakyReLU
+ * or k = 3 on FUSED are refused (use GENERIC).  Dropout and the sine first layer under AUTO run the generic engine.  On the
+ * fused engine at most 7 fidelity columns: the fifth term's partial sum takes the last column's slot (8: refused).
+ * Out of scope, refused with "wave" in the message: the coefficient, weighted, ensemble, balanced-loop and
+ * pinn_adam_loop_ext entries and pinn_residual2_* (nu together with the wave closure).  pinn_residual_coef_count gives 0. */
 int32_t pinn_residual_loss(const pinn_desc* desc, const pinn_residual_spec* spec,
                            const float* params, const float* X, int64_t N,
                            float* term_sums, void* ws, int64_t ws_bytes, void* stream);
@@ -467,7 +494,7 @@ int32_t pinn_residual_loss(const pinn_desc* desc, const pinn_residual_spec* spec
  * Corrected radiation stress (spec.flags bit 0 on physics_equation): k must be 2.  AUTO and FUSED run the tile kernel's own
  * field instances where FUSED serves fields and the network is tanh; LeakyReLU under FUSED is refused ("corrected" in the
  * message), under AUTO it is staged like every GENERIC and WIDE request.  pinn_query_fields_workspace takes the spec and
- * answers for the path the call will take. */
+ * answers for the path the call will take.  The wave closure (bits 0 and 1): the same rule, five fields. */
 #define PINN_NS_FIELDS 3
 #define PINN_PE_FIELDS 3
 #define PINN_CF_FIELDS 2

@@ -23,6 +23,7 @@ PREC_F32, PREC_BF16 = 0, 1
 
 RES_NAVIER_STOKES, RES_PHYSICS_EQUATION, RES_CONTINUITY_FTEMP, RES_CONTINUITY_ONLY = 1, 2, 3, 4
 RES_TERMS = {RES_NAVIER_STOKES: 3, RES_PHYSICS_EQUATION: 3, RES_CONTINUITY_FTEMP: 1, RES_CONTINUITY_ONLY: 3}
+PEW_TERMS = 5      # pinn_hip.h: PINN_PEW_TERMS, the terms and fields of physics_equation with the wave closure (flags = 3)
 RES_COEFS = {RES_NAVIER_STOKES: ("gamma_b",), RES_PHYSICS_EQUATION: ("Cd",), RES_CONTINUITY_FTEMP: (), RES_CONTINUITY_ONLY: ()}   # pinn_residual_coef_*: names, in coef[] order
 RES_FIELDS = {RES_NAVIER_STOKES: 3, RES_PHYSICS_EQUATION: 3, RES_CONTINUITY_FTEMP: 2, RES_CONTINUITY_ONLY: 2}   # pinn_residual_fields' rows
 
@@ -142,6 +143,8 @@ _SIGNATURES = {
     "pinn_last_error": (C.c_char_p, []),
     "pinn_dropout_keep": (C.c_int32, [C.c_uint32, C.c_int32, C.c_int32, C.c_int64, C.c_float]),
     "pinn_pe_corrected_point": (C.c_int32, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pinn_pe_wave_point": (C.c_int32, [C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float)]),
     "pinn_param_count": (C.c_int32, [C.POINTER(PinnDesc), C.POINTER(C.c_int64)]),
     "pinn_query_workspace": (C.c_int32, [C.POINTER(PinnDesc), C.c_int64, C.POINTER(C.c_int64)]),
     "pinn_forward": (C.c_int32, [C.POINTER(PinnDesc), _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),

@@ -439,13 +439,14 @@ def _corrected_is_served(model, handle) -> bool:
 
 
 def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequence[torch.Tensor], corrected: bool = False,
-                   nu: float = 0.0):
+                   nu: float = 0.0, wave_omega: float = 0.0, wave_gamma: float = 0.42):
     """Return the fused loss tensor if every argument is recognisably (input column of /
     output column of) one DNN.forward call, else None.  corrected=True (physics_equation only): the corrected
     radiation stress, hard-wired in the kernels (ResidualSpec.corrected); None as well where the engine that would run
     the call does not serve it.  nu != 0 (Navier_Stokes, physics_equation): the lateral-mixing term -nu lap(U), hard-wired
     on the second-order jets (pinn_residual2_loss_grad: any shape, tanh or LeakyReLU, dropout, plain or corrected); None
-    where the forward call differentiates other inputs than the residual's directions."""
+    where the forward call differentiates other inputs than the residual's directions.  wave_omega > 0 (with corrected=True):
+    the wave closure, hard-wired as well (ResidualSpec.wave_omega), served where the corrected stress is."""
     handle = None
     out_col: List[int] = []
     for o in out_vars:
@@ -472,7 +473,8 @@ def fused_residual(name: str, in_vars: Sequence[torch.Tensor], out_vars: Sequenc
             raise PinnError(f"nu is the lateral mixing of a momentum equation; residual {name!r} has none")
         if not (nu > 0.0 and nu != float("inf")):
             raise PinnError(f"nu = {nu}: the eddy viscosity must be finite and >= 0")
-    spec = ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected), nu=nu)
+    spec = ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected), nu=nu,
+                        wave_omega=float(wave_omega or 0.0), wave_gamma=float(wave_gamma))
     model = handle.model
     if nu != 0:
         if len(handle.grad_cols) != len(dir_of) or len(set(dir_of)) != len(dir_of):

@@ -64,6 +64,18 @@ struct AdamScalars { float w1, b2, w2, eps, step_size, bc2_sqrt; };   // 1 - b1,
 // ResPhysicsEquationCorrected) travels inside the library as a residual id of its own: check_spec (pinn_abi.hip) writes it
 // into the NORMALISED spec, no caller can pass it and pinn_hip.h does not know it.
 constexpr int RES_PE_CORRECTED = 5;
+// ... and bits 0 and 1 together (the corrected residual closed by the dispersion relation and the wave-energy balance,
+// residuals.h: ResPhysicsEquationWave; param[0] = omega, param[1] = gamma) the same way
+constexpr int RES_PE_WAVE = 6;
+// the fused engine's partial-sum rows keep the fifth term's sum in the slot of the eighth fidelity column (fused_kernel.h, term_slot)
+constexpr int WAVE_MAX_COLS = PINN_MAX_ROLES - 1;
+// either of the two: what the engines serve alike (the engine rule, the split request at every width, no cooperative kernel)
+inline bool is_pe_closure(int residual_id) { return residual_id == RES_PE_CORRECTED || residual_id == RES_PE_WAVE; }
+// how a refusal names the request's closure (flags: the caller's spec.flags)
+inline const char* pe_closure_name(bool wave) {
+  return wave ? "the wave closure (spec.flags bits 0 and 1: corrected radiation stress, dispersion and wave-energy terms)"
+              : "the corrected radiation stress (spec.flags bit 0)";
+}
 
 // what a loss call asks the engines for
 // torch.optim.Adam's update folded into the kernel that finishes a loss + gradient pass (pinn_loss_grad_adam_step)

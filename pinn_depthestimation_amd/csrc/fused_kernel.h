@@ -40,6 +40,12 @@ constexpr int TB_FLOATS = 256;                // one 16x16 fp32 block, XOR-swizz
 constexpr int TB_PER_WAVE = 8;                // 4 pads for the Zbar tiles + 4 for the A tiles of one quantity
 constexpr int MAX_SUMS = 12;               // residual terms at [0,4), fidelity columns at [4,12)
 constexpr int MSE_SUM0 = 4;
+// The ONE term -> slot rule of a row of partial sums: terms [0, MSE_SUM0) in their own slots; a residual with more terms (the
+// wave closure's fifth) fills the row from its END, behind the fidelity columns, which then have one slot fewer
+// (WAVE_MAX_COLS, common.h).  Used by the epilogue that adds into the row and by everything that reduces it (pinn_fused.hip:
+// finish_sums2, the reduce_sums calls).  Every residual with at most MSE_SUM0 terms sees terms at [0, n_terms) as before.
+__host__ __device__ constexpr int term_slot(int t) { return t < MSE_SUM0 ? t : MAX_SUMS - 1 - (t - MSE_SUM0); }
+static_assert(term_slot(PINN_PEW_TERMS - 1) == MSE_SUM0 + WAVE_MAX_COLS, "the fifth term's slot is the eighth column's");
 
 struct FusedParams {
   int d_in, d_out, L, act;
@@ -769,11 +775,13 @@ __device__ __forceinline__ void residual_tile(const FusedParams& P, const f4 (&o
   for (int t = 0; t < NT; ++t) sc[t] = GRAD ? P.scale[t] : 0.f;
   if constexpr (std::is_same<RES, ResContinuity>::value)
     RES::template eval<GRAD>(v, sc, g, sq, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
+  else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value)
+    RES::template eval<GRAD>(v, sc, g, sq, P.thr, P.anchor);      // (omega, gamma: set_residual_roles puts spec.param[0..1] there)
   else
     RES::template eval<GRAD>(v, sc, g, sq);
   if (valid && q == 0 && primary) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) sums[t] += sq[t];
+    for (int t = 0; t < NT; ++t) sums[term_slot(t)] += sq[t];
   }
   if constexpr (GRAD) scatter_adjoint<K1, 1 + ND, NR>(tb, g, sm, G, valid, p, q);
 }
@@ -810,7 +818,8 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 // (field_epilogue below) and nothing else happens: no sums, no Y / dY stores, no adjoint, no reverse sweep.
 // EPI_PEC: the loss epilogue with the residual family fixed to ResPhysicsEquationCorrected (pec_epilogue below): serves what
 // EPI_GENERIC serves (residual, residual + fidelity columns, split mode) but stores no Y / dY.  EPI_FIELD_PEC: EPI_FIELD
-// for that residual.  Both are compile-time choices with translation units of their own (the pec units of
+// for that residual.  EPI_WAVE / EPI_FIELD_WAVE: the same pair for ResPhysicsEquationWave (the wave units of
+// pinn_fused_tile.hip; no batch instances).  All are compile-time choices with translation units of their own (the pec units of
 // pinn_fused_tile.hip and pinn_fused_batch.hip), so the generic epilogues do not grow by a branch.
 // EPI_COEF (pinn_residual_coef_loss_grad): the EPI_NS / EPI_PE epilogue with the residual's closure coefficient read from
 // a device array (coef_epilogue below) and its gradient summed beside the term sums; translation units of its own too
@@ -819,7 +828,7 @@ __device__ __forceinline__ void build_scatter_maps(const FusedParams& P, int q, 
 // and weighted term (weighted_epilogue below), and an optional store of the signed fields; translation units of its own
 // (pinn_fused_tile.hip, TF_WEIGHTED).
 constexpr int EPI_GENERIC = 0, EPI_NS = 1, EPI_PE = 2, EPI_CONT = 3, EPI_ADJ = 4, EPI_FIELD = 5, EPI_PEC = 6, EPI_FIELD_PEC = 7,
-              EPI_COEF = 8, EPI_WEIGHTED = 9;
+              EPI_COEF = 8, EPI_WEIGHTED = 9, EPI_WAVE = 10, EPI_FIELD_WAVE = 11;
 constexpr int COEF_SUM = 3;   // EPI_COEF: the term slot of [0, MSE_SUM0) that carries gc[0] (PINN_NS_TERMS = PINN_PE_TERMS = 3 leave it free)
 
 // The mirror of the generic epilogue's Y / dY store: lane (p, q), register r of G[c][0] is output o = 4q + r of point pt;
@@ -853,6 +862,8 @@ __device__ __forceinline__ void field_tile(const FusedParams& P, const f4 (&out)
   }
   if constexpr (std::is_same<RES, ResContinuity>::value)
     RES::fields(v, f, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
+  else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value)
+    RES::fields(v, f, P.thr, P.anchor);
   else
     RES::fields(v, f);
   if (valid && q == 0) {
@@ -978,7 +989,9 @@ __device__ __forceinline__ void weighted_epilogue(const FusedParams& P, const f4
 
 // EPI_PEC: loss_epilogue_impl's generic part (below) with ONE residual family and without the output stores — the split
 // rule and the fidelity columns are its lines, repeated here because that function must stay as the compiler sees it today.
-template <int K1, bool GRAD, bool SPLIT>
+// EPI_WAVE: the same epilogue with RES = ResPhysicsEquationWave (five terms: residual_tile's term_slot rule; at most
+// WAVE_MAX_COLS fidelity columns, which the host checks).
+template <int K1, bool GRAD, bool SPLIT, class RES = ResPhysicsEquationCorrected>
 __device__ __forceinline__ void pec_epilogue(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
                                              float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
                                              const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
@@ -988,7 +1001,7 @@ __device__ __forceinline__ void pec_epilogue(const FusedParams& P, const f4 (&ou
   for (int c = 0; c < K1; ++c) G[c][0] = f4{0.f, 0.f, 0.f, 0.f};
   const bool valid_r = SPLIT ? (valid && pt < P.n_split) : valid;
   const bool valid_m = SPLIT ? (valid && pt >= P.n_split) : valid;
-  if (P.loss_kind & 1) residual_tile<ResPhysicsEquationCorrected, K1, GRAD>(P, out, G, sums, sm, tb, valid_r, false, p, q);
+  if (P.loss_kind & 1) residual_tile<RES, K1, GRAD>(P, out, G, sums, sm, tb, valid_r, false, p, q);
   if (P.loss_kind & 2) {
     float gm[1][PINN_MAX_ROLES];
 #pragma unroll
@@ -1012,8 +1025,8 @@ __device__ __forceinline__ void loss_epilogue_impl(const FusedParams& P, const f
                                               const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
                                               int64_t ptc, bool valid, int p, int q, bool primary = true) {
   static_assert(EPI != EPI_ADJ, "EPI_ADJ has no epilogue: k_fused calls load_adjoint instead");
-  static_assert(EPI != EPI_FIELD && EPI != EPI_FIELD_PEC, "EPI_FIELD has its own epilogue: k_fused calls field_epilogue instead");
-  static_assert(EPI != EPI_PEC, "EPI_PEC has its own epilogue: loss_epilogue calls pec_epilogue instead");
+  static_assert(EPI != EPI_FIELD && EPI != EPI_FIELD_PEC && EPI != EPI_FIELD_WAVE, "EPI_FIELD has its own epilogue: k_fused calls field_epilogue instead");
+  static_assert(EPI != EPI_PEC && EPI != EPI_WAVE, "EPI_PEC has its own epilogue: loss_epilogue calls pec_epilogue instead");
   // EPI != 0: an epilogue specialised to ONE residual family, residual loss only, no output stores.
   // The generic epilogue keeps every family, the fidelity columns and the Y/dY stores behind runtime
   // switches; at width 64 that costs 146 spilled SGPRs (372 v_readlane per tile) against 4 with the
@@ -1092,11 +1105,12 @@ __device__ __forceinline__ void loss_epilogue(const FusedParams& P, const f4 (&o
                                               float (&sums)[MAX_SUMS], const ScatterMap<K1>& sm,
                                               const ScatterMap<K1>& sm_mse, float* __restrict__ tb, int64_t pt,
                                               int64_t ptc, bool valid, int p, int q, bool primary = true) {
-  if constexpr (EPI == EPI_PEC) {     // (primary: the cooperative kernel's, which has no such instance)
+  if constexpr (EPI == EPI_PEC || EPI == EPI_WAVE) {     // (primary: the cooperative kernel's, which has no such instance)
+    typedef typename std::conditional<EPI == EPI_WAVE, ResPhysicsEquationWave, ResPhysicsEquationCorrected>::type RES;
     if constexpr (SPLIT_OK) {
-      if (P.n_split >= 0) { pec_epilogue<K1, GRAD, true>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q); return; }
+      if (P.n_split >= 0) { pec_epilogue<K1, GRAD, true, RES>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q); return; }
     }
-    pec_epilogue<K1, GRAD, false>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+    pec_epilogue<K1, GRAD, false, RES>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
     return;
   } else if constexpr (SPLIT_OK && EPI == EPI_GENERIC) {
     if (P.n_split >= 0) {
@@ -1104,7 +1118,7 @@ __device__ __forceinline__ void loss_epilogue(const FusedParams& P, const f4 (&o
       return;
     }
   }
-  if constexpr (EPI != EPI_PEC) loss_epilogue_impl<K1, GRAD, false, EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q, primary);
+  if constexpr (EPI != EPI_PEC && EPI != EPI_WAVE) loss_epilogue_impl<K1, GRAD, false, EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q, primary);
 }
 
 // Diagnostic build only (-DPINN_DIAG): s_memtime stamps per phase, printed by wave 0 of block 0.
@@ -1158,6 +1172,8 @@ __global__ __launch_bounds__(FUSED_THREADS, WP == 16 ? FUSED_W16_WAVES : FUSED_W
   static_assert(EPI != EPI_FIELD || (!GRAD && !LDSACC && KRO == 0 && !DROP), "field instances: forward only, natural unit order, no dropout");
   static_assert(EPI != EPI_FIELD_PEC || (!GRAD && !LDSACC && KRO == 0 && !DROP && K1 == 3), "field instances: forward only, natural unit order, no dropout");
   static_assert(EPI != EPI_PEC || (KRO == 0 && !DROP && K1 == 3 && ACT == PINN_ACT_TANH), "corrected-residual instances: tanh, k = 2, natural unit order, no dropout");
+  static_assert(EPI != EPI_FIELD_WAVE || (!GRAD && !LDSACC && KRO == 0 && !DROP && K1 == 3), "field instances: forward only, natural unit order, no dropout");
+  static_assert(EPI != EPI_WAVE || (KRO == 0 && !DROP && K1 == 3 && ACT == PINN_ACT_TANH), "wave-closure instances: tanh, k = 2, natural unit order, no dropout");
   static_assert(EPI != EPI_COEF || (KRO == 0 && !DROP && (K1 == 3 || K1 == 4) && ACT == PINN_ACT_TANH), "coefficient instances: tanh, k = 2 or 3, natural unit order, no dropout");
   static_assert(EPI != EPI_WEIGHTED || (KRO == 0 && !DROP && (K1 == 3 || K1 == 4) && ACT == PINN_ACT_TANH), "weighted instances: tanh, k = 2 or 3, natural unit order, no dropout");
   static_assert(ACT != PINN_ACT_SIN_TANH || (EPI == EPI_GENERIC && KRO == 0 && !DROP && (K1 == 1 || K1 == 3 || K1 == 4)), "sine-first-layer instances: generic epilogue, k = 0, 2 or 3, natural unit order, no dropout");

@@ -22,6 +22,8 @@ enum TileFamily {
   TF_SIN,         // sine first layer
   TF_DROP,        // training-mode dropout (width 64 only)
   TF_ENS,         // ensemble: k_fused_ens on a grid (gx, M)
+  TF_WAVE,        // wave closure (corrected stress + dispersion + wave-energy balance), loss
+  TF_FIELD_WAVE,  // wave closure, fields (in TF_WAVE's units)
   TF_COUNT
 };
 struct TileLaunch {

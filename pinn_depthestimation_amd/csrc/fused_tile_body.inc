@@ -140,9 +140,10 @@
     // ---- outputs / loss -----------------------------------------------------------------------
     if constexpr (EPI == EPI_FIELD) field_epilogue<K1>(P, out, pt, ptc, valid, p, q);
     else if constexpr (EPI == EPI_FIELD_PEC) field_tile<ResPhysicsEquationCorrected, K1>(P, out, pt, valid, false, p, q);
+    else if constexpr (EPI == EPI_FIELD_WAVE) field_tile<ResPhysicsEquationWave, K1>(P, out, pt, valid, false, p, q);
     else if constexpr (EPI == EPI_COEF) coef_epilogue<K1, GRAD>(P, out, G, sums, sm, tb, valid, p, q);
     else if constexpr (EPI == EPI_WEIGHTED) weighted_epilogue<K1, GRAD>(P, out, G, sums, sm, tb, pt, ptc, valid, p, q);
-    else if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64 || EPI == EPI_PEC), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
+    else if constexpr (EPI != EPI_ADJ) loss_epilogue<K1, GRAD, (WP < 64 || EPI == EPI_PEC || EPI == EPI_WAVE), EPI>(P, out, G, sums, sm, sm_mse, tb, pt, ptc, valid, p, q);
 
     PINN_STAMP(2);
     // ---- reverse sweep ------------------------------------------------------------------------
@@ -199,7 +200,7 @@
   }
 #endif
 
-  if constexpr (EPI == EPI_FIELD || EPI == EPI_FIELD_PEC) return;   // nothing to reduce: the fields are already where they belong
+  if constexpr (EPI == EPI_FIELD || EPI == EPI_FIELD_PEC || EPI == EPI_FIELD_WAVE) return;   // nothing to reduce: the fields are already where they belong
   // ---- per-workgroup reductions ------------------------------------------------------------------
 #pragma unroll
   for (int j = 0; j < MAX_SUMS; ++j) {

@@ -194,11 +194,29 @@ static int64_t engine_workspace_bytes(int engine, const Net& n, int64_t N) {
 // pinn_query_workspace (which does not see the spec) may not have covered.  The one exception: with dropout_p > 0 the fused
 // dropout instances count as absent and AUTO runs the generic engine, which the query of a dropout descriptor covers
 // already (its forward calls run there).  Pure host logic: nothing touches a device before a refusal.
-static int corrected_engine(const pinn_desc* desc, const Net& n, const LossReq& rq, int* e) {
-  if (rq.kind == 1 || rq.spec.residual_id != RES_PE_CORRECTED) return PINN_OK;
+// The wave closure (bits 0 and 1 -> RES_PE_WAVE) follows the same rule with its own instances of the tile kernel only: the
+// batch and the cooperative kernel, when the descriptor forces them, are refused, and so is an eighth fidelity column on the
+// fused engine (the fifth term's partial sum takes that column's slot: fused_kernel.h, term_slot).
+// rc_pick: pick_engine's own verdict on the descriptor (its reason is in the error buffer); where the closure's rule has
+// nothing to add, a wave request's refusal repeats that reason under the closure's name (name_refusal).
+static int name_refusal(const char* name, int rc) {
+  char picked[sizeof(g_err)];
+  snprintf(picked, sizeof(picked), "%s", g_err);
+  set_error("%s: %.300s; use engine GENERIC", name, picked);
+  return rc;
+}
+static int corrected_engine(const pinn_desc* desc, const Net& n, const LossReq& rq, int* e, int rc_pick) {
+  if (rq.kind == 1 || !is_pe_closure(rq.spec.residual_id)) return PINN_OK;
+  const bool wave = rq.spec.residual_id == RES_PE_WAVE;
+  const char* name = pe_closure_name(wave);
   if (*e == PINN_ENGINE_WIDE) {
-    set_error("the corrected radiation stress (spec.flags bit 0) is not implemented on the wide engine (width 65..256, "
-              "bf16 operands): width %d, precision %d; use engine GENERIC in fp32", n.W, n.prec);
+    set_error("%s is not implemented on the wide engine (width 65..256, "
+              "bf16 operands): width %d, precision %d; use engine GENERIC in fp32", name, n.W, n.prec);
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (wave && *e == PINN_ENGINE_FUSED && (n.fused_kernel == FUSED_KERNEL_BATCH || n.fused_kernel == FUSED_KERNEL_COOP)) {
+    set_error("%s has instances of the tile kernel only: engine %s has none; use engine AUTO, FUSED, FUSED_TILE or GENERIC",
+              name, n.fused_kernel == FUSED_KERNEL_BATCH ? "FUSED_BATCH" : "FUSED_COOP");
     return PINN_ERR_UNSUPPORTED;
   }
   if (*e == PINN_ENGINE_FUSED && n.drop_p > 0.f && asked_engine(desc) == PINN_ENGINE_AUTO) *e = PINN_ENGINE_GENERIC;
@@ -207,11 +225,17 @@ static int corrected_engine(const pinn_desc* desc, const Net& n, const LossReq& 
   if (*e == PINN_ENGINE_FUSED && n.act == PINN_ACT_SIN_TANH && asked_engine(desc) == PINN_ENGINE_AUTO) *e = PINN_ENGINE_GENERIC;
   if (*e == PINN_ENGINE_FUSED) {
     if (const char* why = fused_corrected_refusal(n)) {
-      set_error("the corrected radiation stress (spec.flags bit 0) %s (activation %d, k %d, dropout_p %g)", why, n.act, n.k,
-                (double)n.drop_p);
+      set_error("%s %s (activation %d, k %d, dropout_p %g)", name, why, n.act, n.k, (double)n.drop_p);
+      return PINN_ERR_UNSUPPORTED;
+    }
+    if (wave && rc_pick) return name_refusal(name, rc_pick);
+    if (wave && !rc_pick && rq.kind == 2 && rq.n_cols > WAVE_MAX_COLS) {
+      set_error("%s with %d fidelity columns on the fused engine: the fifth term's partial sum takes the last column's slot, "
+                "at most %d columns are served; use engine GENERIC", name, rq.n_cols, WAVE_MAX_COLS);
       return PINN_ERR_UNSUPPORTED;
     }
   }
+  if (wave && rc_pick) return name_refusal(name, rc_pick);
   return PINN_OK;
 }
 
@@ -219,7 +243,7 @@ static int corrected_engine(const pinn_desc* desc, const Net& n, const LossReq& 
 static int run_loss(const pinn_desc* desc, const Net& n, bool want_grad, const LossReq& rq, const float* params,
                     const float* X, int64_t N, void* ws, int64_t ws_bytes, void* stream) {
   int rc; int e = pick_engine(desc, n, want_grad, &rc);
-  if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
+  if (int rcc = corrected_engine(desc, n, rq, &e, rc)) return rcc;
   if (rc) return rc;
   return on_engine(e, fused_loss, wide_loss, generic_loss)(n, rq, params, X, N, ws, ws_bytes, (hipStream_t)stream);
 }
@@ -247,6 +271,10 @@ static const ResidualInfo* residual_info(int id) {
 }
 // (-1 for an id that names no residual)
 static int residual_terms(int id) { const ResidualInfo* r = residual_info(id); return r ? r->terms : -1; }
+// the caller's spec asks for the wave closure (flags bits 0 and 1 on physics_equation; check_spec refuses bit 1 alone)
+static bool is_wave_spec(const pinn_residual_spec* sp) { return sp->residual_id == PINN_RES_PHYSICS_EQUATION && (sp->flags & 2); }
+// ... the terms (and fields) of the caller's spec: the wave closure adds two to physics_equation's
+static int spec_terms(const pinn_residual_spec* sp) { return is_wave_spec(sp) ? PINN_PEW_TERMS : residual_terms(sp->residual_id); }
 static int residual_dirs(int id) { const ResidualInfo* r = residual_info(id); return r ? r->dirs : -1; }
 // (the terms a point weight applies to: the residual's terms that are sums of a squared field, pinn_hip.h's n_w)
 static int residual_n_weighted(int id) { const ResidualInfo* r = residual_info(id); return !r ? -1 : r->terms < r->fields ? r->terms : r->fields; }
@@ -272,6 +300,18 @@ static int check_spec(const Net& n, const pinn_residual_spec* sp, pinn_residual_
   // holds the four public ones)
   const ResidualInfo* ri = residual_info(sp->residual_id);
   if (!ri) { set_error("unknown residual_id %d", sp->residual_id); return PINN_ERR_INVALID; }
+  if (is_wave_spec(sp)) {   // flags bit 1: the wave closure needs the corrected stress and its two parameters
+    if (!(sp->flags & 1)) {
+      set_error("spec.flags bit 1 (the wave closure) without bit 0: the dispersion and wave-energy terms close the corrected "
+                "radiation stress (flags = 3)");
+      return PINN_ERR_INVALID;
+    }
+    if (!(sp->param[0] > 0.f) || !(sp->param[1] > 0.f)) {
+      set_error("the wave closure (spec.flags bit 1) needs param[0] = omega > 0 and param[1] = gamma > 0 (got %g, %g)",
+                (double)sp->param[0], (double)sp->param[1]);
+      return PINN_ERR_INVALID;
+    }
+  }
   const int nr = ri->roles, nd = ri->dirs;
   for (int r = 0; r < nr; ++r)
     if (sp->out_col[r] < 0 || sp->out_col[r] >= n.d_out) {
@@ -288,6 +328,8 @@ static int check_spec(const Net& n, const pinn_residual_spec* sp, pinn_residual_
   for (int d = nd; d < PINN_MAX_DIRS; ++d) norm->dir_of[d] = -1;
   // flags bit 0 on physics_equation: the corrected radiation stress, carried as an id of its own from here on
   if (sp->residual_id == PINN_RES_PHYSICS_EQUATION && (sp->flags & 1)) norm->residual_id = RES_PE_CORRECTED;
+  // ... and bits 0 and 1: the wave closure
+  if (is_wave_spec(sp)) norm->residual_id = RES_PE_WAVE;
   return PINN_OK;
 }
 
@@ -300,7 +342,7 @@ static int build_request(const Net& n, const pinn_residual_spec* spec, int64_t N
                          const int32_t* out_col, LossReq* rq) {
   memset(rq, 0, sizeof(*rq));
   if (int rc = check_spec(n, spec, &rq->spec)) return rc;
-  rq->n_terms = residual_terms(spec->residual_id);
+  rq->n_terms = spec_terms(spec);
   if (n_res > N) { set_error("n_res=%lld exceeds N=%lld", (long long)n_res, (long long)N); return PINN_ERR_INVALID; }
   if (n_cols < min_cols || n_cols > PINN_MAX_ROLES) {
     set_error("n_cols=%d outside %d..%d", n_cols, min_cols, PINN_MAX_ROLES); return PINN_ERR_INVALID;
@@ -379,6 +421,24 @@ int32_t pinn_pe_corrected_point(const float v[18], const float scale[3], float f
   R::fields(jet, *reinterpret_cast<float (*)[R::NF]>(fields));
   if (!scale || !g) return PINN_OK;
   R::eval<true>(jet, scale, gj, sq);
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
+  return PINN_OK;
+}
+
+int32_t pinn_pe_wave_point(const float v[18], float omega, float gamma, const float scale[5], float fields[5], float g[18]) {
+  typedef ResPhysicsEquationWave R;
+  if (!v || !fields) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
+  if (!(omega > 0.f) || !(gamma > 0.f)) {
+    set_error("pinn_pe_wave_point: the wave closure needs omega > 0 and gamma > 0 (got %g, %g)", (double)omega, (double)gamma);
+    return PINN_ERR_INVALID;
+  }
+  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], sq[R::NT];
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
+  R::fields(jet, *reinterpret_cast<float (*)[R::NF]>(fields), omega, gamma);
+  if (!scale || !g) return PINN_OK;
+  R::eval<true>(jet, scale, gj, sq, omega, gamma);
   for (int c = 0; c <= R::ND; ++c)
     for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
   return PINN_OK;
@@ -580,7 +640,7 @@ int32_t pinn_loss_grad_adam_step(const pinn_desc* desc, const pinn_residual_spec
   rq.scale = term_scale; rq.sums = term_sums;
   rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = col_sums; rq.grad = grad_flat;
   int e = pick_engine(desc, n, true, &rc);
-  if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
+  if (int rcc = corrected_engine(desc, n, rq, &e, rc)) return rcc;
   if (rc) return rc;
   if (e != PINN_ENGINE_FUSED || !fused_supports_adam(n, rq, N)) {
     set_error("pinn_loss_grad_adam_step: needs a one-pass request on the fused engine (use the loss call + pinn_adam_step)");
@@ -784,7 +844,7 @@ int32_t pinn_lbfgs_loop(const pinn_desc* desc, const pinn_residual_spec* spec, c
   rq.T = T; rq.mse_scale = col_scale; rq.mse_sums = p.csums; rq.sums = p.tsums; rq.grad = p.gnew;
   {   // the refusals of the loss request itself, before anything is launched
     int e = pick_engine(desc, n, true, &rc);
-    if (int rcc = corrected_engine(desc, n, rq, &e)) return rcc;
+    if (int rcc = corrected_engine(desc, n, rq, &e, rc)) return rcc;
     if (rc) return rc;
     const int64_t ws_need = engine_workspace_bytes(e, n, N);
     if (ws_need < 0) { set_error("network not supported"); return PINN_ERR_UNSUPPORTED; }
@@ -894,16 +954,16 @@ static int fields_plan(const pinn_desc* desc, const pinn_residual_spec* spec, in
                        FieldsPlan* pl) {
   int rc = make_net(desc, n); if (rc) return rc;
   rc = check_spec(*n, spec, nspec); if (rc) return rc;
-  const bool corrected = nspec->residual_id == RES_PE_CORRECTED;
-  rc = check_k("pinn_residual_fields", *n, spec, corrected ? " (corrected radiation stress)" : ""); if (rc) return rc;
+  const bool corrected = is_pe_closure(nspec->residual_id), wave = nspec->residual_id == RES_PE_WAVE;
+  rc = check_k("pinn_residual_fields", *n, spec, wave ? " (wave closure)" : corrected ? " (corrected radiation stress)" : ""); if (rc) return rc;
   if (N < 1) { set_error("pinn_residual_fields: N = %lld, need at least one point", (long long)N); return PINN_ERR_INVALID; }
   const int asked = asked_engine(desc);
   const char* why = fused_tile_refusal(TILE_FIELD, *n);
   // (the corrected radiation stress: the tile kernel's EPI_FIELD_PEC instances, tanh only; everything else is staged)
   const char* why_pec = corrected ? fused_corrected_refusal(*n) : nullptr;
   if (asked == PINN_ENGINE_FUSED && !why && why_pec) {
-    set_error("pinn_residual_fields on the fused engine: the corrected radiation stress (spec.flags bit 0) %s; engine AUTO "
-              "runs this request through the forward jet", why_pec);
+    set_error("pinn_residual_fields on the fused engine: %s %s; engine AUTO "
+              "runs this request through the forward jet", pe_closure_name(wave), why_pec);
     return PINN_ERR_UNSUPPORTED;
   }
   const bool fused_ok = !why && !why_pec;
@@ -1047,6 +1107,7 @@ int32_t pinn_residual2_point(int32_t residual_id, int32_t flags, float nu, const
   switch (residual_id) {
     case PINN_RES_NAVIER_STOKES: residual2_point<Res2NavierStokes>(nu, v, lap, scale, fields, g, glap); return PINN_OK;
     case PINN_RES_PHYSICS_EQUATION:
+      if (flags & 2) { set_error("pinn_residual2_point: %s has no second-order form", pe_closure_name(true)); return PINN_ERR_UNSUPPORTED; }
       if (flags & 1) residual2_point<Res2PhysicsEquationCorrected>(nu, v, lap, scale, fields, g, glap);
       else residual2_point<Res2PhysicsEquation>(nu, v, lap, scale, fields, g, glap);
       return PINN_OK;
@@ -1061,6 +1122,11 @@ int32_t pinn_residual2_point(int32_t residual_id, int32_t flags, float nu, const
 static int residual2_plan(const pinn_desc* desc, const pinn_residual_spec* spec, Net* n, pinn_residual_spec* nspec, bool* mfma) {
   int rc = make_net(desc, n); if (rc) return rc;
   rc = check_spec(*n, spec, nspec); if (rc) return rc;
+  if (is_wave_spec(spec)) {
+    set_error("pinn_residual2_loss_grad: %s has no second-order form (nu together with the wave closure): use "
+              "pinn_residual_loss_grad, or flags = 1 here", pe_closure_name(true));
+    return PINN_ERR_UNSUPPORTED;
+  }
   if (spec->residual_id == PINN_RES_CONTINUITY_FTEMP || spec->residual_id == PINN_RES_CONTINUITY_ONLY) {
     set_error("pinn_residual2_loss_grad: residual %d has no momentum equation: no second-order term", spec->residual_id);
     return PINN_ERR_UNSUPPORTED;
@@ -1116,7 +1182,7 @@ static bool is_corrected(int residual_id, int flags) { return residual_id == PIN
 static int coef_residual(const char* who, int residual_id, int flags) {
   if (!residual_info(residual_id)) { set_error("unknown residual_id %d", residual_id); return PINN_ERR_INVALID; }
   if (is_corrected(residual_id, flags)) {
-    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no coefficient form", who);
+    set_error("%s: %s has no coefficient form", who, pe_closure_name((flags & 2) != 0));
     return PINN_ERR_UNSUPPORTED;
   }
   if (residual_id != PINN_RES_NAVIER_STOKES && residual_id != PINN_RES_PHYSICS_EQUATION) {
@@ -1164,7 +1230,7 @@ static int extra_rules(const char* who, int family, bool k_first, bool single, c
   if (k_first) { rc = check_k(who, n, spec, ""); if (rc) return rc; }
   if (family == TILE_COEF) { rc = coef_residual(who, spec->residual_id, spec->flags); if (rc) return rc; }
   else if (is_corrected(spec->residual_id, spec->flags)) {
-    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no point-weighted form", who);
+    set_error("%s: %s has no point-weighted form", who, pe_closure_name((spec->flags & 2) != 0));
     return PINN_ERR_UNSUPPORTED;
   }
   if (!k_first) { rc = check_k(who, n, spec, ""); if (rc) return rc; }
@@ -1390,7 +1456,7 @@ static int adam_bal_plan(const char* who, bool query, const pinn_desc* desc, con
   int rc = make_net(desc, n); if (rc) return rc;
   rc = build_request(*n, spec, N_res, N_res, 0, 0, nullptr, res); if (rc) return rc;
   if (is_corrected(spec->residual_id, spec->flags)) {
-    set_error("%s: the corrected radiation stress (spec.flags bit 0) has no natural-order pass in the balanced loop", who);
+    set_error("%s: %s has no natural-order pass in the balanced loop", who, pe_closure_name((spec->flags & 2) != 0));
     return PINN_ERR_UNSUPPORTED;
   }
   rc = check_k(who, *n, spec, ""); if (rc) return rc;

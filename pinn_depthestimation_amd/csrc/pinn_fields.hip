@@ -38,6 +38,8 @@ __global__ __launch_bounds__(256) void k_fields_from_jet(const FieldsJetParams P
   if constexpr (std::is_same<RES, ResContinuity>::value) {
     const bool masked = P.anchor_on && P.X[i * P.d_in + P.xcol] < P.thr;
     RES::fields(v, f, P.anchor_on != 0, masked, P.anchor);
+  } else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value) {
+    RES::fields(v, f, P.thr, P.anchor);      // (spec.param[0..1]: omega, gamma)
   } else {
     RES::fields(v, f);
   }
@@ -63,6 +65,7 @@ int fields_from_jet(const Net& net, const pinn_residual_spec& spec, const float*
     case PINN_RES_NAVIER_STOKES: hipLaunchKernelGGL(k_fields_from_jet<ResNavierStokes>, grid, block, 0, s, P); break;
     case PINN_RES_PHYSICS_EQUATION: hipLaunchKernelGGL(k_fields_from_jet<ResPhysicsEquation>, grid, block, 0, s, P); break;
     case RES_PE_CORRECTED: hipLaunchKernelGGL(k_fields_from_jet<ResPhysicsEquationCorrected>, grid, block, 0, s, P); break;
+    case RES_PE_WAVE: hipLaunchKernelGGL(k_fields_from_jet<ResPhysicsEquationWave>, grid, block, 0, s, P); break;
     default: hipLaunchKernelGGL(k_fields_from_jet<ResContinuity>, grid, block, 0, s, P); break;
   }
   return check_launch("fields from jet");

@@ -18,7 +18,11 @@ namespace {
 
 // a loss request with the corrected radiation stress (common.h, RES_PE_CORRECTED): its own kernel instances (EPI_PEC), on
 // the tile and on the batch kernel, never on the cooperative one
-bool is_pec(const LossReq* rq) { return rq && rq->kind != 1 && rq->spec.residual_id == RES_PE_CORRECTED; }
+// (also true for the wave closure, RES_PE_WAVE, which follows the corrected residual's rules wherever is_pec decides them:
+// the split request in one pass at every width, never the cooperative kernel, no ensemble)
+bool is_pec(const LossReq* rq) { return rq && rq->kind != 1 && is_pe_closure(rq->spec.residual_id); }
+// ... the wave closure itself: its own instances of the tile kernel (EPI_WAVE), never the batch kernel either
+bool is_wave(const LossReq* rq) { return rq && rq->kind != 1 && rq->spec.residual_id == RES_PE_WAVE; }
 // a residual request with runtime closure coefficients (pinn_residual_coef_loss_grad): its own instances of the tile kernel
 // (EPI_COEF), never the batch or the cooperative kernel, natural unit order
 bool is_coef(const LossReq* rq) { return rq && rq->coef != nullptr; }
@@ -285,6 +289,10 @@ __global__ void k_reduce_grads(Net n, int WP, const float* __restrict__ wg, int 
 // the weighted losses.  Called by all 256 threads of ONE block.
 // (finish_sums2: the term sums and the column sums from the partial sums of two different passes — pinn_adam_loop_ext runs
 // the residual and the fidelity points as a pass each; finish_sums below: both from one pass)
+// TAIL_TERMS = false: the caller's requests have at most MSE_SUM0 terms, all in their own slots (pinn_adam_loop_ext and
+// pinn_adam_loop_balanced refuse the wave closure): term_slot is then the identity and is left out, so that their finishing
+// kernels stay as they were compiled before the rule existed.
+template <bool TAIL_TERMS = true>
 __device__ __forceinline__ void finish_sums2(const float* __restrict__ wg_sums, int grid, const float* __restrict__ wg_sums_c, int grid_c,
                                              int n_terms, float* __restrict__ term_sums,
                                              int n_cols, float* __restrict__ col_sums, int n_loss_rows,
@@ -298,7 +306,7 @@ __device__ __forceinline__ void finish_sums2(const float* __restrict__ wg_sums, 
   __syncthreads();
   for (int j = 0; j < n_terms + n_cols; ++j) {
     const float sum = (float)column_sum(j < n_terms ? wg_sums : wg_sums_c, j < n_terms ? grid : grid_c, MAX_SUMS,
-                                        j < n_terms ? j : MSE_SUM0 + (j - n_terms));
+                                        j < n_terms ? (TAIL_TERMS ? term_slot(j) : j) : MSE_SUM0 + (j - n_terms));
     if (threadIdx.x == 0) {
       if (j < n_terms) { term_sums[j] = sum; ssum[row_cols + j] = (double)sum; }
       else { col_sums[j - n_terms] = sum; ssum[j - n_terms] = (double)sum; }
@@ -424,7 +432,7 @@ __global__ void k_finish_adam_ext(Net n, int WP, int PP, int PW, ExtFinish f) {
     return;
   }
   if (b == f.param_blocks) {       // loss sums, weighted losses, coefficients
-    finish_sums2(f.sums_r, f.grid_r, f.sums_f, f.grid_f, f.n_terms, f.term_sums, f.n_cols, f.col_sums, f.n_loss_rows,
+    finish_sums2<false>(f.sums_r, f.grid_r, f.sums_f, f.grid_f, f.n_terms, f.term_sums, f.n_cols, f.col_sums, f.n_loss_rows,
                  f.loss_rows, f.losses, f.row_cols);
     for (int c = 0; c < f.n_coef; ++c) {
       // (the coefficient gradient rode in the free term slot of the residual pass's partial sums: fused_kernel.h, COEF_SUM)
@@ -505,7 +513,7 @@ __global__ void k_finish_adam_bal(Net n, int WP, int PP, int PW, BalFinish f) {
     finish_adam_apply(n, WP, r, f.grad, f.params, f.m, f.v, f.Wp, f.WTp, f.Bp, f.c);
     return;
   }
-  finish_sums2(f.sums_r, f.grid_r, f.sums_f, f.grid_f, f.n_terms, f.term_sums, f.n_cols, f.col_sums, f.n_loss_rows,
+  finish_sums2<false>(f.sums_r, f.grid_r, f.sums_f, f.grid_f, f.n_terms, f.term_sums, f.n_cols, f.col_sums, f.n_loss_rows,
                f.loss_rows, f.losses, f.row_cols);
   if (f.lam_log && threadIdx.x < 2) f.lam_log[threadIdx.x] = f.lam[threadIdx.x];   // the weights this iteration stepped with
 }
@@ -566,13 +574,13 @@ struct FieldReq {
 // asks for (fields, an external adjoint), then what the network needs (dropout, the sine first layer), then the request's
 // epilogue.  run() refuses the combinations without instances; the batch kernel has the adjoint, corrected and loss families.
 TileFamily tile_family(const Net& n, const LossReq* rq, const AdjReq* adj, const FieldReq* fld) {
-  if (fld) return fld->spec.residual_id == RES_PE_CORRECTED ? TF_FIELD_PEC : TF_FIELD;
+  if (fld) return fld->spec.residual_id == RES_PE_WAVE ? TF_FIELD_WAVE : fld->spec.residual_id == RES_PE_CORRECTED ? TF_FIELD_PEC : TF_FIELD;
   if (adj) return TF_ADJ;
   if (n.drop_p > 0.f) return TF_DROP;
   if (n.act == PINN_ACT_SIN_TANH) return TF_SIN;
   if (is_weighted(rq)) return TF_WEIGHTED;
   if (is_coef(rq)) return TF_COEF;
-  return is_pec(rq) ? TF_PEC : TF_LOSS;
+  return is_wave(rq) ? TF_WAVE : is_pec(rq) ? TF_PEC : TF_LOSS;
 }
 
 // One pass of pinn_adam_loop_ext: run() launches the gradient pass ALONE — no reduction, no finishing kernel, the packing
@@ -626,15 +634,20 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
   }
   // (the field epilogue exists in the tile kernel only: every kernel choice of desc.engine lands there; the external-adjoint
   // one in the tile and in the batch kernel)
-  const bool pec = is_pec(rq), fpec = fld && fld->spec.residual_id == RES_PE_CORRECTED;
+  const bool pec = is_pec(rq), fpec = fld && is_pe_closure(fld->spec.residual_id), wave = is_wave(rq);
   if (n.act == PINN_ACT_SIN_TANH && (adj || fld || n.drop_p > 0.f)) {   // (refused upstream: never a tanh kernel on a sine network)
     set_error("fused engine: no kernel for the sine first layer (activation 2) on this request"); return PINN_ERR_UNSUPPORTED;
   }
   if ((pec || fpec) && fused_corrected_refusal(n)) {
-    set_error("fused engine: the corrected radiation stress %s", fused_corrected_refusal(n)); return PINN_ERR_UNSUPPORTED;
+    set_error("fused engine: %s %s", pe_closure_name(wave || (fld && fld->spec.residual_id == RES_PE_WAVE)), fused_corrected_refusal(n));
+    return PINN_ERR_UNSUPPORTED;
+  }
+  if (wave && (n.fused_kernel == FUSED_KERNEL_BATCH || n.fused_kernel == FUSED_KERNEL_COOP || (P.loss_kind & 2 && rq->n_cols > WAVE_MAX_COLS))) {
+    // (refused upstream, pinn_abi.hip corrected_engine: tile-kernel instances only, and the fifth term's sum owns the last column's slot)
+    set_error("fused engine: %s has no kernel for this request", pe_closure_name(true)); return PINN_ERR_UNSUPPORTED;
   }
   const bool natural = po && po->natural;
-  const bool batch = !natural && !fld && !coefq && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
+  const bool batch = !natural && !fld && !coefq && !wave && (adj ? use_batch_adj(n, g, N) : use_batch(n, g, grad, N));
   const bool coop = !adj && !fld && !batch && !pec && !coefq && use_coop(n, g, grad, N);   // (FUSED_COOP with it: the tile kernel)
   if (coop) {
     P.acc_lds = grad ? 1 : 0;
@@ -742,8 +755,10 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
     return check_launch("fused finish + adam");
   }
   if (rq) {
-    if (P.loss_kind & 1)
-      reduce_sums(P.wg_sums, grid, MAX_SUMS, 0, rq->n_terms, rq->sums, s);
+    if (P.loss_kind & 1) {   // (terms beyond the first MSE_SUM0 sit behind the columns: fused_kernel.h, term_slot)
+      reduce_sums(P.wg_sums, grid, MAX_SUMS, 0, std::min(rq->n_terms, MSE_SUM0), rq->sums, s);
+      for (int t = MSE_SUM0; t < rq->n_terms; ++t) reduce_sums(P.wg_sums, grid, MAX_SUMS, term_slot(t), 1, rq->sums + t, s);
+    }
     if (coefq && !wtq && grad && rq->coef_grad)   // the coefficient gradient rode in the free term slot (fused_kernel.h, COEF_SUM)
       reduce_sums_add(P.wg_sums, grid, MAX_SUMS, COEF_SUM, rq->n_coef, rq->coef_grad, s);
     if (P.loss_kind & 2)
@@ -765,7 +780,8 @@ int run(const Net& n, bool grad, const LossReq* rq, const float* params, const f
 int launch_tile(TileFamily f, int WP, const TileLaunch& a) {
   static int (*const unit[TF_COUNT][3])(const TileLaunch&) = {   // (in TileFamily's order)
       TILE_ROW(TF_LOSS), TILE_ROW(TF_ADJ), TILE_ROW(TF_FIELD), TILE_ROW(TF_PEC), TILE_ROW(TF_FIELD_PEC), TILE_ROW(TF_COEF),
-      TILE_ROW(TF_WEIGHTED), TILE_ROW(TF_SIN), {nullptr, nullptr, tile_unit<TF_DROP, 64>}, TILE_ROW(TF_ENS)};
+      TILE_ROW(TF_WEIGHTED), TILE_ROW(TF_SIN), {nullptr, nullptr, tile_unit<TF_DROP, 64>}, TILE_ROW(TF_ENS), TILE_ROW(TF_WAVE),
+      TILE_ROW(TF_FIELD_WAVE)};
   const auto fn = unit[f][WP == 16 ? 0 : WP == 32 ? 1 : 2];
   if (!fn) { set_error("fused engine: no kernel of family %d at padded width %d", (int)f, WP); return PINN_ERR_UNSUPPORTED; }
   return fn(a);
@@ -1138,6 +1154,7 @@ EnsPlan ens_plan(const Net& n, const Geo& g, int M, int64_t N) {
 const char* fused_ensemble_refusal(const Net& n, const LossReq& rq) {
   // (the descriptor's rule first: the entries decide it before they have a request, pinn_abi.hip ensemble_net)
   if (const char* why = fused_tile_refusal(TILE_ENSEMBLE, n)) return why;
+  if (is_wave(&rq)) return "the wave closure (spec.flags bits 0 and 1) has no ensemble kernel";
   if (is_pec(&rq)) return "the corrected radiation stress (spec.flags bit 0) has no ensemble kernel";
   if (rq.kind == 2 && rq.n_split >= 0 && padded_width(n.W) == 64)
     return "the split request (0 <= n_res < N) at hidden width 33..64: the tile kernel carries no split code there";

@@ -120,6 +120,19 @@ int tile_unit<TF_FIELD_PEC, WP_>(const TileLaunch& a) {
   return fwd<3, PINN_ACT_TANH, EPI_FIELD_PEC>(a, WHAT(", corrected fields"));
 }
 
+#elif defined(UNIT_wave)
+// TF_WAVE, TF_FIELD_WAVE — wave-closure epilogues (EPI_WAVE: the corrected residual's loss epilogue with
+// ResPhysicsEquationWave, five terms; EPI_FIELD_WAVE: its per-point fields): the instances of the pec units, K1 = 3, tanh;
+// forward, gradient (LDS / global copy), and a forward-only field instance.
+template <>
+int tile_unit<TF_WAVE, WP_>(const TileLaunch& a) {
+  return fwd_or_bwd<3, PINN_ACT_TANH, EPI_WAVE>(a, WHAT(", wave closure"));
+}
+template <>
+int tile_unit<TF_FIELD_WAVE, WP_>(const TileLaunch& a) {
+  return fwd<3, PINN_ACT_TANH, EPI_FIELD_WAVE>(a, WHAT(", wave-closure fields"));
+}
+
 #elif defined(UNIT_coef)
 // TF_COEF — runtime-coefficient epilogue (EPI_COEF: the EPI_NS / EPI_PE epilogue with gamma_b resp. Cd read from a device
 // array and the coefficient gradient summed beside the term sums): K1 = 4 (Navier_Stokes) and 3 (physics_equation), tanh.

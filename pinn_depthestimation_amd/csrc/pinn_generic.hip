@@ -288,6 +288,8 @@ __global__ void k_residual(const float* __restrict__ yj, int d_out, int64_t N, R
     if constexpr (std::is_same<RES, ResContinuity>::value) {
       const bool masked = anchor_on ? (X[n * d_in + xcol] < thr) : false;
       RES::template eval<GRAD>(v, sc, g, sq, anchor_on != 0, masked, anchor);
+    } else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value) {
+      RES::template eval<GRAD>(v, sc, g, sq, thr, anchor);      // (spec.param[0..1]: omega, gamma)
     } else {
       RES::template eval<GRAD>(v, sc, g, sq);
     }
@@ -600,6 +602,7 @@ int run_loss(const Net& n, const LossReq& rq, const float* params, const float* 
     if (id == PINN_RES_NAVIER_STOKES) LAUNCH_RES(ResNavierStokes, 0, 0);
     else if (id == PINN_RES_PHYSICS_EQUATION) LAUNCH_RES(ResPhysicsEquation, 0, 0);
     else if (id == RES_PE_CORRECTED) LAUNCH_RES(ResPhysicsEquationCorrected, 0, 0);      // (spec.flags bit 0: common.h)
+    else if (id == RES_PE_WAVE) LAUNCH_RES(ResPhysicsEquationWave, 0, 0);                // (spec.flags bits 0 and 1)
     else if (id == PINN_RES_CONTINUITY_FTEMP) LAUNCH_RES(ResContinuity, 0, 0);
     else if (id == PINN_RES_CONTINUITY_ONLY) LAUNCH_RES(ResContinuity, 1, n.dir_col[rq.spec.dir_of[0]]);
     else { set_error("unknown residual_id %d", id); return PINN_ERR_INVALID; }

@@ -239,6 +239,105 @@ struct ResPhysicsEquationCorrected {
   }
 };
 
+// The corrected physics_equation closed by the two wave equations that tie k and Hrms to the depth (the package's
+// physics.physics_equation(..., corrected=True, wave_omega=, wave_gamma=)); selected by pinn_residual_spec.flags bit 1 on top
+// of bit 0, never by an id of its own.  Same roles (h, U, V, eta, R = Hrms, K = k) and directions (x, y); five terms:
+//   0..2  ResPhysicsEquationCorrected's fc, fx, fy (its functions are called, not restated)
+//   3     f_d = G K tanh(s) / omega^2 - 1,  s = K h                       linear dispersion, dimensionless
+//   4     f_E = d/dx (R^2 c_g) + eps,  c_g = (omega / K) (1/2 + n(s))     wave-energy flux balance divided by rho g / 8
+//         eps = (3 sqrt(pi) / 2) (omega / 2 pi) R^5 / (gamma^2 h^3) [1 - (1 + q^2)^(-5/2)],  q = R / (gamma h)
+//         (Thornton & Guza 1983 with B = 1); expanded: f_E = 2 R R_x c_g + R^2 omega [n1 s_x / K - (1/2 + n) K_x / K^2] + eps
+// Waves travel along +x, as the residual's Sxy = 0 has it.  n, n1, n2 are ratio()'s.  tanh s and sech^2 s come from the same
+// t = exp(-2|s|) — tanh = (1 - t) / (1 + t), sech^2 = 4t / (1 + t)^2, nothing overflows — and below ratio()'s threshold
+// |s| = 1/4, where 1 - t cancels, from the Taylor series of tanh through s^11 (first dropped term 2e-10 relative there).
+// No guards beyond that: K = 0 or h = 0 give non-finite values, which propagate as everywhere else; K > 0, h > 0,
+// omega > 0 and gamma > 0 are the caller's to ensure (the C-ABI checks omega and gamma).
+struct ResPhysicsEquationWave {
+  typedef ResPhysicsEquationCorrected R1;
+  static constexpr int NR = 6, ND = 2, NT = 5, NF = 5;
+  __host__ __device__ static inline void tanh_sech2(float s, float& T, float& S2) {
+    const float a = fabsf(s);
+    if (a < 0.25f) {
+      constexpr float B1 = (float)(-1.0 / 3.0), B2 = (float)(2.0 / 15.0), B3 = (float)(-17.0 / 315.0),
+                      B4 = (float)(62.0 / 2835.0), B5 = (float)(-1382.0 / 155925.0);
+      const float u = s * s;
+      T = s * fmaf(fmaf(fmaf(fmaf(fmaf(B5, u, B4), u, B3), u, B2), u, B1), u, 1.f);
+      S2 = fmaf(-T, T, 1.f);
+    } else {
+      const float t = expf(-2.f * a);
+      const float id = 1.0f / (1.f + t);
+      const float m = (1.f - t) * id;
+      T = s < 0.f ? -m : m;
+      S2 = 4.f * t * (id * id);
+    }
+  }
+  // everything fields and eval share of terms 3 and 4
+  struct Mid { float fd, fE, Kd, T, S2, A, n1, n2, ik, s_x, Pk, cg, eps_R, eps_h; };
+  __host__ __device__ static inline Mid mid(const float (&v)[1 + ND][NR], float omega, float gamma) {
+    const float h = v[0][0], R = v[0][4], K = v[0][5];
+    const float h_x = v[1][0], R_x = v[1][4], K_x = v[1][5];
+    const float G = 9.81f;
+    const float C_EPS = (float)(0.75 / 1.7724538509055160273);   // (3 sqrt(pi) / 2) / (2 pi)
+    Mid m;
+    const float s = K * h;
+    float n;
+    R1::ratio(s, n, m.n1, m.n2);
+    tanh_sech2(s, m.T, m.S2);
+    m.Kd = G / (omega * omega);
+    m.fd = m.Kd * K * m.T - 1.f;
+    m.ik = 1.0f / K;
+    m.A = 0.5f + n;
+    m.cg = omega * m.A * m.ik;
+    m.s_x = K_x * h + K * h_x;
+    m.Pk = m.n1 * m.s_x * m.ik - m.A * K_x * (m.ik * m.ik);
+    // breaking: B = 1 - u^(-5/2), u = 1 + q^2, as (1 - r)(1 + r + r^2 + r^3 + r^4) with r = u^(-1/2) and 1 - r =
+    // q^2 r^2 / (1 + r): no cancellation at small q; Bp = dB/dq = 5 q u^(-7/2)
+    const float ih = 1.0f / h, ig = 1.0f / gamma;
+    const float q = R * ig * ih;
+    const float r = 1.0f / sqrtf(1.f + q * q), r2 = r * r;
+    const float B = (q * q) * r2 / (1.f + r) * (1.f + r + r2 + r2 * r + r2 * r2);
+    const float Bp = 5.f * q * (r2 * r2 * r2 * r);
+    const float c0 = C_EPS * omega * (ig * ig) * (ih * ih * ih);
+    const float R4 = (R * R) * (R * R);
+    const float eps = c0 * R4 * R * B;
+    m.eps_R = c0 * R4 * (5.f * B + q * Bp);
+    m.eps_h = -c0 * R4 * R * ih * (3.f * B + q * Bp);
+    m.fE = 2.f * R * R_x * m.cg + (R * R) * omega * m.Pk + eps;
+    return m;
+  }
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF], float omega, float gamma) {
+    float f3[R1::NF];
+    R1::fields(v, f3);
+    const Mid m = mid(v, omega, gamma);
+    f[0] = f3[0]; f[1] = f3[1]; f[2] = f3[2];
+    f[3] = m.fd; f[4] = m.fE;
+  }
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* scale, float (&g)[1 + ND][NR],
+                                              float (&sq)[NT], float omega, float gamma) {
+    float sq3[R1::NT];
+    R1::template eval<GRAD>(v, scale, g, sq3);      // terms 0..2 and, with GRAD, all of g
+    const Mid m = mid(v, omega, gamma);
+    sq[0] = sq3[0]; sq[1] = sq3[1]; sq[2] = sq3[2];
+    sq[3] = m.fd * m.fd; sq[4] = m.fE * m.fE;
+    if (GRAD) {
+      const float h = v[0][0], R = v[0][4], K = v[0][5];
+      const float h_x = v[1][0], R_x = v[1][4], K_x = v[1][5];
+      const float rd = 2.f * scale[3] * m.fd, rE = 2.f * scale[4] * m.fE;
+      const float R2w = (R * R) * omega;
+      const float ds = omega * m.ik * (2.f * R * R_x * m.n1 + (R * R) * (m.n2 * m.s_x - m.n1 * K_x * m.ik));   // d f_E / d s
+      const float gsx = R2w * m.n1 * m.ik;                                                                      // d f_E / d s_x
+      const float dK = -omega * (m.ik * m.ik) * (2.f * R * R_x * m.A + (R * R) * (m.n1 * m.s_x - 2.f * m.A * K_x * m.ik));   // through 1 / K
+      g[0][0] += rd * m.Kd * (K * K) * m.S2 + rE * (ds * K + gsx * K_x + m.eps_h);
+      g[0][4] += rE * (2.f * R_x * m.cg + 2.f * R * omega * m.Pk + m.eps_R);
+      g[0][5] += rd * m.Kd * (m.T + (K * h) * m.S2) + rE * (ds * h + gsx * h_x + dK);
+      g[1][0] += rE * gsx * K;                                   // d/dh_x
+      g[1][4] += rE * 2.f * R * m.cg;                            // d/dHrms_x
+      g[1][5] += rE * (gsx * h - R2w * m.A * (m.ik * m.ik));     // d/dk_x
+    }
+  }
+};
+
 // physics.py:37-47 continuity_ftemp(x, y, h, U, V); physics.py:18-33 continuity_only
 // roles: outputs h=0 U=1 V=2; directions x=0 y=1.
 // fc = d(hU)/dx + d(hV)/dy.  continuity_only adds (h - anchor)^2 on the points

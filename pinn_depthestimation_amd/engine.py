@@ -90,12 +90,37 @@ class ResidualSpec:
     threshold: float = 25.5           # physics.py:26
     anchor: float = 0.75              # physics.py:27
     corrected: bool = False           # physics_equation only: the corrected radiation stress (pinn_residual_spec.flags bit 0)
+    wave_omega: float = 0.0           # physics_equation with corrected=True only: > 0 adds the wave closure (flags bit 1): the
+                                      # dispersion relation and the wave-energy balance at angular frequency omega (rad/s)
+    wave_gamma: float = 0.42          # ... its breaker index (Thornton & Guza 1983)
     nu: float = 0.0                   # lateral mixing -nu lap(U) in the momentum equations (Navier_Stokes, physics_equation), in
                                       # the units of the network's inputs; travels BESIDE the C struct (pinn_residual2_loss_grad)
+
+    def __post_init__(self):
+        if self.wave_omega != 0:
+            if self.name != "physics_equation" or not self.corrected:
+                raise PinnError("wave_omega is the wave closure of physics_equation with corrected=True (the dispersion and "
+                                f"wave-energy terms close the corrected radiation stress); got residual {self.name!r}, "
+                                f"corrected={self.corrected}")
+            if not (self.wave_omega > 0 and self.wave_gamma > 0):
+                raise PinnError(f"the wave closure needs wave_omega > 0 and wave_gamma > 0 (got {self.wave_omega}, {self.wave_gamma})")
+            if self.nu != 0:
+                raise PinnError("the wave closure has no second-order form: nu must be 0 with wave_omega")
 
     @property
     def residual_id(self) -> int:
         return RESIDUAL_ROLES[self.name][0]
+
+    @property
+    def closure_key(self):
+        """What the workspace cache keys and the packed-copy token carry for the residual's closure, in `corrected`'s place:
+        `corrected` itself, or "wave" with the wave closure (one entry, so that the token keeps its shape)."""
+        return "wave" if self.wave else self.corrected
+
+    @property
+    def wave(self) -> bool:
+        """The wave closure is on (pinn_residual_spec.flags bit 1)."""
+        return self.wave_omega != 0
 
     def first_order(self, what: str) -> "ResidualSpec":
         """self, for a first-order entry: raises instead of silently dropping the second-order term."""
@@ -105,12 +130,13 @@ class ResidualSpec:
 
     @property
     def n_terms(self) -> int:
-        return RES_TERMS[self.residual_id]
+        return _lib.PEW_TERMS if self.wave else RES_TERMS[self.residual_id]
 
     @property
     def n_fields(self) -> int:
-        """Rows of Engine.residual_fields: (fc, fm_x, fm_y) / (fc, fx, fy) / (fc, da)."""
-        return RES_FIELDS[self.residual_id]
+        """Rows of Engine.residual_fields: (fc, fm_x, fm_y) / (fc, fx, fy) / (fc, da); (fc, fx, fy, f_d, f_E) with the wave
+        closure."""
+        return _lib.PEW_TERMS if self.wave else RES_FIELDS[self.residual_id]
 
     @property
     def n_weighted_terms(self) -> int:
@@ -145,16 +171,18 @@ class ResidualSpec:
             s.out_col[r] = self.out_col[r] if r < len(self.out_col) else 0
         for d in range(_lib.PINN_MAX_DIRS):
             s.dir_of[d] = self.dir_of[d] if d < len(self.dir_of) else 0
-        s.flags = 1 if self.corrected else 0
-        s.param[0], s.param[1] = self.threshold, self.anchor
+        s.flags = 3 if self.wave else (1 if self.corrected else 0)
+        s.param[0], s.param[1] = (self.wave_omega, self.wave_gamma) if self.wave else (self.threshold, self.anchor)
         return s
 
     @staticmethod
     def from_names(name: str, input_names: Sequence[str], grad_cols: Sequence[int],
-                   output_names: Sequence[str], corrected: bool = False, nu: float = 0.0) -> "ResidualSpec":
+                   output_names: Sequence[str], corrected: bool = False, nu: float = 0.0,
+                   wave_omega: float = 0.0, wave_gamma: float = 0.42) -> "ResidualSpec":
         """Map config variable names (config data_residual.inputs / outputs) onto roles.  corrected=True (physics_equation
         only): E = rho g Hrms^2 / 8 in place of the reference's E == 0, as physics.physics_equation(corrected=True).
-        nu (Navier_Stokes, physics_equation): the lateral-mixing term -nu lap(U) in the momentum equations."""
+        nu (Navier_Stokes, physics_equation): the lateral-mixing term -nu lap(U) in the momentum equations.
+        wave_omega > 0 (with corrected=True): the wave closure, as physics.physics_equation(wave_omega=, wave_gamma=)."""
         if name not in RESIDUAL_ROLES:
             raise PinnError(f"unknown residual {name!r}; known: {sorted(RESIDUAL_ROLES)}")
         if corrected and name != "physics_equation":
@@ -178,7 +206,8 @@ class ResidualSpec:
             if col not in grad_cols:
                 raise PinnError(f"input {r!r} must have requires_grad 'true' for residual {name}")
             dir_of.append(list(grad_cols).index(col))
-        return ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected), nu=nu)
+        return ResidualSpec(name, tuple(out_col), tuple(dir_of), corrected=bool(corrected), nu=nu,
+                            wave_omega=float(wave_omega or 0.0), wave_gamma=float(wave_gamma))
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -461,7 +490,7 @@ class Engine:
     def fields_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual_fields (pinn_query_fields_workspace), cached apart from workspace()'s."""
         spec.first_order("fields_workspace")
-        return self._checked_workspace("fields", "pinn_query_fields_workspace", spec, N, engine, spec.residual_id, spec.corrected)
+        return self._checked_workspace("fields", "pinn_query_fields_workspace", spec, N, engine, spec.residual_id, spec.closure_key)
 
     def residual_fields(self, spec: ResidualSpec, params, X, engine=None) -> torch.Tensor:
         """The residual's signed per-point fields, (n_fields, N): row f is field f at every row of X
@@ -492,7 +521,7 @@ class Engine:
     def residual_coef_workspace(self, spec: ResidualSpec, N: int, engine: Optional[int] = None) -> torch.Tensor:
         """Workspace of residual_coef_loss_grad (pinn_query_residual_coef_workspace), cached apart from the others."""
         spec.first_order("residual_coef_workspace")
-        return self._checked_workspace("coef", "pinn_query_residual_coef_workspace", spec, N, engine, spec.residual_id, spec.corrected)
+        return self._checked_workspace("coef", "pinn_query_residual_coef_workspace", spec, N, engine, spec.residual_id, spec.closure_key)
 
     def residual_coef_loss_grad(self, spec: ResidualSpec, coef: torch.Tensor, term_scale: Optional[torch.Tensor], params, X,
                                 grad: Optional[torch.Tensor] = None, coef_grad: Optional[torch.Tensor] = None,
@@ -526,7 +555,7 @@ class Engine:
         """Workspace of residual_weighted_loss_grad (pinn_query_residual_weighted_workspace), cached apart from the others."""
         spec.first_order("residual_weighted_workspace")
         return self._checked_workspace("weighted", "pinn_query_residual_weighted_workspace", spec, N, engine, spec.residual_id,
-                                       spec.corrected)
+                                       spec.closure_key)
 
     def residual_weighted_loss_grad(self, spec: ResidualSpec, weights: torch.Tensor, scale: Optional[torch.Tensor], theta, X,
                                     grad: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None, fields=None,
@@ -662,7 +691,7 @@ class Engine:
                 self._chk(T, "T", (N - n_res if n_res >= 0 else N, nc))
         n_rows = self._chk_losses(loss_rows, losses, nc + spec.n_terms, () if lrs is None else (len(lrs),))
         ws = self.workspace(N)
-        req = (N, int(n_res), nc, spec.residual_id, spec.corrected)
+        req = (N, int(n_res), nc, spec.residual_id, spec.closure_key)
         st = _adam_state(m, v, step, None if lrs is not None else lr, beta1, beta2, eps,
                          _packed_valid(self._packed_tok, ws, params, params_token, req), n_rows, loss_rows, losses)
         self._packed_tok = None
@@ -749,11 +778,11 @@ class Engine:
             a = (C.c_double * max(k, 1))(*xs); keep.append(a)
             return a
 
-        rc, ws = self._workspace("adamext", ("adamext", kind, spec.residual_id, spec.corrected, N, n_fid), lambda: self._query(
+        rc, ws = self._workspace("adamext", ("adamext", kind, spec.residual_id, spec.closure_key, N, n_fid), lambda: self._query(
             "pinn_query_adam_ext_workspace", C.byref(self._d()), C.byref(spec.c_struct()), C.byref(ex), N, n_fid))
         if self._unsupported(rc, "pinn_query_adam_ext_workspace"):
             return False
-        req = ("ext", kind, N, n_fid, nc, spec.residual_id, spec.corrected)
+        req = ("ext", kind, N, n_fid, nc, spec.residual_id, spec.closure_key)
         st = _adam_state(m, v, step, None, beta1, beta2, eps, _packed_valid(self._packed_tok, ws, params, params_token, req),
                          n_rows, loss_rows, losses)
         self._packed_tok = None
@@ -846,11 +875,11 @@ class Engine:
                                None if lam_log is None else lam_log.data_ptr(), None if stats_log is None else stats_log.data_ptr(),
                                None if group_grads is None else group_grads.data_ptr())
         # (the extended loop's buffer: the same layout with the statistics' partials behind it, one packed copy for both)
-        rc, ws = self._workspace("adamext", ("adambal", spec.residual_id, spec.corrected, N, n_fid), lambda: self._query(
+        rc, ws = self._workspace("adamext", ("adambal", spec.residual_id, spec.closure_key, N, n_fid), lambda: self._query(
             "pinn_query_adam_balanced_workspace", C.byref(self._d()), C.byref(spec.c_struct()), N, n_fid))
         if self._unsupported(rc, "pinn_query_adam_balanced_workspace"):
             return False
-        req = ("bal", N, n_fid, nc, spec.residual_id, spec.corrected)
+        req = ("bal", N, n_fid, nc, spec.residual_id, spec.closure_key)
         st = _adam_state(m, v, step, None, beta1, beta2, eps, _packed_valid(self._packed_tok, ws, params, params_token, req),
                          n_rows, loss_rows, losses)
         self._packed_tok = None
@@ -1009,7 +1038,7 @@ class Engine:
         rc, ws = self._ensemble_workspace(M, N)
         if self._unsupported(rc, "pinn_ensemble_query_workspace"):
             return False
-        req = (M, N, int(n_res), nc, flags, spec.residual_id, spec.corrected)
+        req = (M, N, int(n_res), nc, flags, spec.residual_id, spec.closure_key)
         st = _adam_state(m, v, step, None if lrs is not None else lr, beta1, beta2, eps,
                          _packed_valid(self._ens_packed_tok, ws, params, params_token, req), n_rows, loss_rows, losses)
         self._ens_packed_tok = None

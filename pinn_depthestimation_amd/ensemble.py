@@ -81,6 +81,9 @@ class EnsemblePINN:
         loss = cfg.raw.get("loss", {})
         if float(loss.get("eddy_viscosity", 0.0)) != 0.0:
             raise PinnError("EnsemblePINN has no second-order residual (loss.eddy_viscosity): use trainer.PINN per member")
+        if loss.get("wave_period") is not None:
+            raise PinnError("EnsemblePINN has no wave closure (loss.wave_period): the ensemble kernels do not carry the dispersion "
+                            "and wave-energy terms; use trainer.PINN per member")
         self.spec = ResidualSpec.from_names(residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs,
                                             corrected=bool(loss.get("corrected_radiation_stress", False)))
         Xr_in = residual_input

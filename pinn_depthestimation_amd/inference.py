@@ -12,6 +12,7 @@ a whole-module file or a state_dict file; the residual follows the config's vari
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional
 
 import numpy as np
@@ -31,8 +32,11 @@ FIELD_NAMES = {"Navier_Stokes": ("fc", "fm_x", "fm_y"), "physics_equation": ("fc
 
 class Tester:
     def __init__(self, model, config, device="cuda", residual: Optional[str] = None, corrected: bool = False,
-                 eddy_viscosity: float = 0.0):
-        """corrected (physics_equation only): residual_fields and the physics-only fine-tune use the corrected radiation
+                 eddy_viscosity: float = 0.0, wave_period: Optional[float] = None, wave_gamma: Optional[float] = None):
+        """wave_period (seconds) and wave_gamma, or the config keys loss.wave_period / loss.wave_gamma (with a wave period
+        from either source loss.corrected_radiation_stress is read as well): the wave closure of the corrected physics_equation, five fields
+        (fc, fx, fy, f_d, f_E) and five terms in the fine-tune (physics.physics_equation_wave).
+        corrected (physics_equation only): residual_fields and the physics-only fine-tune use the corrected radiation
         stress (ResidualSpec.corrected, physics.physics_equation_corrected).
         eddy_viscosity (Navier_Stokes, physics_equation): nu of the lateral-mixing term -nu lap(U) in the momentum
         equations, in the units of the network's inputs (normalised to [-1, 1] in the reference's pipeline); residual_fields
@@ -49,6 +53,21 @@ class Tester:
         self.nx, self.ny = dt.get("nx"), dt.get("ny")
         self.residual = residual or self.config.default_residual()
         self.corrected = bool(corrected)
+        loss_cfg = raw.get("loss", {}) or {}
+        if wave_period is None:
+            wave_period = loss_cfg.get("wave_period")
+        if wave_period is not None:      # (with a wave period in effect, from either source, the config's corrected key counts)
+            self.corrected = self.corrected or bool(loss_cfg.get("corrected_radiation_stress", False))
+        self.wave_period = None if wave_period is None else float(wave_period)
+        self.wave_gamma = float(loss_cfg.get("wave_gamma", 0.42) if wave_gamma is None else wave_gamma)
+        if self.wave_period is not None:
+            if self.residual != "physics_equation" or not self.corrected:
+                raise PinnError("wave_period is the wave closure of physics_equation with corrected=True; got residual "
+                                f"{self.residual!r}, corrected={self.corrected}")
+            if not (self.wave_period > 0 and self.wave_gamma > 0):
+                raise PinnError(f"the wave closure needs wave_period > 0 and wave_gamma > 0 (got {self.wave_period}, {self.wave_gamma})")
+            if eddy_viscosity:
+                raise PinnError("the wave closure (wave_period) does not run with eddy_viscosity != 0")
         if self.corrected and self.residual != "physics_equation":
             raise PinnError(f"corrected=True is the radiation stress of physics_equation; residual {self.residual!r} has none")
         self.eddy_viscosity = float(eddy_viscosity)
@@ -58,6 +77,11 @@ class Tester:
             raise PinnError(f"eddy_viscosity is the lateral mixing of a momentum equation; residual {self.residual!r} has none")
         self.init_optimizers()
         self.last_loss = None
+
+    @property
+    def wave_omega(self) -> float:
+        """2 pi / wave_period, 0 without the wave closure."""
+        return 0.0 if self.wave_period is None else 2.0 * math.pi / self.wave_period
 
     def load_model(self, model) -> DNN:
         if isinstance(model, DNN):
@@ -90,6 +114,8 @@ class Tester:
         if self.eddy_viscosity != 0:
             kw = {"corrected": True} if self.corrected else {}
             return getattr(physics, self.residual)(*args, nu=self.eddy_viscosity, **kw)
+        if self.wave_period is not None:
+            return physics.physics_equation_wave(*args, omega=self.wave_omega, gamma=self.wave_gamma)
         fn = physics.physics_equation_corrected if self.corrected else getattr(physics, self.residual)
         return fn(*args)
 
@@ -135,7 +161,7 @@ class Tester:
         names = list(self.test_input_vars)
         grad_cols = tuple(i for i, k in enumerate(names) if "true" in self.test_input_vars[k].get("requires_grad", []))
         spec = ResidualSpec.from_names(self.residual, names, grad_cols, self.test_output_vars, corrected=self.corrected,
-                                       nu=self.eddy_viscosity)
+                                       nu=self.eddy_viscosity, wave_omega=self.wave_omega, wave_gamma=self.wave_gamma)
         key = (tuple(self.model.layer_sizes), grad_cols, self.model.activation_id)
         if getattr(self, "_fields_engine_key", None) != key:
             self._fields_engine = Engine(NetDesc.from_layers(self.model.layer_sizes, grad_cols,
@@ -152,7 +178,7 @@ class Tester:
                 if input_min_max is not None and k in input_min_max:
                     grid = op.denormalize(grid, input_min_max[k][0], input_min_max[k][1])
                 setattr(self, f"plot_input_{k}", grid)
-            for name, row in zip(FIELD_NAMES[self.residual], out):
+            for name, row in zip(FIELD_NAMES[self.residual] + (("f_d", "f_E") if spec.wave else ()), out):
                 setattr(self, f"plot_res_{name}", row.reshape(self.ny, self.nx))
         return out
 

@@ -11,8 +11,11 @@ second-order jet (pinn_forward_jet2); a third derivative raises PinnError.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
+from ._lib import PinnError
 from .autograd import fused_residual
 
 
@@ -92,7 +95,7 @@ def Navier_Stokes(t, x, y, h, z, u, v, nu=0.0, gamma_b=None):
     return _mean_sq(mass, mom_x, mom_y)
 
 
-def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0, Cd=None):
+def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0, Cd=None, wave_omega=None, wave_gamma=0.42):
     """physics.py:91-120 — steady wave-averaged continuity + momentum with quadratic bottom
     friction.  Default is bug-compatible: the reference's E = 1/8**rho*g*Hrms**2 (physics.py:106)
     is exactly 0.0, so the radiation-stress gradients vanish and Hrms, k do not enter.
@@ -109,7 +112,24 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0, 
 
     Cd (an extension too): the drag coefficient, a float or a tensor, in place of the reference's 0.002.  When given, the
     formula below runs with that value and, for a tensor that requires grad, torch autograd supplies d loss / d Cd; the
-    kernel-speed route is Engine.residual_coef_loss_grad (trainer.PINN(trainable_coefficients=("Cd",)))."""
+    kernel-speed route is Engine.residual_coef_loss_grad (trainer.PINN(trainable_coefficients=("Cd",))).
+
+    wave_omega (an extension, with corrected=True only): the wave closure — two more terms that tie k and Hrms to the depth,
+    at the waves' angular frequency omega (rad/s) and the breaker index wave_gamma, with s = k h:
+        f_d = g k tanh(s) / omega^2 - 1                                    (linear dispersion, dimensionless)
+        f_E = d/dx (Hrms^2 c_g) + eps,   c_g = (omega / k) (1/2 + s / sinh 2s)
+        eps = (3 sqrt(pi) / 2) (omega / 2 pi) Hrms^5 / (gamma^2 h^3) [1 - (1 + (Hrms / (gamma h))^2)^(-5/2)]
+    (wave-energy flux balance divided by rho g / 8; dissipation of Thornton & Guza 1983 with B = 1; waves travel along +x,
+    as the residual's Sxy = 0 has it).  k > 0 and h > 0 are the caller's to ensure.  This function evaluates them through
+    compute_gradient like any user residual; physics_equation_wave is the hard-wired route."""
+    if wave_omega is not None:
+        if not corrected:
+            raise PinnError("wave_omega is the wave closure of physics_equation(corrected=True): the dispersion and "
+                            "wave-energy terms close the corrected radiation stress")
+        if nu != 0 or Cd is not None:
+            raise PinnError("the wave closure (wave_omega) has no form with nu or Cd")
+        if not (wave_omega > 0 and wave_gamma > 0):
+            raise PinnError(f"the wave closure needs wave_omega > 0 and wave_gamma > 0 (got {wave_omega}, {wave_gamma})")
     if Cd is not None:
         pass      # the formula route: the hard-wired kernels carry the constant
     elif nu != 0:
@@ -134,6 +154,15 @@ def physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=False, nu=0.0, 
     if nu != 0:
         mom_x = mom_x - nu * _laplacian(U, x, y)
         mom_y = mom_y - nu * _laplacian(V, x, y)
+    if wave_omega is not None:
+        s = k * h
+        disp = g * k * torch.tanh(s) / wave_omega ** 2 - 1
+        cg = (wave_omega / k) * (0.5 + s / torch.sinh(2 * s))
+        q = Hrms / (wave_gamma * h)
+        eps = (1.5 * math.sqrt(math.pi)) * (wave_omega / (2 * math.pi)) * Hrms ** 5 / (wave_gamma ** 2 * h ** 3) \
+            * (1 - (1 + q ** 2) ** (-2.5))
+        energy = d(Hrms ** 2 * cg, x) + eps
+        return _mean_sq(mass, mom_x, mom_y, disp, energy)
     return _mean_sq(mass, mom_x, mom_y)
 
 
@@ -147,3 +176,18 @@ def physics_equation_corrected(x, y, h, U, V, eta_mean, Hrms, k):
     if fused is not None:
         return fused
     return physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=True)
+
+
+def physics_equation_wave(x, y, h, U, V, eta_mean, Hrms, k, omega, gamma=0.42):
+    """physics_equation(..., corrected=True, wave_omega=omega, wave_gamma=gamma) hard-wired: where the arguments are the
+    input and output columns of one DNN.forward call (and the engine serves it: tanh, width <= 64), the five-term loss and
+    d loss / d theta come from ONE kernel with the wave closure in its epilogue (ResidualSpec.wave_omega).  Otherwise the
+    formula itself: the same loss.  One difference: at kh -> 0 the kernels take the limits of kh / sinh 2kh and tanh kh
+    from their series, where the formula loses digits (and gives NaN at kh = 0)."""
+    if not (omega > 0 and gamma > 0):
+        raise PinnError(f"the wave closure needs omega > 0 and gamma > 0 (got {omega}, {gamma})")
+    fused = fused_residual("physics_equation", (x, y), (h, U, V, eta_mean, Hrms, k), corrected=True, wave_omega=omega,
+                           wave_gamma=gamma)
+    if fused is not None:
+        return fused
+    return physics_equation(x, y, h, U, V, eta_mean, Hrms, k, corrected=True, wave_omega=omega, wave_gamma=gamma)

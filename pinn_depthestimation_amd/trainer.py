@@ -14,6 +14,7 @@ restores line-by-line behaviour): log.txt has the same lines, just written in ba
 """
 from __future__ import annotations
 
+import math
 import json
 import os
 from dataclasses import dataclass
@@ -86,7 +87,7 @@ def sa_weight_grad(lam: torch.Tensor, fields: torch.Tensor, term_scale: torch.Te
 
 def weighted_refusal(residual_weights=False, self_adaptive=False, rad_importance=False, reducer_active=False, eddy_viscosity=0.0,
                      coefficients=False, corrected=False, lbfgs_impl="flat", custom_evaluator=False, residual_batch=None,
-                     resample="uniform"):
+                     resample="uniform", wave=False):
     """Why trainer.PINN cannot run this configuration with point weights on the residual — fixed residual_weights, self_adaptive
     or rad_importance (None: it can, or none is asked for).  Pure host logic, evaluated before anything touches a device."""
     if not (residual_weights or self_adaptive or rad_importance):
@@ -97,6 +98,8 @@ def weighted_refusal(residual_weights=False, self_adaptive=False, rad_importance
         return "point weights on the residual do not run with eddy_viscosity != 0 (the second-order residual has no weighted form)"
     if coefficients:
         return "point weights on the residual do not run with runtime closure coefficients (the coefficient kernels have no weights)"
+    if wave:
+        return "point weights on the residual do not run with the wave closure (wave_period: its kernels have no weights)"
     if corrected:
         return "point weights on the residual do not run with the corrected radiation stress (the corrected kernels have no weights)"
     if lbfgs_impl == "device":
@@ -135,7 +138,7 @@ def device_lbfgs_refusal(reducer_active, residual_batch, eddy_viscosity, custom_
 
 
 def coefficient_refusal(residual, coefficients, trainable, corrected=False, eddy_viscosity=0.0, reducer_active=False,
-                        resample="uniform", custom_evaluator=False):
+                        resample="uniform", custom_evaluator=False, wave=False):
     """Why trainer.PINN cannot run this configuration with runtime closure coefficients (None: it can, or none are asked
     for).  Pure host logic.  coefficients: {name: value}; trainable: names."""
     coefficients, trainable = dict(coefficients or {}), tuple(trainable or ())
@@ -143,6 +146,8 @@ def coefficient_refusal(residual, coefficients, trainable, corrected=False, eddy
         return None
     if residual not in RESIDUAL_ROLES:
         return f"unknown residual {residual!r}"
+    if wave:
+        return "the wave closure (wave_period) has no coefficient form (its kernels carry the constant Cd)"
     if corrected:
         return "the corrected radiation stress has no coefficient form (the corrected kernels carry the constant Cd)"
     have = _lib.RES_COEFS[RESIDUAL_ROLES[residual][0]]
@@ -188,7 +193,8 @@ def fold_extras_refusal(fold_extras=False, coefficients=False, weighted=False, r
 
 
 def balance_refusal(loss_balancing=None, groups="sets", every=10, alpha=0.1, ref="residual", fold_extras=False, coefficients=False,
-                    weighted=False, rad_importance=False, eddy_viscosity=0.0, reducer_active=False, custom_evaluator=False):
+                    weighted=False, rad_importance=False, eddy_viscosity=0.0, reducer_active=False, custom_evaluator=False,
+                    wave=False):
     """Why trainer.PINN cannot run this configuration with gradient-statistics loss balancing (None: it can, or none is asked
     for).  Pure host logic, evaluated before anything touches a device."""
     if loss_balancing is None:
@@ -210,12 +216,29 @@ def balance_refusal(loss_balancing=None, groups="sets", every=10, alpha=0.1, ref
                 "two schemes would set the same weights")
     if eddy_viscosity:
         return "loss balancing does not run with eddy_viscosity != 0"
+    if wave:
+        return "loss balancing does not run with the wave closure (wave_period: the balanced loop has no pass for it)"
     if reducer_active:
         return "loss balancing does not run under data parallelism (the statistics are taken on one rank's gradients)"
     if custom_evaluator:
         return "loss balancing needs the library's own evaluator, not a custom one"
     if groups == "terms" and fold_extras:
         return "balance_groups='terms' does not run with fold_extras (the device-enqueued runs balance the two point sets; a group per term needs one-hot passes)"
+    return None
+
+
+def wave_refusal(wave_period, wave_gamma, residual, corrected, eddy_viscosity=0.0):
+    """Why trainer.PINN cannot train with the wave closure as configured (None: it can, or no wave_period is given).  Pure
+    host logic."""
+    if wave_period is None:
+        return None
+    if residual != "physics_equation" or not corrected:
+        return ("wave_period is the wave closure of physics_equation with the corrected radiation stress (corrected=True / "
+                f"loss.corrected_radiation_stress): got residual {residual!r}, corrected={bool(corrected)}")
+    if not (float(wave_period) > 0 and float(wave_gamma) > 0):
+        return f"the wave closure needs wave_period > 0 and wave_gamma > 0 (got {wave_period}, {wave_gamma})"
+    if eddy_viscosity:
+        return "the wave closure (wave_period) does not run with eddy_viscosity != 0 (it has no second-order form)"
     return None
 
 
@@ -470,6 +493,8 @@ class Options:
     every refusal and every later use reads this record."""
     residual: str
     corrected: bool
+    wave_period: Optional[float]     # seconds; None: no wave closure
+    wave_gamma: float
     nu: float                        # eddy_viscosity
     coef_in: dict                    # coefficient values given, by name
     coef_tr: tuple                   # names of the trainable coefficients
@@ -488,6 +513,10 @@ class Options:
     lbfgs_impl: str
     custom_evaluator: bool
     reducer_active: bool
+
+    @property
+    def wave(self) -> bool:
+        return self.wave_period is not None
 
     @property
     def has_coef(self) -> bool:
@@ -516,7 +545,7 @@ class PINN:
                  trainable_coefficients: Sequence[str] = (), residual_weights=None, self_adaptive=None,
                  rad_importance: Optional[bool] = None, fold_extras: bool = False, loss_balancing: Optional[str] = None,
                  balance_every: Optional[int] = None, balance_alpha: Optional[float] = None, balance_ref: Optional[str] = None,
-                 balance_groups: Optional[str] = None):
+                 balance_groups: Optional[str] = None, wave_period: Optional[float] = None, wave_gamma: Optional[float] = None):
         """loss_balancing (or the config key loss.balancing): "max_mean" (Wang, Teng & Perdikaris 2021) or "norm" (Wang et al.
         2023) — the weights of the loss groups are set from the groups' own gradients during the Adam stage
         (include/pinn_hip.h: pinn_balance_update): on every balance_every-th iteration, from the first, the statistics of the
@@ -558,6 +587,12 @@ class PINN:
         corrected (or the config key loss.corrected_radiation_stress; physics_equation only): train on the corrected
         radiation stress, E = rho g Hrms^2 / 8, hard-wired in the kernels (ResidualSpec.corrected) — every path that takes
         the spec follows: the merged launch, the folded Adam runs, residual_fields and resample="rad".
+        wave_period (or the config key loss.wave_period, seconds; with corrected only) and wave_gamma (loss.wave_gamma, default
+        0.42): the wave closure — the dispersion relation and the wave-energy balance as a fourth and a fifth residual term at
+        omega = 2 pi / wave_period (ResidualSpec.wave_omega, physics.physics_equation_wave), weight 1 each like the other
+        terms.  Every path that takes the spec follows: the merged launch, the folded Adam runs, residual_fields,
+        resample="rad", lbfgs_impl="device".  What is refused: wave_refusal decides, and the coefficient, weighted and
+        balancing refusals name it.
         eddy_viscosity (or the config key loss.eddy_viscosity; Navier_Stokes and physics_equation): nu of the lateral-mixing
         term -nu lap(U) in the momentum equations (ResidualSpec.nu), in the units of the network's inputs — normalised to
         [-1, 1] in the reference's pipeline.  The residual then runs on Engine.residual2_loss_grad, the fidelity term
@@ -575,6 +610,8 @@ class PINN:
         o = self.options = Options(
             residual=residual or cfg.default_residual(),
             corrected=bool(corrected) or bool(loss_cfg.get("corrected_radiation_stress", False)),
+            wave_period=given(wave_period, loss_cfg.get("wave_period")),
+            wave_gamma=float(given(wave_gamma, loss_cfg.get("wave_gamma", 0.42))),
             nu=float(eddy_viscosity) if eddy_viscosity else float(loss_cfg.get("eddy_viscosity", 0.0)),
             coef_in=dict(coefficients) if coefficients else dict(loss_cfg.get("coefficients") or {}),
             coef_tr=tuple(trainable_coefficients) if trainable_coefficients else tuple(loss_cfg.get("trainable_coefficients") or ()),
@@ -592,12 +629,13 @@ class PINN:
             if why:
                 raise PinnError(why)
         # every refusal is pure host logic on the record, decided before anything touches a device
+        refuse(wave_refusal(o.wave_period, o.wave_gamma, o.residual, o.corrected, o.nu))
         refuse(coefficient_refusal(o.residual, o.coef_in, o.coef_tr, o.corrected, o.nu, o.reducer_active, o.resample,
-                                   o.custom_evaluator))
+                                   o.custom_evaluator, o.wave))
         refuse(weighted_refusal(o.fixed_weights, o.sa_opt is not None, o.rad_imp, o.reducer_active, o.nu, o.has_coef, o.corrected,
-                                o.lbfgs_impl, o.custom_evaluator, o.residual_batch, o.resample))
+                                o.lbfgs_impl, o.custom_evaluator, o.residual_batch, o.resample, o.wave))
         refuse(balance_refusal(o.balancing, o.balance_groups, o.balance_every, o.balance_alpha, o.balance_ref, o.fold_extras,
-                               o.has_coef, o.weighted, o.rad_imp, o.nu, o.reducer_active, o.custom_evaluator))
+                               o.has_coef, o.weighted, o.rad_imp, o.nu, o.reducer_active, o.custom_evaluator, o.wave))
         if o.balancing is not None and (fidelity_input is None or residual_input is None or
                                         len(fidelity_input) == 0 or len(residual_input) == 0):
             raise PinnError("loss balancing weighs the fidelity set against the collocation set: it needs points in both")
@@ -626,8 +664,10 @@ class PINN:
         P = self.theta.numel()
 
         self.corrected, self.eddy_viscosity = o.corrected, o.nu
+        self.wave_period, self.wave_gamma = o.wave_period, o.wave_gamma
         self.spec = ResidualSpec.from_names(o.residual, cfg.residual_inputs, cfg.grad_cols, cfg.residual_outputs,
-                                            corrected=o.corrected, nu=o.nu)   # (PinnError on any other residual)
+                                            corrected=o.corrected, nu=o.nu, wave_gamma=o.wave_gamma,
+                                            wave_omega=2.0 * math.pi / float(o.wave_period) if o.wave else 0.0)   # (PinnError on any other residual)
         # i-th fidelity output is compared with output column i (train.py:137-138, train_newmethod.py:129-131)
         self.fid_cols = list(range(len(cfg.fidelity_outputs)))
         self.weight_fidelity, self.weight_residual = cfg.weight_fid, cfg.weight_res

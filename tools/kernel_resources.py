@@ -29,7 +29,7 @@ def parse(path):
 
 
 def nice(n):
-    m = re.search(r"k_fusedILi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELi(\d)ELi(\d)ELi(\d)ELb(\d)", n)
+    m = re.search(r"k_fusedILi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)", n)
     return "k_fused<WP=%s,K1=%s,GRAD=%s,LDSACC=%s,ACT=%s,EPI=%s,KRO=%s,DROP=%s>" % m.groups() if m else n
 
 
