@@ -757,6 +757,16 @@ __device__ __forceinline__ void scatter_adjoint(float* __restrict__ tb, const fl
   __builtin_amdgcn_wave_barrier();
 }
 
+// The residual's closure (residuals.h) from the parameter block — the one place here that knows which residual takes what:
+// continuity its anchor switch, this point's mask and the anchor value; the wave closure (omega, gamma), which
+// set_residual_roles puts into P.thr and P.anchor (spec.param[0..1]); the others nothing.
+template <class RES>
+__device__ __forceinline__ typename RES::Closure residual_closure(const FusedParams& P, bool masked) {
+  if constexpr (std::is_same<RES, ResContinuity>::value) return {P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor};
+  else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value) return {P.thr, P.anchor};
+  else return {};
+}
+
 // Evaluate one residual family on the gathered jet; writes the adjoint tile G (acc layout).
 template <class RES, int K1, bool GRAD>
 __device__ __forceinline__ void residual_tile(const FusedParams& P, const f4 (&out)[K1][1], f4 (&G)[K1][1],
@@ -773,12 +783,7 @@ __device__ __forceinline__ void residual_tile(const FusedParams& P, const f4 (&o
   }
 #pragma unroll
   for (int t = 0; t < NT; ++t) sc[t] = GRAD ? P.scale[t] : 0.f;
-  if constexpr (std::is_same<RES, ResContinuity>::value)
-    RES::template eval<GRAD>(v, sc, g, sq, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
-  else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value)
-    RES::template eval<GRAD>(v, sc, g, sq, P.thr, P.anchor);      // (omega, gamma: set_residual_roles puts spec.param[0..1] there)
-  else
-    RES::template eval<GRAD>(v, sc, g, sq);
+  RES::template eval<GRAD>(v, residual_closure<RES>(P, masked), sc, g, sq);
   if (valid && q == 0 && primary) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) sums[term_slot(t)] += sq[t];
@@ -860,12 +865,7 @@ __device__ __forceinline__ void field_tile(const FusedParams& P, const f4 (&out)
 #pragma unroll
     for (int r = 0; r < NR; ++r) v[c][r] = gather_out(tile, P.out_col[r], p);
   }
-  if constexpr (std::is_same<RES, ResContinuity>::value)
-    RES::fields(v, f, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
-  else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value)
-    RES::fields(v, f, P.thr, P.anchor);
-  else
-    RES::fields(v, f);
+  RES::fields(v, residual_closure<RES>(P, masked), f);
   if (valid && q == 0) {
 #pragma unroll
     for (int t = 0; t < NF; ++t) P.Y[(int64_t)t * P.N + pt] = f[t];
@@ -950,16 +950,10 @@ __device__ __forceinline__ void residual_tile_weighted(const FusedParams& P, con
   // the weighted sums and the field store take the fields formed apart from the adjoint's arithmetic (residuals.h,
   // isolated_fields): the forward-only and the gradient instance round them alike
   float f[NF];
-  if constexpr (std::is_same<RES, ResContinuity>::value)
-    isolated_fields<RES>(v, f, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
-  else
-    isolated_fields<RES>(v, f);
+  isolated_fields<RES>(v, residual_closure<RES>(P, masked), f);
 #pragma unroll
   for (int t = 0; t < NT; ++t) sc[t] = GRAD ? (t < NW ? P.scale[t] * w[t] : P.scale[t]) : 0.f;
-  if constexpr (std::is_same<RES, ResContinuity>::value)
-    RES::template eval<GRAD>(v, sc, g, sq, P.residual_id == PINN_RES_CONTINUITY_ONLY, masked, P.anchor);
-  else
-    RES::template eval<GRAD>(v, sc, g, sq);
+  RES::template eval<GRAD>(v, residual_closure<RES>(P, masked), sc, g, sq);
   if (valid && q == 0) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) sums[t] = t < NW ? __fmaf_rn(w[t], f[t] * f[t], sums[t]) : sums[t] + sq[t];

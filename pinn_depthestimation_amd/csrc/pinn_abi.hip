@@ -400,6 +400,18 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
   if (i < P) p[i] = adam_update(p[i], g[i], m[i], v[i], c);
 }
 
+// The *_point entries' copy-in / copy-out (the residuals of residuals.h at ONE point, on the host): the flat jet v ->
+// jet[1 + ND][NR], body(jet, gj), and, where body says it formed the adjoint, gj -> the flat g.
+template <class R, class F>
+static void point_jet(const float* v, float* g, F body) {
+  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR];
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
+  if (!body(jet, gj)) return;
+  for (int c = 0; c <= R::ND; ++c)
+    for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
+}
+
 }  // namespace pinn
 
 using namespace pinn;
@@ -415,14 +427,13 @@ const char* pinn_last_error(void) { return g_err; }
 int32_t pinn_pe_corrected_point(const float v[18], const float scale[3], float fields[3], float g[18]) {
   typedef ResPhysicsEquationCorrected R;
   if (!v || !fields) { set_error("NULL pointer argument"); return PINN_ERR_INVALID; }
-  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], sq[R::NT];
-  for (int c = 0; c <= R::ND; ++c)
-    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
-  R::fields(jet, *reinterpret_cast<float (*)[R::NF]>(fields));
-  if (!scale || !g) return PINN_OK;
-  R::eval<true>(jet, scale, gj, sq);
-  for (int c = 0; c <= R::ND; ++c)
-    for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
+  point_jet<R>(v, g, [&](const float (&jet)[1 + R::ND][R::NR], float (&gj)[1 + R::ND][R::NR]) {
+    float sq[R::NT];
+    R::fields(jet, R::Closure(), *reinterpret_cast<float (*)[R::NF]>(fields));
+    if (!scale || !g) return false;
+    R::eval<true>(jet, R::Closure(), scale, gj, sq);
+    return true;
+  });
   return PINN_OK;
 }
 
@@ -433,14 +444,14 @@ int32_t pinn_pe_wave_point(const float v[18], float omega, float gamma, const fl
     set_error("pinn_pe_wave_point: the wave closure needs omega > 0 and gamma > 0 (got %g, %g)", (double)omega, (double)gamma);
     return PINN_ERR_INVALID;
   }
-  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], sq[R::NT];
-  for (int c = 0; c <= R::ND; ++c)
-    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
-  R::fields(jet, *reinterpret_cast<float (*)[R::NF]>(fields), omega, gamma);
-  if (!scale || !g) return PINN_OK;
-  R::eval<true>(jet, scale, gj, sq, omega, gamma);
-  for (int c = 0; c <= R::ND; ++c)
-    for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
+  const R::Closure cl = {omega, gamma};
+  point_jet<R>(v, g, [&](const float (&jet)[1 + R::ND][R::NR], float (&gj)[1 + R::ND][R::NR]) {
+    float sq[R::NT];
+    R::fields(jet, cl, *reinterpret_cast<float (*)[R::NF]>(fields));
+    if (!scale || !g) return false;
+    R::eval<true>(jet, cl, scale, gj, sq);
+    return true;
+  });
   return PINN_OK;
 }
 
@@ -1079,18 +1090,15 @@ template <class B>
 static void residual2_point(float nu, const float* v, const float* lap, const float* scale, float* fields, float* g,
                             float* glap) {
   typedef Residual2<B> R;
-  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], f[R::NF], gl[2];
+  float f[R::NF];
   const float l2[2] = {lap[0], lap[1]};
-  for (int c = 0; c <= R::ND; ++c)
-    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
-  if (!scale || !g || !glap) {
-    R::fields(jet, l2, nu, f);
-  } else {
+  point_jet<R>(v, g, [&](const float (&jet)[1 + R::ND][R::NR], float (&gj)[1 + R::ND][R::NR]) {
+    if (!scale || !g || !glap) { R::fields(jet, l2, nu, f); return false; }
+    float gl[2];
     R::template eval<true>(jet, l2, nu, scale, f, gj, gl);
-    for (int c = 0; c <= R::ND; ++c)
-      for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
     glap[0] = gl[0]; glap[1] = gl[1];
-  }
+    return true;
+  });
   for (int t = 0; t < R::NF; ++t) fields[t] = f[t];
 }
 }  // extern "C++"
@@ -1164,16 +1172,15 @@ int32_t pinn_residual2_loss_grad(const pinn_desc* desc, const pinn_residual_spec
 extern "C++" {
 template <class R>
 static void residual_coef_point(const float* v, const float* coef, const float* scale, float* fields, float* g, float* gcoef) {
-  float jet[1 + R::ND][R::NR], gj[1 + R::ND][R::NR], f[R::NF], sq[R::NT], gc[R::NC];
-  for (int c = 0; c <= R::ND; ++c)
-    for (int r = 0; r < R::NR; ++r) jet[c][r] = v[c * R::NR + r];
-  R::fields(jet, coef, f);
-  for (int t = 0; t < R::NF; ++t) fields[t] = f[t];
-  if (!scale || !g || !gcoef) return;
-  R::template eval<true>(jet, coef, scale, gj, sq, gc);
-  for (int c = 0; c <= R::ND; ++c)
-    for (int r = 0; r < R::NR; ++r) g[c * R::NR + r] = gj[c][r];
-  for (int j = 0; j < R::NC; ++j) gcoef[j] = gc[j];
+  point_jet<R>(v, g, [&](const float (&jet)[1 + R::ND][R::NR], float (&gj)[1 + R::ND][R::NR]) {
+    float f[R::NF], sq[R::NT], gc[R::NC];
+    R::fields(jet, coef, f);
+    for (int t = 0; t < R::NF; ++t) fields[t] = f[t];
+    if (!scale || !g || !gcoef) return false;
+    R::template eval<true>(jet, coef, scale, gj, sq, gc);
+    for (int j = 0; j < R::NC; ++j) gcoef[j] = gc[j];
+    return true;
+  });
 }
 }  // extern "C++"
 

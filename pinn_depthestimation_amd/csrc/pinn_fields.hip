@@ -21,6 +21,21 @@ struct FieldsJetParams {
   float thr, anchor;
 };
 
+// The residual's closure (residuals.h) from the parameter block — the one place here that knows which residual takes what:
+// continuity its anchor switch, point i's mask and the anchor value; the wave closure (omega, gamma) = spec.param[0..1],
+// which arrive as (thr, anchor); the others nothing.
+template <class RES>
+__device__ inline typename RES::Closure residual_closure(const FieldsJetParams& P, int64_t i) {
+  if constexpr (std::is_same<RES, ResContinuity>::value) {
+    const bool masked = P.anchor_on && P.X[i * P.d_in + P.xcol] < P.thr;
+    return {P.anchor_on != 0, masked, P.anchor};
+  } else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value) {
+    return {P.thr, P.anchor};
+  } else {
+    return {};
+  }
+}
+
 // one thread per point: the roles' columns of the jet -> RES::fields -> fields[f * N + n0 + i]
 template <class RES>
 __global__ __launch_bounds__(256) void k_fields_from_jet(const FieldsJetParams P) {
@@ -35,14 +50,7 @@ __global__ __launch_bounds__(256) void k_fields_from_jet(const FieldsJetParams P
 #pragma unroll
     for (int d = 0; d < ND; ++d) v[1 + d][r] = P.dY[((int64_t)P.dir_of[d] * P.n + i) * P.d_out + o];
   }
-  if constexpr (std::is_same<RES, ResContinuity>::value) {
-    const bool masked = P.anchor_on && P.X[i * P.d_in + P.xcol] < P.thr;
-    RES::fields(v, f, P.anchor_on != 0, masked, P.anchor);
-  } else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value) {
-    RES::fields(v, f, P.thr, P.anchor);      // (spec.param[0..1]: omega, gamma)
-  } else {
-    RES::fields(v, f);
-  }
+  RES::fields(v, residual_closure<RES>(P, i), f);
 #pragma unroll
   for (int t = 0; t < NF; ++t) P.fields[(int64_t)t * P.N + P.n0 + i] = f[t];
 }

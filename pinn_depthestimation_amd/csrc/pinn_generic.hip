@@ -264,6 +264,22 @@ struct RoleMap {
   int q_of[PINN_MAX_DIRS];  // quantity index (1 + direction index) of each direction role
 };
 
+// The residual's closure (residuals.h) from the residual kernels' arguments — the one place here that knows which residual
+// takes what: continuity its anchor switch, point n's mask (x < thr, continuity_only) and the anchor value; the wave closure
+// (omega, gamma) = spec.param[0..1], which arrive as (thr, anchor); the others nothing.
+template <class RES>
+__device__ inline typename RES::Closure residual_closure(const float* __restrict__ X, int64_t n, int d_in, int xcol,
+                                                         int anchor_on, float thr, float anchor) {
+  if constexpr (std::is_same<RES, ResContinuity>::value) {
+    const bool masked = anchor_on ? (X[n * d_in + xcol] < thr) : false;
+    return {anchor_on != 0, masked, anchor};
+  } else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value) {
+    return {thr, anchor};
+  } else {
+    return {};
+  }
+}
+
 template <class RES, bool GRAD>
 __global__ void k_residual(const float* __restrict__ yj, int d_out, int64_t N, RoleMap rm,
                            const float* __restrict__ scale, const float* __restrict__ X, int d_in, int xcol,
@@ -285,14 +301,7 @@ __global__ void k_residual(const float* __restrict__ yj, int d_out, int64_t N, R
     float sc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) sc[t] = GRAD ? scale[t] : 0.f;
-    if constexpr (std::is_same<RES, ResContinuity>::value) {
-      const bool masked = anchor_on ? (X[n * d_in + xcol] < thr) : false;
-      RES::template eval<GRAD>(v, sc, g, sq, anchor_on != 0, masked, anchor);
-    } else if constexpr (std::is_same<RES, ResPhysicsEquationWave>::value) {
-      RES::template eval<GRAD>(v, sc, g, sq, thr, anchor);      // (spec.param[0..1]: omega, gamma)
-    } else {
-      RES::template eval<GRAD>(v, sc, g, sq);
-    }
+    RES::template eval<GRAD>(v, residual_closure<RES>(X, n, d_in, xcol, anchor_on, thr, anchor), sc, g, sq);
     if (GRAD) {
 #pragma unroll
       for (int c = 0; c <= ND; ++c) {
@@ -333,14 +342,9 @@ __global__ void k_residual_weighted(const float* __restrict__ yj, int d_out, int
 #pragma unroll
     for (int t = 0; t < NT; ++t) sc[t] = GRAD ? (t < NW ? scale[t] * wt[t] : scale[t]) : 0.f;
     // (the fields of the sums and of the store: formed apart from the adjoint's arithmetic, residuals.h isolated_fields)
-    if constexpr (std::is_same<RES, ResContinuity>::value) {
-      const bool masked = anchor_on ? (X[n * d_in + xcol] < thr) : false;
-      isolated_fields<RES>(v, f, anchor_on != 0, masked, anchor);
-      RES::template eval<GRAD>(v, sc, g, st, anchor_on != 0, masked, anchor);
-    } else {
-      isolated_fields<RES>(v, f);
-      RES::template eval<GRAD>(v, sc, g, st);
-    }
+    const typename RES::Closure cl = residual_closure<RES>(X, n, d_in, xcol, anchor_on, thr, anchor);
+    isolated_fields<RES>(v, cl, f);
+    RES::template eval<GRAD>(v, cl, sc, g, st);
 #pragma unroll
     for (int t = 0; t < NT; ++t) sq[t] = t < NW ? wt[t] * (f[t] * f[t]) : st[t];
     if (fields) {

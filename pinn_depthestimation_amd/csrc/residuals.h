@@ -9,65 +9,106 @@
 // restates.  v[c][r]: c = 0 value, c = 1+d the derivative along direction role
 // d; r = output role.  g has the same shape and receives
 // sum_t scale[t] * d(field_t^2)/dv.
+//
+// Each PDE states its field expressions ONCE and its adjoint ONCE, as __host__ __device__ functions (the *_point entries
+// of pinn_abi.hip run them on the host, where tests hold them to fp64 without a GPU):
+//   fields(v, closure, f)                 the signed fields
+//   adjoint(v, rc, rx, ry, g)             g <- rc dfc/dv + rx dfx/dv + ry dfy/dv  (rc, rx, ry: 2 scale[t] f[t] in eval)
+//   eval<GRAD>(v, closure, scale, g, sq)  fields, their squares and, with GRAD, the adjoint
+// and everything else is derived from them: the coefficient structs pass a run-time closure constant to the same
+// functions, the second-order structs add only which roles carry the Laplacian.  `closure` is the
+// residual's own small Closure type — what it needs beside the jet — so that every caller has one call shape.
+// Three pairs remain, each marked THE ONLY PAIR with its reason: the field lines of Navier_Stokes and of physics_equation
+// under a second rounding contract, and the corrected physics_equation's adjoint inside its eval.
+// In an eval, rc, rx, ry are NAMED before the adjoint call, in that order: the order instructions reach the optimiser in
+// decides which product of a sum of two is fused into the multiply-add, i.e. the last bits (tools/residual_parity.py).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace pinn {
 
+struct NoClosure {};
+
 // physics.py:50-88  Navier_Stokes(t, x, y, h, z, u, v)
 // roles: outputs h=0 z=1 u=2 v=3; directions t=0 x=1 y=2
+// The breaking constant CB = 3/16 g gamma_b^2 (physics.py:76-78) is an argument of the shared functions (*_cb): this struct
+// passes the compile-time constant formed in double, ResNavierStokesCoef the fp32 run-time value.
 struct ResNavierStokes {
-  static constexpr int NR = 4, ND = 3, NT = 3;
-  template <bool GRAD>
-  __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* scale,
-                                     float (&g)[1 + ND][NR], float (&sq)[NT]) {
+  static constexpr int NR = 4, ND = 3, NT = 3, NF = 3;
+  typedef NoClosure Closure;
+  static constexpr float CB0 = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78));   // physics.py:76-78
+  // the signed fields f = (fc, fm_x, fm_y)
+  __host__ __device__ static inline void fields_cb(const float (&v)[1 + ND][NR], float CB, float (&f)[NF]) {
     const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
     const float z_t = v[1][1], u_t = v[1][2], w_t = v[1][3];
     const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
     const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
     const float G = 9.81f;                                      // physics.py:75
-    const float CB = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78)); // physics.py:76-78
     const float H = h + z;                  // total depth h+z (physics.py:64-68)
     const float Hx = h_x + z_x, Hy = h_y + z_y;
     const float hu_x = Hx * u + H * u_x;    // d((h+z)u)/dx  physics.py:67
     const float hv_y = Hy * w + H * w_y;    // d((h+z)v)/dy  physics.py:68
     const float Fbr_x = CB * Hx * H, Fbr_y = CB * Hy * H;       // physics.py:77-78
-    const float fc = z_t + hu_x + hv_y;                          // physics.py:81
-    const float fmx = u_t + u * u_x + w * u_y + G * z_x + Fbr_x; // physics.py:82
-    const float fmy = w_t + u * w_x + w * w_y + G * z_y + Fbr_y; // physics.py:83
-    sq[0] = fc * fc; sq[1] = fmx * fmx; sq[2] = fmy * fmy;       // physics.py:86
-    if (GRAD) {
-      const float rc = 2.f * scale[0] * fc, rx = 2.f * scale[1] * fmx, ry = 2.f * scale[2] * fmy;
-      const float gh = rc * (u_x + w_y) + CB * (rx * Hx + ry * Hy);
-      g[0][0] = gh; g[0][1] = gh;
-      g[0][2] = rc * Hx + rx * u_x + ry * w_x;
-      g[0][3] = rc * Hy + rx * u_y + ry * w_y;
-      g[1][0] = 0.f; g[1][1] = rc; g[1][2] = rx; g[1][3] = ry;
-      const float ghx = rc * u + rx * CB * H;
-      g[2][0] = ghx; g[2][1] = ghx + rx * G;
-      g[2][2] = rc * H + rx * u; g[2][3] = ry * u;
-      const float ghy = rc * w + ry * CB * H;
-      g[3][0] = ghy; g[3][1] = ghy + ry * G;
-      g[3][2] = rx * w; g[3][3] = rc * H + ry * w;
-    }
+    f[0] = z_t + hu_x + hv_y;                                // physics.py:81
+    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;        // physics.py:82
+    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;        // physics.py:83
   }
-  // the signed fields themselves (pinn_residual_fields): f = (fc, fm_x, fm_y), eval's expressions term for term
-  static constexpr int NF = 3;
-  __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+  // THE ONLY PAIR: fields_cb's lines once more under contract(off), for ResNavierStokesCoef.  Its fields must round the same
+  // way in every instance (the forward-only sums equal the gradient call's bit for bit), the plain fields keep the
+  // contraction the compiler chooses (switching them off would change the bits of every plain kernel), and the pragma is
+  // lexical — it does not follow an inlined callee — so two rounding contracts are two statements.  Change both or neither.
+  __host__ __device__ static inline void fields_cb_strict(const float (&v)[1 + ND][NR], float CB, float (&f)[NF]) {
+#pragma clang fp contract(off)
     const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
     const float z_t = v[1][1], u_t = v[1][2], w_t = v[1][3];
     const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
     const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
     const float G = 9.81f;
-    const float CB = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78));
     const float H = h + z;
     const float Hx = h_x + z_x, Hy = h_y + z_y;
     const float hu_x = Hx * u + H * u_x;
     const float hv_y = Hy * w + H * w_y;
     const float Fbr_x = CB * Hx * H, Fbr_y = CB * Hy * H;
-    f[0] = z_t + hu_x + hv_y;                                // physics.py:81
-    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;        // physics.py:82
-    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;        // physics.py:83
+    f[0] = z_t + hu_x + hv_y;
+    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;
+    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;
+  }
+  // g <- rc dfc/dv + rx dfm_x/dv + ry dfm_y/dv
+  __host__ __device__ static inline void adjoint_cb(const float (&v)[1 + ND][NR], float CB, float rc, float rx, float ry,
+                                                    float (&g)[1 + ND][NR]) {
+    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
+    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
+    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
+    const float G = 9.81f;
+    const float H = h + z;
+    const float Hx = h_x + z_x, Hy = h_y + z_y;
+    const float gh = rc * (u_x + w_y) + CB * (rx * Hx + ry * Hy);
+    g[0][0] = gh; g[0][1] = gh;
+    g[0][2] = rc * Hx + rx * u_x + ry * w_x;
+    g[0][3] = rc * Hy + rx * u_y + ry * w_y;
+    g[1][0] = 0.f; g[1][1] = rc; g[1][2] = rx; g[1][3] = ry;
+    const float ghx = rc * u + rx * CB * H;
+    g[2][0] = ghx; g[2][1] = ghx + rx * G;
+    g[2][2] = rc * H + rx * u; g[2][3] = ry * u;
+    const float ghy = rc * w + ry * CB * H;
+    g[3][0] = ghy; g[3][1] = ghy + ry * G;
+    g[3][2] = rx * w; g[3][3] = rc * H + ry * w;
+  }
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const Closure&, float (&f)[NF]) { fields_cb(v, CB0, f); }
+  __host__ __device__ static inline void adjoint(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
+                                                 float (&g)[1 + ND][NR]) {
+    adjoint_cb(v, CB0, rc, rx, ry, g);
+  }
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const Closure& cl, const float* scale,
+                                              float (&g)[1 + ND][NR], float (&sq)[NT]) {
+    float f[NF];
+    fields(v, cl, f);
+    sq[0] = f[0] * f[0]; sq[1] = f[1] * f[1]; sq[2] = f[2] * f[2];   // physics.py:86
+    if (GRAD) {
+      const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
+      adjoint(v, rc, rx, ry, g);
+    }
   }
 };
 
@@ -75,61 +116,88 @@ struct ResNavierStokes {
 // roles: outputs h=0 U=1 V=2 eta_mean=3 Hrms=4 k=5; directions x=0 y=1.
 // Bug-compatible with physics.py:106: E = 1/8**rho*g*Hrms**2 == 0.0, so the
 // radiation-stress terms Sxx_x, Syy_y contribute exactly 0 to loss and gradient
-// and Hrms, k receive zero adjoints.  The zero is written 0 * |rx + ry|: +0 at every finite point, NaN
-// where the point's momentum fields are not finite, so that the gradient of the two output biases is NaN at a NaN point as
-// the reference's is (0.0 * nan; tests/test_nonfinite_gpu.py).  It is a NaN carrier only, not physics.py's expression: there
-// E = 0.0 * Hrms**2 also makes fx and fy NaN when Hrms or k ALONE is not finite, which these kernels' forward does not.
+// and Hrms, k receive zero adjoints.
+// The friction constant RC = rho Cd (physics.py:102-103) is an argument of the shared functions (*_rc): this struct passes
+// the compile-time constant formed in double, ResPhysicsEquationCoef the fp32 run-time value.
 struct ResPhysicsEquation {
-  static constexpr int NR = 6, ND = 2, NT = 3;
-  template <bool GRAD>
-  __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* scale,
-                                     float (&g)[1 + ND][NR], float (&sq)[NT]) {
+  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3;
+  typedef NoClosure Closure;
+  static constexpr float RC0 = (float)(1025 * 0.002);     // rho*Cd  physics.py:102-103
+  // the signed fields f = (fc, fx, fy)
+  __host__ __device__ static inline void fields_rc(const float (&v)[1 + ND][NR], float RC, float (&f)[NF]) {
     const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
     const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
     const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
     const float G = 9.81f, RHO = 1025.f;
-    const float RC = (float)(1025 * 0.002);      // rho*Cd  physics.py:102-103
     const float tbx = (RC * U) * fabsf(U);       // tau_bx  physics.py:102
     const float tby = (RC * V) * fabsf(V);       // tau_by  physics.py:103
     const float D = 1.0f / (RHO * (eta + h));    // physics.py:114-115
-    const float fc = U_x + V_y;                                  // physics.py:113
-    const float fx = U * U_x + V * U_y + G * e_x + D * tbx;      // physics.py:114 (Sxx_x+Sxy_y == 0)
-    const float fy = U * V_x + V * V_y + G * e_y + D * tby;      // physics.py:115
-    sq[0] = fc * fc; sq[1] = fx * fx; sq[2] = fy * fy;           // physics.py:118
-    if (GRAD) {
-      const float rc = 2.f * scale[0] * fc, rx = 2.f * scale[1] * fx, ry = 2.f * scale[2] * fy;
-#pragma unroll
-      for (int c = 0; c < 1 + ND; ++c)
-#pragma unroll
-        for (int r = 0; r < NR; ++r) g[c][r] = 0.f;
-      const float dD = -RHO * D * D;             // d D / d(eta+h)
-      const float gS = dD * (rx * tbx + ry * tby);
-      g[0][0] = gS; g[0][3] = gS;
-      g[0][4] = g[0][5] = 0.f * fabsf(rx + ry);
-      g[0][1] = rx * (U_x + D * RC * 2.f * fabsf(U)) + ry * V_x;
-      g[0][2] = rx * U_y + ry * (V_y + D * RC * 2.f * fabsf(V));
-      g[1][1] = rc + rx * U;   // d/dU_x
-      g[1][2] = ry * U;        // d/dV_x
-      g[1][3] = rx * G;        // d/deta_x
-      g[2][1] = rx * V;        // d/dU_y
-      g[2][2] = rc + ry * V;   // d/dV_y
-      g[2][3] = ry * G;        // d/deta_y
-    }
+    f[0] = U_x + V_y;                                        // physics.py:113
+    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;            // physics.py:114 (Sxx_x+Sxy_y == 0)
+    f[2] = U * V_x + V * V_y + G * e_y + D * tby;            // physics.py:115
   }
-  // f = (fc, fx, fy), eval's expressions term for term
-  static constexpr int NF = 3;
-  __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+  // THE ONLY PAIR: fields_rc's lines once more under contract(off), for ResPhysicsEquationCoef — as
+  // ResNavierStokes::fields_cb_strict, for the same reasons.  Change both or neither.
+  __host__ __device__ static inline void fields_rc_strict(const float (&v)[1 + ND][NR], float RC, float (&f)[NF]) {
+#pragma clang fp contract(off)
     const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
     const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
     const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
     const float G = 9.81f, RHO = 1025.f;
-    const float RC = (float)(1025 * 0.002);
     const float tbx = (RC * U) * fabsf(U);
     const float tby = (RC * V) * fabsf(V);
     const float D = 1.0f / (RHO * (eta + h));
-    f[0] = U_x + V_y;                                        // physics.py:113
-    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;            // physics.py:114
-    f[2] = U * V_x + V * V_y + G * e_y + D * tby;            // physics.py:115
+    f[0] = U_x + V_y;
+    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;
+    f[2] = U * V_x + V * V_y + G * e_y + D * tby;
+  }
+  // g <- rc dfc/dv + rx dfx/dv + ry dfy/dv; zero on Hrms, k and on every derivative the fields do not read
+  __host__ __device__ static inline void adjoint_rc(const float (&v)[1 + ND][NR], float RC, float rc, float rx, float ry,
+                                                    float (&g)[1 + ND][NR]) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
+    const float U_x = v[1][1], V_x = v[1][2];
+    const float U_y = v[2][1], V_y = v[2][2];
+    const float G = 9.81f, RHO = 1025.f;
+    const float tbx = (RC * U) * fabsf(U);
+    const float tby = (RC * V) * fabsf(V);
+    const float D = 1.0f / (RHO * (eta + h));
+#pragma unroll
+    for (int c = 0; c < 1 + ND; ++c)
+#pragma unroll
+      for (int r = 0; r < NR; ++r) g[c][r] = 0.f;
+    const float dD = -RHO * D * D;             // d D / d(eta+h)
+    const float gS = dD * (rx * tbx + ry * tby);
+    g[0][0] = gS; g[0][3] = gS;
+    g[0][1] = rx * (U_x + D * RC * 2.f * fabsf(U)) + ry * V_x;
+    g[0][2] = rx * U_y + ry * (V_y + D * RC * 2.f * fabsf(V));
+    g[1][1] = rc + rx * U;   // d/dU_x
+    g[1][2] = ry * U;        // d/dV_x
+    g[1][3] = rx * G;        // d/deta_x
+    g[2][1] = rx * V;        // d/dU_y
+    g[2][2] = rc + ry * V;   // d/dV_y
+    g[2][3] = ry * G;        // d/deta_y
+  }
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const Closure&, float (&f)[NF]) { fields_rc(v, RC0, f); }
+  __host__ __device__ static inline void adjoint(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
+                                                 float (&g)[1 + ND][NR]) {
+    adjoint_rc(v, RC0, rc, rx, ry, g);
+  }
+  // THE NaN CARRIER, in this eval only — never in the coefficient or the second-order form, whose callers and tests know
+  // exact zeros there.  The zero adjoint of Hrms and k is written 0 * |rx + ry|: +0 at every finite point, NaN where the
+  // point's momentum fields are not finite, so that the gradient of the two output biases is NaN at a NaN point as the
+  // reference's is (0.0 * nan; tests/test_nonfinite_gpu.py).  It is a NaN carrier only, not physics.py's expression: there
+  // E = 0.0 * Hrms**2 also makes fx and fy NaN when Hrms or k ALONE is not finite, which these kernels' forward does not.
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const Closure& cl, const float* scale,
+                                              float (&g)[1 + ND][NR], float (&sq)[NT]) {
+    float f[NF];
+    fields(v, cl, f);
+    sq[0] = f[0] * f[0]; sq[1] = f[1] * f[1]; sq[2] = f[2] * f[2];   // physics.py:118
+    if (GRAD) {
+      const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
+      adjoint(v, rc, rx, ry, g);
+      g[0][4] = g[0][5] = 0.f * fabsf(rx + ry);
+    }
   }
 };
 
@@ -137,9 +205,9 @@ struct ResPhysicsEquation {
 // physics.physics_equation(..., corrected=True)): E = rho g Hrms^2 / 8, Sxx = E (2n + 1/2), Syy = E n, n = kh / sinh 2kh.
 // Same roles and directions as ResPhysicsEquation; selected by pinn_residual_spec.flags bit 0, never by an id of its own.
 //   fx = U U_x + V U_y + G eta_x + D (tbx + d Sxx / dx),   fy likewise with d Syy / dy
-// __host__ __device__: pinn_pe_corrected_point (pinn_abi.hip) evaluates the very same functions on the host.
 struct ResPhysicsEquationCorrected {
   static constexpr int NR = 6, ND = 2, NT = 3, NF = 3;
+  typedef NoClosure Closure;
   // n(s) = s / sinh 2s with n1 = dn/ds = (S - 2sC) / S^2 and n2 = d2n/ds2 = 4 (s S^2 - C S + 2s) / S^3 (S = sinh 2s,
   // C = cosh 2s).  Formed from t = exp(-2|s|): 1/S = 2t / (1 - t^2), C/S = (1 + t^2) / (1 - t^2) — nothing overflows,
   // however large |s| (t underflows to 0 and with it n, n1, n2) — and by parity (n, n2 even, n1 odd).  Below |s| = 1/4
@@ -165,7 +233,7 @@ struct ResPhysicsEquationCorrected {
       n2 = 4.f * iS * (a - ct + 2.f * a * (iS * iS));
     }
   }
-  // everything eval and fields share
+  // everything the fields and the adjoint share
   struct Mid { float D, tbx, tby, E, n, n1, n2, s_x, s_y, E_x, E_y, Sx, Sy; };
   __host__ __device__ static inline Mid mid(const float (&v)[1 + ND][NR]) {
     const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3], R = v[0][4], K = v[0][5];
@@ -186,7 +254,7 @@ struct ResPhysicsEquationCorrected {
     m.Sy = m.E_y * m.n + m.E * m.n1 * m.s_y;                        // d Syy / dy
     return m;
   }
-  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF]) {
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const Closure&, float (&f)[NF]) {
     const float U = v[0][1], V = v[0][2];
     const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
     const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
@@ -196,11 +264,48 @@ struct ResPhysicsEquationCorrected {
     f[1] = U * U_x + V * U_y + G * e_x + m.D * (m.tbx + m.Sx);
     f[2] = U * V_x + V * V_y + G * e_y + m.D * (m.tby + m.Sy);
   }
+  // The adjoint on given (rc, rx, ry), for Residual2<> — eval's lines below once more: THE ONLY PAIR of this struct, kept
+  // because eval written as a call of this function does not compile to the parent's code (the sum g[0][1] has its two
+  // products fused the other way round and the gradient's last bits differ: DESIGN.md 2.20).  Change both or neither.
+  __host__ __device__ static inline void adjoint(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
+                                                 float (&g)[1 + ND][NR]) {
+    const float h = v[0][0], U = v[0][1], V = v[0][2], R = v[0][4], K = v[0][5];
+    const float h_x = v[1][0], U_x = v[1][1], V_x = v[1][2], R_x = v[1][4], K_x = v[1][5];
+    const float h_y = v[2][0], U_y = v[2][1], V_y = v[2][2], R_y = v[2][4], K_y = v[2][5];
+    const float G = 9.81f, RHO = 1025.f;
+    const float RC = (float)(1025 * 0.002);
+    const float C_E = (float)(1025 * 9.81 / 8.0);
+    const Mid m = mid(v);
+    const float ax = rx * m.D, ay = ry * m.D;
+    const float dD = -RHO * m.D * m.D;             // d D / d(eta+h)
+    const float gS = dD * (rx * (m.tbx + m.Sx) + ry * (m.tby + m.Sy));
+    const float ds = ax * (2.f * m.E_x * m.n1 + 2.f * m.E * m.n2 * m.s_x) + ay * (m.E_y * m.n1 + m.E * m.n2 * m.s_y);   // adjoint of s = kh
+    const float gsx = 2.f * ax * m.E * m.n1, gsy = ay * m.E * m.n1;   // adjoints of s_x, s_y
+    const float nn = 2.f * m.n + 0.5f;
+    g[0][0] = gS + ds * K + gsx * K_x + gsy * K_y;
+    g[0][1] = rx * (U_x + m.D * RC * 2.f * fabsf(U)) + ry * V_x;
+    g[0][2] = rx * U_y + ry * (V_y + m.D * RC * 2.f * fabsf(V));
+    g[0][3] = gS;
+    g[0][4] = ax * (2.f * C_E * R_x * nn + 4.f * C_E * R * m.n1 * m.s_x) + ay * (2.f * C_E * R_y * m.n + 2.f * C_E * R * m.n1 * m.s_y);
+    g[0][5] = ds * h + gsx * h_x + gsy * h_y;
+    g[1][0] = gsx * K;       // d/dh_x
+    g[1][1] = rc + rx * U;   // d/dU_x
+    g[1][2] = ry * U;        // d/dV_x
+    g[1][3] = rx * G;        // d/deta_x
+    g[1][4] = 2.f * ax * C_E * R * nn;   // d/dHrms_x
+    g[1][5] = gsx * h;       // d/dk_x
+    g[2][0] = gsy * K;
+    g[2][1] = rx * V;
+    g[2][2] = rc + ry * V;
+    g[2][3] = ry * G;
+    g[2][4] = 2.f * ay * C_E * R * m.n;
+    g[2][5] = gsy * h;
+  }
   template <bool GRAD>
-  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* scale,
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const Closure& cl, const float* scale,
                                               float (&g)[1 + ND][NR], float (&sq)[NT]) {
     float f[NF];
-    fields(v, f);
+    fields(v, cl, f);
     sq[0] = f[0] * f[0]; sq[1] = f[1] * f[1]; sq[2] = f[2] * f[2];
     if (GRAD) {
       const float h = v[0][0], U = v[0][1], V = v[0][2], R = v[0][4], K = v[0][5];
@@ -255,6 +360,7 @@ struct ResPhysicsEquationCorrected {
 struct ResPhysicsEquationWave {
   typedef ResPhysicsEquationCorrected R1;
   static constexpr int NR = 6, ND = 2, NT = 5, NF = 5;
+  struct Closure { float omega, gamma; };   // pinn_residual_spec.param[0..1]
   __host__ __device__ static inline void tanh_sech2(float s, float& T, float& S2) {
     const float a = fabsf(s);
     if (a < 0.25f) {
@@ -305,19 +411,20 @@ struct ResPhysicsEquationWave {
     m.fE = 2.f * R * R_x * m.cg + (R * R) * omega * m.Pk + eps;
     return m;
   }
-  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF], float omega, float gamma) {
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const Closure& cl, float (&f)[NF]) {
     float f3[R1::NF];
-    R1::fields(v, f3);
-    const Mid m = mid(v, omega, gamma);
+    R1::fields(v, R1::Closure(), f3);
+    const Mid m = mid(v, cl.omega, cl.gamma);
     f[0] = f3[0]; f[1] = f3[1]; f[2] = f3[2];
     f[3] = m.fd; f[4] = m.fE;
   }
   template <bool GRAD>
-  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* scale, float (&g)[1 + ND][NR],
-                                              float (&sq)[NT], float omega, float gamma) {
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const Closure& cl, const float* scale,
+                                              float (&g)[1 + ND][NR], float (&sq)[NT]) {
+    const float omega = cl.omega;
     float sq3[R1::NT];
-    R1::template eval<GRAD>(v, scale, g, sq3);      // terms 0..2 and, with GRAD, all of g
-    const Mid m = mid(v, omega, gamma);
+    R1::template eval<GRAD>(v, R1::Closure(), scale, g, sq3);      // terms 0..2 and, with GRAD, all of g
+    const Mid m = mid(v, omega, cl.gamma);
     sq[0] = sq3[0]; sq[1] = sq3[1]; sq[2] = sq3[2];
     sq[3] = m.fd * m.fd; sq[4] = m.fE * m.fE;
     if (GRAD) {
@@ -340,73 +447,63 @@ struct ResPhysicsEquationWave {
 
 // physics.py:37-47 continuity_ftemp(x, y, h, U, V); physics.py:18-33 continuity_only
 // roles: outputs h=0 U=1 V=2; directions x=0 y=1.
-// fc = d(hU)/dx + d(hV)/dy.  continuity_only adds (h - anchor)^2 on the points
+// fc = d(hU)/dx + d(hV)/dy.  continuity_only (anchor_on) adds (h - anchor)^2 on the points
 // with x < threshold (physics.py:26-28); `masked` says whether this point is one.
 struct ResContinuity {
-  static constexpr int NR = 3, ND = 2, NT = 3;
-  template <bool GRAD>
-  __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* scale,
-                                     float (&g)[1 + ND][NR], float (&sq)[NT],
-                                     bool anchor_on, bool masked, float anchor) {
+  static constexpr int NR = 3, ND = 2, NT = 3, NF = 2;
+  struct Closure { bool anchor_on, masked; float anchor; };
+  // f = (fc, da): da = h - anchor on the masked points of continuity_only, 0 elsewhere and for continuity_ftemp
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const Closure& cl, float (&f)[NF]) {
     const float h = v[0][0], U = v[0][1], V = v[0][2];
     const float h_x = v[1][0], U_x = v[1][1];
     const float h_y = v[2][0], V_y = v[2][2];
-    const float fc = h_x * U + h * U_x + h_y * V + h * V_y;      // physics.py:20-23,39-42
+    f[0] = h_x * U + h * U_x + h_y * V + h * V_y;                        // physics.py:20-23,39-42
+    f[1] = (cl.anchor_on && cl.masked) ? (h - cl.anchor) : 0.f;          // physics.py:27-28
+  }
+  // sq = (fc^2, da^2, 1 on a masked point of continuity_only: the count the anchor's mean divides by)
+  template <bool GRAD>
+  __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const Closure& cl, const float* scale,
+                                              float (&g)[1 + ND][NR], float (&sq)[NT]) {
+    float f[NF];
+    fields(v, cl, f);
+    const float fc = f[0], da = f[1];
     sq[0] = fc * fc;
-    const float da = (anchor_on && masked) ? (h - anchor) : 0.f; // physics.py:27-28
     sq[1] = da * da;
-    sq[2] = (anchor_on && masked) ? 1.f : 0.f;
+    sq[2] = (cl.anchor_on && cl.masked) ? 1.f : 0.f;
     if (GRAD) {
+      const float h = v[0][0], U = v[0][1], V = v[0][2];
+      const float h_x = v[1][0], U_x = v[1][1];
+      const float h_y = v[2][0], V_y = v[2][2];
       const float rc = 2.f * scale[0] * fc;
 #pragma unroll
       for (int c = 0; c < 1 + ND; ++c)
 #pragma unroll
         for (int r = 0; r < NR; ++r) g[c][r] = 0.f;
-      g[0][0] = rc * (U_x + V_y) + (anchor_on ? 2.f * scale[1] * da : 0.f);
+      g[0][0] = rc * (U_x + V_y) + (cl.anchor_on ? 2.f * scale[1] * da : 0.f);
       g[0][1] = rc * h_x;
       g[0][2] = rc * h_y;
       g[1][0] = rc * U; g[1][1] = rc * h;
       g[2][0] = rc * V; g[2][2] = rc * h;
     }
   }
-  // f = (fc, da): da = h - anchor on the masked points of continuity_only, 0 elsewhere and for continuity_ftemp
-  static constexpr int NF = 2;
-  __device__ static inline void fields(const float (&v)[1 + ND][NR], float (&f)[NF],
-                                       bool anchor_on, bool masked, float anchor) {
-    const float h = v[0][0], U = v[0][1], V = v[0][2];
-    const float h_x = v[1][0], U_x = v[1][1];
-    const float h_y = v[2][0], V_y = v[2][2];
-    f[0] = h_x * U + h * U_x + h_y * V + h * V_y;            // physics.py:20-23,39-42
-    f[1] = (anchor_on && masked) ? (h - anchor) : 0.f;       // physics.py:27-28
-  }
 };
 
 // ---- runtime closure coefficients (pinn_residual_coef_loss_grad) -----------------------------------------------------
 // Navier_Stokes and the plain physics_equation with their one physical closure read from an array instead of the literal
 // above: coef[0] = gamma_b (physics.py:76, default 0.78) resp. Cd (physics.py:99, default 0.002).  NC coefficients;
-// gc[j] <- d/d coef[j] sum_t scale[t] field_t^2 at this point (0 without GRAD).  The formulas are the structs' above with
-// CB resp. RC formed in fp32 at run time (there: in double at compile time), so at the defaults the two agree to
-// rounding, not bit for bit.  __host__ __device__: pinn_residual_coef_point runs the very same functions on the host.
+// gc[j] <- d/d coef[j] sum_t scale[t] field_t^2 at this point (0 without GRAD).  The formulas are the plain structs' own
+// functions with CB resp. RC formed in fp32 at run time (there: in double at compile time), so at the defaults the two
+// agree to rounding, not bit for bit; the fields and their squares are formed under contract(off) (fields_*_strict above).
 struct ResNavierStokesCoef {
-  static constexpr int NR = 4, ND = 3, NT = 3, NF = 3, NC = 1;
+  typedef ResNavierStokes P;
+  static constexpr int NR = P::NR, ND = P::ND, NT = P::NT, NF = P::NF, NC = 1;
   static constexpr float DEFAULTS[NC] = {0.78f};
-  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const float* coef, float (&f)[NF]) {
-#pragma clang fp contract(off)   // the fields round the same way in every instance: the forward-only sums equal the gradient call's bit for bit
-    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
-    const float z_t = v[1][1], u_t = v[1][2], w_t = v[1][3];
-    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
-    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
-    const float G = 9.81f;
+  __host__ __device__ static inline float cb(const float* coef) {
     const float gb = coef[0];
-    const float CB = (float)(3.0 / 16.0 * 9.81) * (gb * gb);   // physics.py:76-78
-    const float H = h + z;
-    const float Hx = h_x + z_x, Hy = h_y + z_y;
-    const float hu_x = Hx * u + H * u_x;
-    const float hv_y = Hy * w + H * w_y;
-    const float Fbr_x = CB * Hx * H, Fbr_y = CB * Hy * H;
-    f[0] = z_t + hu_x + hv_y;                                // physics.py:81
-    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;        // physics.py:82
-    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;        // physics.py:83
+    return (float)(3.0 / 16.0 * 9.81) * (gb * gb);   // physics.py:76-78
+  }
+  __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const float* coef, float (&f)[NF]) {
+    P::fields_cb_strict(v, cb(coef), f);
   }
   template <bool GRAD>
   __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* coef, const float* scale,
@@ -419,47 +516,21 @@ struct ResNavierStokesCoef {
     }
     gc[0] = 0.f;
     if (GRAD) {
-      const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
-      const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
-      const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
-      const float G = 9.81f;
-      const float gb = coef[0];
-      const float CB = (float)(3.0 / 16.0 * 9.81) * (gb * gb);
-      const float H = h + z;
-      const float Hx = h_x + z_x, Hy = h_y + z_y;
+      const float H = v[0][0] + v[0][1], Hx = v[2][0] + v[2][1], Hy = v[3][0] + v[3][1];
       const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
-      const float gh = rc * (u_x + w_y) + CB * (rx * Hx + ry * Hy);
-      g[0][0] = gh; g[0][1] = gh;
-      g[0][2] = rc * Hx + rx * u_x + ry * w_x;
-      g[0][3] = rc * Hy + rx * u_y + ry * w_y;
-      g[1][0] = 0.f; g[1][1] = rc; g[1][2] = rx; g[1][3] = ry;
-      const float ghx = rc * u + rx * CB * H;
-      g[2][0] = ghx; g[2][1] = ghx + rx * G;
-      g[2][2] = rc * H + rx * u; g[2][3] = ry * u;
-      const float ghy = rc * w + ry * CB * H;
-      g[3][0] = ghy; g[3][1] = ghy + ry * G;
-      g[3][2] = rx * w; g[3][3] = rc * H + ry * w;
-      gc[0] = (rx * Hx * H + ry * Hy * H) * ((float)(3.0 / 8.0 * 9.81) * gb);   // d CB / d gamma_b = 3/8 g gamma_b
+      P::adjoint_cb(v, cb(coef), rc, rx, ry, g);
+      gc[0] = (rx * Hx * H + ry * Hy * H) * ((float)(3.0 / 8.0 * 9.81) * coef[0]);   // d CB / d gamma_b = 3/8 g gamma_b
     }
   }
 };
 
 struct ResPhysicsEquationCoef {   // the plain residual (E == 0, physics.py:106); the corrected stress has no coefficient form
-  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3, NC = 1;
+  typedef ResPhysicsEquation P;
+  static constexpr int NR = P::NR, ND = P::ND, NT = P::NT, NF = P::NF, NC = 1;
   static constexpr float DEFAULTS[NC] = {0.002f};
+  __host__ __device__ static inline float rho_cd(const float* coef) { return 1025.f * coef[0]; }   // physics.py:102-103
   __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const float* coef, float (&f)[NF]) {
-#pragma clang fp contract(off)   // the fields round the same way in every instance: the forward-only sums equal the gradient call's bit for bit
-    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
-    const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
-    const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
-    const float G = 9.81f, RHO = 1025.f;
-    const float RC = RHO * coef[0];              // rho*Cd  physics.py:102-103
-    const float tbx = (RC * U) * fabsf(U);
-    const float tby = (RC * V) * fabsf(V);
-    const float D = 1.0f / (RHO * (eta + h));
-    f[0] = U_x + V_y;                                        // physics.py:113
-    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;            // physics.py:114
-    f[2] = U * V_x + V * V_y + G * e_y + D * tby;            // physics.py:115
+    P::fields_rc_strict(v, rho_cd(coef), f);
   }
   template <bool GRAD>
   __host__ __device__ static inline void eval(const float (&v)[1 + ND][NR], const float* coef, const float* scale,
@@ -473,29 +544,10 @@ struct ResPhysicsEquationCoef {   // the plain residual (E == 0, physics.py:106)
     gc[0] = 0.f;
     if (GRAD) {
       const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
-      const float U_x = v[1][1], V_x = v[1][2];
-      const float U_y = v[2][1], V_y = v[2][2];
-      const float G = 9.81f, RHO = 1025.f;
-      const float RC = RHO * coef[0];
-      const float tbx = (RC * U) * fabsf(U);
-      const float tby = (RC * V) * fabsf(V);
+      const float RHO = 1025.f;
       const float D = 1.0f / (RHO * (eta + h));
       const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
-#pragma unroll
-      for (int c = 0; c < 1 + ND; ++c)
-#pragma unroll
-        for (int r = 0; r < NR; ++r) g[c][r] = 0.f;
-      const float dD = -RHO * D * D;             // d D / d(eta+h)
-      const float gS = dD * (rx * tbx + ry * tby);
-      g[0][0] = gS; g[0][3] = gS;
-      g[0][1] = rx * (U_x + D * RC * 2.f * fabsf(U)) + ry * V_x;
-      g[0][2] = rx * U_y + ry * (V_y + D * RC * 2.f * fabsf(V));
-      g[1][1] = rc + rx * U;   // d/dU_x
-      g[1][2] = ry * U;        // d/dV_x
-      g[1][3] = rx * G;        // d/deta_x
-      g[2][1] = rx * V;        // d/dU_y
-      g[2][2] = rc + ry * V;   // d/dV_y
-      g[2][3] = ry * G;        // d/deta_y
+      P::adjoint_rc(v, rho_cd(coef), rc, rx, ry, g);
       gc[0] = D * RHO * (rx * (U * fabsf(U)) + ry * (V * fabsf(V)));   // d tau_b / d Cd = rho U|U|
     }
   }
@@ -508,129 +560,11 @@ struct ResPhysicsEquationCoef {   // the plain residual (E == 0, physics.py:106)
 // caller forms them from whatever pair layout it carries.  Adjoint: the first-order one with rx = 2 scale[1] fx and
 // ry = 2 scale[2] fy of the SHIFTED fields, and glap = (-nu rx, -nu ry), which the caller puts on the (x, x) and (y, y)
 // pairs of role u and of role v; every other second-order adjoint is zero.
-// Each base restates its residual's first-order formulas as __host__ __device__ code (pinn_residual2_point runs them on
-// the host) split into fields1 and adjoint1(rc, rx, ry); the first-order structs above are left as they are.
-struct Res2NavierStokes {   // ResNavierStokes' roles and directions; u = role 2, v = role 3, x = direction 1, y = direction 2
-  static constexpr int NR = 4, ND = 3, NT = 3, NF = 3, RU = 2, RV = 3, DX = 1, DY = 2;
-  __host__ __device__ static inline void fields1(const float (&v)[1 + ND][NR], float (&f)[NF]) {
-    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
-    const float z_t = v[1][1], u_t = v[1][2], w_t = v[1][3];
-    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
-    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
-    const float G = 9.81f;
-    const float CB = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78));
-    const float H = h + z;
-    const float Hx = h_x + z_x, Hy = h_y + z_y;
-    const float hu_x = Hx * u + H * u_x;
-    const float hv_y = Hy * w + H * w_y;
-    const float Fbr_x = CB * Hx * H, Fbr_y = CB * Hy * H;
-    f[0] = z_t + hu_x + hv_y;                                // physics.py:81
-    f[1] = u_t + u * u_x + w * u_y + G * z_x + Fbr_x;        // physics.py:82
-    f[2] = w_t + u * w_x + w * w_y + G * z_y + Fbr_y;        // physics.py:83
-  }
-  __host__ __device__ static inline void adjoint1(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
-                                                  float (&g)[1 + ND][NR]) {
-    const float h = v[0][0], z = v[0][1], u = v[0][2], w = v[0][3];
-    const float h_x = v[2][0], z_x = v[2][1], u_x = v[2][2], w_x = v[2][3];
-    const float h_y = v[3][0], z_y = v[3][1], u_y = v[3][2], w_y = v[3][3];
-    const float G = 9.81f;
-    const float CB = (float)(3.0 / 16.0 * 9.81 * (0.78 * 0.78));
-    const float H = h + z;
-    const float Hx = h_x + z_x, Hy = h_y + z_y;
-    const float gh = rc * (u_x + w_y) + CB * (rx * Hx + ry * Hy);
-    g[0][0] = gh; g[0][1] = gh;
-    g[0][2] = rc * Hx + rx * u_x + ry * w_x;
-    g[0][3] = rc * Hy + rx * u_y + ry * w_y;
-    g[1][0] = 0.f; g[1][1] = rc; g[1][2] = rx; g[1][3] = ry;
-    const float ghx = rc * u + rx * CB * H;
-    g[2][0] = ghx; g[2][1] = ghx + rx * G;
-    g[2][2] = rc * H + rx * u; g[2][3] = ry * u;
-    const float ghy = rc * w + ry * CB * H;
-    g[3][0] = ghy; g[3][1] = ghy + ry * G;
-    g[3][2] = rx * w; g[3][3] = rc * H + ry * w;
-  }
-};
-
-struct Res2PhysicsEquation {   // ResPhysicsEquation's roles and directions (E == 0, physics.py:106); U = role 1, V = role 2
-  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3, RU = 1, RV = 2, DX = 0, DY = 1;
-  __host__ __device__ static inline void fields1(const float (&v)[1 + ND][NR], float (&f)[NF]) {
-    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
-    const float U_x = v[1][1], V_x = v[1][2], e_x = v[1][3];
-    const float U_y = v[2][1], V_y = v[2][2], e_y = v[2][3];
-    const float G = 9.81f, RHO = 1025.f;
-    const float RC = (float)(1025 * 0.002);
-    const float tbx = (RC * U) * fabsf(U);
-    const float tby = (RC * V) * fabsf(V);
-    const float D = 1.0f / (RHO * (eta + h));
-    f[0] = U_x + V_y;                                        // physics.py:113
-    f[1] = U * U_x + V * U_y + G * e_x + D * tbx;            // physics.py:114
-    f[2] = U * V_x + V * V_y + G * e_y + D * tby;            // physics.py:115
-  }
-  __host__ __device__ static inline void adjoint1(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
-                                                  float (&g)[1 + ND][NR]) {
-    const float h = v[0][0], U = v[0][1], V = v[0][2], eta = v[0][3];
-    const float U_x = v[1][1], V_x = v[1][2];
-    const float U_y = v[2][1], V_y = v[2][2];
-    const float G = 9.81f, RHO = 1025.f;
-    const float RC = (float)(1025 * 0.002);
-    const float tbx = (RC * U) * fabsf(U);
-    const float tby = (RC * V) * fabsf(V);
-    const float D = 1.0f / (RHO * (eta + h));
-    for (int c = 0; c < 1 + ND; ++c)
-      for (int r = 0; r < NR; ++r) g[c][r] = 0.f;
-    const float dD = -RHO * D * D;             // d D / d(eta+h)
-    const float gS = dD * (rx * tbx + ry * tby);
-    g[0][0] = gS; g[0][3] = gS;
-    g[0][1] = rx * (U_x + D * RC * 2.f * fabsf(U)) + ry * V_x;
-    g[0][2] = rx * U_y + ry * (V_y + D * RC * 2.f * fabsf(V));
-    g[1][1] = rc + rx * U;   // d/dU_x
-    g[1][2] = ry * U;        // d/dV_x
-    g[1][3] = rx * G;        // d/deta_x
-    g[2][1] = rx * V;        // d/dU_y
-    g[2][2] = rc + ry * V;   // d/dV_y
-    g[2][3] = ry * G;        // d/deta_y
-  }
-};
-
-struct Res2PhysicsEquationCorrected {   // ResPhysicsEquationCorrected: its own fields and mid, its adjoint on given (rc, rx, ry)
-  typedef ResPhysicsEquationCorrected R1;
-  static constexpr int NR = 6, ND = 2, NT = 3, NF = 3, RU = 1, RV = 2, DX = 0, DY = 1;
-  __host__ __device__ static inline void fields1(const float (&v)[1 + ND][NR], float (&f)[NF]) { R1::fields(v, f); }
-  __host__ __device__ static inline void adjoint1(const float (&v)[1 + ND][NR], float rc, float rx, float ry,
-                                                  float (&g)[1 + ND][NR]) {
-    const float h = v[0][0], U = v[0][1], V = v[0][2], R = v[0][4], K = v[0][5];
-    const float h_x = v[1][0], U_x = v[1][1], V_x = v[1][2], R_x = v[1][4], K_x = v[1][5];
-    const float h_y = v[2][0], U_y = v[2][1], V_y = v[2][2], R_y = v[2][4], K_y = v[2][5];
-    const float G = 9.81f, RHO = 1025.f;
-    const float RC = (float)(1025 * 0.002);
-    const float C_E = (float)(1025 * 9.81 / 8.0);
-    const R1::Mid m = R1::mid(v);
-    const float ax = rx * m.D, ay = ry * m.D;
-    const float dD = -RHO * m.D * m.D;             // d D / d(eta+h)
-    const float gS = dD * (rx * (m.tbx + m.Sx) + ry * (m.tby + m.Sy));
-    const float ds = ax * (2.f * m.E_x * m.n1 + 2.f * m.E * m.n2 * m.s_x) + ay * (m.E_y * m.n1 + m.E * m.n2 * m.s_y);   // adjoint of s = kh
-    const float gsx = 2.f * ax * m.E * m.n1, gsy = ay * m.E * m.n1;   // adjoints of s_x, s_y
-    const float nn = 2.f * m.n + 0.5f;
-    g[0][0] = gS + ds * K + gsx * K_x + gsy * K_y;
-    g[0][1] = rx * (U_x + m.D * RC * 2.f * fabsf(U)) + ry * V_x;
-    g[0][2] = rx * U_y + ry * (V_y + m.D * RC * 2.f * fabsf(V));
-    g[0][3] = gS;
-    g[0][4] = ax * (2.f * C_E * R_x * nn + 4.f * C_E * R * m.n1 * m.s_x) + ay * (2.f * C_E * R_y * m.n + 2.f * C_E * R * m.n1 * m.s_y);
-    g[0][5] = ds * h + gsx * h_x + gsy * h_y;
-    g[1][0] = gsx * K;       // d/dh_x
-    g[1][1] = rc + rx * U;   // d/dU_x
-    g[1][2] = ry * U;        // d/dV_x
-    g[1][3] = rx * G;        // d/deta_x
-    g[1][4] = 2.f * ax * C_E * R * nn;   // d/dHrms_x
-    g[1][5] = gsx * h;       // d/dk_x
-    g[2][0] = gsy * K;
-    g[2][1] = rx * V;
-    g[2][2] = rc + ry * V;
-    g[2][3] = ry * G;
-    g[2][4] = 2.f * ay * C_E * R * m.n;
-    g[2][5] = gsy * h;
-  }
-};
+// Each base IS its first-order struct — its fields and its adjoint(rc, rx, ry), so without ResPhysicsEquation::eval's NaN
+// carrier — and adds only which roles carry the momentum and which directions are x and y.
+struct Res2NavierStokes : ResNavierStokes { static constexpr int RU = 2, RV = 3, DX = 1, DY = 2; };
+struct Res2PhysicsEquation : ResPhysicsEquation { static constexpr int RU = 1, RV = 2, DX = 0, DY = 1; };
+struct Res2PhysicsEquationCorrected : ResPhysicsEquationCorrected { static constexpr int RU = 1, RV = 2, DX = 0, DY = 1; };
 
 // f <- the shifted fields; with GRAD also g <- sum_t scale[t] d(f_t^2) / dv and glap <- (-nu rx, -nu ry)
 template <class B>
@@ -638,7 +572,7 @@ struct Residual2 {
   static constexpr int NR = B::NR, ND = B::ND, NT = B::NT, NF = B::NF;
   __host__ __device__ static inline void fields(const float (&v)[1 + ND][NR], const float (&lap)[2], float nu,
                                                 float (&f)[NF]) {
-    B::fields1(v, f);
+    B::fields(v, typename B::Closure(), f);
     f[1] = f[1] - nu * lap[0];
     f[2] = f[2] - nu * lap[1];
   }
@@ -653,7 +587,7 @@ struct Residual2 {
   __host__ __device__ static inline void adjoint(const float (&v)[1 + ND][NR], const float (&f)[NF], float nu,
                                                  const float* scale, float (&g)[1 + ND][NR], float (&glap)[2]) {
     const float rc = 2.f * scale[0] * f[0], rx = 2.f * scale[1] * f[1], ry = 2.f * scale[2] * f[2];
-    B::adjoint1(v, rc, rx, ry, g);
+    B::adjoint(v, rc, rx, ry, g);
     glap[0] = -nu * rx;
     glap[1] = -nu * ry;
   }
@@ -775,14 +709,15 @@ __device__ __forceinline__ float opaque(float x) {
   return x;
 }
 // the signed fields f[NF] of one point from its jet v, through the barrier on both sides
-template <class RES, class... A>
-__device__ __forceinline__ void isolated_fields(const float (&v)[1 + RES::ND][RES::NR], float (&f)[RES::NF], A... a) {
+template <class RES>
+__device__ __forceinline__ void isolated_fields(const float (&v)[1 + RES::ND][RES::NR], const typename RES::Closure& cl,
+                                                float (&f)[RES::NF]) {
   float vb[1 + RES::ND][RES::NR];
 #pragma unroll
   for (int c = 0; c <= RES::ND; ++c)
 #pragma unroll
     for (int r = 0; r < RES::NR; ++r) vb[c][r] = opaque(v[c][r]);
-  RES::fields(vb, f, a...);
+  RES::fields(vb, cl, f);
 #pragma unroll
   for (int t = 0; t < RES::NF; ++t) f[t] = opaque(f[t]);
 }
